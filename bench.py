@@ -83,7 +83,14 @@ def parse_args(argv=None):
                          "which terminates the process - seen in 1 of 5 runs with a one-rank RCCL group")
     ap.add_argument("--train-graph-timeout", type=float, default=240.0,
                     help="seconds the graphed data-parallel leg may take before it is reported as timed out")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the frames the LAST timed rollout returned (rank 0; every family "
+                         "measured) as DIR/<family>_frames.npy, float32 (n_past + n_future, B, C, 64, 64); over 64 MB in all, "
+                         "every file keeps the same number of leading clips")
+    a = ap.parse_args(argv)
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def self_launch(args) -> int:
@@ -109,6 +116,24 @@ def self_launch(args) -> int:
     if last_json is not None:
         print(last_json, flush=True)
     return rc if (rc != 0 or last_json is not None) else 1
+
+
+DUMP_BYTES = 64 * 2**20   # --dump-outputs: all files together
+
+
+def dump_outputs(dirname: str, arrays: dict) -> dict:
+    """name -> float32 tensor (frames, B, C, H, W), on the host.  Over DUMP_BYTES, every array keeps its first `keep` clips
+    (the same count for all): a fixed sample, so two runs with the same arguments write the same clips."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = sum(a.numel() * 4 for a in arrays.values())
+    out = {}
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            a = a[:, :max(1, a.shape[1] * DUMP_BYTES // total)]
+        np.save(os.path.join(dirname, f"{name}.npy"), a.contiguous().numpy().astype(np.float32, copy=False))
+        out[name] = list(a.shape)
+    return out
 
 
 CHECK_BAR = 1e-4   # BASELINE.json north_star: "outputs match the reference CPU path within 1e-4 relative on fp32 frames"
@@ -205,9 +230,10 @@ def cpu_baseline(model: str, batch: int, n_past: int, n_eval: int, seed: int, bu
     return (res, frames) if case is not None else res
 
 
-def measure_rollout(ctx: Ctx, args, model: str, steps: int, warmup: int) -> dict:
+def measure_rollout(ctx: Ctx, args, model: str, steps: int, warmup: int, keep_outputs: bool = False) -> dict:
     """W untimed + K timed rollouts of one family; barrier + synchronize on both sides, max over ranks.
-    Rank 0 adds the per-kernel HIP-event leg (roofline of the dominant kernel)."""
+    Rank 0 adds the per-kernel HIP-event leg (roofline of the dominant kernel).  `keep_outputs`: rank 0 also returns, under
+    "_outputs", a host copy of the frame list the last timed rollout returned (frames, B, C, H, W)."""
     import torch
     from dvg_amd import ops
     from dvg_amd.data import SyntheticMovingMNIST
@@ -255,10 +281,18 @@ def measure_rollout(ctx: Ctx, args, model: str, steps: int, warmup: int) -> dict
     per_rank = ctx.all_ranks(time.perf_counter() - t0)
     dt = max(per_rank)
     assert bool(torch.isfinite(out[-1]).all())
+    outputs = None
+    if keep_outputs and ctx.rank == 0:
+        # the graphs' static frame buffers are overwritten by the next replay: copied now.  run() issues the warmup and then
+        # the timed rollouts round-robin over the chains from chain 0, so the last timed one ran on chain (W + K - 1) % inflight
+        last = out if cr is None else cr.rollouts[(warmup + steps - 1) % inflight].frames
+        outputs = torch.stack([f.detach().float().cpu() for f in last])
     frames = args.batch * args.n_future * steps * ctx.world
     res = {"value": round(frames / dt, 1), "ms_per_step": round(1000 * dt / steps, 3), "rollouts_in_flight": inflight,
            # wall time of the K timed steps on every rank, rank order (the reported time is the max)
            "per_rank_ms_per_step": [round(1000 * t / steps, 3) for t in per_rank]}
+    if outputs is not None:
+        res["_outputs"] = outputs
     if ctx.rank == 0 and not args.no_check:
         # the frames the TIMED region left behind (every chain's last replay) and what the oracle needs to redo them; the
         # comparison itself runs later, on the host, outside every timed region (main: cpu_baseline / check)
@@ -484,8 +518,10 @@ def main():
         print(f"bench.py: refusing to measure {build['path']} ({build['raw']}): not the product build of libdvg_hip.so "
               "(DVG_HIP_LIB set to a variant, or a timing-experiment build).  --allow-variant to run anyway.", file=sys.stderr)
         sys.exit(4)
-    main_res = measure_rollout(ctx, args, args.model, args.steps, args.warmup)
+    dump = args.dump_outputs is not None
+    main_res = measure_rollout(ctx, args, args.model, args.steps, args.warmup, keep_outputs=dump)
     main_case = main_res.pop("_case", None)
+    outputs = {f"{args.model}_frames": main_res.pop("_outputs")} if ctx.rank == 0 and dump else {}
     result = {
         "metric": "predicted frames/sec at 64x64, batch 64, 10-in/10-out",
         "value": main_res["value"], "unit": "frames/s", "n_gpus": ctx.world, "steps": args.steps,
@@ -541,10 +577,14 @@ def main():
 
     if not args.no_families:
         other = "dcgan" if args.model == "vgg" else "vgg"
-        fam = measure_rollout(ctx, args, other, args.steps, args.warmup)
+        fam = measure_rollout(ctx, args, other, args.steps, args.warmup, keep_outputs=dump)
         fam_case = fam.pop("_case", None)
+        if "_outputs" in fam:
+            outputs[f"{other}_frames"] = fam.pop("_outputs")
         fam["workload"] = result["config"]["workload"].replace(f"{args.model}_64", f"{other}_64")
         result["families"] = {other: fam}
+    if outputs:
+        result["dump_outputs"] = {"dir": args.dump_outputs, "shapes": dump_outputs(args.dump_outputs, outputs)}
     if not args.no_make_gifs_leg and not args.no_graph:
         ctx.barrier()
         result["make_gifs"] = {m: make_gifs_leg(ctx, args, m, args.nsample)

@@ -244,6 +244,51 @@ def write_reference_checkpoint():
     print("wrote", path, os.path.getsize(path) // 1024, "KiB (", len(buf.getvalue()) // 2**20, "MiB raw )")
 
 
+PICKLE_WEIGHT_KEY = {"dcgan_64": "c2.main.0.weight", "vgg_64": "c2.0.main.0.weight"}
+
+
+def write_reference_pickles():
+    """The reference's own encoder / decoder objects (dcgan_64, vgg_64; torch.manual_seed(0), default init), pickled WHOLE by
+    class path `models.<name>.<class>` as train.py:380-383 does - the fixture of tests/test_checkpoint_compat.py.  Every tensor is
+    zeroed except one conv weight per family, which keeps its seeded values; beside the modules: the reference's state_dict key
+    lists and the SHA-256 of that weight's bytes, taken before pickling.  Data only (class paths + tensors)."""
+    import gzip
+    import hashlib
+    import io
+    import types
+    fixture, mods = {}, {}
+    for name, key in PICKLE_WEIGHT_KEY.items():
+        torch.manual_seed(0)
+        mod = mods[name] = ref_import(name)
+        enc, dec = mod.encoder(90, 1), mod.decoder(90, 1)
+        w = enc.state_dict()[key].clone()
+        with torch.no_grad():
+            for m in (enc, dec):
+                for t in list(m.parameters()) + list(m.buffers()):
+                    t.zero_()
+            enc.state_dict()[key].copy_(w)
+        fixture[name] = {"modules": {"encoder": enc, "decoder": dec}, "weight_key": key,
+                         "weight_sha256": hashlib.sha256(w.contiguous().numpy().tobytes()).hexdigest(),
+                         "encoder_keys": list(enc.state_dict().keys()), "decoder_keys": list(dec.state_dict().keys())}
+    saved = {k: v for k, v in sys.modules.items() if k == "models" or k.startswith("models.")}
+    for k in saved:
+        del sys.modules[k]
+    pkg = types.ModuleType("models")
+    pkg.__path__ = [os.path.join(REF, "models")]
+    sys.modules.update({"models": pkg} | {f"models.{n}": m for n, m in mods.items()})
+    try:
+        buf = io.BytesIO()
+        torch.save(fixture, buf)
+    finally:
+        for k in ["models"] + [f"models.{n}" for n in mods]:
+            sys.modules.pop(k, None)
+        sys.modules.update(saved)
+    path = os.path.join(HERE, "reference_pickled_modules.pth.gz")
+    with gzip.GzipFile(path, "wb", compresslevel=9, mtime=0) as f:
+        f.write(buf.getvalue())
+    print("wrote", path, os.path.getsize(path) // 1024, "KiB")
+
+
 def main():
     out = OrderedDict()
     run_backbone("vgg", 64, 1, 2, False, 100, out, "vgg_64/eval")
@@ -263,6 +308,7 @@ def main():
     np.savez_compressed(path, **out)
     print("wrote", path, os.path.getsize(path) // 1024, "KiB")
     write_reference_checkpoint()
+    write_reference_pickles()
 
 
 if __name__ == "__main__":

@@ -427,3 +427,30 @@ def test_pooled_streams_are_made_once_per_role_and_index(monkeypatch):
     assert len(made) == 5
     monkeypatch.setattr(torch.cuda, "current_device", lambda: 1)          # another device: its own streams
     assert rollout.pooled_stream("chain", 0) is not chains[0][0] and len(made) == 6
+
+
+def test_bench_dump_outputs_arguments_and_size_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs DIR: the flag parses, --steps / --warmup are checked, and dump_outputs() writes float32 .npy
+    files - whole arrays within the budget, above it the same leading clips of every array (a fixed sample) within it."""
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    a = bench.parse_args(["--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path)])
+    assert a.steps == 7 and a.warmup == 2 and a.dump_outputs == str(tmp_path)
+    assert bench.parse_args([]).dump_outputs is None
+    for bad in (["--steps", "0"], ["--warmup", "-1"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+    frames = torch.randn(4, 6, 1, 8, 8)
+    other = torch.randn(4, 6, 1, 8, 8, dtype=torch.float64)
+    shapes = bench.dump_outputs(str(tmp_path / "all"), {"vgg_frames": frames, "dcgan_frames": other})
+    assert shapes == {"vgg_frames": [4, 6, 1, 8, 8], "dcgan_frames": [4, 6, 1, 8, 8]}
+    got = np.load(tmp_path / "all" / "vgg_frames.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, frames.numpy())
+    assert np.load(tmp_path / "all" / "dcgan_frames.npy").dtype == np.float32
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2 * 2 * (4 * 8 * 8 * 4))     # room for two clips of each of the two arrays
+    shapes = bench.dump_outputs(str(tmp_path / "cut"), {"vgg_frames": frames, "dcgan_frames": other})
+    assert shapes == {"vgg_frames": [4, 2, 1, 8, 8], "dcgan_frames": [4, 2, 1, 8, 8]}
+    cut = np.load(tmp_path / "cut" / "vgg_frames.npy")
+    assert np.array_equal(cut, frames[:, :2].numpy())
+    assert sum(os.path.getsize(tmp_path / "cut" / f) for f in os.listdir(tmp_path / "cut")) <= bench.DUMP_BYTES + 2 * 256
