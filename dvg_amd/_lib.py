@@ -11,7 +11,7 @@ import os
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-# DVG_HIP_LIB: an alternative BUILD of the same library (kernel A/B experiments, tools/ab_variants.sh); still no fallback
+# DVG_HIP_LIB: an alternative BUILD of the same library (kernel A/B experiments, `make variant`); still no fallback
 LIB_PATH = os.environ.get("DVG_HIP_LIB") or os.path.join(_HERE, "csrc", "libdvg_hip.so")
 
 _p = C.c_void_p
@@ -170,10 +170,9 @@ def lib() -> C.CDLL:
 
 
 def build_info() -> dict:
-    """dvg_build_info() parsed: {"abi": 9, "bf16x3": 1, "x3_terms": 6, "ablate": 0, "first_selects": 0, "timing_experiments": 0,
-    "variant": "", "src": "<sha256[:12] of the sources>"} plus "path" (the file loaded), "from_env" (DVG_HIP_LIB was set) and
-    "product": True only for the library the repository ships - the default path or the in-tree f32-MFMA comparison build,
-    no timing-experiment knob, no variant name."""
+    """dvg_build_info() parsed: {"abi": 9, "bf16x3": 1, "variant": "", "src": "<sha256[:12] of the sources>"} plus "path"
+    (the file loaded), "from_env" (DVG_HIP_LIB was set) and "product": True only for the library the repository ships - the
+    default path or the in-tree f32-MFMA comparison build, no variant name."""
     raw = lib().dvg_build_info().decode()
     d = {}
     for tok in raw.split():
@@ -183,8 +182,7 @@ def build_info() -> dict:
     d["path"] = LIB_PATH
     d["from_env"] = bool(os.environ.get("DVG_HIP_LIB"))
     shipped = {os.path.join(_HERE, "csrc", "libdvg_hip.so"), os.path.join(_HERE, "csrc", "libdvg_hip_f32mfma.so")}
-    d["product"] = (os.path.abspath(LIB_PATH) in shipped and d.get("x3_terms") == 6 and d.get("ablate") == 0 and
-                    d.get("first_selects") == 0 and d.get("timing_experiments") == 0 and d.get("variant", "") == "")
+    d["product"] = os.path.abspath(LIB_PATH) in shipped and d.get("variant", "") == ""
     return d
 
 

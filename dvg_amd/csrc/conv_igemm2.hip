@@ -21,73 +21,34 @@
 
 #include "dvg_common.h"
 
-// Stage schedule knobs, fixed by same-box A/B runs (tools/ab_variants.sh) over the 18 vgg_64 layers at B = 64:
-//  DVG_WRITE_OVERLAP 1: barrier BEFORE the last tap's MFMAs, next stage's ds_writes interleaved with them
-//                       (0: MFMA-less write pass between two barriers).                      84.7 % vs 80.8 % of peak
-//  DVG_VMEM_POLICY: where the next stage's global loads issue: 0 = left to hipcc (sinks them behind the last taps:
-//                       latency exposed at the ds_write), 1 = all at the stage top (delays the first MFMAs), 2 = two
-//                       per tap from tap 0, 3 = three per tap, 4 = two per tap from tap 2.   4: 84.7, 2: 84.4, 3: 84.3
-//                       (4 generalises to the 4- / 8-tap modes: from tap 0, enough per tap to place every load)
-#ifndef DVG_VMEM_POLICY
-#define DVG_VMEM_POLICY 4
-#endif
-#ifndef DVG_WRITE_OVERLAP
-#define DVG_WRITE_OVERLAP 1
-#endif
-//  DVG_STAGE_PRIO 1: s_setprio(3 - (stage & 3)) at every stage start (see the stage loop)
-#ifndef DVG_STAGE_PRIO
-#define DVG_STAGE_PRIO 1
-#endif
-
-//  DVG_ABLATE / DVG_X3_TERMS / DVG_FIRST_SELECTS (timing experiments, WRONG results): declared in dvg_common.h, which refuses
-//  to compile them unless the build says -DDVG_TIMING_EXPERIMENTS=1 (only `make variant` can pass that; dvg_build_info()
-//  reports it and bench.py refuses to print a headline from such a library).
-//  DVG_ABLATE: 1 = the stage loop issues no global loads (the next stage's LDS stores write stale registers), 2 = and no LDS
-//  stores, 3 = and no workgroup barriers - what the staging costs the loop; 4 / 5 = no weight / activation LDS stores;
-//  6 / 7 = neither loads nor stores of the weight / activation tile in the loop (6: what a weight-stationary workgroup would
-//  save at most); 8 = 2 + the GEMM mode stores one product value per lane instead of 16; 9 = 8 without the workgroup
-//  barriers: the bare fragment-read + MFMA loop
-#ifndef DVG_GEMM_NT_STORE
-#define DVG_GEMM_NT_STORE 0
-#endif
-//  DVG_GEMM_WGS_PER_CU: workgroups per CU the 64-row GEMM-mode tile is compiled for (register budget 512 / this per lane)
-#ifndef DVG_GEMM_WGS_PER_CU
-#define DVG_GEMM_WGS_PER_CU (DVG_BF16X3 ? 3 : 4)
-#endif
-//  DVG_GEMM128_WGS / _GT / _LEAN: the 128-row GEMM-mode tile.  bf16 triples: 3 workgroups per CU with K = 32 per stage (37 KB
-//  of LDS) and the LEAN fragment schedule (158 VGPRs) - what the transposed-conv mode's best tile runs at; r04 same-box A/B at
-//  the conditioning batch: 2077 us per pass against 2246 (2 per CU, K = 64) and 2267 (the 64-row tile).  f32 MFMA: as before.
-#ifndef DVG_GEMM128_WGS
-#define DVG_GEMM128_WGS (DVG_BF16X3 ? 3 : 2)
-#endif
-#ifndef DVG_GEMM128_GT
-#define DVG_GEMM128_GT (DVG_BF16X3 ? 2 : 4)
-#endif
-#ifndef DVG_GEMM128_LEAN
-#define DVG_GEMM128_LEAN 1
-#endif
-//  DVG_GEMM128_MIN_WGS: the batched GEMM takes the 128-row tile from this many (128-row) workgroups on - four residency rounds
-//  (tile2 below; r06 A/B under the steady-state power cap: profiles/r06_ab_gemm128_threshold.txt)
-//  DVG_GEMM_NT2: under the ENERGY tile policy (dvg_set_tile_policy) the batched GEMM takes the 128 x 128 tile (64 x 64 per wave,
-//  NT = 2, two workgroups per CU) from this many workgroups of it on (0: never).  r06: under three rollouts in flight the board sits at its power cap (1 365 W, 1.98 GHz:
-//  profiles/r06_power_trace_vgg.txt), so what a launch costs is its ENERGY, and the 128 x 128 tile moves a quarter of the LDS
-//  bytes and half of the L2 -> LDS bytes per MFMA of the 64 x 64 one: vgg_64 rollouts in flight 49.2 -> 51.5 k frames/s (+4.6 %),
-//  while ONE chain of launches - not power-bound, the finer tiles balance the CUs better - goes 15.7 -> 16.1 ms
-//  (profiles/r06_ab_gemm_nt2.txt: thresholds 128 / 256 / 512 and 2 / 3 / 4 rollouts in flight).
-#ifndef DVG_GEMM_NT2
-#define DVG_GEMM_NT2 256
-#endif
-//  DVG_TILE16_MIN_WGS: under the ENERGY tile policy the 8 x 16 pixel tile (two accumulator tiles per wave: a third fewer fragment
-//  reads per MFMA) from this many workgroups of it on, else 8 x 8 (LATENCY policy: 512, two workgroups per CU).  256 = one per CU, for the same reason as
-//  DVG_GEMM_NT2: in flight dcgan_64 217.2 -> 219.3 k, vgg_64 50.1 -> 50.3 k frames/s, one chain unchanged (profiles/r06_ab_tile16.txt)
-#ifndef DVG_TILE16_MIN_WGS
-#define DVG_TILE16_MIN_WGS 256
-#endif
-#ifndef DVG_GEMM128_MIN_WGS
-#define DVG_GEMM128_MIN_WGS (4 * 768)
-#endif
-
 namespace dvg {
+
+// Tuning constants, each fixed by a same-box A/B run:
+//  workgroups per CU the 64-row GEMM-mode tile is compiled for (register budget 512 / this per lane)
+constexpr int DVG_GEMM_WGS_PER_CU = DVG_BF16X3 ? 3 : 4;
+//  the 128-row GEMM-mode tile.  bf16 triples: 3 workgroups per CU with K = 32 per stage (37 KB of LDS) and the LEAN fragment
+//  schedule (158 VGPRs) - what the transposed-conv mode's best tile runs at; r04 same-box A/B at the conditioning batch: 2077 us
+//  per pass against 2246 (2 per CU, K = 64) and 2267 (the 64-row tile) (profiles/r04_gemm_tile_variants.txt).  f32 MFMA: as before.
+constexpr int DVG_GEMM128_WGS = DVG_BF16X3 ? 3 : 2;
+constexpr int DVG_GEMM128_GT = DVG_BF16X3 ? 2 : 4;
+//  16-channel slabs per stage of the 64-row GEMM tile: 4 (K = 64, 60 KB of LDS with the 128-row tile); 8 was measured 10-25 %
+//  slower on every Winograd shape (80 KB per workgroup: the second workgroup no longer fits the CU)
+constexpr int DVG_GEMM_GT = 4;
+//  the batched GEMM takes the 128-row tile from this many (128-row) workgroups on - four residency rounds (tile2 below; r06 A/B
+//  under the steady-state power cap: profiles/r06_ab_gemm128_threshold.txt)
+constexpr int DVG_GEMM128_MIN_WGS = 4 * 768;
+//  under the ENERGY tile policy (dvg_set_tile_policy) the batched GEMM takes the 128 x 128 tile (64 x 64 per wave, NT = 2, two
+//  workgroups per CU) from this many workgroups of it on.  r06: under three rollouts in flight the board sits at its power cap
+//  (1 365 W, 1.98 GHz: profiles/r06_power_trace_vgg.txt), so what a launch costs is its ENERGY, and the 128 x 128 tile moves a
+//  quarter of the LDS bytes and half of the L2 -> LDS bytes per MFMA of the 64 x 64 one: vgg_64 rollouts in flight 49.2 -> 51.5 k
+//  frames/s (+4.6 %), while ONE chain of launches - not power-bound, the finer tiles balance the CUs better - goes 15.7 -> 16.1 ms
+//  (profiles/r06_ab_gemm_nt2.txt: thresholds 128 / 256 / 512 and 2 / 3 / 4 rollouts in flight).  bf16-triple build only.
+[[maybe_unused]] constexpr int DVG_GEMM_NT2 = 256;
+//  under the ENERGY tile policy the 8 x 16 pixel tile (two accumulator tiles per wave: a third fewer fragment reads per MFMA)
+//  from this many workgroups of it on, else 8 x 8 (LATENCY policy: 512, two workgroups per CU).  256 = one per CU, for the same
+//  reason as DVG_GEMM_NT2: in flight dcgan_64 217.2 -> 219.3 k, vgg_64 50.1 -> 50.3 k frames/s, one chain unchanged
+//  (profiles/r06_ab_tile16.txt)
+constexpr int DVG_TILE16_MIN_WGS = 256;
 
 // M2_GEMM: batched GEMM y[n][px][co] = sum_ci x[n][px][ci] * w[n][ci][co] on the same machinery (a "1x1 conv" whose weight
 // depends on the image index n): the 16 Winograd-domain products of dvg_winograd_* (n = transform position).  A stage is
@@ -181,11 +142,8 @@ struct Cfg2 {
     // cycles per 8 reads instead of 8) pixels apart).  Found by exhaustive search (tools/lds_layout_search.py, which also
     // checks that vertical 2 x 2 pool partners stay in one lane: register blocks (0, 1) and (2, 3)).  The padding pixels are
     // never read and cost no LDS: the staged rows were already rounded up to whole 256-thread store passes.
-    // DVG_HALO_LAYOUT=0: the r05 layout (lane l = pixel l, unpadded pitches).
-#ifndef DVG_HALO_LAYOUT
-#define DVG_HALO_LAYOUT 1
-#endif
-    static constexpr bool LAYOUT = !GEMM && DVG_HALO_LAYOUT != 0;
+    // (A/B against the r05 layout: profiles/r06_ab_halo_layout_*.txt.)
+    static constexpr bool LAYOUT = !GEMM;
     static constexpr int HWP = !LAYOUT ? HW : (TW == 16 ? HW : (TW == 8 ? 12 : 6));         // pixel pitch of a halo row
     static constexpr int IMG = (LAYOUT && TI == 4) ? (PAR4 ? 30 : 40) : HH * HWP;           // pixel pitch of an image
     static_assert(IMG >= HH * HWP && HWP >= HW, "halo layout");
@@ -210,11 +168,6 @@ struct Cfg2 {
     static constexpr int row_c(int reg) { return 4 * (int)((P0PACK >> (4 * (reg >> 2))) & 15u) + (reg & 3); }
     static constexpr int BM = TI * TH * TW, MT = BM / 64, BN = 64 * NT;
     static constexpr int NTAPS = GEMM ? 1 : ((MODE == M2_CONV3) ? 9 : 16);
-    // DVG_GEMM_GT: 16-channel slabs per stage of the GEMM modes.  4 (K = 64, 60 KB of LDS with the 128-row tile); 8 was
-    // measured 10-25 % slower on every Winograd shape (80 KB per workgroup: the second workgroup no longer fits the CU).
-#ifndef DVG_GEMM_GT
-#define DVG_GEMM_GT 4
-#endif
     // (NT = 2: two slabs, K = 32, so that two 48 KB workgroups share a CU)
     static constexpr int GT = (MODE == M2_CONV3) ? 9 : (MODE == M2_CONV4S2 ? 4 : (GEMM ? (NT == 2 ? 2 : (BM == 128 ? DVG_GEMM128_GT : DVG_GEMM_GT)) : 4));  // taps (GEMM: 16-channel slabs) per stage
     static constexpr int NG = (MODE == M2_CONV4S2) ? 16 / GT : 1;                     // stages per K chunk
@@ -383,11 +336,6 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
         if constexpr (FIRST) {
             // the halo tile's channels of vgg_layer(1, 64) from the frame patch: 9 taps per value, folded BatchNorm, LeakyReLU;
             // slots outside the image are the SECOND layer's zero padding
-#if DVG_FIRST_SELECTS == 2     // diagnostic: the select form behind a full drain of the memory counters
-            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-#elif DVG_FIRST_SELECTS == 3   // diagnostic: the select form with the scheduler fenced off (no MFMA interleaved with it)
-            __builtin_amdgcn_sched_barrier(0);
-#endif
 #pragma unroll
             for (int i = 0; i < NLA; ++i) {
                 const int hp = min(C::hp_of((tid + i * 256) >> 2), HP - 1);
@@ -400,21 +348,12 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
                     for (int e = 0; e < 4; ++e) v[e] = fmaf(fw[t][e], px, v[e]);
                 }
                 // LeakyReLU as max(a, slope a) (0 < slope < 1) and the padding as a multiply by 0 / 1: no lane masks in this block
-#if DVG_FIRST_SELECTS      // diagnostic build only (tools/ubench/first_pair_selects.md): the form that gave run-to-run different tiles
-                const bool okb = (okmask >> i) & 1u;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float a = v[e] * fw[9][e] + fw[10][e];
-                    v[e] = okb ? (a > 0.f ? a : a * p.first_slope) : 0.f;
-                }
-#else
                 const float okf = (float)((okmask >> i) & 1u);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const float a = v[e] * fw[9][e] + fw[10][e];
                     v[e] = fmaxf(a, a * p.first_slope) * okf;
                 }
-#endif
                 ra[i] = v;
             }
         }
@@ -538,10 +477,8 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
         constexpr int ngrp = (grp + 1) % NG;
         constexpr bool next_a = has_next && (ngrp == 0 || C::PAR4);        // PAR4: every stage has its own A tile
         const int nchunk = nchunk_override >= 0 ? nchunk_override : chunk + (ngrp == 0 ? CPS : 0);
-        if (DVG_ABLATE < 1 || DVG_ABLATE == 6 || DVG_ABLATE == 7) {        // 6: the weight tile stays what the prologue loaded, 7: the A tile
-            if constexpr (next_a) { if (DVG_ABLATE != 7) gload_a(nchunk * C::KC, ra, C::PAR4 ? ngrp : 0); }
-            if constexpr (has_next) { if (DVG_ABLATE != 6) gload_b(nchunk, ngrp, rb); }
-        }
+        if constexpr (next_a) gload_a(nchunk * C::KC, ra, C::PAR4 ? ngrp : 0);
+        if constexpr (has_next) gload_b(nchunk, ngrp, rb);
 
         // ---- all taps of this stage from LDS; fragments double-buffered across taps ----
         // a lane's fragment of a tap: NP 16-byte pieces per 32-row tile - f32: its k-values 0..3 and 4..7 of the lane's
@@ -565,7 +502,7 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
             // LEAN (the 64 x 64 wave tile): the next tap's planes are read when the current tap no longer needs the plane -
             // h up front into a second buffer, l after the two groups that use l, m after the three that use m - so that 16
             // instead of 48 VGPRs double-buffer the fragments (the whole set twice does not fit 256 registers)
-            constexpr bool LEAN = X3 && (NT == 2 || (GEMM && MT == 2 && DVG_GEMM128_LEAN));
+            constexpr bool LEAN = X3 && (NT == 2 || (GEMM && MT == 2));
             auto read_plane = [&](int j) {
                 const int ao = tap_lds(grp, tt + 1);
 #pragma unroll
@@ -588,16 +525,13 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
                         fb[nxt][nt][j] = *reinterpret_cast<const f32x4*>(&Bs[b_base[nt] + (tt + 1) * 64 * LDB + j * PSTEP]);
                 }
             }
-            constexpr bool overlap_writes = DVG_WRITE_OVERLAP && has_next;
-            if (overlap_writes && tt == GT - 1) {
+            if (has_next && tt == GT - 1) {
                 // The last tap's fragments are in registers: every wave is done reading this stage's tiles after
                 // this barrier, and the next stage's ds_writes interleave with the last tap's MFMAs instead of
-                // forming an MFMA-less pass between two barriers.
-                if (DVG_ABLATE < 3 || (DVG_ABLATE >= 4 && DVG_ABLATE != 9)) __syncthreads();
-                if (DVG_ABLATE < 2 || (DVG_ABLATE >= 4 && DVG_ABLATE < 8)) {      // 4: no B stores, 5: no A stores (timing only)
-                    if constexpr (next_a) { if (DVG_ABLATE != 5 && DVG_ABLATE != 7) lds_store_a(ra, C::PAR4 ? ngrp : 0); }
-                    if (DVG_ABLATE != 4 && DVG_ABLATE != 6) lds_store_b(rb);
-                }
+                // forming an MFMA-less pass between two barriers (84.7 % vs 80.8 % of peak: docs/DESIGN_NOTES_r01-r03.md §3.1).
+                __syncthreads();
+                if constexpr (next_a) lds_store_a(ra, C::PAR4 ? ngrp : 0);
+                lds_store_b(rb);
             }
             if constexpr (X3) {
                 // six bf16 MFMAs per 32 x 32 tile and K = 16 slab, small terms first: (l,h) (m,m) (h,l) (m,h) (h,m) (h,h)
@@ -610,21 +544,19 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
                                 __builtin_bit_cast(bf16x8_t, fa[cur][mt][pa]), __builtin_bit_cast(bf16x8_t, fb[cur][nt][pb]),
                                 acc[mt * NT + nt], 0, 0, 0);
                 };
-                // DVG_X3_TERMS (timing experiments only, WRONG results below 6): 3 keeps (m,h) (h,m) (h,h) - what a two-piece
-                // operand split would issue - to measure how the rollout rate follows the MFMA count (notes r05 §8)
                 if constexpr (LEAN) {
-                    if (DVG_X3_TERMS >= 6) mm(2, 0);
-                    if (DVG_X3_TERMS >= 6) mm(0, 2);
+                    mm(2, 0);
+                    mm(0, 2);
                     if (tt + 1 < GT) read_plane(2);
-                    if (DVG_X3_TERMS >= 6) mm(1, 1);
+                    mm(1, 1);
                     mm(1, 0);
                     mm(0, 1);
                     if (tt + 1 < GT) read_plane(1);
                     mm(0, 0);
                 } else {
-                    if (DVG_X3_TERMS >= 6) mm(2, 0);
-                    if (DVG_X3_TERMS >= 6) mm(1, 1);
-                    if (DVG_X3_TERMS >= 6) mm(0, 2);
+                    mm(2, 0);
+                    mm(1, 1);
+                    mm(0, 2);
                     mm(1, 0);
                     mm(0, 1);
                     mm(0, 0);
@@ -641,23 +573,18 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
             // Pin the software pipeline: hipcc otherwise sinks the next tap's ds_reads down to their first use
             // (ds_read x3 -> s_waitcnt -> mfma x8), exposing the LDS latency every 8 MFMAs.  One ds_read_b128 per two
             // MFMAs, issued a full tap (16 / 8 MFMAs) ahead of its consumer.
-            constexpr int NREAD = NP * (MT + NT), NMFMA = (X3 ? DVG_X3_TERMS : 8) * MT * NT, MPR = NMFMA >= 2 * NREAD ? 2 : 1;
-            // next stage's global loads: two per tap behind the first taps' MFMAs.  Left free, hipcc sinks them to
-            // the end of the stage (latency exposed at their ds_write); all at the top they delay the first MFMAs.
+            constexpr int NREAD = NP * (MT + NT), NMFMA = (X3 ? 6 : 8) * MT * NT, MPR = NMFMA >= 2 * NREAD ? 2 : 1;
+            // next stage's global loads: left free, hipcc sinks them to the end of the stage (latency exposed at their
+            // ds_write); all at the top they delay the first MFMAs.  Spread over the taps that are followed by another tap,
+            // starting at tap 2 in the 9-tap mode and at tap 0 in the 4- / 8-tap modes, at least two and as many per tap as it
+            // takes to place ALL of them (84.7 % of peak; two or three per tap from tap 0: 84.4, 84.3 - the same notes)
             constexpr int NVMEM = (next_a ? (FIRST ? 11 : NLA) : 0) + (has_next ? NLB : 0);
-            constexpr int POLICY = DVG_VMEM_POLICY;
-            // policy 4 (default): spread over the taps that are followed by another tap, starting at tap 2 in the 9-tap
-            // mode and at tap 0 in the 4- / 8-tap modes, as many per tap as it takes to place ALL of them (with the
-            // 9-tap constants, the 4-tap transposed mode pinned 2 of its 6-7 loads and the rest sank to the stage's end)
-            constexpr int VT0 = (POLICY == 4) ? (GT >= 9 ? 2 : 0) : 0;
+            constexpr int VT0 = GT >= 9 ? 2 : 0;
             constexpr int SLOTS = (GT - 1 - VT0) > 0 ? (GT - 1 - VT0) : 1;
             constexpr int VNEED = (NVMEM + SLOTS - 1) / SLOTS;
-            constexpr int VPT = (POLICY == 3) ? 3 : (POLICY == 4 ? (VNEED > 2 ? VNEED : 2) : 2);
+            constexpr int VPT = VNEED > 2 ? VNEED : 2;
             constexpr int VTAPS = (NVMEM + VPT - 1) / VPT;
-            if (tt == 0) {
-                if (POLICY == 1 && NVMEM > 0) __builtin_amdgcn_sched_group_barrier(0x020, NVMEM, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, NREAD, 0);  // tap 0's own fragments
-            }
+            if (tt == 0) __builtin_amdgcn_sched_group_barrier(0x100, NREAD, 0);  // tap 0's own fragments
             if (LEAN && tt + 1 < GT) {
                 constexpr int G = MT * NT, R = MT + NT;
 #pragma unroll
@@ -684,7 +611,7 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
                     __builtin_amdgcn_sched_group_barrier(0x008, MPR, 0);
                 }
                 if (NMFMA > MPR * NREAD) __builtin_amdgcn_sched_group_barrier(0x008, NMFMA - MPR * NREAD, 0);
-            } else if (overlap_writes) {
+            } else if (has_next) {     // the next stage's ds_writes between the last tap's MFMAs
                 constexpr int NW = (next_a ? NLA * (X3 ? 3 : 1) : 0) + NLB;
 #pragma unroll
                 for (int r = 0; r < NW; ++r) {
@@ -695,17 +622,10 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
             } else {
                 __builtin_amdgcn_sched_group_barrier(0x008, NMFMA, 0);
             }
-            if (POLICY >= 2 && tt >= VT0 && tt < VT0 + VTAPS && tt + 1 < GT) __builtin_amdgcn_sched_group_barrier(0x020, VPT, 0);
+            if (tt >= VT0 && tt < VT0 + VTAPS && tt + 1 < GT) __builtin_amdgcn_sched_group_barrier(0x020, VPT, 0);
         }
 
-        if constexpr (has_next) {
-            if (!DVG_WRITE_OVERLAP) {
-                __syncthreads();  // every wave has finished reading this stage's tiles
-                if constexpr (next_a) lds_store_a(ra, C::PAR4 ? ngrp : 0);
-                lds_store_b(rb);
-            }
-            if (DVG_ABLATE < 3 || (DVG_ABLATE >= 4 && DVG_ABLATE != 9)) __syncthreads();
-        }
+        if constexpr (has_next) __syncthreads();
     };
     using std::integral_constant;
     // Progress-based wave priority.  The MFMA issue arbiter breaks ties by wave age, so of the two workgroups that share a
@@ -714,7 +634,6 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
     // SIMD, which cannot saturate the f32 pipe.  With priority 3 - (stage & 3) a workgroup that is one stage AHEAD of its
     // neighbour has the lower priority on 3 of every 4 stages: the pair stays within a stage of each other and both
     // finish together.  Needs no knowledge of who the neighbour is.
-#if DVG_STAGE_PRIO
     const bool prio_on = p.stage_prio != 0;
     auto set_prio = [&](int st) {
         if (!prio_on) return;
@@ -725,9 +644,6 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
             default: __builtin_amdgcn_s_setprio(0); break;
         }
     };
-#else
-    auto set_prio = [](int) {};
-#endif
     int chunk = chunk_begin, st = 0;
     if constexpr (GEMM) {
         // gemm_ni images back to back in ONE software pipeline: the loads of image i+1's first stage are in flight while
@@ -762,15 +678,9 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
 #pragma unroll
                     for (int reg = 0; reg < 16; ++reg) {
                         const int mu = mbase + (reg & 3) + 8 * (reg >> 2);       // the uniform part of m (4 hh is in lane_off)
-                        // (DVG_ABLATE 8 / 9, timing only: one product value per lane instead of the tile's 16)
-                        if (DVG_ABLATE < 8 || reg == 0) {
-                            float* const dst = (yb + (size_t)((y0 + mu / TW) * p.W + x0 + mu % TW) * p.Cout + nt * 32) + lane_off;
-#if DVG_GEMM_NT_STORE      // A/B (r05): the products are written once and read once, by the next kernel
-                            __builtin_nontemporal_store(acc[mt * NT + nt][reg], dst);
-#else
-                            *dst = acc[mt * NT + nt][reg];
-#endif
-                        }
+                        // (a plain store: the nontemporal one was no faster, profiles/r05_ab_nontemporal.txt)
+                        float* const dst = (yb + (size_t)((y0 + mu / TW) * p.W + x0 + mu % TW) * p.Cout + nt * 32) + lane_off;
+                        *dst = acc[mt * NT + nt][reg];
                         acc[mt * NT + nt][reg] = 0.f;
                     }
             }
@@ -796,9 +706,7 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
     for (; chunk + CPS < chunk_end; chunk += CPS) chunk_stages(chunk, integral_constant<bool, false>{});
     chunk_stages(chunk, integral_constant<bool, true>{});
     }
-#if DVG_STAGE_PRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     unsigned long long clk_loop = 0;
     if (p.clk) clk_loop = clock64();
     auto clk_exit = [&]() {
@@ -1437,9 +1345,9 @@ extern "C" int dvg_gemm_batched_k16(const float* x, const float* w_k16, float* y
     int Hg = H, Wg = W, ti, th, tw;
     DVG_REQUIRE(tile2(M2_GEMM, NB, Hg, Wg, Cout, &ti, &th, &tw) == 0 && ti == 1, DVG_ERR_SHAPE,
                 "dvg_gemm_batched_k16: no tile for %dx%d", H, W);
-#if DVG_BF16X3 && DVG_GEMM_NT2
+#if DVG_BF16X3
     // 128 x 128 workgroup tile (64 x 64 per wave: half the fragment reads and half the L2 -> LDS bytes per MFMA of the 128 x 64
-    // tile) from DVG_GEMM_NT2 workgroups on: the energy-lean tile (see the knob above)
+    // tile) from DVG_GEMM_NT2 workgroups on: the energy-lean tile (see the constant above)
     if (g_tile_policy && Cout % 128 == 0 && Wg % 16 == 0 && (long)NB * (Hg / 8) * (Wg / 16) * (Cout / 128) >= DVG_GEMM_NT2)
         return launch2<M2_GEMM, 1, 8, 16, 2>(p, Hg, Wg, workspace, workspace_floats, (hipStream_t)stream);
 #endif

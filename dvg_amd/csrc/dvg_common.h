@@ -44,28 +44,6 @@ typedef __bf16 bf16x8_t __attribute__((ext_vector_type(8)));
 #endif
 #define DVG_WROW (DVG_BF16X3 ? 24 : 16)   // floats per packed weight row (16 k-values of one output channel)
 
-// ---- timing experiments (WRONG results) ---------------------------------------------------------------------------------
-// conv_igemm2.hip carries three knobs that change what the kernels COMPUTE, for pricing experiments only: DVG_ABLATE (parts
-// of the stage loop removed), DVG_X3_TERMS (< 6: fewer of the six bf16 MFMAs per product slab), DVG_FIRST_SELECTS (diagnostic
-// forms of the fused first layer).  They exist only in builds that say -DDVG_TIMING_EXPERIMENTS=1: `make all` / `make
-// f32mfma` never pass it (the Makefile hands DEFS to the `variant` target alone), anything else fails to compile here, and
-// dvg_build_info() carries the values so that a loaded library can be told from the product (bench.py refuses such a build).
-#ifndef DVG_TIMING_EXPERIMENTS
-#define DVG_TIMING_EXPERIMENTS 0
-#endif
-#ifndef DVG_ABLATE
-#define DVG_ABLATE 0
-#endif
-#ifndef DVG_X3_TERMS
-#define DVG_X3_TERMS 6
-#endif
-#ifndef DVG_FIRST_SELECTS
-#define DVG_FIRST_SELECTS 0
-#endif
-#if !DVG_TIMING_EXPERIMENTS && (DVG_ABLATE != 0 || DVG_X3_TERMS != 6 || DVG_FIRST_SELECTS != 0)
-#error "DVG_ABLATE / DVG_X3_TERMS / DVG_FIRST_SELECTS give WRONG results: timing builds only (-DDVG_TIMING_EXPERIMENTS=1 via `make variant`)"
-#endif
-
 // two fp32 values -> their three bf16 terms, each pair packed into one dword (low half = the first value).  Nine VALU
 // instructions: v_cvt_pk_bf16_f32 (round to nearest even) x 3, the two halves of a packed pair back to fp32 (shift / mask) x 2,
 // v_pk_add_f32 x 2.  (A truncating split - mask instead of convert - costs the same and leaves dropped terms of up to
@@ -92,29 +70,17 @@ __device__ __forceinline__ void bf16x3_split_pair(float a0, float a1, unsigned& 
 // DVG_BF16X3 a row is [3 planes h, m, l][16 bf16], and the two 16-byte halves of every plane are swapped for rows with
 // (co % 64) & 8 (the LDS image of the tile is this memory image: b128 fragment reads of 16 consecutive rows then hit 16
 // distinct 16-byte slots).
-#ifndef DVG_WROW_SHORT_STORES
-#define DVG_WROW_SHORT_STORES 0
-#endif
-// Two adjacent k-values (k even) of a packed row as ONE 4-byte store per plane.
+// Two adjacent k-values (k even) of a packed row as ONE 4-byte store per plane (the r06 packed-row writer fix; the same values
+// as 2 x 2-byte stores were equally clean: profiles/r06_dp_race_bisect.txt).
 __device__ __forceinline__ void wrow_store_pair(float* __restrict__ rows, size_t row, int co_local, int k, float v0, float v1) {
 #if DVG_BF16X3
     unsigned* d = reinterpret_cast<unsigned*>(rows + row * 24);
     unsigned ph, pm, pl;
     bf16x3_split_pair(v0, v1, ph, pm, pl);
     const int pos2 = ((((k >> 3) ^ ((co_local >> 3) & 1)) << 3) + (k & 7)) >> 1;
-#if DVG_WROW_SHORT_STORES   // A/B knob (make variant): the same values as 2 x 2-byte stores per plane - which half of the fix matters
-    unsigned short* d16 = reinterpret_cast<unsigned short*>(d);
-    d16[2 * pos2] = (unsigned short)(ph & 0xffffu);
-    d16[2 * pos2 + 1] = (unsigned short)(ph >> 16);
-    d16[16 + 2 * pos2] = (unsigned short)(pm & 0xffffu);
-    d16[16 + 2 * pos2 + 1] = (unsigned short)(pm >> 16);
-    d16[32 + 2 * pos2] = (unsigned short)(pl & 0xffffu);
-    d16[32 + 2 * pos2 + 1] = (unsigned short)(pl >> 16);
-#else
     d[pos2] = ph;
     d[8 + pos2] = pm;
     d[16 + pos2] = pl;
-#endif
 #else
     (void)co_local;
     rows[row * 16 + k] = v0;

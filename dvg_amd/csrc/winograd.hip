@@ -14,34 +14,7 @@
 
 #include "dvg_common.h"
 
-// Nontemporal hints on the transforms' read-once M loads / written-once V stores.  r05 same-box A/B on the vgg_64 rollout, each
-// twice: M loads of the chain kernels nontemporal 49.41 / 49.53 k frames/s in flight against 48.87 / 49.23 (+0.9 %), one chain
-// 15.28 against 15.34 ms -> default; V stores nontemporal 49.32 / 49.24 (noise) -> not taken; the GEMM's M store nontemporal
-// 48.86 / 49.07 (-0.3 %) -> not taken; the same load hint in the 8 x 8 hand-over and the plain output kernels 49.11 / 49.01
-// against 49.13 / 48.94 (noise) -> not taken.
-#ifndef DVG_WINO_NT_LOAD
-#define DVG_WINO_NT_LOAD 1
-#endif
-#ifndef DVG_WINO_NT_STORE
-#define DVG_WINO_NT_STORE 0
-#endif
-
 namespace dvg {
-
-template <typename V> __device__ __forceinline__ V wino_ld(const V* p) {
-#if DVG_WINO_NT_LOAD
-    return __builtin_nontemporal_load(p);
-#else
-    return *p;
-#endif
-}
-template <typename V> __device__ __forceinline__ void wino_st(V* p, const V& v) {
-#if DVG_WINO_NT_STORE
-    __builtin_nontemporal_store(v, p);
-#else
-    *p = v;
-#endif
-}
 
 // wrow_owner_note - why the two weight transforms have the shape they have (r06, profiles/r06_dp_race_bisect.txt).
 // Until r06 the F(4x4) kernel ran one k-value per thread (thread i = (co, ci), 2-byte stores).  Alone on the device it was right in
@@ -523,8 +496,9 @@ __global__ __launch_bounds__(NT) void winograd4_chain_kernel(const float* __rest
 #pragma unroll
         for (int b = 0; b < 6; ++b) {
             V q[6];
+            // read-once M: nontemporal, +0.9 % vgg_64 rollouts in flight (r05 same-box A/B, profiles/r05_ab_nontemporal.txt)
 #pragma unroll
-            for (int a = 0; a < 6; ++a) q[a] = wino_ld(reinterpret_cast<const V*>(m) + ((size_t)(a * 6 + b) * T + t) * CVg + cg);
+            for (int a = 0; a < 6; ++a) q[a] = __builtin_nontemporal_load(reinterpret_cast<const V*>(m) + ((size_t)(a * 6 + b) * T + t) * CVg + cg);
             V col[4];
             at4(q, col);
 #pragma unroll
@@ -596,8 +570,9 @@ __global__ __launch_bounds__(NT) void winograd4_chain_kernel(const float* __rest
         for (int a = 0; a < 6; ++a) {
             V o[6];
             bt4(e[a], o);
+            // plain stores: a nontemporal V store measured noise (profiles/r05_ab_nontemporal.txt)
 #pragma unroll
-            for (int b = 0; b < 6; ++b) wino_st(reinterpret_cast<V*>(v) + ((size_t)(a * 6 + b) * T2 + t2) * CVg + cg, o[b]);
+            for (int b = 0; b < 6; ++b) reinterpret_cast<V*>(v)[((size_t)(a * 6 + b) * T2 + t2) * CVg + cg] = o[b];
         }
     }
 }
