@@ -4,10 +4,16 @@
 A "step" is ONE rollout sample (one pass of the make_gifs sample loop, generate_frames.py:143-177)
 over one batch of synthetic Moving-MNIST: B=64, 64x64, 10 conditioning + 10 predicted frames
 (19 encoder calls, 10 decoder calls, 19 LSTM steps, 1 GP trigger sample at i=15), i.e.
-BASELINE.json configs[1].  value = B * n_future * steps * n_gpus / time  (vgg_64; the dcgan_64 family of
+BASELINE.json configs[1].  value = B * n_future * steps * n_gpus / time  (vgg_64; with --full the dcgan_64 family of
 the same metric is measured in the same process and reported under "families").
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs: it sets up, warms up, times the K steps of the `--model` family, writes the frames
+with --dump-outputs (the other family's too: its rollouts run for that alone) and prints the line.  Every other leg - the
+`sustained` and `single_chain` figures, the per-kernel roofline, the other family, make_gifs, C1, GPtrigger_gen, the HBM-bound
+layers, the CPU baseline and the oracle `check`, the f32-MFMA build, the training legs - runs with --full (the `--no-*`
+switches then leave single legs out).
 
 N > 1: one rank per GPU over RCCL.  When the driver launches the ranks itself (torch.distributed.run sets
 WORLD_SIZE) each rank runs main(); from a bare shell `python bench.py --gpus N` spawns that launcher as a
@@ -50,11 +56,14 @@ def parse_args(argv=None):
     ap.add_argument("--n_past", type=int, default=10)
     ap.add_argument("--n_future", type=int, default=10)
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every leg beside the headline (see the module docstring); a plain run times the steps alone")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true",
                     help="skip the oracle check of the frames the timed region produced (rank 0; `check` in the JSON line)")
-    ap.add_argument("--sustained-s", type=float, default=5.0,
-                    help="seconds of back-to-back rollouts (same graphs) for the `sustained` figure beside `value`; 0 = skip")
+    ap.add_argument("--sustained-s", type=float, default=None,
+                    help="seconds of back-to-back rollouts (same graphs) for the `sustained` figure beside `value`; 0 = skip "
+                         "(--full only; default 5 there)")
     ap.add_argument("--allow-variant", action="store_true",
                     help="emit a line although DVG_HIP_LIB points at another build of the library or the loaded build is a "
                          "timing experiment (X3_TERMS != 6, ABLATE != 0, ...): the line then says so in `build`")
@@ -90,6 +99,14 @@ def parse_args(argv=None):
     a = ap.parse_args(argv)
     if a.steps < 1 or a.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    if a.sustained_s is None:
+        a.sustained_s = 5.0 if a.full else 0.0
+    elif a.sustained_s > 0 and not a.full:
+        ap.error("--sustained-s needs --full")
+    if not a.full:
+        # a plain run: the timed steps and nothing else (main() runs the other family only to write its frames)
+        a.no_check = a.no_cpu_baseline = a.no_roofline = a.no_train_leg = a.no_f32mfma_leg = True
+        a.no_make_gifs_leg = a.no_extra_legs = True
     return a
 
 
@@ -232,8 +249,9 @@ def cpu_baseline(model: str, batch: int, n_past: int, n_eval: int, seed: int, bu
 
 def measure_rollout(ctx: Ctx, args, model: str, steps: int, warmup: int, keep_outputs: bool = False) -> dict:
     """W untimed + K timed rollouts of one family; barrier + synchronize on both sides, max over ranks.
-    Rank 0 adds the per-kernel HIP-event leg (roofline of the dominant kernel).  `keep_outputs`: rank 0 also returns, under
-    "_outputs", a host copy of the frame list the last timed rollout returned (frames, B, C, H, W)."""
+    With --full: `sustained`, `single_chain` and, on rank 0, the oracle snapshot and the per-kernel HIP-event leg (roofline of
+    the dominant kernel).  `keep_outputs`: rank 0 also returns, under "_outputs", a host copy of the frame list the last timed
+    rollout returned (frames, B, C, H, W)."""
     import torch
     from dvg_amd import ops
     from dvg_amd.data import SyntheticMovingMNIST
@@ -312,7 +330,7 @@ def measure_rollout(ctx: Ctx, args, model: str, steps: int, warmup: int, keep_ou
         res["sustained"] = {"value": round(args.batch * args.n_future * n_sus * ctx.world / dts, 1), "steps": n_sus,
                             "seconds": round(dts, 2), "ms_per_step": round(1000 * dts / n_sus, 3),
                             "ratio_to_value": round((args.batch * args.n_future * n_sus * ctx.world / dts) / (frames / dt), 4)}
-    if inflight > 1:
+    if inflight > 1 and args.full:
         # the same K rollouts as ONE serial chain of launches (one graph, one stream), for comparison: a graph of its own,
         # captured under the LATENCY tile policy (what a caller with one chain gets: rollout.GraphedRollout's default; the
         # chains above carry the energy-lean tiles, which make one chain 3 % slower and three in flight 4.6 % faster)
@@ -475,7 +493,7 @@ def f32mfma_leg(args) -> dict:
         return {"skipped": "dvg_amd/csrc/libdvg_hip_f32mfma.so not built (make -C dvg_amd/csrc f32mfma)"}
     cmd = [sys.executable, os.path.abspath(__file__), "--gpus", "1", "--steps", str(args.steps), "--warmup", str(args.warmup),
            "--model", args.model, "--batch", str(args.batch), "--n_past", str(args.n_past), "--n_future", str(args.n_future),
-           "--seed", str(args.seed), "--inflight", str(args.inflight), "--no-families", "--no-cpu-baseline", "--no-train-leg",
+           "--seed", str(args.seed), "--inflight", str(args.inflight), "--full", "--no-families", "--no-cpu-baseline", "--no-train-leg",
            "--no-f32mfma-leg", "--no-make-gifs-leg", "--no-extra-legs", "--sustained-s", "0"] + (["--no-graph"] if args.no_graph else []) + \
         (["--no-check"] if args.no_check else [])
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
@@ -525,7 +543,7 @@ def main():
     result = {
         "metric": "predicted frames/sec at 64x64, batch 64, 10-in/10-out",
         "value": main_res["value"], "unit": "frames/s", "n_gpus": ctx.world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": main_res["ms_per_step"], "higher_is_better": True,
+        "warmup": args.warmup, "ms_per_step": main_res["ms_per_step"], "higher_is_better": True, "full": args.full,
         "single_chain": main_res.get("single_chain"), "per_rank_ms_per_step": main_res.get("per_rank_ms_per_step"),
         "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
         # the same graphs for >= 5 s (the chip is power-managed; the K timed steps are a fraction of a second)
@@ -575,7 +593,7 @@ def main():
         if ctx.rank == 0:
             print(json.dumps(result), flush=True)
 
-    if not args.no_families:
+    if not args.no_families and (args.full or dump):
         other = "dcgan" if args.model == "vgg" else "vgg"
         fam = measure_rollout(ctx, args, other, args.steps, args.warmup, keep_outputs=dump)
         fam_case = fam.pop("_case", None)

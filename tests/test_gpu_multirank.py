@@ -29,7 +29,7 @@ def test_bench_ranks_rehearsal(ranks):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(DVG_DP_SHARE_GPU="1", DVG_DP_BACKEND="gloo", OMP_NUM_THREADS="2")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "3", "--warmup", "1",
-                        "--model", "dcgan", "--no-families", "--no-cpu-baseline", "--train-iters", "1",
+                        "--full", "--model", "dcgan", "--no-families", "--no-cpu-baseline", "--train-iters", "1",
                         "--train-graph-timeout", "120"],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]

@@ -454,3 +454,21 @@ def test_bench_dump_outputs_arguments_and_size_budget(tmp_path, monkeypatch):
     cut = np.load(tmp_path / "cut" / "vgg_frames.npy")
     assert np.array_equal(cut, frames[:, :2].numpy())
     assert sum(os.path.getsize(tmp_path / "cut" / f) for f in os.listdir(tmp_path / "cut")) <= bench.DUMP_BYTES + 2 * 256
+
+
+def test_bench_plain_run_leaves_every_other_leg_to_full():
+    """A plain `bench.py` times the headline steps alone: every leg beside them is off unless --full is given, and under --full
+    the defaults and the --no-* switches are what they were."""
+    if ROOT not in sys.path:
+        sys.path.insert(0, ROOT)
+    import bench
+    legs = ("no_check", "no_cpu_baseline", "no_roofline", "no_train_leg", "no_f32mfma_leg", "no_make_gifs_leg", "no_extra_legs")
+    plain = bench.parse_args(["--steps", "7", "--warmup", "2"])
+    assert not plain.full and plain.sustained_s == 0.0 and all(getattr(plain, k) for k in legs)
+    assert plain.steps == 7 and plain.warmup == 2 and plain.inflight == 3 and plain.model == "vgg" and not plain.no_families
+    full = bench.parse_args(["--full"])
+    assert full.full and full.sustained_s == 5.0 and not any(getattr(full, k) for k in legs)
+    assert bench.parse_args(["--full", "--no-roofline", "--sustained-s", "0"]).no_roofline
+    assert bench.parse_args(["--sustained-s", "0"]).sustained_s == 0.0
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--sustained-s", "20"])       # a figure only --full measures

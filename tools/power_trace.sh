@@ -11,7 +11,7 @@ mkdir -p gpurun_out
     sleep 0.5
   done ) &
 sampler=$!
-timeout -k 10 200 python3 bench.py --model $m --no-families --no-train-leg --no-cpu-baseline --no-f32mfma-leg --no-make-gifs-leg \
+timeout -k 10 200 python3 bench.py --full --model $m --no-families --no-train-leg --no-cpu-baseline --no-f32mfma-leg --no-make-gifs-leg \
     --no-extra-legs --no-roofline --no-check --sustained-s 20 > gpurun_out/power_bench_$m.json 2> gpurun_out/power_bench_$m.err
 kill $sampler 2>/dev/null
 wait $sampler 2>/dev/null

@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT"
 out=gpurun_out/final
 rm -rf $out; mkdir -p $out
 t0=$SECONDS
-timeout 500 python3 bench.py > $out/bench.json 2> $out/bench.err < /dev/null
+timeout 500 python3 bench.py --full > $out/bench.json 2> $out/bench.err < /dev/null
 echo "bench wall $((SECONDS - t0)) s" > $out/bench_wall.txt
 for m in vgg dcgan; do
   timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $out/stats_train_$m -o train -- python3 tools/bench_train.py --model $m --iters 2 > $out/train_${m}_under_rocprof.log 2>&1 < /dev/null
