@@ -63,6 +63,8 @@ SIGNATURES = {
     "dvg_channel_stats_rows": (_i, [_l]),
     "dvg_channel_stats": (_i, [_p, _p, _l, _i, _i, _p]),
     "dvg_bn_finalize": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _d, _f, _f, _p, _i, _i, _p, _p]),
+    "dvg_channel_stats_pivot": (_i, [_p, _p, _p, _l, _i, _i, _p]),
+    "dvg_bn_finalize_pivot": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _d, _f, _f, _p, _i, _i, _p, _p]),
     "dvg_bn_running_update": (_i, [_p, _p, _i, _i, _f, _f, _f, _p, _p, _p, _i, _p]),
     "dvg_bn_act_apply": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
     "dvg_gemm_nt_bias_act": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
@@ -86,6 +88,8 @@ SIGNATURES = {
     "dvg_bn_act_bwd_rows": (_i, [_i, _i, _i, _i]),
     "dvg_bn_act_bwd_reduce": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
     "dvg_bn_bwd_finalize": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _d, _i, _i, _i, _p]),
+    "dvg_bn_act_bwd_reduce_centered": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
+    "dvg_bn_bwd_finalize_centered": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _d, _i, _i, _i, _p]),
     "dvg_affine3_apply": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _p, _i, _i, _p]),
     "dvg_act_bwd": (_i, [_p, _p, _p, _l, _i, _f, _p]),
     "dvg_upsample2x_bwd": (_i, [_p, _p, _i, _i, _i, _i, _p]),

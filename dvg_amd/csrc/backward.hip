@@ -19,7 +19,9 @@ __device__ __forceinline__ float act_grad_from_y(float y, int act, float slope) 
 }
 
 // ---------------------------------------------------------------------------------------
-// dp = (dy + maxpool_scatter(dyp)) * act'(y);   partial[blk] = { sum dp, sum dp*u } per channel
+// dp = (dy + maxpool_scatter(dyp)) * act'(y);   partial[blk] = { sum dp, sum dp*(u - mean) } per channel
+// (mean: the BatchNorm's mean, [G][C], or NULL: sum dp*u - the ABI-9 rows; summing dp*u and subtracting mean * sum dp in
+// the finalize cancels away the digits of sum dp*xhat once |mean| >> std)
 // One thread = one 2x2 window (POOL) or one pixel, 4 channels.  blockDim = 256 = TC x TP with
 // TC = min(C/4, 256) channel quads; rows of TP pixels reduce through LDS (deterministic).
 // ---------------------------------------------------------------------------------------
@@ -27,7 +29,8 @@ template <bool POOL>
 __global__ __launch_bounds__(256) void bn_act_bwd_reduce_kernel(const float* __restrict__ dy,
                                                                 const float* __restrict__ dyp,
                                                                 const float* __restrict__ y,
-                                                                const float* __restrict__ u, float* __restrict__ dp,
+                                                                const float* __restrict__ u,
+                                                                const float* __restrict__ mean, float* __restrict__ dp,
                                                                 float* __restrict__ partial, int N, int H, int W,
                                                                 int C, int act, float slope, int units_per_block,
                                                                 int bpg) {
@@ -44,6 +47,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_reduce_kernel(const float* __r
     const long u0 = g_ * units + lb * units_per_block;
     const long u1 = min((g_ + 1) * units, u0 + units_per_block);
     for (int c4 = tc; c4 < C4; c4 += TC) {  // C4 > 256 only when C > 1024: not on this path, kept for safety
+        const f32x4 mu = mean ? *reinterpret_cast<const f32x4*>(mean + g_ * C + c4 * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
         f32x4 s1 = {0.f, 0.f, 0.f, 0.f}, s2 = {0.f, 0.f, 0.f, 0.f};
         for (long w_ = u0 + tp; w_ < u1; w_ += TP) {
             if (POOL) {
@@ -76,7 +80,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_reduce_kernel(const float* __r
                         const float t = (d[k] + (win ? g[k] : 0.f)) * act_grad_from_y(yv[q][k], act, slope);
                         d[k] = t;
                         s1[k] += t;
-                        s2[k] = fmaf(t, uv[k], s2[k]);
+                        s2[k] = fmaf(t, uv[k] - mu[k], s2[k]);
                     }
                     reinterpret_cast<f32x4*>(dp)[off[q]] = d;
                 }
@@ -90,7 +94,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_reduce_kernel(const float* __r
                     const float t = d[k] * act_grad_from_y(yv[k], act, slope);
                     d[k] = t;
                     s1[k] += t;
-                    s2[k] = fmaf(t, uv[k], s2[k]);
+                    s2[k] = fmaf(t, uv[k] - mu[k], s2[k]);
                 }
                 reinterpret_cast<f32x4*>(dp)[off] = d;
             }
@@ -128,7 +132,8 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __re
                                                                float* __restrict__ coefA, float* __restrict__ coefB,
                                                                float* __restrict__ coefC, float* __restrict__ dgamma,
                                                                float* __restrict__ dbeta, float* __restrict__ dbias,
-                                                               int C, double count, int train, int accumulate) {
+                                                               int C, double count, int train, int accumulate,
+                                                               int centered) {
     __shared__ double red[64 * 16 * 2];
     // blockIdx.y = group (time-batched training): rows [g * nrows, (g + 1) * nrows) and row g of every [G][C] array -
     // dgamma / dbeta / dbias included (the host sums them over the groups: dvg_colsum)
@@ -176,7 +181,7 @@ __global__ __launch_bounds__(1024) void bn_bwd_finalize_kernel(const float* __re
     }
     const double mu = mean[c], is = invstd[c];
     const double g = gamma ? gamma[c] : 1.0;
-    const double G = is * (s2 - mu * s1);  // sum dp * xhat
+    const double G = centered ? is * s2 : is * (s2 - mu * s1);  // sum dp * xhat (centered: the reduce summed dp * (u - mean))
     const double A = g * is;
     // accumulate != 0: the three outputs ARE the parameters' .grad buffers (autograd.py writes gradients in place: no
     // per-use gradient tensor, no accumulation launch)
@@ -238,6 +243,7 @@ __global__ void affine3_scalar_kernel(const float* __restrict__ dp, const float*
 __global__ __launch_bounds__(256) void act_bwd_reduce_scalar_kernel(const float* __restrict__ dy,
                                                                     const float* __restrict__ y,
                                                                     const float* __restrict__ u,
+                                                                    const float* __restrict__ mean,
                                                                     float* __restrict__ dp,
                                                                     float* __restrict__ partial, long rows, int C,
                                                                     int act, float slope, int rows_per_block, int bpg) {
@@ -245,12 +251,13 @@ __global__ __launch_bounds__(256) void act_bwd_reduce_scalar_kernel(const float*
     const long g_ = blockIdx.x / bpg, lb = blockIdx.x % bpg;
     const long r0 = g_ * rows + lb * rows_per_block, r1 = min((g_ + 1) * rows, r0 + rows_per_block);
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        const float mu = mean ? mean[g_ * C + c] : 0.f;
         float s1 = 0.f, s2 = 0.f;
         for (long r = r0; r < r1; ++r) {
             const float t = dy[r * C + c] * act_grad_from_y(y[r * C + c], act, slope);
             dp[r * C + c] = t;
             s1 += t;
-            s2 = fmaf(t, u[r * C + c], s2);
+            s2 = fmaf(t, u[r * C + c] - mu, s2);
         }
         partial[(size_t)blockIdx.x * 2 * C + c] = s1;
         partial[(size_t)blockIdx.x * 2 * C + C + c] = s2;
@@ -648,9 +655,9 @@ extern "C" int dvg_bn_act_bwd_rows(int N, int H, int W, int pool) {
     return (int)((units + upb - 1) / upb);
 }
 
-extern "C" int dvg_bn_act_bwd_reduce(const float* dy, const float* dyp, const float* y, const float* u, float* dp,
-                                     float* partial, int N, int H, int W, int C, int act, float slope, int groups,
-                                     void* stream) {
+// mean == NULL: the ABI-9 rows { sum dp, sum dp*u } (dvg_bn_act_bwd_reduce); else { sum dp, sum dp*(u - mean) }
+static int bwd_reduce(const float* dy, const float* dyp, const float* y, const float* u, const float* mean, float* dp,
+                      float* partial, int N, int H, int W, int C, int act, float slope, int groups, hipStream_t stream) {
     DVG_REQUIRE(y && u && dp && partial, DVG_ERR_NULL, "dvg_bn_act_bwd_reduce: NULL pointer");
     DVG_REQUIRE(dy || dyp, DVG_ERR_NULL, "dvg_bn_act_bwd_reduce: no incoming gradient");
     DVG_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && groups > 0 && N % groups == 0, DVG_ERR_SHAPE,
@@ -664,38 +671,67 @@ extern "C" int dvg_bn_act_bwd_reduce(const float* dy, const float* dyp, const fl
         const int rpb = bwd_units_per_block(rows);
         const int bpg = (int)((rows + rpb - 1) / rpb);
         hipLaunchKernelGGL(act_bwd_reduce_scalar_kernel, dim3((unsigned)bpg * groups), dim3(C >= 256 ? 256 : 64), 0,
-                           (hipStream_t)stream, dy, y, u, dp, partial, rows, C, act, slope, rpb, bpg);
+                           stream, dy, y, u, mean, dp, partial, rows, C, act, slope, rpb, bpg);
         return check_launch("dvg_bn_act_bwd_reduce");
     }
     DVG_REQUIRE(C <= 1024 && (256 % (C / 4 < 256 ? C / 4 : 256)) == 0, DVG_ERR_SHAPE,
                 "dvg_bn_act_bwd_reduce: C/4 must divide 256 (C=%d)", C);
-    DVG_REQUIRE(aligned16(dy) && aligned16(dyp) && aligned16(y) && aligned16(u) && aligned16(dp), DVG_ERR_ALIGN,
-                "dvg_bn_act_bwd_reduce: alignment");
+    DVG_REQUIRE(aligned16(dy) && aligned16(dyp) && aligned16(y) && aligned16(u) && aligned16(mean) && aligned16(dp),
+                DVG_ERR_ALIGN, "dvg_bn_act_bwd_reduce: alignment");
     if (pool) DVG_REQUIRE(H % 2 == 0 && W % 2 == 0, DVG_ERR_SHAPE, "dvg_bn_act_bwd_reduce: odd H/W with pool");
     const long units = pool ? (long)N * (H / 2) * (W / 2) : (long)N * H * W;
     const int upb = bwd_units_per_block(units);
     const int bpg = (int)((units + upb - 1) / upb);
     const unsigned grid = (unsigned)bpg * groups;
     if (pool)
-        hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<true>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, dyp, y,
-                           u, dp, partial, N, H, W, C, act, slope, upb, bpg);
+        hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<true>), dim3(grid), dim3(256), 0, stream, dy, dyp, y,
+                           u, mean, dp, partial, N, H, W, C, act, slope, upb, bpg);
     else
-        hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<false>), dim3(grid), dim3(256), 0, (hipStream_t)stream, dy, dyp,
-                           y, u, dp, partial, N, H, W, C, act, slope, upb, bpg);
+        hipLaunchKernelGGL((bn_act_bwd_reduce_kernel<false>), dim3(grid), dim3(256), 0, stream, dy, dyp,
+                           y, u, mean, dp, partial, N, H, W, C, act, slope, upb, bpg);
     return check_launch("dvg_bn_act_bwd_reduce");
+}
+
+extern "C" int dvg_bn_act_bwd_reduce(const float* dy, const float* dyp, const float* y, const float* u, float* dp,
+                                     float* partial, int N, int H, int W, int C, int act, float slope, int groups,
+                                     void* stream) {
+    return bwd_reduce(dy, dyp, y, u, nullptr, dp, partial, N, H, W, C, act, slope, groups, (hipStream_t)stream);
+}
+
+extern "C" int dvg_bn_act_bwd_reduce_centered(const float* dy, const float* dyp, const float* y, const float* u,
+                                              const float* mean, float* dp, float* partial, int N, int H, int W, int C,
+                                              int act, float slope, int groups, void* stream) {
+    DVG_REQUIRE(mean, DVG_ERR_NULL, "dvg_bn_act_bwd_reduce_centered: NULL mean");
+    return bwd_reduce(dy, dyp, y, u, mean, dp, partial, N, H, W, C, act, slope, groups, (hipStream_t)stream);
+}
+
+static int bwd_finalize(const float* partial, int nrows, const float* gamma, const float* mean, const float* invstd,
+                        float* coefA, float* coefB, float* coefC, float* dgamma, float* dbeta, float* dbias, int C,
+                        double count, int train, int accumulate, int groups, int centered, hipStream_t stream) {
+    DVG_REQUIRE(partial && mean && invstd && coefA && coefB && coefC, DVG_ERR_NULL, "dvg_bn_bwd_finalize: NULL");
+    DVG_REQUIRE(C > 0 && nrows > 0 && count >= 1.0 && groups > 0 && groups < 65536, DVG_ERR_SHAPE, "dvg_bn_bwd_finalize: bad shape");
+    DVG_REQUIRE(groups == 1 || !accumulate, DVG_ERR_SHAPE,
+                "dvg_bn_bwd_finalize: with several groups dgamma / dbeta / dbias are [G][C] scratch rows (no accumulation)");
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 15) / 16, groups), dim3(1024), 0, stream, partial, nrows,
+                       gamma, mean, invstd, coefA, coefB, coefC, dgamma, dbeta, dbias, C, count, train, accumulate, centered);
+    return check_launch("dvg_bn_bwd_finalize");
 }
 
 extern "C" int dvg_bn_bwd_finalize(const float* partial, int nrows, const float* gamma, const float* mean,
                                    const float* invstd, float* coefA, float* coefB, float* coefC, float* dgamma,
                                    float* dbeta, float* dbias, int C, double count, int train, int accumulate,
                                    int groups, void* stream) {
-    DVG_REQUIRE(partial && mean && invstd && coefA && coefB && coefC, DVG_ERR_NULL, "dvg_bn_bwd_finalize: NULL");
-    DVG_REQUIRE(C > 0 && nrows > 0 && count >= 1.0 && groups > 0 && groups < 65536, DVG_ERR_SHAPE, "dvg_bn_bwd_finalize: bad shape");
-    DVG_REQUIRE(groups == 1 || !accumulate, DVG_ERR_SHAPE,
-                "dvg_bn_bwd_finalize: with several groups dgamma / dbeta / dbias are [G][C] scratch rows (no accumulation)");
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 15) / 16, groups), dim3(1024), 0, (hipStream_t)stream, partial, nrows,
-                       gamma, mean, invstd, coefA, coefB, coefC, dgamma, dbeta, dbias, C, count, train, accumulate);
-    return check_launch("dvg_bn_bwd_finalize");
+    return bwd_finalize(partial, nrows, gamma, mean, invstd, coefA, coefB, coefC, dgamma, dbeta, dbias, C, count, train,
+                        accumulate, groups, 0, (hipStream_t)stream);
+}
+
+// rows of dvg_bn_act_bwd_reduce_centered: sum dp*(u - mean) is used as it is (no s2 - mean * s1)
+extern "C" int dvg_bn_bwd_finalize_centered(const float* partial, int nrows, const float* gamma, const float* mean,
+                                            const float* invstd, float* coefA, float* coefB, float* coefC, float* dgamma,
+                                            float* dbeta, float* dbias, int C, double count, int train, int accumulate,
+                                            int groups, void* stream) {
+    return bwd_finalize(partial, nrows, gamma, mean, invstd, coefA, coefB, coefC, dgamma, dbeta, dbias, C, count, train,
+                        accumulate, groups, 1, (hipStream_t)stream);
 }
 
 extern "C" int dvg_affine3_apply(const float* dp, const float* u, const float* A, const float* B, const float* Cc,

@@ -72,15 +72,18 @@ __global__ void layout_kernel(const float* __restrict__ x, float* __restrict__ y
 // grid.x slabs of rows, each writes one partial row [2][C] (deterministic).
 // Groups (time-batched training): the rows are `groups` consecutive runs of `rows` rows, every run gets its own `bpg`
 // slabs (no slab straddles two groups) and the partial rows come out group-major.
-__global__ void channel_stats_kernel(const float* __restrict__ u, float* __restrict__ partial, long rows, int C,
-                                     int rows_per_block, int bpg) {
+// pivot (optional, [C]): the sums are of v - K and (v - K)^2, K = pivot[c] (NULL: K = 0).  fp32 slab sums of raw v and v^2
+// lose the digits E[v^2] - mean^2 needs once |mean| >> std; around a K near the mean they keep them (bn_finalize_kernel).
+__global__ void channel_stats_kernel(const float* __restrict__ u, float* __restrict__ partial,
+                                     const float* __restrict__ pivot, long rows, int C, int rows_per_block, int bpg) {
     const long g = blockIdx.x / bpg, lb = blockIdx.x % bpg;
     const long r0 = g * rows + lb * rows_per_block;
     const long r1 = min((g + 1) * rows, r0 + rows_per_block);
     for (int c = threadIdx.x; c < C; c += blockDim.x) {
+        const float k = pivot ? pivot[c] : 0.f;
         float s1 = 0.f, s2 = 0.f;
         for (long r = r0; r < r1; ++r) {
-            const float v = u[r * C + c];
+            const float v = u[r * C + c] - k;
             s1 += v;
             s2 += v * v;
         }
@@ -133,10 +136,12 @@ __device__ __forceinline__ void partial_colsums(const float* __restrict__ partia
     }
 }
 
+// pivot: the K the partial rows were summed around (NULL: 0).  A caller may pass the layer's running_mean as K, so pivot and
+// running_mean may be ONE buffer (no __restrict__ on either): every thread reads K of its channel before it updates it.
 __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restrict__ partial, int nrows,
-                                                           const float* __restrict__ gamma,
+                                                           const float* pivot, const float* __restrict__ gamma,
                                                            const float* __restrict__ beta, float* __restrict__ scale,
-                                                           float* __restrict__ shift, float* __restrict__ running_mean,
+                                                           float* __restrict__ shift, float* running_mean,
                                                            float* __restrict__ running_var,
                                                            float* __restrict__ save_mean,
                                                            float* __restrict__ save_invstd, int C, double count,
@@ -160,8 +165,9 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
     double s1, s2;
     partial_colsums(partial, nrows, C, c, rl, red, s1, s2);
     if (rl != 0 || c >= C) return;
-    const double mean = s1 / count;
-    double var = s2 / count - mean * mean;
+    const double d = s1 / count;                          // mean - K
+    const double mean = (pivot ? (double)pivot[c] : 0.0) + d;
+    double var = s2 / count - d * d;
     if (var < 0.0) var = 0.0;
     const float invstd = (float)(1.0 / sqrt(var + (double)eps));
     const float g = gamma ? gamma[c] : 1.f, b = beta ? beta[c] : 0.f;
@@ -577,7 +583,7 @@ __global__ __launch_bounds__(1024) void mse_sum_grad_kernel(const float* __restr
 
 using namespace dvg;
 
-extern "C" int dvg_abi_version(void) { return 9; }  // 9: + dvg_build_info, sync-BN partial rows (r06); 8: y_from (skip tensors of part of a batch), r05 entry points; 3: first igemm schedule retired; 4: + dvg_winograd_wgrad_*; 5: + dvg_gp_elbo(_bwd); 6: GP kernels fp64-internal, + dvg_gp_(bwd_)precision; 7: blocked packed weights, dvg_mfma_mode / dvg_packed_row_floats
+extern "C" int dvg_abi_version(void) { return 9; }  // 9: + dvg_build_info, sync-BN partial rows (r06), + (additive: no ABI-9 entry point changed) dvg_channel_stats_pivot, dvg_bn_finalize_pivot, dvg_bn_act_bwd_reduce_centered, dvg_bn_bwd_finalize_centered; 8: y_from (skip tensors of part of a batch), r05 entry points; 3: first igemm schedule retired; 4: + dvg_winograd_wgrad_*; 5: + dvg_gp_elbo(_bwd); 6: GP kernels fp64-internal, + dvg_gp_(bwd_)precision; 7: blocked packed weights, dvg_mfma_mode / dvg_packed_row_floats
 extern "C" const char* dvg_last_error(void) { return err_buf(); }
 
 extern "C" long dvg_stream_capture_id(void* stream) {
@@ -628,29 +634,43 @@ extern "C" int dvg_channel_stats_rows(long rows) {
     return (int)((rows + rpb - 1) / rpb);
 }
 
-extern "C" int dvg_channel_stats(const float* u, float* stats_partial, long rows, int C, int groups, void* stream) {
+extern "C" int dvg_channel_stats_pivot(const float* u, float* stats_partial, const float* pivot, long rows, int C,
+                                       int groups, void* stream) {
     DVG_REQUIRE(u && stats_partial, DVG_ERR_NULL, "dvg_channel_stats: NULL pointer");
     DVG_REQUIRE(rows > 0 && C > 0 && groups > 0, DVG_ERR_SHAPE, "dvg_channel_stats: bad shape");
     long rpb = (rows + 1023) / 1024;
     if (rpb < 16) rpb = 16;
     const int nblk = (int)((rows + rpb - 1) / rpb);
     hipLaunchKernelGGL(channel_stats_kernel, dim3((unsigned)nblk * groups), dim3(C >= 256 ? 256 : (C > 64 ? 128 : 64)), 0,
-                       (hipStream_t)stream, u, stats_partial, rows, C, (int)rpb, nblk);
+                       (hipStream_t)stream, u, stats_partial, pivot, rows, C, (int)rpb, nblk);
     return check_launch("dvg_channel_stats");
+}
+
+extern "C" int dvg_channel_stats(const float* u, float* stats_partial, long rows, int C, int groups, void* stream) {
+    return dvg_channel_stats_pivot(u, stats_partial, nullptr, rows, C, groups, stream);
+}
+
+extern "C" int dvg_bn_finalize_pivot(const float* stats_partial, int nrows, const float* pivot, const float* gamma,
+                                     const float* beta, float* scale, float* shift, float* running_mean, float* running_var,
+                                     float* save_mean, float* save_invstd, int C, double count, float eps, float momentum,
+                                     int64_t* num_batches_tracked, int nbt_inc, int groups, float* group_var, void* stream) {
+    DVG_REQUIRE(stats_partial && scale && shift, DVG_ERR_NULL, "dvg_bn_finalize: NULL pointer");
+    DVG_REQUIRE(C > 0 && nrows > 0 && count >= 1.0 && groups > 0 && groups < 65536, DVG_ERR_SHAPE, "dvg_bn_finalize: bad shape");
+    DVG_REQUIRE(groups == 1 || (running_mean == nullptr && running_var == nullptr && num_batches_tracked == nullptr),
+                DVG_ERR_SHAPE, "dvg_bn_finalize: with several groups the running statistics are dvg_bn_running_update's job");
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + DVG_COLSUM_CT - 1) / DVG_COLSUM_CT, groups), dim3(1024), 0,
+                       (hipStream_t)stream, stats_partial, nrows, pivot, gamma, beta, scale, shift, running_mean, running_var,
+                       save_mean, save_invstd, C, count, eps, momentum, (long long*)num_batches_tracked, nbt_inc, group_var);
+    return check_launch("dvg_bn_finalize");
 }
 
 extern "C" int dvg_bn_finalize(const float* stats_partial, int nrows, const float* gamma, const float* beta,
                                float* scale, float* shift, float* running_mean, float* running_var,
                                float* save_mean, float* save_invstd, int C, double count, float eps, float momentum,
                                int64_t* num_batches_tracked, int nbt_inc, int groups, float* group_var, void* stream) {
-    DVG_REQUIRE(stats_partial && scale && shift, DVG_ERR_NULL, "dvg_bn_finalize: NULL pointer");
-    DVG_REQUIRE(C > 0 && nrows > 0 && count >= 1.0 && groups > 0 && groups < 65536, DVG_ERR_SHAPE, "dvg_bn_finalize: bad shape");
-    DVG_REQUIRE(groups == 1 || (running_mean == nullptr && running_var == nullptr && num_batches_tracked == nullptr),
-                DVG_ERR_SHAPE, "dvg_bn_finalize: with several groups the running statistics are dvg_bn_running_update's job");
-    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + DVG_COLSUM_CT - 1) / DVG_COLSUM_CT, groups), dim3(1024), 0,
-                       (hipStream_t)stream, stats_partial, nrows, gamma, beta, scale, shift, running_mean, running_var,
-                       save_mean, save_invstd, C, count, eps, momentum, (long long*)num_batches_tracked, nbt_inc, group_var);
-    return check_launch("dvg_bn_finalize");
+    return dvg_bn_finalize_pivot(stats_partial, nrows, nullptr, gamma, beta, scale, shift, running_mean, running_var,
+                                 save_mean, save_invstd, C, count, eps, momentum, num_batches_tracked, nbt_inc, groups,
+                                 group_var, stream);
 }
 
 extern "C" int dvg_bn_running_update(const float* mean, const float* unbiased_var, int groups, int C, float mom_first,

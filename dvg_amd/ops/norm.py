@@ -12,17 +12,20 @@ from .dense import colsum
 # ----------------------------------------------------------------------------------
 # BatchNorm (train mode) helpers
 # ----------------------------------------------------------------------------------
-def channel_stats(u2d: torch.Tensor, groups: int = 1) -> torch.Tensor:
+def channel_stats(u2d: torch.Tensor, groups: int = 1, *, pivot=None) -> torch.Tensor:
     """u2d: [rows][C] contiguous -> partial stats [r][2][C]; groups: the rows are `groups` equal consecutive runs, each with
-    its own partial rows (group-major: [groups * r][2][C])."""
+    its own partial rows (group-major: [groups * r][2][C]).  pivot (optional [C] device tensor near the channels' means): the
+    rows are sums of u - pivot and (u - pivot)^2 (recorded as .pivot; bn_finalize must get the same one)."""
     _dev_f32(u2d, "channel_stats")
     rows, c = u2d.shape
     if rows % groups:
         raise RuntimeError(f"channel_stats: {rows} rows do not split into {groups} groups")
     r = lib().dvg_channel_stats_rows(rows // groups)
     st = torch.empty((groups * r, 2, c), device=u2d.device, dtype=torch.float32)
-    check(lib().dvg_channel_stats(_p(u2d), _p(st), rows // groups, c, groups, _stream()), "channel_stats")
+    check(lib().dvg_channel_stats_pivot(_p(u2d), _p(st), _p(pivot), rows // groups, c, groups, _stream()),
+          "channel_stats")
     st.grouped = groups       # rows are per-group runs already (fused.group_stats)
+    st.pivot = pivot
     return st
 
 
@@ -63,12 +66,14 @@ def sync_partial_rows(partial: torch.Tensor, groups: int = 1) -> torch.Tensor:
     lo = (tot - hi.to(torch.float64)).to(torch.float32)
     out = torch.stack([hi, lo], 1).reshape(groups * 2, two, c)
     out.grouped = groups
+    out.pivot = getattr(partial, "pivot", None)     # (summed across ranks: a pivot must then be the same on every rank)
     return out
 
 
 def bn_finalize(stats_partial, gamma, beta, running_mean, running_var, count, eps, momentum, save=False,
-                num_batches_tracked=None, passes=0, groups=1, group_momenta=None):
+                num_batches_tracked=None, passes=0, groups=1, group_momenta=None, pivot=None):
     """`num_batches_tracked` (int64 device scalar of nn.BatchNorm2d) is advanced by `passes` inside the same launch.
+    `pivot`: the [C] tensor the partial rows were summed around (the writers' `pivot`; it may be running_mean itself).
     groups > 1 (time-batched training): stats_partial holds `groups` equal runs of partial rows, `count` is PER GROUP, the
     results are [groups][C] and the running statistics advance group after group (dvg_bn_running_update) with
     group_momenta = (first, middle, last); `passes` = the total over all groups."""
@@ -79,17 +84,19 @@ def bn_finalize(stats_partial, gamma, beta, running_mean, running_var, count, ep
         shift = torch.empty(c, device=dev, dtype=torch.float32)
         sm = torch.empty(c, device=dev, dtype=torch.float32) if save else None
         si = torch.empty(c, device=dev, dtype=torch.float32) if save else None
-        check(lib().dvg_bn_finalize(_p(stats_partial), rows, _p(gamma), _p(beta), _p(scale), _p(shift), _p(running_mean),
-                                    _p(running_var), _p(sm), _p(si), c, float(count), eps, momentum,
-                                    _p(num_batches_tracked), int(passes), 1, None, _stream()),
+        check(lib().dvg_bn_finalize_pivot(_p(stats_partial), rows, _p(pivot), _p(gamma), _p(beta), _p(scale), _p(shift),
+                                          _p(running_mean), _p(running_var), _p(sm), _p(si), c, float(count), eps, momentum,
+                                          _p(num_batches_tracked), int(passes), 1, None, _stream()),
               "bn_finalize")
         return (scale, shift, sm, si) if save else (scale, shift)
     if rows % groups:
         raise RuntimeError(f"bn_finalize: {rows} partial rows do not split into {groups} groups")
     buf = torch.empty((5, groups, c), device=dev, dtype=torch.float32)
     scale, shift, sm, si, gv = buf[0], buf[1], buf[2], buf[3], buf[4]
-    check(lib().dvg_bn_finalize(_p(stats_partial), rows // groups, _p(gamma), _p(beta), _p(scale), _p(shift), None, None,
-                                _p(sm), _p(si), c, float(count), eps, 0.0, None, 0, groups, _p(gv), _stream()), "bn_finalize")
+    check(lib().dvg_bn_finalize_pivot(_p(stats_partial), rows // groups, _p(pivot), _p(gamma), _p(beta), _p(scale),
+                                      _p(shift), None, None, _p(sm), _p(si), c, float(count), eps, 0.0, None, 0, groups,
+                                      _p(gv), _stream()),
+          "bn_finalize")
     if running_mean is not None:
         m0, m1, m2 = group_momenta
         check(lib().dvg_bn_running_update(_p(sm), _p(gv), groups, c, m0, m1, m2, _p(running_mean), _p(running_var),
@@ -127,25 +134,25 @@ def bn_act_bwd(dy, dyp, y, u, gamma, mean, invstd, count, *, act, slope, train=T
     dev = y.device
     partial = torch.empty((groups * rows, 2, c), device=dev, dtype=torch.float32)
     dp = torch.empty_like(u)
-    _run("bn_act_bwd_reduce", 0.0, 4.0 * 4 * y.numel(), lib().dvg_bn_act_bwd_reduce, _p(dy), _p(dyp), _p(y), _p(u),
-         _p(dp), _p(partial), n, h, w, c, act, slope, groups, _stream())
+    mean = mean.contiguous()
+    _run("bn_act_bwd_reduce", 0.0, 4.0 * 4 * y.numel(), lib().dvg_bn_act_bwd_reduce_centered, _p(dy), _p(dyp), _p(y),
+         _p(u), _p(mean), _p(dp), _p(partial), n, h, w, c, act, slope, groups, _stream())
     coef = torch.empty((3, groups, c), device=dev, dtype=torch.float32)
+    finalize = lib().dvg_bn_bwd_finalize_centered      # the rows hold sum dp * (u - mean): no s2 - mean * s1 cancellation
     if train and SYNC_BN is not None:
         # sync-BN (mean / invstd are statistics of the GLOBAL batch): the coefficients of du need the two per-channel sums over
         # all ranks and the global count; dgamma / dbeta / dbias stay LOCAL sums below - the gradient all-reduce averages them
         # over the ranks like every other parameter gradient (each rank's dy carries its own 1 / local-batch factor).
         glob = sync_partial_rows(partial, groups)
-        check(lib().dvg_bn_bwd_finalize(_p(glob), 2, _p(gamma), _p(mean), _p(invstd), _p(coef[0]), _p(coef[1]), _p(coef[2]),
-                                        None, None, None, c, float(count) * SYNC_BN[2], 1, 0, groups, _stream()),
-              "bn_bwd_finalize")
+        check(finalize(_p(glob), 2, _p(gamma), _p(mean), _p(invstd), _p(coef[0]), _p(coef[1]), _p(coef[2]), None, None, None,
+                       c, float(count) * SYNC_BN[2], 1, 0, groups, _stream()), "bn_bwd_finalize")
         coef_keep, coef = coef, torch.empty((3, groups, c), device=dev, dtype=torch.float32)   # the local pass's: discarded
     else:
         coef_keep = None
     if groups > 1:
         pg = torch.empty((3, groups, c), device=dev, dtype=torch.float32)       # per-group dgamma, dbeta, dbias
-        check(lib().dvg_bn_bwd_finalize(_p(partial), rows, _p(gamma), _p(mean), _p(invstd), _p(coef[0]), _p(coef[1]),
-                                        _p(coef[2]), _p(pg[0]), _p(pg[1]), _p(pg[2]), c, float(count), int(train), 0,
-                                        groups, _stream()), "bn_bwd_finalize")
+        check(finalize(_p(partial), rows, _p(gamma), _p(mean), _p(invstd), _p(coef[0]), _p(coef[1]), _p(coef[2]), _p(pg[0]),
+                       _p(pg[1]), _p(pg[2]), c, float(count), int(train), 0, groups, _stream()), "bn_bwd_finalize")
         if sinks is None:
             dgamma, dbeta, dbias = colsum(pg[0]), colsum(pg[1]), colsum(pg[2])
         else:
@@ -163,9 +170,8 @@ def bn_act_bwd(dy, dyp, y, u, gamma, mean, invstd, count, *, act, slope, train=T
         else:
             dgamma = dbeta = dbias = None
             outs, acc = sinks, 1
-        check(lib().dvg_bn_bwd_finalize(_p(partial), rows, _p(gamma), _p(mean), _p(invstd), _p(coef[0]), _p(coef[1]),
-                                        _p(coef[2]), _p(outs[0]), _p(outs[1]), _p(outs[2]), c, float(count), int(train),
-                                        acc, 1, _stream()), "bn_bwd_finalize")
+        check(finalize(_p(partial), rows, _p(gamma), _p(mean), _p(invstd), _p(coef[0]), _p(coef[1]), _p(coef[2]), _p(outs[0]),
+                       _p(outs[1]), _p(outs[2]), c, float(count), int(train), acc, 1, _stream()), "bn_bwd_finalize")
     if coef_keep is not None:
         coef = coef_keep
     sum_t, sum_mode = (None, 0) if du_sum is None else du_sum

@@ -302,6 +302,11 @@ int dvg_convT_gather(const float* d1, const float* d2, const float* bias, float*
  * Used for the small BN inputs (encoder head, decoder stem) and the Winograd-form training layers.        */
 int dvg_channel_stats_rows(long rows);
 int dvg_channel_stats(const float* u, float* stats_partial, long rows, int C, int groups, void* stream);
+/* The same around a per-channel pivot (pivot NULL or [C]): the rows hold the sums of u - K and (u - K)^2, K = pivot[c].
+ * A K near the channel's mean keeps the digits fp32 sums of raw u and u^2 lose when |mean| >> std; finalise such rows with
+ * dvg_bn_finalize_pivot and the same K.  (Added within ABI 9: no existing entry point changed.)                        */
+int dvg_channel_stats_pivot(const float* u, float* stats_partial, const float* pivot, long rows, int C, int groups,
+                            void* stream);
 
 /* Train-mode BatchNorm2d finalisation (vgg_64.py:9; torch semantics: biased
  * variance for normalisation, unbiased for the running estimate, eps 1e-5):
@@ -319,6 +324,13 @@ int dvg_bn_finalize(const float* stats_partial, int nrows, const float* gamma,
                     int C, double count, float eps, float momentum,
                     int64_t* num_batches_tracked /* may be NULL; += nbt_inc */, int nbt_inc, int groups,
                     float* group_var, void* stream);
+/* dvg_bn_finalize of rows summed around a pivot K (dvg_channel_stats_pivot; NULL = 0 = dvg_bn_finalize), one [C] for all
+ * groups: mean = K + S1 / count, var_b = S2 / count - (S1 / count)^2.  K may be running_mean itself (read before the
+ * update).                                                                                                           */
+int dvg_bn_finalize_pivot(const float* stats_partial, int nrows, const float* pivot, const float* gamma,
+                          const float* beta, float* scale, float* shift, float* running_mean, float* running_var,
+                          float* save_mean, float* save_invstd, int C, double count, float eps, float momentum,
+                          int64_t* num_batches_tracked, int nbt_inc, int groups, float* group_var, void* stream);
 /* running <- (1 - m_g) running + m_g stat_g for g = 0 .. groups-1 in order, the update nn.BatchNorm2d applies per call
  * (vgg_64.py:9), from dvg_bn_finalize's save_mean and group_var; m_0 = mom_first, m_{G-1} = mom_last, mom_mid otherwise
  * (the first / last frame of a sequence is encoded once per closure, the others twice: train.py:158-162,184-188,217-221);
@@ -462,6 +474,12 @@ int dvg_bn_act_bwd_rows(int N, int H, int W, int pool);
 int dvg_bn_act_bwd_reduce(const float* dy, const float* dyp, const float* y, const float* u,
                           float* dp, float* partial, int N, int H, int W, int C, int act,
                           float slope, int groups, void* stream);
+/* The same with partial[r] = { sum dp, sum dp*(u - mean) }: mean = the BatchNorm's mean ([G][C], 16-byte aligned when
+ * C % 4 == 0).  Finalise with dvg_bn_bwd_finalize_centered, which uses that sum as it is: s2 - mean * s1 over raw rows
+ * cancels away the digits of sum dp*xhat once |mean| >> std.  (Added within ABI 9.)                                   */
+int dvg_bn_act_bwd_reduce_centered(const float* dy, const float* dyp, const float* y, const float* u, const float* mean,
+                                   float* dp, float* partial, int N, int H, int W, int C, int act, float slope,
+                                   int groups, void* stream);
 /* pass 2: per-channel coefficients of du = A*dp + B*u + Cc (train: batch-statistics
  * BN backward; eval: plain affine), plus dgamma, dbeta, dbias (any may be NULL).
  * groups > 1: nrows / count per group; mean, invstd, coef*, dgamma, dbeta, dbias are [G][C] (the parameter gradients per
@@ -470,6 +488,10 @@ int dvg_bn_bwd_finalize(const float* partial, int nrows, const float* gamma, con
                         const float* invstd, float* coefA, float* coefB, float* coefC,
                         float* dgamma, float* dbeta, float* dbias, int C, double count,
                         int train, int accumulate /* dgamma / dbeta / dbias += */, int groups, void* stream);
+int dvg_bn_bwd_finalize_centered(const float* partial, int nrows, const float* gamma, const float* mean,
+                                 const float* invstd, float* coefA, float* coefB, float* coefC,
+                                 float* dgamma, float* dbeta, float* dbias, int C, double count,
+                                 int train, int accumulate, int groups, void* stream);
 /* pass 3: du = A[c]*dp + B[c]*u + Cc[c] over n elements (n %% C == 0); du may alias dp.  `sum` (optional second output,
  * same shape, not aliasing du): sum_mode 1: sum = du, 2: sum += du, 0: unused - d(addend) of the decoder calls of one
  * time step that share a skip half (train.py:227-231) is collected there instead of by separate additions.           */
