@@ -20,11 +20,11 @@ autograd.DIRECT_PARAM_GRADS = False returns the gradients to autograd instead (s
 from __future__ import annotations
 
 import os
-import weakref
 
 import torch
 
 from . import fused, ops
+from ._derived import derived
 from .ops import ACT_NONE, MODE_CONV3, MODE_CONV4S2, MODE_CONVT4S2
 
 DIRECT_PARAM_GRADS = True      # the backward kernels add parameter gradients straight into `.grad` (tests toggle it)
@@ -175,59 +175,38 @@ def _sink(p, needed=True):
     return g
 
 
-# Packed-weight cache for the training path: a parameter is re-packed once per optimizer step (its `_version`
-# changes), not once per forward/backward call — train_model alone calls the encoder 2*S and the decoder 3*S times
-# between two optimizer steps (train.py:213-232).
-_pack_cache = {}
-
-
+# Derived weights of the training path: a parameter is re-packed once per optimizer step (its `_version` changes),
+# not once per forward/backward call — train_model alone calls the encoder 2*S and the decoder 3*S times between two
+# optimizer steps (train.py:213-232).
 def _packed(weight, transposed=False, lo=None, hi=None, dim=0):
-    key = (id(weight), transposed, lo, hi, dim)
-    hit = _pack_cache.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == (weight._version, weight.data_ptr()):
-        return hit[2]
-    w = weight.detach()
-    if lo is not None:
-        w = _c(w[lo:hi] if dim == 0 else w[:, lo:hi])
-    wp = ops.pack_igemm_weight(w, transposed)
-    if len(_pack_cache) > 4096:
-        _pack_cache.clear()
-    _pack_cache[key] = (weakref.ref(weight), (weight._version, weight.data_ptr()), wp)
-    return wp
+    def build():
+        w = weight.detach()
+        if lo is not None:
+            w = _c(w[lo:hi] if dim == 0 else w[:, lo:hi])
+        return ops.pack_igemm_weight(w, transposed)
+
+    return derived(weight, ("wp", transposed, lo, hi, dim), (weight,), build)
 
 
 def _transposed(weight):
     """Contiguous transpose of a 2-D parameter, cached per parameter version: the data gradients of Linear / LSTMCell are
     NT GEMMs against W^T, and BPTT asked for the same transpose once per time step."""
-    key = (id(weight), "T")
-    hit = _pack_cache.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == (weight._version, weight.data_ptr()):
-        return hit[2]
-    wt = ops.transpose2d(weight.detach())
-    if len(_pack_cache) > 4096:
-        _pack_cache.clear()
-    _pack_cache[key] = (weakref.ref(weight), (weight._version, weight.data_ptr()), wt)
-    return wt
+    return derived(weight, "T", (weight,), lambda: ops.transpose2d(weight.detach()))
 
 
 def _wino(weight, m, lo=None, hi=None, dgrad=False):
     """Winograd-domain weights U (ops.winograd_weight) of a Conv2d weight for F(m x m, 3x3), cached per parameter version:
     forward form, or - dgrad - of the flipped / transposed kernel (optionally of the input-channel slice [lo, hi)) whose
     3x3 correlation with d(out) is the data gradient."""
-    key = (id(weight), "wino", m, lo, hi, dgrad)
-    hit = _pack_cache.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == (weight._version, weight.data_ptr()):
-        return hit[2]
-    w = weight.detach()
-    if lo is not None:
-        w = w[:, lo:hi]
-    if dgrad:
-        w = w.transpose(0, 1).flip(2, 3)
-    u = ops.winograd_weight(w.contiguous(), m)
-    if len(_pack_cache) > 4096:
-        _pack_cache.clear()
-    _pack_cache[key] = (weakref.ref(weight), (weight._version, weight.data_ptr()), u)
-    return u
+    def build():
+        w = weight.detach()
+        if lo is not None:
+            w = w[:, lo:hi]
+        if dgrad:
+            w = w.transpose(0, 1).flip(2, 3)
+        return ops.winograd_weight(w.contiguous(), m)
+
+    return derived(weight, ("wino", m, lo, hi, dgrad), (weight,), build)
 
 
 # Keep the forward's Winograd input transform V (2.25 x the layer input) for the weight gradient instead of recomputing it in
@@ -280,22 +259,14 @@ def _bn_forward(bn, u, stats, count, act, slope, pool):
 
 
 def _upconv_weights(weight, c1):
-    """K4 = W[:, :c1] (*) ones(2x2) as a ConvTranspose2d weight (C1, Cout, 4, 4) (see fused._upconv_packed: nearest-x2
-    upsampling + 3x3 conv == 4x4 stride-2 transposed conv), packed for the forward (transposed mode) and for the data
-    gradient (the adjoint: a plain 4x4 stride-2 conv with the same weight).  Cached per parameter version."""
-    key = (id(weight), "k4", c1)
-    hit = _pack_cache.get(key)
-    if hit is not None and hit[0]() is weight and hit[1] == (weight._version, weight.data_ptr()):
-        return hit[2]
-    w = weight.detach()[:, :c1]
-    k4 = torch.zeros((w.shape[0], c1, 4, 4), device=w.device, dtype=torch.float32)
-    for ty in range(3):
-        for tx in range(3):
-            k4[:, :, 2 - ty:4 - ty, 2 - tx:4 - tx] += w[:, :, ty:ty + 1, tx:tx + 1]
-    k4 = k4.permute(1, 0, 2, 3).contiguous()                       # (C1, Cout, 4, 4)
-    res = (ops.pack_igemm_weight(k4, transposed=True), ops.pack_igemm_weight(k4, transposed=False))
-    _pack_cache[key] = (weakref.ref(weight), (weight._version, weight.data_ptr()), res)
-    return res
+    """K4 = W[:, :c1] (*) ones(2x2) as a ConvTranspose2d weight (C1, Cout, 4, 4) (fused.k4_weight: nearest-x2 upsampling +
+    3x3 conv == 4x4 stride-2 transposed conv), packed for the forward (transposed mode) and for the data gradient (the
+    adjoint: a plain 4x4 stride-2 conv with the same weight).  Cached per parameter version."""
+    def build():
+        k4 = fused.k4_weight(weight, c1)
+        return ops.pack_igemm_weight(k4, transposed=True), ops.pack_igemm_weight(k4, transposed=False)
+
+    return derived(weight, ("k4", c1), (weight,), build)
 
 
 class _ConvBlock(torch.autograd.Function):
@@ -725,5 +696,5 @@ def gp_train_autograd(layer, h, noise):
 # nn.Linear / nn.LSTMCell / the LSTM sequence: dvg_amd/autograd_recurrent.py (r06).  Imported LAST: that module reads this one's
 # helpers and switches through the module object at call time.
 from .autograd_recurrent import (  # noqa: E402,F401
-    _Linear, _LSTMCell, _LSTMSequence, _ZERO_STATES, _zero_state, linear_autograd, lstm_cell_autograd, lstm_sequence_autograd,
+    _Linear, _LSTMCell, _LSTMSequence, linear_autograd, lstm_cell_autograd, lstm_sequence_autograd,
 )

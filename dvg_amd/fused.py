@@ -20,34 +20,15 @@ import weakref
 import torch
 import torch.nn as nn
 
-from . import ops
+from . import _derived, ops
+from ._derived import derived, version_key as _ver
 from .ops import ACT_LRELU, ACT_NONE, ACT_SIGMOID, ACT_TANH
-
-_cache: "weakref.WeakKeyDictionary[nn.Module, dict]" = weakref.WeakKeyDictionary()
-
-
-def _slot(mod: nn.Module) -> dict:
-    d = _cache.get(mod)
-    if d is None:
-        d = {}
-        _cache[mod] = d
-    return d
-
-
-def _ver(*ts) -> tuple:
-    return tuple((t.data_ptr(), t._version) if t is not None else None for t in ts)
 
 
 def packed_weight(conv: nn.Module) -> torch.Tensor:
     """[taps][Cout][Cin] repack of a Conv2d / ConvTranspose2d weight, cached per parameter version."""
-    slot = _slot(conv)
-    key = _ver(conv.weight)
-    hit = slot.get("wp")
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    wp = ops.pack_igemm_weight(conv.weight, transposed=isinstance(conv, nn.ConvTranspose2d))
-    slot["wp"] = (key, wp)
-    return wp
+    return derived(conv, "wp", (conv.weight,),
+                   lambda: ops.pack_igemm_weight(conv.weight, transposed=isinstance(conv, nn.ConvTranspose2d)))
 
 
 # Winograd F(m x m, 3x3) for the eval-mode 3x3 layers (ops.conv3x3_winograd): 4x (m = 4) / 2.25x (m = 2) fewer
@@ -90,14 +71,7 @@ def winograd_tile(n, c, h, w, cout) -> int:
 
 def winograd_weight(conv: nn.Module, m: int) -> torch.Tensor:
     """U = G g G^T in the batched-GEMM layout, cached per parameter version and tile size."""
-    slot = _slot(conv)
-    key = _ver(conv.weight)
-    hit = slot.get(("wino", m))
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    u = ops.winograd_weight(conv.weight, m)
-    slot[("wino", m)] = (key, u)
-    return u
+    return derived(conv, ("wino", m), (conv.weight,), lambda: ops.winograd_weight(conv.weight, m))
 
 
 # x half of a decoder block's upsample + concat conv in Winograd F(4x4) form when the skip half is hoisted (eval-mode
@@ -108,14 +82,8 @@ _UPCONV_WINO_MAX = 16     # largest output map side that takes this form (32 x 3
 
 def _winograd_weight_x(conv: nn.Module, c1: int) -> torch.Tensor:
     """U = G g G^T of the x half W[:, :c1] of a concat conv (F(4x4,3x3)), cached per parameter version."""
-    slot = _slot(conv)
-    key = (_ver(conv.weight), c1)
-    hit = slot.get("wino_x")
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    u = ops.winograd_weight(conv.weight.detach()[:, :c1].contiguous(), 4)
-    slot["wino_x"] = (key, u)
-    return u
+    return derived(conv, ("wino_x", c1), (conv.weight,),
+                   lambda: ops.winograd_weight(conv.weight.detach()[:, :c1].contiguous(), 4))
 
 
 def gemm_weight(conv: nn.Module, kind: str) -> torch.Tensor:
@@ -128,45 +96,38 @@ def gemm_weight(conv: nn.Module, kind: str) -> torch.Tensor:
     kind == "stem_t": the same transposed to [KP][N], rows zero-padded to KP in {96, 128} (dvg_stem_gemm), or None
         when dim > 128 / N % 32 != 0.
     """
-    slot = _slot(conv)
-    key = _ver(conv.weight)
-    hit = slot.get("gw" + kind)
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    w = conv.weight.detach()
-    if kind == "head":
-        n, c, kh, kw = w.shape
-        gw = w.permute(0, 2, 3, 1).reshape(n, kh * kw * c).contiguous()
-    elif kind == "stem_t":
-        k, c, kh, kw = w.shape
-        gw = None
-        if k <= 128 and (kh * kw * c) % 32 == 0:
-            gw = torch.zeros((96 if k <= 96 else 128, kh * kw * c), device=w.device, dtype=torch.float32)
-            gw[:k] = w.permute(0, 2, 3, 1).reshape(k, kh * kw * c)
-    else:
-        k, c, kh, kw = w.shape
-        gw = w.permute(2, 3, 1, 0).reshape(kh * kw * c, k).contiguous()
-    slot["gw" + kind] = (key, gw)
-    return gw
+    def build():
+        w = conv.weight.detach()
+        if kind == "head":
+            n, c, kh, kw = w.shape
+            gw = w.permute(0, 2, 3, 1).reshape(n, kh * kw * c).contiguous()
+        elif kind == "stem_t":
+            k, c, kh, kw = w.shape
+            gw = None
+            if k <= 128 and (kh * kw * c) % 32 == 0:
+                gw = torch.zeros((96 if k <= 96 else 128, kh * kw * c), device=w.device, dtype=torch.float32)
+                gw[:k] = w.permute(0, 2, 3, 1).reshape(k, kh * kw * c)
+        else:
+            k, c, kh, kw = w.shape
+            gw = w.permute(2, 3, 1, 0).reshape(kh * kw * c, k).contiguous()
+        return gw
+
+    return derived(conv, "gw" + kind, (conv.weight,), build)
 
 
 def folded_affine(conv: nn.Module, bn: nn.BatchNorm2d):
     """Eval-mode BN folded with the conv bias: y = conv_nobias(x)*scale + shift."""
-    slot = _slot(bn)
-    key = _ver(conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)
-    hit = slot.get("fold")
-    if hit is not None and hit[0] == key:
-        return hit[1], hit[2]
-    with torch.no_grad():
-        inv = torch.rsqrt(bn.running_var + bn.eps)
-        scale = (bn.weight * inv) if bn.weight is not None else inv
-        bias = conv.bias if conv.bias is not None else torch.zeros_like(bn.running_mean)
-        shift = (bias - bn.running_mean) * scale
-        if bn.bias is not None:
-            shift = shift + bn.bias
-        scale, shift = scale.contiguous(), shift.contiguous()
-    slot["fold"] = (key, scale, shift)
-    return scale, shift
+    def build():
+        with torch.no_grad():
+            inv = torch.rsqrt(bn.running_var + bn.eps)
+            scale = (bn.weight * inv) if bn.weight is not None else inv
+            bias = conv.bias if conv.bias is not None else torch.zeros_like(bn.running_mean)
+            shift = (bias - bn.running_mean) * scale
+            if bn.bias is not None:
+                shift = shift + bn.bias
+            return scale.contiguous(), shift.contiguous()
+
+    return derived(bn, "fold", (conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var), build)
 
 
 def _needs_grad(*ts) -> bool:
@@ -368,6 +329,9 @@ def clear_skip_hoist_cache():
     _frozen.clear()
 
 
+_derived.register("skip_hoist", clear_skip_hoist_cache, _skip_seen.values)
+
+
 def declare_frozen_skips(skips) -> None:
     """A rollout tells the decoder blocks that these skip tensors will not change for the remaining steps
     (generate_frames.py:154-157: the skip is only refreshed while i < n_past): the first decoder call then already
@@ -382,17 +346,13 @@ def declare_frozen_skips(skips) -> None:
 
 def _split_packed(conv, c1: int):
     """Packed weights of the x half and the skip half of a concat conv, cached per parameter version."""
-    slot = _slot(conv)
-    key = (_ver(conv.weight), c1)
-    hit = slot.get("wp_split")
-    if hit is not None and hit[0] == key:
-        return hit[1], hit[2]
-    w = conv.weight.detach()
-    tr = isinstance(conv, nn.ConvTranspose2d)
-    wx, wsk = (w[:c1], w[c1:]) if tr else (w[:, :c1], w[:, c1:])
-    px, ps = ops.pack_igemm_weight(wx.contiguous(), transposed=tr), ops.pack_igemm_weight(wsk.contiguous(), transposed=tr)
-    slot["wp_split"] = (key, px, ps)
-    return px, ps
+    def build():
+        w = conv.weight.detach()
+        tr = isinstance(conv, nn.ConvTranspose2d)
+        wx, wsk = (w[:c1], w[c1:]) if tr else (w[:, :c1], w[:, c1:])
+        return ops.pack_igemm_weight(wx.contiguous(), transposed=tr), ops.pack_igemm_weight(wsk.contiguous(), transposed=tr)
+
+    return derived(conv, ("wp_split", c1), (conv.weight,), build)
 
 
 _SHARE_SCOPE = None   # dict while inside share_skip_halves(), else None
@@ -417,25 +377,24 @@ def skip_share_scope():
     return _SHARE_SCOPE
 
 
-def _upconv_packed(conv, c1: int):
+def k4_weight(weight, c1: int) -> torch.Tensor:
     """nearest-x2 upsampling followed by a 3x3 conv (pad 1) IS a stride-2 transposed conv with the 4x4 kernel
-    K4 = W (*) ones(2x2): of the 9 taps of an output pixel only 4 distinct low-resolution inputs contribute.  Returns
-    the packed K4 of the x half W[:, :c1] (ConvTranspose2d layout (Cin, Cout, 4, 4)), cached per parameter version:
-    the x half of every decoder block's first conv (vgg_64.py:98-105) then runs on the CONVT4S2 igemm mode with 4/9 of
-    the MACs.  Tap t (0..2) of the 3x3 kernel lands on k = 2 - t and k = 3 - t of the 4-tap kernel, per axis."""
-    slot = _slot(conv)
-    key = (_ver(conv.weight), c1)
-    hit = slot.get("k4")
-    if hit is not None and hit[0] == key:
-        return hit[1]
-    w = conv.weight.detach()[:, :c1]                      # (Cout, C1, 3, 3)
+    K4 = W (*) ones(2x2): of the 9 taps of an output pixel only 4 distinct low-resolution inputs contribute.  Returns K4
+    of the x half W[:, :c1] of a Conv2d weight in ConvTranspose2d layout (C1, Cout, 4, 4).  Tap t (0..2) of the 3x3
+    kernel lands on k = 2 - t and k = 3 - t of the 4-tap kernel, per axis."""
+    w = weight.detach()[:, :c1]                           # (Cout, C1, 3, 3)
     k4 = torch.zeros((w.shape[0], c1, 4, 4), device=w.device, dtype=torch.float32)
     for ty in range(3):
         for tx in range(3):
             k4[:, :, 2 - ty:4 - ty, 2 - tx:4 - tx] += w[:, :, ty:ty + 1, tx:tx + 1]
-    kp = ops.pack_igemm_weight(k4.permute(1, 0, 2, 3).contiguous(), transposed=True)
-    slot["k4"] = (key, kp)
-    return kp
+    return k4.permute(1, 0, 2, 3).contiguous()
+
+
+def _upconv_packed(conv, c1: int):
+    """The packed K4 (k4_weight) of the x half of a concat conv, cached per parameter version: the x half of every decoder
+    block's first conv (vgg_64.py:98-105) then runs on the CONVT4S2 igemm mode with 4/9 of the MACs."""
+    return derived(conv, ("k4", c1), (conv.weight,),
+                   lambda: ops.pack_igemm_weight(k4_weight(conv.weight, c1), transposed=True))
 
 
 def precompute_skip_half(conv, skip, kind: str) -> None:
@@ -655,12 +614,8 @@ def conv3_first_pair(conv0, bn0, conv1, bn1, x_nchw, *, pool=False, slope=0.2, y
     y_from: as conv3_bn_act."""
     sc0, sh0 = folded_affine(conv0, bn0)
     sc1, sh1 = folded_affine(conv1, bn1)
-    slot, key = _slot(conv0), _ver(conv0.weight)
-    hit = slot.get("w_t9x64")
-    if hit is None or hit[0] != key:
-        hit = (key, conv0.weight.detach().reshape(64, 9).t().contiguous())      # [tap][channel]
-        slot["w_t9x64"] = hit
-    return ops.conv3x3_first_pair(x_nchw, hit[1], sc0, sh0, packed_weight(conv1), sc1, sh1, slope=slope, pool=pool, y_from=y_from)
+    w_t = derived(conv0, "w_t9x64", (conv0.weight,), lambda: conv0.weight.detach().reshape(64, 9).t().contiguous())  # [tap][channel]
+    return ops.conv3x3_first_pair(x_nchw, w_t, sc0, sh0, packed_weight(conv1), sc1, sh1, slope=slope, pool=pool, y_from=y_from)
 
 
 def conv4s2_bn_act(conv, bn, x, *, act=ACT_LRELU, slope=0.2):

@@ -16,6 +16,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from .._derived import derived
 from ..ops import ACT_NONE, ACT_TANH
 
 
@@ -45,33 +46,24 @@ def reparameterize(mu: torch.Tensor, logvar: torch.Tensor) -> torch.Tensor:
     return eps * torch.exp(0.5 * logvar) + mu
 
 
-_FOLD_CACHE = {}   # id(module) -> (weakref, versions, w_x, bias)
-
-
 def folded_first_cell(embed: nn.Linear, cell0: nn.LSTMCell):
     """W_x = W_ih W_e (4H, Kxp: rows zero-padded to a multiple of 4 floats) and bias = W_ih b_e + b_ih + b_hh of the first
     cell with the embedding folded in (see dvg_lstm_cell_x), cached per parameter version; None when the shapes do not fit
     the kernel.  Both products run through dvg_gemm_nt_bias_act."""
-    import weakref
     kx, hid = embed.in_features, cell0.hidden_size
     if kx % 2 or kx > 128 or hid % 64 or embed.out_features != cell0.input_size or embed.bias is None:
         return None
-    ps = (embed.weight, embed.bias, cell0.weight_ih, cell0.bias_ih, cell0.bias_hh)
-    key = tuple((p.data_ptr(), p._version) for p in ps)
-    hit = _FOLD_CACHE.get(id(cell0))
-    if hit is not None and hit[0]() is cell0 and hit[1] == key:
-        return hit[2], hit[3]
-    with torch.no_grad():
-        w_ih = cell0.weight_ih.detach()
-        kxp = (kx + 3) // 4 * 4
-        w_x = torch.zeros((4 * hid, kxp), device=w_ih.device, dtype=torch.float32)
-        ops.gemm_nt(w_ih, embed.weight.detach().t().contiguous(), None, None, out=w_x[:, :kx])
-        bias = ops.gemm_nt(w_ih, embed.bias.detach().view(1, -1), None, None).view(-1)
-        bias = (bias + cell0.bias_ih.detach() + cell0.bias_hh.detach()).contiguous()
-    if len(_FOLD_CACHE) > 64:
-        _FOLD_CACHE.clear()
-    _FOLD_CACHE[id(cell0)] = (weakref.ref(cell0), key, w_x, bias)
-    return w_x, bias
+    def build():
+        with torch.no_grad():
+            w_ih = cell0.weight_ih.detach()
+            kxp = (kx + 3) // 4 * 4
+            w_x = torch.zeros((4 * hid, kxp), device=w_ih.device, dtype=torch.float32)
+            ops.gemm_nt(w_ih, embed.weight.detach().t().contiguous(), None, None, out=w_x[:, :kx])
+            bias = ops.gemm_nt(w_ih, embed.bias.detach().view(1, -1), None, None).view(-1)
+            bias = (bias + cell0.bias_ih.detach() + cell0.bias_hh.detach()).contiguous()
+        return w_x, bias
+
+    return derived(cell0, "embed_fold", (embed.weight, embed.bias, cell0.weight_ih, cell0.bias_ih, cell0.bias_hh), build)
 
 
 class _Recurrent(nn.Module):

@@ -22,7 +22,7 @@ from .winograd import (  # noqa: F401
 )
 from .edge import (  # noqa: F401
     conv3x3_first, first_pair_ok, conv3x3_first_pair, convT3x3_last, conv4x4s2_first, convT4x4s2_last, pixel_proj,
-    _SKIP_PROJ_CACHE, clear_skip_proj_cache, _cached_skip_proj, _last_wmat, _WMAT_CACHE, _last_wmat_cached,
+    _SKIP_PROJ_CACHE, clear_skip_proj_cache, _cached_skip_proj, _last_wmat, _last_wmat_cached,
     precompute_skip_proj, convT_last_two_step, eval_frames, moving_mnist_compose,
 )
 from .dense import (  # noqa: F401

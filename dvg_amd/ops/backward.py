@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import torch
 
+from .._derived import register
 from .._lib import check, lib
 from ._core import MODE_CONV3, MODE_CONVT4S2, _dev_f32, _p, _run, _stream, is_nhwc, nhwc_empty
 
@@ -12,6 +13,7 @@ from ._core import MODE_CONV3, MODE_CONVT4S2, _dev_f32, _p, _run, _stream, is_nh
 # backward (training) wrappers
 # ----------------------------------------------------------------------------------
 _LOSS_W = {}     # (device, weights) -> device tensor of per-call weights
+register("loss_weights", _LOSS_W.clear, _LOSS_W.values)
 
 
 def frame_losses(pred, target, weights):

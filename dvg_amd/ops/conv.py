@@ -4,6 +4,7 @@ from __future__ import annotations
 
 import torch
 
+from .._derived import register
 from .._lib import check, lib
 from ._core import ACT_LRELU, MODE_CONV3, MODE_CONV4S2, MODE_CONVT4S2, _dev_f32, _p, _run, _stream, is_nhwc, nhwc_empty
 
@@ -94,6 +95,7 @@ def _splitk_ws(mode, n, h, w, cin, cout, out_numel, device):
 
 
 _SPLITK_WS = {}
+register("splitk_ws", _SPLITK_WS.clear, _SPLITK_WS.values)
 
 
 def evict_captured_workspaces() -> None:
@@ -149,6 +151,7 @@ class SharedBlocks:
 
 
 _MAP_CACHE = {}
+register("group_maps", _MAP_CACHE.clear, _MAP_CACHE.values)
 
 
 def shared_map(map_host, device):

@@ -5,6 +5,7 @@ from __future__ import annotations
 
 import torch
 
+from .._derived import derived, register
 from .._lib import check, lib
 from ._core import ACT_LRELU, ACT_SIGMOID, ACT_TANH, _dev_f32, _p, _run, _stream, is_nhwc, nhwc_empty
 from .conv import SharedBlocks, _stats_buf, _wp_dims
@@ -123,6 +124,9 @@ def clear_skip_proj_cache():
     _SKIP_PROJ_CACHE.clear()
 
 
+register("skip_proj", clear_skip_proj_cache, _SKIP_PROJ_CACHE.values)
+
+
 def _cached_skip_proj(skip, wm_fn, w):
     """The skip tensor of a rollout is frozen after the conditioning frames (generate_frames.py:154-157), so its
     share of the last layer's projection is computed once and reused while (tensor identity, version, weight
@@ -143,22 +147,10 @@ def _last_wmat(wpart, t):
     return wpart.permute(2, 3, 1, 0).reshape(t, wpart.shape[0]).contiguous()          # [(kh,kw,co)][ci]
 
 
-_WMAT_CACHE = {}   # (id(w), lo, hi) -> (weakref(w), version, data_ptr, matrix)
-
-
 def _last_wmat_cached(w, lo, hi, t):
     """[(kh,kw,co)][ci] projection matrix of rows lo:hi of the last layer's ConvTranspose2d weight, per weight version (it
     used to be re-permuted and copied on every decoder call)."""
-    import weakref
-    key = (id(w), lo, hi)
-    hit = _WMAT_CACHE.get(key)
-    if hit is not None and hit[0]() is w and hit[1] == w._version and hit[2] == w.data_ptr():
-        return hit[3]
-    m = _last_wmat(w.detach()[lo:hi], t)
-    if len(_WMAT_CACHE) > 64:
-        _WMAT_CACHE.clear()
-    _WMAT_CACHE[key] = (weakref.ref(w), w._version, w.data_ptr(), m)
-    return m
+    return derived(w, ("wmat", lo, hi), (w,), lambda: _last_wmat(w.detach()[lo:hi], t))
 
 
 def precompute_skip_proj(skip, w, ks: int) -> None:

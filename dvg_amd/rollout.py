@@ -22,14 +22,15 @@ from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from . import fused, ops
+from . import _derived, fused, ops
 
 
 def drop_version_keyed_caches() -> None:
-    """Forget every tensor the module-level caches hold (packed / transposed / Winograd-domain weights, BatchNorm folds,
-    embed-folded cell weights, GEMM-operand forms, hoisted skip halves and projections, device index maps, the LSTM's shared
-    zero state).  For the one situation in which an entry can be WRONG although its key matches: a hipGraph capture that
-    raised part-way.  During a capture a cache miss allocates from the graph's private pool and records the kernels that
+    """Forget every tensor the module-level caches hold - every cache registered with _derived: packed / transposed /
+    Winograd-domain weights, BatchNorm folds, embed-folded cell weights, GEMM-operand forms, hoisted skip halves and
+    projections, device index maps and loss weights, split-K workspaces, the LSTM's shared zero state.  For the one
+    situation in which an entry can be WRONG although its key matches: a hipGraph capture that raised part-way.
+    During a capture a cache miss allocates from the graph's private pool and records the kernels that
     would fill the tensor - nothing executes - and the entry is stored under the current parameter version; when the
     capture is abandoned the pool is freed, but the entry would still be hit by the next eager call, which would read
     never-written (and freed) memory.  Everything here is rebuilt on demand from the parameters.
@@ -37,18 +38,8 @@ def drop_version_keyed_caches() -> None:
     end-of-backward callback, so operands queued during it - pointers into the freed pool, never written - would be
     flushed into .grad by the next eager backward (or block its flush: the `flush queued` flag stays set)."""
     from . import autograd as ag
-    from .models import lstm as lstm_mod
     ag.drop_deferred_wgrads()
-    ag._pack_cache.clear()
-    for slot in list(fused._cache.values()):
-        slot.clear()
-    ops._WMAT_CACHE.clear()
-    ops._MAP_CACHE.clear()
-    ops._SPLITK_WS.clear()
-    ops.clear_skip_proj_cache()
-    fused.clear_skip_hoist_cache()
-    lstm_mod._FOLD_CACHE.clear()
-    _ZERO_STATE.clear()
+    _derived.drop_all()
 
 
 # make_gifs: the prediction steps before the first GP trigger step once per batch instead of once per sample (GraphedSampler)
@@ -74,45 +65,23 @@ def _adjacent_view(frames):
     return torch.as_strided(f0, shape, torch.empty(shape, device="meta").stride(), f0.storage_offset())
 
 
-_ZERO_STATE = {}
-
 # Graph captures use the thread-local error mode: what OTHER threads do while this thread captures (torch.distributed's
 # watchdog polling the events of earlier collectives when a process group exists) is none of the capture's business.
 CAPTURE_KW = {"capture_error_mode": "thread_local"}
 
 
 def snapshot_eager_caches() -> list:
-    """Strong references to every tensor the module-level caches hold right now: the LSTM's shared zero state, packed /
-    transposed / Winograd-domain weights, BatchNorm folds, the embed-folded first-cell weights, GEMM-operand forms of the
-    dense ends.  A captured hipGraph reads such tensors by RAW POINTER when they were created eagerly during its warm-up;
-    the caches evict (`.clear()` past 16 / 64 / 4096 entries) and replace entries when a parameter version changes
+    """Strong references to every tensor the module-level caches hold right now - every cache registered with _derived: the
+    LSTM's shared zero state, packed / transposed / Winograd-domain weights, BatchNorm folds, the embed-folded first-cell
+    weights, GEMM-operand forms of the dense ends, skip halves and projections, device index maps and loss weights.
+    A captured hipGraph reads such tensors by RAW POINTER when they were created eagerly during its warm-up;
+    the caches drop entries with their owner or past a size bound, and replace them when a parameter version changes
     (load_state_dict, an optimiser step), after which the allocator may hand the block to someone else while live graphs
     still read it.  Every graph holder keeps the snapshot taken right after its capture for as long as it lives."""
-    from . import autograd as ag
-    from .models import lstm as lstm_mod
-    keep = []
-
-    def walk(o):
-        if torch.is_tensor(o):
-            keep.append(o)
-        elif isinstance(o, (tuple, list)):
-            for v in o:
-                walk(v)
-        elif isinstance(o, dict):
-            for v in o.values():
-                walk(v)
-        elif hasattr(o, "__dict__") and type(o).__module__.startswith("dvg_amd"):
-            walk(vars(o))          # ops.WinoV and similar small holders
-
-    walk(list(_ZERO_STATE.values()))
-    walk(list(ops._WMAT_CACHE.values()))
-    walk(list(ops._SKIP_PROJ_CACHE.values()))
-    walk(list(lstm_mod._FOLD_CACHE.values()))
-    walk(list(ag._pack_cache.values()))
-    walk([dict(d) for d in list(fused._cache.values())])
     if not torch.cuda.is_current_stream_capturing():
-        ops.evict_captured_workspaces()      # the capture that just ended no longer needs its split-K workspace OBJECTS
-    return keep
+        # the capture that just ended no longer needs its split-K workspace OBJECTS (and the snapshot must not pin them)
+        ops.evict_captured_workspaces()
+    return _derived.snapshot()
 
 
 def _zero_hidden(frame_predictor):
@@ -121,15 +90,9 @@ def _zero_hidden(frame_predictor):
     rejects in-place updates), and the tensors are only ever replaced in the `hidden` list."""
     if not hasattr(frame_predictor, "step_state_only"):
         return frame_predictor.init_hidden()
-    dev = frame_predictor.embed.weight.device
-    key = (dev, frame_predictor.batch_size, frame_predictor.hidden_size)
-    z = _ZERO_STATE.get(key)
+    z = _derived.zero_state(frame_predictor.batch_size, frame_predictor.hidden_size, frame_predictor.embed.weight.device)
     if z is None:
-        if torch.cuda.is_current_stream_capturing():
-            return frame_predictor.init_hidden()    # never cache a tensor that lives in a graph's private pool
-        if len(_ZERO_STATE) > 16:
-            _ZERO_STATE.clear()
-        z = _ZERO_STATE[key] = torch.zeros(frame_predictor.batch_size, frame_predictor.hidden_size, device=dev)
+        return frame_predictor.init_hidden()    # never cache a tensor that lives in a graph's private pool
     return [(z, z) for _ in range(frame_predictor.n_layers)]
 
 

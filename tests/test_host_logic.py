@@ -472,3 +472,129 @@ def test_bench_plain_run_leaves_every_other_leg_to_full():
     assert bench.parse_args(["--sustained-s", "0"]).sustained_s == 0.0
     with pytest.raises(SystemExit):
         bench.parse_args(["--sustained-s", "20"])       # a figure only --full measures
+
+
+def test_derived_rebuilds_on_version_or_pointer_change_and_dies_with_its_owner():
+    """_derived.derived: one entry per (owner, tag), valid while every source tensor keeps its (data_ptr, _version); the
+    store does not keep the owner alive and forgets it when it dies."""
+    import gc
+    from dvg_amd import _derived
+    _derived.drop_all()
+    conv = torch.nn.Conv2d(2, 3, 3)
+    built = []
+
+    def get(tag="a", owner=None, sources=None, value=None):
+        def build():
+            built.append(tag)
+            return value if value is not None else torch.zeros(1)
+        return _derived.derived(owner if owner is not None else conv, tag, (conv.weight,) if sources is None else sources, build)
+    first = get()
+    assert get() is first and built == ["a"]                     # unchanged sources: the same object, build not called
+    with torch.no_grad():
+        conv.weight.add_(1)                                      # in-place update: new _version
+    second = get()
+    assert second is not first and get() is second and built == ["a", "a"]
+    conv.weight.data = conv.weight.data.clone()                  # re-allocated storage (load_state_dict / .to()): new data_ptr
+    third = get()
+    assert third is not second and get() is third and built == ["a"] * 3
+    other = get("b")                                             # two tags on one owner are independent
+    assert other is not third and get() is third and get("b") is other and built == ["a"] * 3 + ["b"]
+    assert get(("c", 1), sources=(None, conv.weight)) is get(("c", 1), sources=(None, conv.weight))   # a None source stays None
+    n = len(built)
+    assert _derived.derived(conv, "none", (conv.weight,), lambda: built.append("none")) is None        # None is a legal value ...
+    assert _derived.derived(conv, "none", (conv.weight,), lambda: built.append("none")) is None and len(built) == n + 1  # ... and a hit
+    # a parameter as owner (tensors are never compared with ==)
+    p_val = get("p", owner=conv.weight)
+    assert get("p", owner=conv.weight) is p_val
+    held = {id(t) for t in _derived.snapshot()}
+    assert {id(third), id(other), id(p_val)} <= held and id(first) not in held and id(second) not in held
+    ids = (id(third), id(other), id(p_val))
+    keys = (id(conv), id(conv.weight))
+    assert all(k in _derived._store for k in keys)
+    del conv
+    gc.collect()
+    assert not any(k in _derived._store for k in keys)
+    assert not {id(t) for t in _derived.snapshot()} & set(ids)
+    _derived.drop_all()
+
+
+def test_every_module_level_cache_is_registered_dropped_and_snapshotted(monkeypatch):
+    """The registry of _derived: rollout.snapshot_eager_caches() holds every tensor of every registered cache,
+    rollout.drop_version_keyed_caches() empties every one of them and the deferred weight-gradient queues.  The names are
+    listed literally: a new module-level cache means a new name here."""
+    from dvg_amd import _derived, fused, ops, rollout
+    from dvg_amd import autograd as ag
+    from dvg_amd.ops import edge
+    assert set(_derived.registered()) == {"derived", "zero_state", "splitk_ws", "group_maps", "skip_proj", "loss_weights",
+                                          "skip_hoist"}
+    rollout.drop_version_keyed_caches()
+    made = []
+
+    def t():
+        made.append(torch.zeros(2))
+        return made[-1]
+    monkeypatch.setattr(ops, "pack_igemm_weight", lambda w, transposed=False: t())
+    monkeypatch.setattr(ops, "winograd_weight", lambda w, m: t())
+    monkeypatch.setattr(ops, "transpose2d", lambda w: t())
+    monkeypatch.setattr(edge, "pixel_proj", lambda x, wm: t())
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)       # (asks the device otherwise)
+    conv, bn, lin = torch.nn.Conv2d(8, 4, 3, 1, 1), torch.nn.BatchNorm2d(4), torch.nn.Linear(3, 2)
+    last = torch.nn.ConvTranspose2d(8, 1, 3, 1, 1)
+    # "derived": the sites of fused, autograd and ops.edge, stub builders where the real one launches a kernel
+    got = [fused.packed_weight(conv), fused.winograd_weight(conv, 4), fused._winograd_weight_x(conv, 4),
+           fused.gemm_weight(conv, "head"), *fused.folded_affine(conv, bn), *fused._split_packed(conv, 4),
+           fused._upconv_packed(conv, 4), ag._packed(conv.weight), ag._transposed(lin.weight), ag._wino(conv.weight, 4),
+           *ag._upconv_weights(conv.weight, 4), ops._last_wmat_cached(last.weight, 4, 8, 9)]
+    assert fused.packed_weight(conv) is got[0] and ag._transposed(lin.weight) is got[10]
+    k4 = fused.k4_weight(conv.weight.double(), 4).double()      # K4 = W (*) ones(2x2): every tap lands 4 times
+    assert k4.shape == (4, 4, 4, 4) and torch.allclose(k4.sum((2, 3)), 4 * conv.weight.detach().double()[:, :4].sum((2, 3)).t(), rtol=1e-5, atol=1e-7)
+    # the plain caches, one entry each
+    z = _derived.zero_state(2, 3, torch.device("cpu"))
+    assert z is _derived.zero_state(2, 3, torch.device("cpu")) and z.shape == (2, 3) and not z.any()
+    ops._SPLITK_WS[(0, 0, 2, 0)] = ws = t()
+    gmap = ops.shared_map((0, 1, 1), torch.device("cpu"))
+    skip, x = torch.zeros(1, 4, 2, 2), torch.zeros(1, 4, 2, 2)
+    proj = ops._cached_skip_proj(skip, lambda: None, last.weight)
+    ops._LOSS_W[("cpu", (1.0,))] = lw = t()
+    fused.declare_frozen_skips([skip])
+    _, s_half = fused._hoisted_skip(conv, x, skip, lambda ps: t())
+    want = got + [z, ws, gmap, proj, lw, s_half]
+    held = {id(k) for k in rollout.snapshot_eager_caches()}
+    assert all(id(w) in held for w in want), [i for i, w in enumerate(want) if id(w) not in held]
+    ag._wgrad_queues["k"] = [object()]
+    ag._dense_queues["k"] = [object()]
+    ag._wgrad_flush_queued = True
+    rollout.drop_version_keyed_caches()
+    for name, cache in (("derived", _derived._store), ("zero_state", _derived._zero_states), ("splitk_ws", ops._SPLITK_WS),
+                        ("group_maps", ops._MAP_CACHE), ("skip_proj", ops._SKIP_PROJ_CACHE), ("loss_weights", ops._LOSS_W),
+                        ("skip_hoist", fused._skip_seen), ("skip_hoist", fused._frozen)):
+        assert len(cache) == 0, name
+    assert rollout.snapshot_eager_caches() == []
+    assert not ag._wgrad_queues and not ag._dense_queues and ag._wgrad_flush_queued is False
+    assert fused.packed_weight(conv) is not got[0]                # rebuilt on demand
+    rollout.drop_version_keyed_caches()
+
+
+def test_version_counters_are_read_in_one_place_and_the_cache_walkers_name_no_private_dict():
+    """`(data_ptr, _version)` bookkeeping lives in dvg_amd/_derived.py; the files below read `._version` for something that
+    is not a parameter-derived cache.  rollout's two functions over all caches go through the registry: they name no
+    underscore attribute of another module."""
+    import glob
+    import inspect
+    import re
+    from dvg_amd import rollout
+    allowed = {
+        "_derived.py": "the helper itself",
+        "fused.py": "skip sightings: activation-keyed (tensor identity + version of the SKIP), another life cycle",
+        "autograd.py": "share-scope key of one time step's skip halves (activation, not a parameter)",
+        "autograd_recurrent.py": "backward checks that the saved parameters were not stepped since the forward",
+        os.path.join("ops", "edge.py"): "skip projection: keyed on the skip activation and the weight it was projected with",
+    }
+    base = os.path.join(ROOT, "dvg_amd")
+    readers = {os.path.relpath(f, base) for f in glob.glob(os.path.join(base, "**", "*.py"), recursive=True)
+               if re.search(r"\._version\b", open(f).read())}
+    assert readers == set(allowed), sorted(readers ^ set(allowed))
+    for fn in (rollout.drop_version_keyed_caches, rollout.snapshot_eager_caches):
+        src = inspect.getsource(fn)
+        src = src[src.index('"""', src.index('"""') + 3) + 3:]          # the body: the docstring may speak of anything
+        assert not re.search(r"\b(ag|fused|ops|lstm_mod)\._\w", src), src

@@ -169,8 +169,8 @@ def main():
         if a.noise_child == "train" and r == 1:
             print("ready", flush=True)
         if a.drop_caches:
-            from dvg_amd import autograd as ag_
-            ag_._pack_cache.clear()
+            from dvg_amd.rollout import drop_version_keyed_caches
+            drop_version_keyed_caches()
         tr.optimizer.zero_grad()      # the GP / likelihood gradients, which train_model leaves to accumulate (reference behaviour)
         tr._train_model_dev(x)
         torch.cuda.current_stream().synchronize()

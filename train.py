@@ -354,7 +354,7 @@ class Trainer:
                 gneg = self._loss_w.get(("neg1", elbo.device, elbo.numel()))
                 if gneg is None:
                     gneg = torch.full((elbo.numel(),), -1.0, device=elbo.device)
-                    if not torch.cuda.is_current_stream_capturing():   # as autograd._zero_state: a tensor first made during a
+                    if not torch.cuda.is_current_stream_capturing():   # as _derived.zero_state: a tensor first made during a
                         self._loss_w[("neg1", elbo.device, elbo.numel())] = gneg   # capture is written only when that graph replays
                 loss = torch.dot(elbo.detach(), gneg)
                 elbo.backward(gneg)
