@@ -203,6 +203,58 @@ def eval_frames(gt, pred):
     return out[0].mean(1), out[1].mean(1)
 
 
+QUANT_TRUNC, QUANT_NEAREST = 0, 1                       # DVG_QUANT_*
+MOSAIC_BLACK, MOSAIC_RED, MOSAIC_GREEN = 0, 1, 2        # DVG_MOSAIC_* cell colours
+MOSAIC_SEL_NONE, MOSAIC_SEL_BEST, MOSAIC_SEL_PICK = 0, 1, 2
+MOSAIC_CELL_INTS = 8                                    # {src, base, stride, sel, b, k, colour, label}
+
+
+def frame_mosaic(sources, cells, *, nc, H, W, F, R, Cc, cell_h, cell_w, pad_y=0, pad_x=0, oy=0, ox=0, best=None,
+                 picks=None, labels=None, quant=QUANT_TRUNC):
+    """uint8 (F, GH, GW, 3) mosaics of images picked from up to three fp32 device tensors by the DEVICE cell table `cells`
+    (int32, F*R*Cc*8 entries; include/dvg_hip.h: dvg_frame_mosaic).  `sources[i]`: None or a contiguous tensor that is a
+    run of nc x H x W images (any leading dims).  `best` (int64, 1-D) / `picks` (int32, 2-D) / `labels` (uint8, (n, lh, lw))
+    stay on the device: nothing here reads a value back, so the call does not synchronise."""
+    srcs = list(sources) + [None] * (3 - len(sources))
+    if len(srcs) != 3:
+        raise RuntimeError("frame_mosaic: at most three sources")
+    dev, counts = None, []
+    for i, s in enumerate(srcs):
+        if s is None:
+            counts.append(0)
+            continue
+        _dev_f32(s, f"frame_mosaic.sources[{i}]")
+        if not s.is_contiguous() or s.numel() == 0 or s.numel() % (nc * H * W):
+            raise RuntimeError(f"frame_mosaic: source {i} {tuple(s.shape)} is not a contiguous run of {nc}x{H}x{W} images")
+        counts.append(s.numel() // (nc * H * W))
+        dev = s.device
+    if dev is None:
+        raise RuntimeError("frame_mosaic: no source")
+
+    def aux(t, dtype, dim, name):
+        if t is None:
+            return
+        if not t.is_cuda or t.dtype != dtype or t.dim() != dim or not t.is_contiguous() or t.numel() == 0:
+            raise RuntimeError(f"frame_mosaic: {name} must be a contiguous {dim}-D {dtype} device tensor")
+    # a column of an argsort is a strided view: packed here (a device copy, no read-back)
+    best, picks = (None if t is None else t.contiguous() for t in (best, picks))
+    aux(best, torch.int64, 1, "best")
+    aux(picks, torch.int32, 2, "picks")
+    aux(labels, torch.uint8, 3, "labels")
+    if not cells.is_cuda or cells.dtype != torch.int32 or not cells.is_contiguous() or \
+            cells.numel() != F * R * Cc * MOSAIC_CELL_INTS:
+        raise RuntimeError(f"frame_mosaic: cells must be a contiguous int32 device tensor of {F}x{R}x{Cc}x{MOSAIC_CELL_INTS}")
+    gh, gw = R * cell_h + (R - 1) * pad_y, Cc * cell_w + (Cc - 1) * pad_x
+    out = torch.empty((F, gh, gw, 3), device=dev, dtype=torch.uint8)
+    read = 4.0 * nc * H * W * F * R * Cc
+    _run("frame_mosaic", 0.0, read + out.numel(), lib().dvg_frame_mosaic, _p(srcs[0]), counts[0], _p(srcs[1]), counts[1],
+         _p(srcs[2]), counts[2], nc, H, W, _p(cells), F, R, Cc, cell_h, cell_w, pad_y, pad_x, oy, ox, _p(best),
+         0 if best is None else best.shape[0], _p(picks), 0 if picks is None else picks.shape[0],
+         0 if picks is None else picks.shape[1], _p(labels), *((0, 0, 0) if labels is None else labels.shape), quant,
+         _p(out), _stream())
+    return out
+
+
 def moving_mnist_compose(sprites, ids, pos, seq_len, image_size):
     """(T,B,1,S,S) frames from sprites (N,D,D), ids (B,ND) int32 and pos (B,ND,T,2) int32 (dvg_moving_mnist_compose)."""
     _dev_f32(sprites, "moving_mnist_compose.sprites")

@@ -42,3 +42,69 @@ def normalize_data(opt, dtype, sequence):
     if targets is not None and torch.is_tensor(targets) and torch.cuda.is_available():
         targets = targets.cuda()
     return frames, targets
+
+
+# ---- the image writers (utils.py:104-199) ------------------------------------------------------------------------------------
+# Same signatures, same nested lists of (device) tensors as the reference passes; but nothing is gridded on the host: the
+# helpers that build pixels there (add_border, draw_text_tensor, image_tensor) return DESCRIPTIONS here, and a writer turns its
+# description into one cell table, one `ops.frame_mosaic` launch (dvg_frame_mosaic: selection, borders, labels, clamp and
+# byte conversion on the device) and one encoder call.  Only uint8 pixels cross to the host.
+class Figure:
+    """What image_tensor returns here: the grid it describes, composed on demand."""
+
+    def __init__(self, rows, pad_y, pad_x):
+        self.rows, self.pad_y, self.pad_x = rows, pad_y, pad_x
+
+    def bytes(self, quant):
+        """uint8 (GH, GW, 3) device tensor."""
+        return _compose_figures([self], quant)[0]
+
+
+def _compose_figures(figures, quant):
+    from . import viz
+    pads = {(f.pad_y, f.pad_x) for f in figures}
+    assert len(pads) == 1, "frames of one GIF share their padding"
+    (pad_y, pad_x), = pads
+    layout, source = viz.grid_layout([f.rows for f in figures], pad_y, pad_x, quant)
+    return viz.compose(layout, [source])
+
+
+def image_tensor(inputs, padding=1):
+    """utils.py:104-150: a flat list of images side by side, a list of lists as a grid (inner level always padded by 1)."""
+    from . import viz
+    assert len(inputs) > 0
+    return Figure(*viz.figure_grid(inputs, padding))
+
+
+def add_border(x, color, pad=1):
+    """generate_frames.py:306-319: a (w+2pad+30) x (w+2pad) cell of `color` ('red' / 'green' = 0.7 in that channel, else black)
+    with the image at (pad, pad)."""
+    from . import viz
+    return viz.Cell(x, color, pad, 30)
+
+
+def draw_text_tensor(tensor, text):
+    """utils.py:167-173: `text` in black at (4, 64) of the cell, Pillow's default font."""
+    from . import viz
+    c = tensor if isinstance(tensor, viz.Cell) else viz.Cell(tensor)
+    return viz.Cell(c.x, c.color, c.pad, c.extra, text)
+
+
+def save_tensors_image(filename, inputs, padding=1):
+    """utils.py:197-199 (-> make_image -> scipy.misc.toimage): PNG, rounded to nearest."""
+    from . import viz
+    viz.write_png(filename, image_tensor(inputs, padding).bytes(viz.QUANT_NEAREST))
+
+
+def save_gif(filename, inputs, duration=0.25):
+    """utils.py:175-182: one frame per element of `inputs`, each image_tensor(element, padding=0)."""
+    from . import viz
+    viz.write_gif(filename, _compose_figures([image_tensor(t, padding=0) for t in inputs], viz.QUANT_TRUNC), duration)
+
+
+def save_gif_with_text(filename, inputs, text, duration=0.25):
+    """utils.py:184-191: per frame a flat list of cells, each with its label, joined with padding 0."""
+    from . import viz
+    figs = [image_tensor([draw_text_tensor(ti, texti) for ti, texti in zip(tensor, txt)], padding=0)
+            for tensor, txt in zip(inputs, text)]
+    viz.write_gif(filename, _compose_figures(figs, viz.QUANT_TRUNC), duration)

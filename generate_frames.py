@@ -12,9 +12,12 @@ overridden, and runs either
     the GP predictive variance, then a variance-threshold trigger `value > mean + (2+0.01*depth)*std` over a
     12-long sliding window decides per step between a GP sample and the LSTM path.
 
-Image/GIF writing and SSIM are out of scope: results (frames, per-sample PSNR, best-of-N
-index, trigger steps) are saved as tensors.  `--synthetic_ckpt` builds a randomly initialised checkpoint so
-the script can run without a trained model.
+Results (frames, per-sample SSIM / PSNR, best-of-N index, trigger steps) are saved as tensors, and beside them the
+reference's figures: `<log_dir>/gen/sample_lstm_<idx>.gif` (:185-217) and, with `--gp_trigger`,
+`<log_dir>/gen/recursive_generation/<index>/heuristic_gp_trigger_<depth>_<n>.png` (plot_rec, :235-245).  The figures are
+composed on the device from the rollout tensors (dvg_amd/viz.py, dvg_frame_mosaic): only uint8 pixels are copied to the
+host.  `--no_images` writes the tensors only.  `--synthetic_ckpt` builds a randomly initialised checkpoint so the script can
+run without a trained model.
 """
 import argparse
 import os
@@ -28,7 +31,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 import utils  # noqa: E402
-from dvg_amd import ops  # noqa: E402
+from dvg_amd import ops, viz  # noqa: E402
 from dvg_amd.data import SyntheticMovingMNIST, synthetic_video  # noqa: E402
 from dvg_amd.rollout import (GraphedSampler, GraphedTrigger, condition, posterior_from, sample_from, sample_rollout,  # noqa: E402
                              trigger_body, trigger_log, trigger_warmup)
@@ -66,6 +69,9 @@ def build_parser():
     p.add_argument('--no_share_prefix', action='store_true',
                    help='make_gifs: run the prediction steps before the first GP trigger step once per SAMPLE, like the reference '
                         'loop (default: once per batch - they are the same for every sample; identical results)')
+    p.add_argument('--no_images', action='store_true', help='write the .pt tensors only, no GIF / PNG')
+    p.add_argument('--gif_rows', type=int, default=1,
+                   help='make_gifs: batch rows to write a GIF for (the reference returns after row 0, generate_frames.py:217)')
     p.add_argument('--synthetic_data', action='store_true',
                    help='datasets other than smmnist: synthetic clips of the right shape (--data_root is not read)')
     return p
@@ -84,6 +90,10 @@ class Generator:
             m.to(device).eval()
         self.frame_predictor.batch_size = opt.batch_size
         self._sampler, self._sampler_key = None, None
+        # the figures' random sample indices (generate_frames.py:190): a stream of their own, so that writing images draws
+        # nothing from the global numpy / torch generators and every saved tensor is what it is without them
+        self._viz_rng = np.random.RandomState(opt.seed)
+        self._layouts = {}
 
     def _gp(self, h):
         return self.likelihood(self.gp_layer(h.transpose(0, 1).view(self.opt.g_dim, h.shape[0], 1)))
@@ -136,6 +146,42 @@ class Generator:
         best = ssim.mean(2).argsort(1)[:, -1]   # generate_frames.py:188-189,207: np.argsort(mean_ssim)[-1]
         return {'posterior': torch.stack(post), 'samples': torch.stack(all_gen), 'ssim': ssim, 'psnr': psnr,
                 'best': best}
+
+    def write_gifs(self, x, res, idx, out_dir, name='lstm', rows=1):
+        """generate_frames.py:185-217 on make_gifs' result: `<out_dir>/sample_<name>_<idx + i>.gif` for batch rows i < rows,
+        six labelled columns per frame (ground truth, posterior, res['best'][i], three random samples).  One launch composes
+        all rows' frames from the tensors where they are; `best` is read on the device.  Returns the paths written."""
+        opt = self.opt
+        T, B = opt.n_eval, x[0].shape[0]
+        H, W = x[0].shape[-2:]
+        rows = min(rows, B)
+        key = ('gifs', T, opt.n_past, B, H, W, rows)
+        if key not in self._layouts:
+            self._layouts[key] = viz.make_gifs_layout(T, opt.n_past, B, H, W, rows)
+        picks = viz.random_picks(self._viz_rng, rows, 3, res['samples'].shape[0])
+        gt = torch.stack(list(x[:T]))
+        frames = viz.compose(self._layouts[key], [gt, res['posterior'], res['samples']], best=res['best'], picks=picks).cpu()
+        paths = []
+        for i in range(rows):
+            path = '%s/sample_%s_%d.gif' % (out_dir, name, idx + i)
+            if viz.write_gif(path, frames[i * T:(i + 1) * T]):
+                paths.append(path)
+        return paths
+
+    def write_trigger_pngs(self, res, out_dir, depth=1, frames_generated=0):
+        """plot_rec (generate_frames.py:235-245) for every entry of gp_trigger_gen's result: every third frame of the index's
+        rollout in one row, `<out_dir>/recursive_generation/<index>/heuristic_gp_trigger_<depth>_<n>.png`."""
+        paths = []
+        for r in res:
+            fr = r['frames'].to(self.dev).unsqueeze(1)                    # (T,1,C,H,W)
+            key = ('rec', fr.shape[0]) + tuple(fr.shape[-2:])
+            if key not in self._layouts:
+                self._layouts[key] = viz.plot_rec_layout(fr.shape[0], fr.shape[-2], fr.shape[-1])
+            d = '%s/recursive_generation/%d' % (out_dir, r['index'])
+            os.makedirs(d, exist_ok=True)
+            paths.append('%s/heuristic_gp_trigger_%d_%d.png' % (d, depth, frames_generated))
+            viz.write_png(paths[-1], viz.compose(self._layouts[key], [fr])[0])
+        return paths
 
     @torch.no_grad()
     def _generation(self, x_in, skip):
@@ -321,6 +367,8 @@ def main(argv=None):
             res = gen.gp_trigger_gen(test_x, args.trigger_indices, total=opt.n_eval)
             torch.save(res, '%s/gen/gp_trigger_%d.pt' % (opt.log_dir, i))
             print('batch %d: trigger steps of index 0: %s' % (i, res[0]['triggers']))
+            if not args.no_images:
+                gen.write_trigger_pngs(res, '%s/gen' % opt.log_dir)
         else:
             res = gen.make_gifs(test_x, args.nsample)
             torch.save({'posterior': res['posterior'][:, 0].cpu(), 'best': res['best'].cpu(), 'psnr': res['psnr'].cpu(),
@@ -330,6 +378,8 @@ def main(argv=None):
             sel = res['best'].view(-1, 1, 1).expand(-1, 1, res['ssim'].shape[2])
             print('batch %d: best-of-%d by mean SSIM: SSIM %.4f, PSNR %.3f dB' % (
                 i, args.nsample, float(res['ssim'].gather(1, sel).mean()), float(res['psnr'].gather(1, sel).mean())))
+            if not args.no_images:
+                gen.write_gifs(test_x, res, i, '%s/gen' % opt.log_dir, rows=args.gif_rows)
 
 
 if __name__ == '__main__':

@@ -591,6 +591,44 @@ int dvg_moving_mnist_compose(const float* sprites, const int* ids, const int* po
 int dvg_eval_frames(const float* gt, const float* pred, float* ssim, float* psnr, int n_images, int H, int W,
                     void* stream);
 
+/* The reference's figures as uint8 RGB mosaics, composed on the device in ONE launch.  Replaces, at their call sites
+ * generate_frames.py:185-217 (make_gifs -> utils.save_gif_with_text), :235-245 (plot_rec -> utils.save_tensors_image) and
+ * train.py:291-335 (plot -> save_tensors_image + utils.save_gif), the chain utils.image_tensor (utils.py:104-150),
+ * add_border (generate_frames.py:306-319), draw_text_tensor (utils.py:167-173) and make_image (utils.py:160-165), which
+ * work on .cpu() tensors in Python loops.  Only the bytes leave the device.  An addition within ABI 9.
+ *
+ * out: uint8 [F][GH][GW][3], GH = R*cell_h + (R-1)*pad_y, GW = Cc*cell_w + (Cc-1)*pad_x: F frames, each an R x Cc grid of
+ * cell_h x cell_w cells separated by pad_y / pad_x pixels of 1.0 (image_tensor's canvas of ones).  A cell is filled with its
+ * colour (DVG_MOSAIC_BLACK, _RED = 0.7 in channel 0, _GREEN = 0.7 in channel 1: add_border) and holds one H x W image at
+ * (oy, ox); nc = 1 is replicated to three channels, nc = 3 copied.  Where the cell's label mask is set the pixel is black
+ * (draw_text_tensor's fill (0,0,0)); labels: uint8 [n_labels][lh][lw] anchored at the cell's corner, NULL = none.
+ *
+ * cells: DEVICE int32 [F][R][Cc][DVG_MOSAIC_CELL_INTS] = {src, base, stride, sel, b, k, colour, label}: the image is number
+ * base + s * stride of source `src` (0..2; images are nc*H*W contiguous floats, so an NCHW batch (.., B, C, H, W) is a run of
+ * them) with s = 0 (DVG_MOSAIC_SEL_NONE), best[b] (_SEL_BEST; int64 [n_best]) or picks[b][k] (_SEL_PICK; int32
+ * [n_pick_rows][pick_k]), read ON THE DEVICE: no index is read back before the launch.  label = -1: none.  The kernel
+ * checks every table entry and index against n0 / n1 / n2 (the sources' image counts), n_best, n_pick_rows, pick_k and
+ * n_labels; an entry that fails (src = -1 included) draws its background only.
+ *
+ * quant: DVG_QUANT_TRUNC = uint8(clamp(v,0,1) * 255) (draw_text_tensor's np.uint8(np_x*255): the GIFs), DVG_QUANT_NEAREST =
+ * uint8(clamp(v,0,1) * 255 + 0.5) (scipy.misc.toimage's bytescale with cmin = 0, cmax = 1: the PNGs); product and add are
+ * separately rounded fp32.  The one deviation: toimage stretches by the image's minimum, (v - min) * 255 * max / (max - min);
+ * that differs only for a figure without a single 0 pixel, and the function no longer exists in scipy. */
+#define DVG_MOSAIC_CELL_INTS 8
+#define DVG_MOSAIC_BLACK 0
+#define DVG_MOSAIC_RED 1
+#define DVG_MOSAIC_GREEN 2
+#define DVG_MOSAIC_SEL_NONE 0
+#define DVG_MOSAIC_SEL_BEST 1
+#define DVG_MOSAIC_SEL_PICK 2
+#define DVG_QUANT_TRUNC 0
+#define DVG_QUANT_NEAREST 1
+int dvg_frame_mosaic(const float* src0, long n0, const float* src1, long n1, const float* src2, long n2, int nc, int H,
+                     int W, const int* cells, int F, int R, int Cc, int cell_h, int cell_w, int pad_y, int pad_x, int oy,
+                     int ox, const long* best, int n_best, const int* picks, int n_pick_rows, int pick_k,
+                     const unsigned char* labels, int n_labels, int lh, int lw, int quant, unsigned char* out,
+                     void* stream);
+
 /* Fused Adam step over one flat parameter group (train.py:95-106: torch.optim.Adam(lr=0.002) with default
  * betas (0.9, 0.999) and eps 1e-8; torch.optim.Adam arithmetic, non-amsgrad): param / exp_avg / exp_avg_sq are
  * updated in place, `step` is the 1-based step count used for the bias corrections; when `step_dev` is not NULL the

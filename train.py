@@ -41,7 +41,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 import utils  # noqa: E402
-from dvg_amd import fused, parallel  # noqa: E402
+from dvg_amd import fused, parallel, viz  # noqa: E402
 from dvg_amd.data import SyntheticMovingMNIST, make_batch_generator, synthetic_video  # noqa: E402,F401
 from dvg_amd.models.gp_models import GaussianLikelihood, GPRegressionLayer1, VariationalELBO  # noqa: E402
 from dvg_amd.optim import FlatArena, FusedAdam, zero_grads  # noqa: E402
@@ -78,6 +78,7 @@ def build_parser():
     p.add_argument('--last_frame_skip', action='store_true')
     p.add_argument('--save_every', type=int, default=4)
     p.add_argument('--no_save', action='store_true')
+    p.add_argument('--no_images', action='store_true', help='do not write sample_<epoch>.png / .gif beside the tensors')
     p.add_argument('--hip_graph', action='store_true',
                    help='(the default) replay each training iteration as one hipGraph (GraphedIteration; same losses and '
                         'parameters as the eager loop, tested; 1.5-2.7x the train frames/s); with more than one rank: as a '
@@ -643,7 +644,7 @@ class Trainer:
         return mse_ctrl, indices, temp_loss
 
 
-    # ---- qualitative rollout of train.py:256-289 (tensors only; PNG/GIF writers are out of scope) ------
+    # ---- qualitative rollout of train.py:256-289; write_plot below turns its result into the figures of :291-335 ------
     @torch.no_grad()
     def plot(self, x, epoch, nsample=5, eps_by_sample=None):
         """train.py:256-310 without the image writers: `nsample` rollouts whose ONE GP-sampled step is i == 10 (:281;
@@ -680,6 +681,10 @@ class Trainer:
         gt = torch.stack(list(x[:opt.n_eval]))           # (T,B,C,H,W)
         sse = ((gen - gt.unsqueeze(0)) ** 2).sum((1, 3, 4, 5))   # (S,B) — train.py:303-310 best-of-N
         return gen, sse.argmin(0)
+
+    def write_plot(self, x, gen, best, epoch, out_dir):   # train.py:291-335: sample_<epoch>.png / .gif (viz.PlotWriter)
+        self._plot_writer = getattr(self, '_plot_writer', None) or viz.PlotWriter(getattr(self.opt, 'seed', 1))
+        return self._plot_writer(x, gen, best, epoch, out_dir)
 
     def save(self, path):
         """train.py:380-388: whole-module pickles + GP / likelihood / GP-optimiser state dicts.  Every tensor written owns
@@ -777,6 +782,7 @@ def main(argv=None):
                 torch.save({'gen': gen[:, :, :min(opt.local_batch, 10)].cpu(), 'best': best.cpu()},
                            '%s/sample_%d.pt' % (opt.output_path, epoch))
                 tr.save('%s/model.pth' % opt.output_path)
+                opt.no_images or tr.write_plot(test_x, gen, best, epoch, opt.output_path)   # sample_<epoch>.png / .gif
         if epoch % 10 == 0 and rank == 0:
             print('log dir: %s' % opt.log_dir)
     if opt.print_param_checksum:   # tests: every rank must end with the same parameters
