@@ -4,8 +4,10 @@
 rebuild on mismatch, store": packed / transposed / Winograd-domain weights, BatchNorm folds, GEMM-operand forms.
 
 Correctness under hipGraph capture needs two operations over ALL module-level caches of the package (see
-rollout.drop_version_keyed_caches / rollout.snapshot_eager_caches): forget everything, and hold everything alive.  A cache
-that lives at module level calls `register` next to its definition, or it is neither dropped nor kept alive.
+graphs.drop_version_keyed_caches / graphs.snapshot_eager_caches): forget everything, and hold everything alive.  A cache
+that lives at module level calls `register` next to its definition, or it is neither dropped nor kept alive.  The caches keyed
+on a rollout's skip tensors name their dicts there as well: graph holders forget what ONE capture added to them
+(`skip_mark` / `skip_drop_since`).
 
 Imports torch and weakref only, so that every module of the package can import it."""
 from __future__ import annotations
@@ -15,13 +17,28 @@ import weakref
 import torch
 
 _registry = {}     # name -> (clear, tensors)
+_skip_keyed = []   # the dicts whose entries depend on a rollout's skip tensors
 
 
-def register(name: str, clear, tensors) -> None:
-    """clear(): forget every entry.  tensors(): an iterable of what the cache holds now (nested containers allowed)."""
+def register(name: str, clear, tensors, skip_keyed=()) -> None:
+    """clear(): forget every entry.  tensors(): an iterable of what the cache holds now (nested containers allowed).
+    skip_keyed: the cache's dicts, if its entries are keyed on skip activations."""
     if name in _registry:
         raise RuntimeError(f"cache {name!r} is registered twice")
     _registry[name] = (clear, tensors)
+    _skip_keyed.extend(skip_keyed)
+
+
+def skip_mark() -> list:
+    """The keys the skip-keyed caches hold now."""
+    return [set(d) for d in _skip_keyed]
+
+
+def skip_drop_since(mark) -> None:
+    """Forget every entry of the skip-keyed caches whose key was not there at `mark`."""
+    for d, had in zip(_skip_keyed, mark):
+        for k in [k for k in d if k not in had]:
+            del d[k]
 
 
 def registered() -> tuple:

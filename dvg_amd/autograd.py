@@ -133,7 +133,7 @@ def flush_wgrads():
 
 
 def drop_deferred_wgrads() -> None:
-    """Forget every queued weight-gradient operand WITHOUT flushing it (rollout.drop_version_keyed_caches: after a hipGraph
+    """Forget every queued weight-gradient operand WITHOUT flushing it (graphs.drop_version_keyed_caches: after a hipGraph
     capture that raised inside backward() the queued (dY, X, V) tensors point into the freed graph pool and were never
     written; the engine skipped its end-of-backward callback, so the queues and the flag would otherwise survive)."""
     global _wgrad_flush_queued

@@ -248,8 +248,7 @@ def hbm_bound_layers(ctx: Ctx, args) -> dict:
     (lstm.py:65-72; 3 launches, 4.4 MB of weights: latency-bound, reported in us); gp_sample: one sampling call of the GP
     trigger (gp_models.py:10-24)."""
     import torch
-    from dvg_amd import fused, ops
-    from dvg_amd.rollout import pooled_stream
+    from dvg_amd import fused, graphs, ops
     B = args.batch
     enc, dec, fp, gp, lik = build_models("vgg", B, 1, ctx.dev, args.seed)
     x = torch.rand(B, 1, 64, 64, device=ctx.dev)
@@ -257,15 +256,9 @@ def hbm_bound_layers(ctx: Ctx, args) -> dict:
     def timed(fn, reps=20, replays=10):
         """us per call: `reps` back-to-back calls captured as ONE hipGraph (no host launch latency between them - the rollout
         itself runs as graph replays), `replays` replays between two HIP events on the launch stream."""
-        side = pooled_stream("warmup")
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(3):
-                fn()
-        torch.cuda.current_stream().wait_stream(side)
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g, capture_error_mode="thread_local"):
-            keep = [fn() for _ in range(reps)]
+        graphs.warm_up(fn, 3)
+        with graphs.skip_scope():
+            g, keep, alive = graphs.capture(lambda: [fn() for _ in range(reps)])
         g.replay()
         torch.cuda.synchronize()
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -274,7 +267,7 @@ def hbm_bound_layers(ctx: Ctx, args) -> dict:
             g.replay()
         e1.record()
         torch.cuda.synchronize()
-        del keep
+        del keep, alive
         return e0.elapsed_time(e1) / (reps * replays) * 1e3
 
     def row(us, nbytes, launches, what):

@@ -329,7 +329,7 @@ def clear_skip_hoist_cache():
     _frozen.clear()
 
 
-_derived.register("skip_hoist", clear_skip_hoist_cache, _skip_seen.values)
+_derived.register("skip_hoist", clear_skip_hoist_cache, _skip_seen.values, skip_keyed=(_skip_seen, _frozen))
 
 
 def declare_frozen_skips(skips) -> None:

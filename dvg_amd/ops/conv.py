@@ -100,7 +100,7 @@ register("splitk_ws", _SPLITK_WS.clear, _SPLITK_WS.values)
 
 def evict_captured_workspaces() -> None:
     """Drop the split-K workspaces that were allocated from a hipGraph's private pool (capture id != 0).  Called by
-    rollout.snapshot_eager_caches right after a capture has ended: the graph replays through raw pointers and its pool
+    graphs.snapshot_eager_caches right after a capture has ended: the graph replays through raw pointers and its pool
     keeps the memory, so the tensor objects are only needed WHILE the capture runs (later launches of the same size reuse
     them) - kept afterwards they would pin segments of a pool that GraphedIteration._release() / a sampler rebuild wants
     to free."""

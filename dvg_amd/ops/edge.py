@@ -119,12 +119,12 @@ _SKIP_PROJ_CACHE = {}   # id(skip) -> (weakref(skip), skip._version, id(w), w._v
 
 
 def clear_skip_proj_cache():
-    """Drop cached skip projections (rollout.GraphedRollout calls this around a capture: buffers allocated while
+    """Drop cached skip projections (graphs.skip_scope calls this around a group of captures: buffers allocated while
     capturing belong to the graph's pool and must not leak into eager calls, nor the reverse)."""
     _SKIP_PROJ_CACHE.clear()
 
 
-register("skip_proj", clear_skip_proj_cache, _SKIP_PROJ_CACHE.values)
+register("skip_proj", clear_skip_proj_cache, _SKIP_PROJ_CACHE.values, skip_keyed=(_SKIP_PROJ_CACHE,))
 
 
 def _cached_skip_proj(skip, wm_fn, w):

@@ -16,30 +16,11 @@ Index bookkeeping (row K of SURVEY.md §8) is integer logic kept in `trigger_ste
 """
 from __future__ import annotations
 
-import os
-
 from typing import Dict, List, Optional, Sequence
 
 import torch
 
-from . import _derived, fused, ops
-
-
-def drop_version_keyed_caches() -> None:
-    """Forget every tensor the module-level caches hold - every cache registered with _derived: packed / transposed /
-    Winograd-domain weights, BatchNorm folds, embed-folded cell weights, GEMM-operand forms, hoisted skip halves and
-    projections, device index maps and loss weights, split-K workspaces, the LSTM's shared zero state.  For the one
-    situation in which an entry can be WRONG although its key matches: a hipGraph capture that raised part-way.
-    During a capture a cache miss allocates from the graph's private pool and records the kernels that
-    would fill the tensor - nothing executes - and the entry is stored under the current parameter version; when the
-    capture is abandoned the pool is freed, but the entry would still be hit by the next eager call, which would read
-    never-written (and freed) memory.  Everything here is rebuilt on demand from the parameters.
-    The deferred weight-gradient queues go with them: a capture that dies INSIDE backward() skips autograd's
-    end-of-backward callback, so operands queued during it - pointers into the freed pool, never written - would be
-    flushed into .grad by the next eager backward (or block its flush: the `flush queued` flag stays set)."""
-    from . import autograd as ag
-    ag.drop_deferred_wgrads()
-    _derived.drop_all()
+from . import _derived, fused, graphs, ops
 
 
 # make_gifs: the prediction steps before the first GP trigger step once per batch instead of once per sample (GraphedSampler)
@@ -50,38 +31,23 @@ def trigger_steps(n_past: int, n_eval: int, period: int = 15) -> List[int]:
     return [i for i in range(n_past, n_eval) if i % period == 0]
 
 
-def _adjacent_view(frames):
-    """If the frames are consecutive contiguous slices of ONE buffer (data.batch_device(), GraphedRollout's static inputs),
-    the batch of all of them is a view: no concat launch per rollout.  None otherwise."""
+def frames_as_batch(frames):
+    """The frames of a clip as ONE batch.  If they are consecutive contiguous slices of one buffer (data.batch_device(),
+    GraphedRollout's static inputs) the batch is a view of it: no concat launch per rollout; a concat otherwise."""
     f0 = frames[0]
-    if not all(t.is_contiguous() and t.shape == f0.shape and t.dtype == f0.dtype for t in frames):
-        return None
     step = f0.numel() * f0.element_size()
     st = f0.untyped_storage()
     for i, t in enumerate(frames):
-        if t.untyped_storage().data_ptr() != st.data_ptr() or t.data_ptr() != f0.data_ptr() + i * step:
-            return None
+        if (not t.is_contiguous() or t.shape != f0.shape or t.dtype != f0.dtype or
+                t.untyped_storage().data_ptr() != st.data_ptr() or t.data_ptr() != f0.data_ptr() + i * step):
+            return torch.cat(list(frames), 0)
     shape = (len(frames) * f0.shape[0],) + tuple(f0.shape[1:])
     return torch.as_strided(f0, shape, torch.empty(shape, device="meta").stride(), f0.storage_offset())
 
 
-# Graph captures use the thread-local error mode: what OTHER threads do while this thread captures (torch.distributed's
-# watchdog polling the events of earlier collectives when a process group exists) is none of the capture's business.
-CAPTURE_KW = {"capture_error_mode": "thread_local"}
-
-
-def snapshot_eager_caches() -> list:
-    """Strong references to every tensor the module-level caches hold right now - every cache registered with _derived: the
-    LSTM's shared zero state, packed / transposed / Winograd-domain weights, BatchNorm folds, the embed-folded first-cell
-    weights, GEMM-operand forms of the dense ends, skip halves and projections, device index maps and loss weights.
-    A captured hipGraph reads such tensors by RAW POINTER when they were created eagerly during its warm-up;
-    the caches drop entries with their owner or past a size bound, and replace them when a parameter version changes
-    (load_state_dict, an optimiser step), after which the allocator may hand the block to someone else while live graphs
-    still read it.  Every graph holder keeps the snapshot taken right after its capture for as long as it lives."""
-    if not torch.cuda.is_current_stream_capturing():
-        # the capture that just ended no longer needs its split-K workspace OBJECTS (and the snapshot must not pin them)
-        ops.evict_captured_workspaces()
-    return _derived.snapshot()
+def gp_input(gp_layer, h):
+    """The encoder / LSTM output h (B, D) as the GP layer's input (D, B, 1): one independent GP per latent dimension."""
+    return h.transpose(0, 1).view(gp_layer.num_dims, h.shape[0], 1)
 
 
 def _zero_hidden(frame_predictor):
@@ -118,33 +84,10 @@ def _encode_conditioning(encoder, x, n_past, last_frame_skip):
     ONE batch of B*(n_past-1) frames — bit-identical per-sample math, 9 passes' worth of launches folded into one and
     9x more tiles per launch for the deep 8x8 layers.  Returns ([h_1 .. h_{n_past-1}], skip of the last step)."""
     b = x[0].shape[0]
-    frames = _adjacent_view(x[:n_past - 1])
-    if frames is None:
-        frames = torch.cat([x[i] for i in range(n_past - 1)], 0)
-    last = n_past - 2
-    h_all, skip = _encode(encoder, frames, last * b)      # the skips of the last frame x[n_past-2] alone (b images each)
+    last = n_past - 2     # the skips of the last frame x[n_past-2] alone (b images each)
+    h_all, skip = _encode(encoder, frames_as_batch(x[:n_past - 1]), last * b)
     hs = [h_all[i * b:(i + 1) * b] for i in range(n_past - 1)]
     return hs, skip
-
-
-# Streams are made ONCE per process and shared by every graph holder of this module.  torch hands out streams from a pool of 32
-# per device, round-robin and without telling: a process that builds many samplers (bench.py: two families x (three chains +
-# make_gifs) + C1) wraps around the pool, after which two "concurrent" chains may sit on ONE hip stream (silently serial), or a
-# chain's stream may be the one torch captures graphs on - the r06 bench died with a segmentation fault inside
-# hipGraphLaunch (hip::Graph::UpdateStreams) at exactly that point.  Work on one stream runs in order, so sharing the streams
-# between holders is safe; it only orders work that a caller issues from different holders at the same time.
-_streams = {}
-
-
-def pooled_stream(role: str, index: int = 0) -> "torch.cuda.Stream":
-    key = (torch.cuda.current_device(), role, index)
-    if key not in _streams:
-        _streams[key] = torch.cuda.Stream()
-    return _streams[key]
-
-
-def _hoist_stream():
-    return pooled_stream("hoist")
 
 
 def _step_discard(frame_predictor, h):
@@ -173,7 +116,7 @@ def condition(encoder, frame_predictor, x: Sequence[torch.Tensor], n_past: int, 
             # small latency-bound launches: the decoder's loop-invariant skip halves (fused._hoisted_skip) are computed
             # meanwhile on a second stream (a parallel branch of the hipGraph when captured) instead of on the critical
             # path of the first decoder call.
-            side, cur = _hoist_stream(), torch.cuda.current_stream()
+            side, cur = graphs.pooled_stream("hoist"), torch.cuda.current_stream()
             side.wait_stream(cur)
             with torch.cuda.stream(side):
                 fused.declare_frozen_skips(skip)
@@ -189,11 +132,9 @@ def condition(encoder, frame_predictor, x: Sequence[torch.Tensor], n_past: int, 
     return {"hidden": list(frame_predictor.hidden), "skip": skip, "frames": [x[i] for i in range(n_past)]}
 
 
-@torch.no_grad()
-def sample_from(state: dict, encoder, decoder, frame_predictor, gp_layer, likelihood, n_past: int, n_eval: int,
-                last_frame_skip: bool = False, period: int = 15,
-                eps_by_step: Optional[Dict[int, torch.Tensor]] = None) -> List[torch.Tensor]:
-    """The prediction phase of one sample (generate_frames.py:163-176), starting from a `condition()` state."""
+def _predict_from(state: dict, encoder, decoder, frame_predictor, n_past: int, n_eval: int, last_frame_skip: bool,
+                  latent) -> List[torch.Tensor]:
+    """The prediction steps n_past ... n_eval - 1 from a `condition()` state; latent(i, h, h_pred) is what step i decodes."""
     frame_predictor.hidden = list(state["hidden"])   # lstm_cell returns new tensors: the saved state is never mutated
     frames = list(state["frames"])
     skip = state["skip"]
@@ -206,14 +147,22 @@ def sample_from(state: dict, encoder, decoder, frame_predictor, gp_layer, likeli
         if i == n_past and not last_frame_skip and not decoder.training:
             fused.declare_frozen_skips(skip)    # frozen from here on: decoder blocks hoist their skip halves now
         h_pred = frame_predictor(h)
-        if period and i % period == 0:
-            pred = likelihood(gp_layer(h.transpose(0, 1).view(gp_layer.num_dims, h.shape[0], 1)))
-            z = pred.rsample(None if eps_by_step is None else eps_by_step[i])
-            x_in = decoder([z.transpose(0, 1), skip])
-        else:
-            x_in = decoder([h_pred, skip])
+        x_in = decoder([latent(i, h, h_pred), skip])
         frames.append(x_in)
     return frames
+
+
+@torch.no_grad()
+def sample_from(state: dict, encoder, decoder, frame_predictor, gp_layer, likelihood, n_past: int, n_eval: int,
+                last_frame_skip: bool = False, period: int = 15,
+                eps_by_step: Optional[Dict[int, torch.Tensor]] = None) -> List[torch.Tensor]:
+    """The prediction phase of one sample (generate_frames.py:163-176), starting from a `condition()` state."""
+    def latent(i, h, h_pred):
+        if not (period and i % period == 0):
+            return h_pred
+        pred = likelihood(gp_layer(gp_input(gp_layer, h)))
+        return pred.rsample(None if eps_by_step is None else eps_by_step[i]).transpose(0, 1)
+    return _predict_from(state, encoder, decoder, frame_predictor, n_past, n_eval, last_frame_skip, latent)
 
 
 @torch.no_grad()
@@ -248,7 +197,7 @@ def posterior_rollout(encoder, decoder, frame_predictor, gp_layer, likelihood, x
             x_in = x[i]
         else:
             h_pred = frame_predictor(h)
-            pred = likelihood(gp_layer(h_pred.transpose(0, 1).view(gp_layer.num_dims, h_pred.shape[0], 1)))
+            pred = likelihood(gp_layer(gp_input(gp_layer, h_pred)))
             x_in = decoder([pred.mean.transpose(0, 1), skip])
         frames.append(x_in)
     return frames
@@ -261,22 +210,8 @@ def posterior_from(state: dict, encoder, decoder, frame_predictor, gp_layer, lik
     (generate_frames.py:113-121 for i < n_past: the encoder on x[i-1], the LSTM stepped with the output discarded, the skip
     tensors of the last such frame, x[i] handed on) is the same computation as the samples' (:147-162), so `make_gifs` runs it
     once for both."""
-    frame_predictor.hidden = list(state["hidden"])
-    frames = list(state["frames"])
-    skip = state["skip"]
-    x_in = frames[n_past - 1]
-    for i in range(n_past, n_eval):
-        keep = last_frame_skip or skip is None
-        h, sk = _encode(encoder, x_in, 0 if keep else x_in.shape[0])
-        if keep:
-            skip = sk
-        if i == n_past and not last_frame_skip and not decoder.training:
-            fused.declare_frozen_skips(skip)
-        h_pred = frame_predictor(h)
-        pred = likelihood(gp_layer(h_pred.transpose(0, 1).view(gp_layer.num_dims, h_pred.shape[0], 1)))
-        x_in = decoder([pred.mean.transpose(0, 1), skip])
-        frames.append(x_in)
-    return frames
+    return _predict_from(state, encoder, decoder, frame_predictor, n_past, n_eval, last_frame_skip,
+                         lambda i, h, h_pred: likelihood(gp_layer(gp_input(gp_layer, h_pred))).mean.transpose(0, 1))
 
 
 # ---- GPtrigger_gen (generate_frames.py:220-298) without a host round trip per step --------------------------------------------
@@ -303,7 +238,7 @@ def trigger_warmup(encoder, decoder, frame_predictor, gp_layer, likelihood, x0, 
             skip = sk
         if i == skip_steps - 1 and not decoder.training:
             fused.declare_frozen_skips(skip)            # final from here on (:268-271)
-        pred = likelihood(gp_layer(h.transpose(0, 1).view(gp_layer.num_dims, b, 1)))
+        pred = likelihood(gp_layer(gp_input(gp_layer, h)))
         norms.append(ops.gp_var_norms(pred.variance))
         x_in = decoder([frame_predictor(h), skip])      # generation(): its encoder call is the one above (eval mode)
         frames.append(x_in)
@@ -323,7 +258,7 @@ def trigger_body(state: dict, encoder, decoder, frame_predictor, gp_layer, likel
     x_in, skip, frames = state["x_in"], state["skip"], []
     for i in range(warmup, total):
         h, _ = _encode(encoder, x_in, b)
-        pred = likelihood(gp_layer(h.transpose(0, 1).view(gp_layer.num_dims, b, 1)))
+        pred = likelihood(gp_layer(gp_input(gp_layer, h)))
         z = pred.rsample(eps_all[i - warmup])                       # (D,B); the same launch leaves the variance
         ops.gp_trigger_step(pred.variance, probe, ctx, coef, log["flag"], log["values"], log["thresholds"], log["flags"], i)
         old = [t for hc in frame_predictor.hidden for t in hc]
@@ -356,33 +291,19 @@ class GraphedTrigger:
         self.eps = torch.zeros(max(1, total - warmup), d, b, device=dev)
         self.ctx = torch.zeros(warmup, device=dev)
         self.log = trigger_log(total, dev)
-        side = pooled_stream("warmup")
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):      # first-launch work (weight packs, LDS attributes, BN folds) must not be captured
-            st = self._warm()
-            self._body(st)
-        torch.cuda.current_stream().wait_stream(side)
-        ops.clear_skip_proj_cache()
-        fused.clear_skip_hoist_cache()
-        self.warm_graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.warm_graph, **CAPTURE_KW):
-            self.state = self._warm()
-            self.warm_stack = torch.stack(self.state["frames"])
-        self._keep_w = snapshot_eager_caches()
-        # (the skip-dependent cache entries the warm-up graph created stay while the body is captured: it reads those buffers)
-        self.body_graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.body_graph, **CAPTURE_KW):
-            fr = self._body(self.state)
-            self.body_stack = torch.stack(fr) if fr else None
-        self._keep_b = snapshot_eager_caches()
-        ops.clear_skip_proj_cache()
-        fused.clear_skip_hoist_cache()
+        graphs.warm_up(lambda: self._body(self._warm()[0]))
+        with graphs.skip_scope():
+            self.warm_graph, (self.state, self.warm_stack), self._keep_w = graphs.capture(self._warm)
+            # (the skip-dependent cache entries the warm-up graph created stay while the body is captured: it reads those buffers)
+            self.body_graph, self.body_stack, self._keep_b = graphs.capture(lambda: self._body(self.state))
 
     def _warm(self):
-        return trigger_warmup(*self._mods, self.x0, self.warmup, self.skip_steps)
+        st = trigger_warmup(*self._mods, self.x0, self.warmup, self.skip_steps)
+        return st, torch.stack(st["frames"])
 
     def _body(self, st):
-        return trigger_body(st, *self._mods, self.ctx, self.coef, self.eps, self.log, self.warmup, self.total, self.probe)
+        fr = trigger_body(st, *self._mods, self.ctx, self.coef, self.eps, self.log, self.warmup, self.total, self.probe)
+        return torch.stack(fr) if fr else None
 
     def warm(self, x0) -> None:
         self.x0.copy_(x0)
@@ -427,20 +348,10 @@ class GraphedRollout:
         self.eps = {i: torch.randn(gp_layer.num_dims, x[0].shape[0], device=x[0].device)
                     for i in (trigger_steps(n_past, n_eval, period) if period else [])}
         self._kw["eps_by_step"] = self.eps
-        side = pooled_stream("warmup")
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(warmup):   # first-launch work (weight packs, LDS attributes, BN folds) must not be captured
-                sample_rollout(*self._args, self.static_x, **self._kw)
-        torch.cuda.current_stream().wait_stream(side)
-        self.graph = torch.cuda.CUDAGraph()
-        ops.clear_skip_proj_cache()   # nothing cached eagerly may be referenced by the graph ...
-        fused.clear_skip_hoist_cache()
-        with torch.cuda.graph(self.graph, **CAPTURE_KW):
-            self.frames = sample_rollout(*self._args, self.static_x, **self._kw)
-        self._keepalive = snapshot_eager_caches()   # eager tensors the graph reads by raw pointer live as long as it does
-        ops.clear_skip_proj_cache()   # ... and nothing from the graph's pool by later eager calls
-        fused.clear_skip_hoist_cache()
+        run = lambda: sample_rollout(*self._args, self.static_x, **self._kw)   # noqa: E731
+        graphs.warm_up(run, warmup)
+        with graphs.skip_scope():
+            self.graph, self.frames, self._keepalive = graphs.capture(run)
 
     def __call__(self, x: Optional[Sequence[torch.Tensor]] = None,
                  eps_by_step: Optional[Dict[int, torch.Tensor]] = None) -> List[torch.Tensor]:
@@ -481,7 +392,7 @@ class ConcurrentRollouts:
         with ops.tile_policy(self.energy_tiles):
             self.rollouts = [GraphedRollout(encoder, decoder, frame_predictor, gp_layer, likelihood, x, n_past, n_eval,
                                             last_frame_skip, period) for _ in range(inflight)]
-        self.streams = [pooled_stream("chain", k) for k in range(inflight)]
+        self.streams = [graphs.pooled_stream("chain", k) for k in range(inflight)]
         self._next = 0
 
     def run(self, n: int, x: Optional[Sequence[torch.Tensor]] = None, chains: Optional[int] = None) -> List[List[torch.Tensor]]:
@@ -545,56 +456,36 @@ class GraphedSampler:
         self.chains = []
         for k in range(max(1, inflight)):
             self.chains.append({"eps": {i: torch.zeros(D, B, device=dev) for i in self.steps},
-                                "stream": pooled_stream("chain", k)})
-        self.post_stream = pooled_stream("post")
-        side = pooled_stream("warmup")
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):      # first-launch work (weight packs, LDS attributes, BN folds) must not be captured
+                                "stream": graphs.pooled_stream("chain", k)})
+        self.post_stream = graphs.pooled_stream("post")
+
+        def eager():
             self.b = {"state": self._condition()}
             self.b["post"] = self._posterior()
             self.b["pre"] = self._prefix() if self.share else None
             self._body(self.chains[0])
-            self.b = None
-        torch.cuda.current_stream().wait_stream(side)
-        ops.clear_skip_proj_cache()
-        fused.clear_skip_hoist_cache()
+        graphs.warm_up(eager)
         # Three graphs for the sample-independent part: the conditioning, then - independent of each other, replayed on two
         # streams - the posterior rollout's prediction steps and the samples' shared prefix.  The conditioning graph comes
         # first: the skip-dependent tensors it creates (hoisted skip halves) and those of the first decoder call after it (the
         # skip's share of the last projection) stay in the caches while the later graphs are captured, so those read buffers
         # written once per batch, before they replay, instead of recomputing them per sample.
-        shared = (fused._skip_seen, fused._frozen, ops._SKIP_PROJ_CACHE)
-
-        def capture(fn):
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, **CAPTURE_KW):
-                out = fn()
-            return g, out, snapshot_eager_caches()
-
-        def keys():
-            return [set(c) for c in shared]
-
-        def drop_new(keep):     # what a graph added belongs to THAT graph's pool and replays: not for the next capture
-            for cache, k0 in zip(shared, keep):
-                for k in [k for k in cache if k not in k0]:
-                    del cache[k]
-
+        # What a graph added belongs to THAT graph's pool and replays: where the next capture must not see it, it is dropped.
         self.b = {}
-        self.cond_graph, self.b["state"], self._keep_c = capture(self._condition)
-        after_cond = keys()
-        # the posterior graph replays BESIDE the prefix graph (another stream): it may read what the conditioning graph wrote,
-        # never what the prefix graph writes
-        self.post_graph, self.b["post"], self._keep_o = capture(self._posterior)
-        drop_new(after_cond)
-        self.pre_graph, self.b["pre"] = None, None
-        if self.share:
-            self.pre_graph, self.b["pre"], self._keep_p = capture(self._prefix)
-        main_stream = keys()    # written by graphs that replay on the main stream before any sample graph
-        for ch in (() if self.t0 == n_eval else self.chains):
-            ch["graph"], (ch["frames"], ch["ssim"], ch["psnr"]), ch["keepalive"] = capture(lambda: self._body(ch))
-            drop_new(main_stream)
-        ops.clear_skip_proj_cache()
-        fused.clear_skip_hoist_cache()
+        with graphs.skip_scope() as skips:
+            self.cond_graph, self.b["state"], self._keep_c = graphs.capture(self._condition)
+            after_cond = skips.mark()
+            # the posterior graph replays BESIDE the prefix graph (another stream): it may read what the conditioning graph
+            # wrote, never what the prefix graph writes
+            self.post_graph, self.b["post"], self._keep_o = graphs.capture(self._posterior)
+            skips.drop_since(after_cond)
+            self.pre_graph, self.b["pre"] = None, None
+            if self.share:
+                self.pre_graph, self.b["pre"], self._keep_p = graphs.capture(self._prefix)
+            main_stream = skips.mark()    # written by graphs that replay on the main stream before any sample graph
+            for ch in (() if self.t0 == n_eval else self.chains):
+                ch["graph"], (ch["frames"], ch["ssim"], ch["psnr"]), ch["keepalive"] = graphs.capture(lambda: self._body(ch))
+                skips.drop_since(main_stream)
 
     def _metrics(self, frames, lo, hi):
         m = [ops.eval_frames(self.x[t], frames[t]) for t in range(lo, hi)]

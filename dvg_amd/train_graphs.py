@@ -6,7 +6,8 @@ import sys
 
 import torch
 
-from . import fused
+from . import fused, graphs
+
 
 class GraphedIteration:
     """`Trainer.iteration` as ONE hipGraph (torch.cuda.CUDAGraph): forward, the three backward passes, the gradient
@@ -42,28 +43,29 @@ class GraphedIteration:
         torch.cuda.synchronize()
 
     def _capture(self, x):
-        from dvg_amd.rollout import snapshot_eager_caches
         tr = self.tr
         self._release()
         self.static_x = [t.clone() for t in x]
         for o in tr.optimizers():
             o.begin_capture()
         torch.cuda.synchronize()
-        self.graph = torch.cuda.CUDAGraph()
-        self._capture_body(self.static_x)
+        self._record()
         for o in tr.optimizers():
             o.end_capture()                          # every group a captured zero_grads() ticked was stepped in the capture
-        self._keepalive = snapshot_eager_caches()    # eager tensors the graph reads by raw pointer stay alive with it
+        self._keepalive = graphs.snapshot_eager_caches()    # eager tensors the graph reads by raw pointer stay alive with it
         self.sig = self._signature(x)
 
-    def _capture_body(self, static_x):
+    def _record(self):
+        with graphs.capturing() as self.graph:
+            self._body()
+
+    def _body(self):
         tr = self.tr
-        with torch.cuda.graph(self.graph, capture_error_mode="thread_local"):   # see rollout.CAPTURE_KW
-            mse_latent, loss = tr._train_model_dev(self.static_x)
-            fp = gp = None
-            if tr.opt.ft:
-                fp, gp = tr._finetune_dev(self.static_x)
-            self.outs = (mse_latent, loss, fp, gp)
+        mse_latent, loss = tr._train_model_dev(self.static_x)
+        fp = gp = None
+        if tr.opt.ft:
+            fp, gp = tr._finetune_dev(self.static_x)
+        self.outs = (mse_latent, loss, fp, gp)
 
     def __call__(self, x):
         tr = self.tr
@@ -84,8 +86,7 @@ class GraphedIteration:
                 # ... except the module-level caches: a miss DURING the capture stored a tensor from the graph's pool whose
                 # fill was recorded, never run, under the current parameter version.  The eager iteration below must not
                 # hit those entries (never-written, freed memory): drop every version-keyed cache, rebuilt on demand.
-                from dvg_amd.rollout import drop_version_keyed_caches
-                drop_version_keyed_caches()
+                graphs.drop_version_keyed_caches()
                 tr._ft_cache = None
                 tr.frame_predictor.hidden = None
                 print(f"train: hipGraph capture failed ({type(e).__name__}: {str(e)[:200]}); continuing with eager "
@@ -124,24 +125,13 @@ class SegmentedIteration(GraphedIteration):
         self.items, self._pool, self._cur, self._ctx = [], None, None, None
         super()._release()
 
-    def _capture(self, x):
-        from dvg_amd.rollout import snapshot_eager_caches
+    def _record(self):
         tr = self.tr
-        self._release()
-        self.static_x = [t.clone() for t in x]
-        for o in tr.optimizers():
-            o.begin_capture()
-        torch.cuda.synchronize()
-        seg = self
-        tr._segmenter = seg
+        tr._segmenter = self
         try:
-            seg._begin()
-            mse_latent, loss = tr._train_model_dev(self.static_x)
-            fp = gp = None
-            if tr.opt.ft:
-                fp, gp = tr._finetune_dev(self.static_x)
-            self.outs = (mse_latent, loss, fp, gp)
-            seg._end()
+            self._begin()
+            self._body()
+            self._end()
         except BaseException:
             if self._ctx is not None:          # a segment is still being captured: end the capture before unwinding
                 ctx, self._ctx, self._cur = self._ctx, None, None
@@ -152,22 +142,11 @@ class SegmentedIteration(GraphedIteration):
             raise
         finally:
             tr._segmenter = None
-        for o in tr.optimizers():
-            o.end_capture()
         self.graph = [g for kind, g in self.items if kind == "graph"]   # (truthy: "captured"; replay goes through items)
-        self._keepalive = snapshot_eager_caches()
-        self.sig = self._signature(x)
 
     def _begin(self):
-        self._cur = torch.cuda.CUDAGraph()
-        # thread_local: calls made by OTHER threads while a segment is being captured (the c10d watchdog polling the events
-        # of earlier eager collectives) are none of the capture's business; the autograd engine's worker threads still
-        # launch into the capturing stream
-        kw = {"capture_error_mode": "thread_local"}
-        if self._pool is not None:
-            kw["pool"] = self._pool
-        self._ctx = torch.cuda.graph(self._cur, **kw)
-        self._ctx.__enter__()
+        self._ctx = graphs.capturing(self._pool)
+        self._cur = self._ctx.__enter__()
 
     def _end(self):
         self._ctx.__exit__(None, None, None)

@@ -33,7 +33,7 @@ sys.path.insert(0, ROOT)
 import utils  # noqa: E402
 from dvg_amd import ops, viz  # noqa: E402
 from dvg_amd.data import SyntheticMovingMNIST, synthetic_video  # noqa: E402
-from dvg_amd.rollout import (GraphedSampler, GraphedTrigger, condition, posterior_from, sample_from, sample_rollout,  # noqa: E402
+from dvg_amd.rollout import (GraphedSampler, GraphedTrigger, condition, gp_input, posterior_from, sample_from, sample_rollout,  # noqa: E402
                              trigger_body, trigger_log, trigger_warmup)
 from gp_models import GaussianLikelihood, GPRegressionLayer1  # noqa: E402
 
@@ -96,7 +96,7 @@ class Generator:
         self._layouts = {}
 
     def _gp(self, h):
-        return self.likelihood(self.gp_layer(h.transpose(0, 1).view(self.opt.g_dim, h.shape[0], 1)))
+        return self.likelihood(self.gp_layer(gp_input(self.gp_layer, h)))
 
     @torch.no_grad()
     def make_gifs(self, x, nsample, eps_by_sample=None):

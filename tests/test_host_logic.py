@@ -406,11 +406,12 @@ def test_environment_switches_are_the_documented_ten_and_no_file_is_a_monolith()
 
 
 def test_pooled_streams_are_made_once_per_role_and_index(monkeypatch):
-    """rollout.pooled_stream: torch hands streams out of a pool of 32 per device, round-robin; graph holders that made fresh ones
+    """graphs.pooled_stream: torch hands streams out of a pool of 32 per device, round-robin; graph holders that made fresh ones
     (six per ConcurrentRollouts) wrapped around it in bench.py and hipGraphLaunch crashed (r06).  Every (device, role, index) stream is
     made once per process and shared by all holders - checked here without a GPU, on a stand-in for torch.cuda.Stream."""
+    import inspect
     import torch
-    from dvg_amd import rollout
+    from dvg_amd import graphs, rollout
     made = []
 
     class FakeStream:
@@ -418,15 +419,17 @@ def test_pooled_streams_are_made_once_per_role_and_index(monkeypatch):
             made.append(self)
     monkeypatch.setattr(torch.cuda, "Stream", FakeStream)
     monkeypatch.setattr(torch.cuda, "current_device", lambda: 0)
-    monkeypatch.setattr(rollout, "_streams", {})
-    chains = [[rollout.pooled_stream("chain", k) for k in range(3)] for _ in range(14)]     # 14 holders x 3 chains
-    warm = [rollout.pooled_stream("warmup") for _ in range(14 * 3)]
+    monkeypatch.setattr(graphs, "_streams", {})
+    chains = [[graphs.pooled_stream("chain", k) for k in range(3)] for _ in range(14)]     # 14 holders x 3 chains
+    warm = [graphs.pooled_stream("warmup") for _ in range(14 * 3)]
     assert all(c[k] is chains[0][k] for c in chains for k in range(3)) and len({id(s) for s in chains[0]}) == 3
     assert all(w is warm[0] for w in warm) and warm[0] not in chains[0]
-    assert rollout._hoist_stream() is rollout.pooled_stream("hoist")
+    hoist = graphs.pooled_stream("hoist")       # the hoist stream of rollout.condition() is the pooled one
+    assert 'graphs.pooled_stream("hoist")' in inspect.getsource(rollout.condition) and "cuda.Stream(" not in inspect.getsource(rollout)
+    assert hoist is graphs.pooled_stream("hoist") and hoist is not warm[0] and hoist not in chains[0]
     assert len(made) == 5
     monkeypatch.setattr(torch.cuda, "current_device", lambda: 1)          # another device: its own streams
-    assert rollout.pooled_stream("chain", 0) is not chains[0][0] and len(made) == 6
+    assert graphs.pooled_stream("chain", 0) is not chains[0][0] and len(made) == 6
 
 
 def test_bench_dump_outputs_arguments_and_size_budget(tmp_path, monkeypatch):
@@ -519,15 +522,15 @@ def test_derived_rebuilds_on_version_or_pointer_change_and_dies_with_its_owner()
 
 
 def test_every_module_level_cache_is_registered_dropped_and_snapshotted(monkeypatch):
-    """The registry of _derived: rollout.snapshot_eager_caches() holds every tensor of every registered cache,
-    rollout.drop_version_keyed_caches() empties every one of them and the deferred weight-gradient queues.  The names are
+    """The registry of _derived: graphs.snapshot_eager_caches() holds every tensor of every registered cache,
+    graphs.drop_version_keyed_caches() empties every one of them and the deferred weight-gradient queues.  The names are
     listed literally: a new module-level cache means a new name here."""
-    from dvg_amd import _derived, fused, ops, rollout
+    from dvg_amd import _derived, fused, graphs, ops
     from dvg_amd import autograd as ag
     from dvg_amd.ops import edge
     assert set(_derived.registered()) == {"derived", "zero_state", "splitk_ws", "group_maps", "skip_proj", "loss_weights",
                                           "skip_hoist"}
-    rollout.drop_version_keyed_caches()
+    graphs.drop_version_keyed_caches()
     made = []
 
     def t():
@@ -559,30 +562,46 @@ def test_every_module_level_cache_is_registered_dropped_and_snapshotted(monkeypa
     fused.declare_frozen_skips([skip])
     _, s_half = fused._hoisted_skip(conv, x, skip, lambda ps: t())
     want = got + [z, ws, gmap, proj, lw, s_half]
-    held = {id(k) for k in rollout.snapshot_eager_caches()}
+    held = {id(k) for k in graphs.snapshot_eager_caches()}
     assert all(id(w) in held for w in want), [i for i, w in enumerate(want) if id(w) not in held]
     ag._wgrad_queues["k"] = [object()]
     ag._dense_queues["k"] = [object()]
     ag._wgrad_flush_queued = True
-    rollout.drop_version_keyed_caches()
+    graphs.drop_version_keyed_caches()
     for name, cache in (("derived", _derived._store), ("zero_state", _derived._zero_states), ("splitk_ws", ops._SPLITK_WS),
                         ("group_maps", ops._MAP_CACHE), ("skip_proj", ops._SKIP_PROJ_CACHE), ("loss_weights", ops._LOSS_W),
                         ("skip_hoist", fused._skip_seen), ("skip_hoist", fused._frozen)):
         assert len(cache) == 0, name
-    assert rollout.snapshot_eager_caches() == []
+    assert graphs.snapshot_eager_caches() == []
     assert not ag._wgrad_queues and not ag._dense_queues and ag._wgrad_flush_queued is False
     assert fused.packed_weight(conv) is not got[0]                # rebuilt on demand
-    rollout.drop_version_keyed_caches()
+    graphs.drop_version_keyed_caches()
+
+
+def _code_only(path):
+    """The source of a Python file without its docstrings and comments (they may speak of anything)."""
+    import ast
+    import io
+    import tokenize
+    src = open(path).read()
+    lines = src.splitlines(keepends=True)
+    for node in ast.walk(ast.parse(src)):
+        body = getattr(node, "body", None)
+        if (isinstance(node, (ast.Module, ast.ClassDef, ast.FunctionDef, ast.AsyncFunctionDef)) and body and
+                isinstance(body[0], ast.Expr) and isinstance(body[0].value, ast.Constant) and isinstance(body[0].value.value, str)):
+            for ln in range(body[0].lineno - 1, body[0].end_lineno):
+                lines[ln] = "\n"
+    toks = [t for t in tokenize.generate_tokens(io.StringIO("".join(lines)).readline) if t.type != tokenize.COMMENT]
+    return tokenize.untokenize(toks)
 
 
 def test_version_counters_are_read_in_one_place_and_the_cache_walkers_name_no_private_dict():
     """`(data_ptr, _version)` bookkeeping lives in dvg_amd/_derived.py; the files below read `._version` for something that
-    is not a parameter-derived cache.  rollout's two functions over all caches go through the registry: they name no
-    underscore attribute of another module."""
+    is not a parameter-derived cache.  The capture protocol (graphs.py) and the graph holders of rollout.py go through the
+    registry and the public functions of the modules that own the caches: in their whole source they name no underscore
+    attribute of another module."""
     import glob
-    import inspect
     import re
-    from dvg_amd import rollout
     allowed = {
         "_derived.py": "the helper itself",
         "fused.py": "skip sightings: activation-keyed (tensor identity + version of the SKIP), another life cycle",
@@ -594,7 +613,149 @@ def test_version_counters_are_read_in_one_place_and_the_cache_walkers_name_no_pr
     readers = {os.path.relpath(f, base) for f in glob.glob(os.path.join(base, "**", "*.py"), recursive=True)
                if re.search(r"\._version\b", open(f).read())}
     assert readers == set(allowed), sorted(readers ^ set(allowed))
-    for fn in (rollout.drop_version_keyed_caches, rollout.snapshot_eager_caches):
-        src = inspect.getsource(fn)
-        src = src[src.index('"""', src.index('"""') + 3) + 3:]          # the body: the docstring may speak of anything
-        assert not re.search(r"\b(ag|fused|ops|lstm_mod)\._\w", src), src
+    for name in ("graphs.py", "rollout.py"):
+        src = _code_only(os.path.join(base, name))
+        assert "def " in src and "import" in src
+        hit = re.search(r"\b(ag|autograd|fused|ops|edge|lstm_mod|graphs|_derived)\._\w+", src)
+        assert not hit, (name, hit.group(0))
+
+
+def test_the_capture_protocol_is_written_in_graphs_only():
+    """Inside dvg_amd/, graph objects are made, captures are opened, the capture error mode is named and the skip-dependent
+    caches are cleared in graphs.py and nowhere else (the two `def`s stay where the caches live)."""
+    import glob
+    import re
+    base = os.path.join(ROOT, "dvg_amd")
+    pats = {"CUDAGraph(": r"torch\.cuda\.CUDAGraph\(", "graph(": r"torch\.cuda\.graph\(", "capture_error_mode": r"capture_error_mode",
+            "clear_skip_*_cache()": r"(?<!def )\bclear_skip_(hoist|proj)_cache\("}
+    found = {k: set() for k in pats}
+    files = glob.glob(os.path.join(base, "**", "*.py"), recursive=True)
+    assert len(files) > 20
+    for f in files:
+        src = open(f).read()
+        for k, pat in pats.items():
+            if re.search(pat, src):
+                found[k].add(os.path.relpath(f, base))
+    assert all(v == {"graphs.py"} for v in found.values()), found
+
+
+class _FakeGraph:
+    made = []
+
+    def __init__(self):
+        _FakeGraph.made.append(self)
+
+
+class _FakeCapture:
+    """Stand-in for torch.cuda.graph: remembers how it was opened and closed, swallows nothing."""
+    log = []
+
+    def __init__(self, graph, **kw):
+        self.graph, self.kw = graph, kw
+
+    def __enter__(self):
+        _FakeCapture.log.append(("enter", self.graph, self.kw))
+
+    def __exit__(self, et, ev, tb):
+        _FakeCapture.log.append(("exit", self.graph, et))
+        return False
+
+
+def test_a_capture_that_raises_drops_every_cache_and_a_successful_one_keeps_them_alive(monkeypatch):
+    """graphs.capture, rule 5: an fn that fills a registered cache, queues a deferred weight gradient and then raises - the
+    same exception comes out, every registered cache and the deferred weight-gradient queues are empty afterwards (their
+    tensors would live in the abandoned pool, never written).  Rule 4: a capture that succeeds returns a keepalive that holds
+    what fn cached.  torch.cuda.CUDAGraph / torch.cuda.graph / the stream calls of warm_up are stand-ins: no GPU."""
+    from dvg_amd import _derived, graphs
+    from dvg_amd import autograd as ag
+
+    class FakeStream:
+        def wait_stream(self, other):
+            pass
+    monkeypatch.setattr(_FakeGraph, "made", [])
+    monkeypatch.setattr(_FakeCapture, "log", [])
+    monkeypatch.setattr(torch.cuda, "CUDAGraph", _FakeGraph)
+    monkeypatch.setattr(torch.cuda, "graph", _FakeCapture)
+    monkeypatch.setattr(torch.cuda, "Stream", FakeStream)
+    monkeypatch.setattr(torch.cuda, "current_device", lambda: 0)
+    monkeypatch.setattr(torch.cuda, "current_stream", lambda: FakeStream())
+    monkeypatch.setattr(torch.cuda, "stream", lambda s: __import__("contextlib").nullcontext())
+    monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)
+    monkeypatch.setattr(graphs, "_streams", {})
+    graphs.drop_version_keyed_caches()
+    conv = torch.nn.Conv2d(2, 3, 3)
+    cached = []
+
+    def fill():
+        cached.append(_derived.derived(conv, "t", (conv.weight,), lambda: torch.zeros(3)))
+        z = _derived.zero_state(2, 3, torch.device("cpu"))
+        return z
+    calls = []
+    assert graphs.warm_up(lambda: calls.append(1) or len(calls), times=3) == 3 and calls == [1, 1, 1]
+    assert graphs.warm_up(fill) is _derived.zero_state(2, 3, torch.device("cpu"))
+
+    class Boom(RuntimeError):
+        pass
+    boom = Boom("out of memory for the private pool")
+
+    def failing():
+        fill()
+        ag._wgrad_queues["k"] = [object()]
+        ag._dense_queues["k"] = [object()]
+        ag._wgrad_flush_queued = True
+        raise boom
+    with pytest.raises(Boom) as info:
+        graphs.capture(failing)
+    assert info.value is boom
+    assert [e[0] for e in _FakeCapture.log] == ["enter", "exit"] and _FakeCapture.log[1][2] is Boom
+    assert _FakeCapture.log[0][2] == {"capture_error_mode": "thread_local"} == graphs.CAPTURE_KW
+    assert len(_derived._store) == 0 and len(_derived._zero_states) == 0
+    assert _derived.snapshot() == [] and graphs.snapshot_eager_caches() == []
+    assert not ag._wgrad_queues and not ag._dense_queues and ag._wgrad_flush_queued is False
+    # the context-manager form alone (SegmentedIteration's segments): the same on a raise, the shared pool handed on
+    with pytest.raises(Boom):
+        with graphs.capturing(pool="POOL") as g:
+            assert g is _FakeGraph.made[-1] and _FakeCapture.log[-1] == ("enter", g, {"capture_error_mode": "thread_local", "pool": "POOL"})
+            failing()
+    assert _derived.snapshot() == [] and not ag._wgrad_queues and ag._wgrad_flush_queued is False
+    assert graphs.CAPTURE_KW == {"capture_error_mode": "thread_local"}          # (not written to)
+    # a capture that succeeds: graph, result, and a keepalive that holds the tensors fn cached
+    del cached[:]
+    g, out, keep = graphs.capture(fill)
+    assert g is _FakeGraph.made[-1] and _FakeCapture.log[-1] == ("exit", g, None)
+    assert out is _derived.zero_state(2, 3, torch.device("cpu"))
+    assert {id(cached[0]), id(out)} <= {id(t) for t in keep}
+    graphs.drop_version_keyed_caches()
+    assert any(t is cached[0] for t in keep) and _derived.snapshot() == []       # the holder's references outlive the caches
+
+
+def test_skip_scope_clears_around_a_group_and_drops_what_one_capture_added():
+    """graphs.skip_scope, rule 2: the skip-keyed caches are empty on entry and after exit; inside, entries stay from one
+    capture to the next, and drop_since(mark) forgets exactly the keys added after the mark (GraphedSampler: what the
+    posterior graph added goes, what the conditioning graph added stays)."""
+    from dvg_amd import _derived, fused, graphs, ops
+    from dvg_amd.ops import edge
+    dicts = (fused._skip_seen, fused._frozen, edge._SKIP_PROJ_CACHE)
+    assert all(any(d is k for k in _derived._skip_keyed) for d in dicts) and len(_derived._skip_keyed) == 3
+    a, b = torch.zeros(1), torch.zeros(1)
+    fused.declare_frozen_skips([a])
+    edge._SKIP_PROJ_CACHE[id(a)] = "eager"
+    with graphs.skip_scope() as skips:
+        assert not any(dicts)
+        fused.declare_frozen_skips([a])
+        fused._skip_seen[(1, id(a))] = "cond"
+        mark = skips.mark()
+        fused.declare_frozen_skips([b])
+        fused._skip_seen[(1, id(b))] = "post"
+        edge._SKIP_PROJ_CACHE[id(b)] = "post"
+        skips.drop_since(mark)
+        assert set(fused._frozen) == {id(a)} and fused._skip_seen == {(1, id(a)): "cond"} and not edge._SKIP_PROJ_CACHE
+        skips.drop_since(mark)
+        assert set(fused._frozen) == {id(a)}
+    assert not any(dicts)
+    with pytest.raises(KeyError):
+        with graphs.skip_scope():
+            fused.declare_frozen_skips([a])
+            raise KeyError("x")
+    assert not any(dicts)
+    assert ops.clear_skip_proj_cache is edge.clear_skip_proj_cache

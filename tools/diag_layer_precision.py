@@ -50,7 +50,7 @@ def main():
 
     def run():
         fused.clear_skip_hoist_cache()
-        from dvg_amd.rollout import drop_version_keyed_caches
+        from dvg_amd.graphs import drop_version_keyed_caches
         drop_version_keyed_caches()
         with torch.no_grad():
             h, sk = enc(xd)

@@ -169,7 +169,7 @@ def main():
         if a.noise_child == "train" and r == 1:
             print("ready", flush=True)
         if a.drop_caches:
-            from dvg_amd.rollout import drop_version_keyed_caches
+            from dvg_amd.graphs import drop_version_keyed_caches
             drop_version_keyed_caches()
         tr.optimizer.zero_grad()      # the GP / likelihood gradients, which train_model leaves to accumulate (reference behaviour)
         tr._train_model_dev(x)

@@ -45,6 +45,7 @@ from dvg_amd import fused, parallel, viz  # noqa: E402
 from dvg_amd.data import SyntheticMovingMNIST, make_batch_generator, synthetic_video  # noqa: E402,F401
 from dvg_amd.models.gp_models import GaussianLikelihood, GPRegressionLayer1, VariationalELBO  # noqa: E402
 from dvg_amd.optim import FlatArena, FusedAdam, zero_grads  # noqa: E402
+from dvg_amd.rollout import frames_as_batch, gp_input  # noqa: E402
 
 
 def build_parser():
@@ -252,9 +253,6 @@ class Trainer:
         return (self.lstm_sequence and self.time_batched and self.frame_predictor.training and torch.is_grad_enabled()
                 and sequence_applies(self.frame_predictor))
 
-    def _gp_in(self, h):
-        return h.transpose(0, 1).view(self.opt.g_dim, h.shape[0], 1)
-
     def _skip_rule(self, i, enc_out, skip):
         """train.py:158-161,184-187,217-220: skip is refreshed only while i < n_past (or last_frame_skip)."""
         if self.opt.last_frame_skip or i < self.opt.n_past:
@@ -287,12 +285,8 @@ class Trainer:
         pass counts of the per-frame path (first / last frame once, middle frames twice).  Same losses, gradients and
         buffers up to fp32 summation order (tests/test_gpu_train.py); every conv launch is T x larger."""
         from dvg_amd.autograd import split_batch
-        from dvg_amd.rollout import _adjacent_view
-        frames = _adjacent_view(list(x[:T]))
-        if frames is None:
-            frames = torch.cat(list(x[:T]), 0)
         with torch.set_grad_enabled(grad), fused.bn_groups(T, (1, 2, 1)):
-            h_all, skips_all = self.encoder(frames)
+            h_all, skips_all = self.encoder(frames_as_batch(list(x[:T])))
         hs = split_batch(h_all, T)
         sks = [split_batch(s, T) for s in skips_all]
         return [(hs[t], [sk[t] for sk in sks]) for t in range(T)]
@@ -372,7 +366,7 @@ class Trainer:
                 # parameter updates, none of the wasted encoder backward.
                 h, skip = self._skip_rule(i, self._enc(enc_all, x, i - 1, g), skip)
                 h_target = self._enc(enc_all, x, i, g)[0].detach()
-                h_pred = self.gp_layer(self._gp_in(h))
+                h_pred = self.gp_layer(gp_input(self.gp_layer, h))
                 max_ll = max_ll - self.mll(h_pred, h_target.transpose(0, 1))
         loss = max_ll.sum()
         loss.backward()
@@ -439,7 +433,6 @@ class Trainer:
         and buffers equal the step-by-step path up to fp32 summation order (tests/test_gpu_train.py)."""
         from dvg_amd import ops
         from dvg_amd.autograd import split_batch
-        from dvg_amd.rollout import _adjacent_view
         opt = self.opt
         T = opt.n_past + opt.n_future
         S = T - 1
@@ -448,9 +441,7 @@ class Trainer:
         zero_grads([self.encoder_optimizer, self.decoder_optimizer, self.frame_predictor_optimizer] +
                    ([] if self.reference_gp_grad_leak else [self.optimizer]))
         self.frame_predictor.hidden = None    # (the step-by-step branch below re-creates it; the sequence form never reads it)
-        frames = _adjacent_view(list(x[:T]))
-        if frames is None:
-            frames = torch.cat(list(x[:T]), 0)
+        frames = frames_as_batch(list(x[:T]))
         with fused.bn_groups(T, (1, 2, 1)):
             h_all, skips_all = self.encoder(frames)
         staged = self.staged_backward
@@ -515,14 +506,17 @@ class Trainer:
             mse, ae_mse, mse_gp = sq[0], sq[1], sq[2]
             loss = 1000 * ae_mse + 0.001 * mse + 0.01 * mse_latent + 0.001 * mse_gp + 0.0001 * max_ll.sum()
             loss.backward()
-        if staged:
+        self._encoder_backward_and_step(
+            [(h_all, h_leaf.grad)] + [(s, l.grad) for s, l in zip(skips_all, sk_leaf) if l.grad is not None] if staged else None)
+        return mse_latent.detach(), loss.detach()
+
+    def _encoder_backward_and_step(self, pairs):
+        """The end of train_model (train.py:240-245).  pairs: with the staged backward, (encoder output, gradient of the loss
+        with respect to it) for every output the decoder / LSTM / GP phase reached; None: backward() went all the way."""
+        if pairs is not None:
+            # gradients of GP, likelihood, LSTM and decoder are final: their all-reduce runs under the encoder phase
             self._ar(("start", "a", (self.rng_gp[0], self.rng_dec[1])))
-            outs, seeds = [h_all], [h_leaf.grad]
-            for s, l in zip(skips_all, sk_leaf):
-                if l.grad is not None:
-                    outs.append(s)
-                    seeds.append(l.grad)
-            torch.autograd.backward(outs, seeds)
+            torch.autograd.backward([t for t, _ in pairs], [g for _, g in pairs])
             self._ar(("start", "b", self.rng_enc), ("finish", "a"), ("finish", "b"))
         else:
             self._ar(("reduce", (self.rng_gp[0], self.rng_enc[1])))
@@ -530,7 +524,6 @@ class Trainer:
         self.encoder_optimizer.step()
         self.decoder_optimizer.step()
         self.optimizer.step()
-        return mse_latent.detach(), loss.detach()
 
     def _train_model_dev(self, x):
         opt = self.opt
@@ -571,7 +564,7 @@ class Trainer:
             with torch.cuda.stream(side if side is not None else cur):
                 h_pred = self.frame_predictor(h)
                 mse_latent = mse_latent + self.mse_latent_criterion(h_pred, h_target)
-                gp_pred = self.gp_layer(self._gp_in(h))
+                gp_pred = self.gp_layer(gp_input(self.gp_layer, h))
                 max_ll = max_ll - self.mll(gp_pred, h_target.transpose(0, 1))
                 gp_mean = gp_pred.mean.transpose(0, 1)
             if side is not None:
@@ -595,23 +588,9 @@ class Trainer:
         loss.backward()
         if side is not None:
             cur.wait_stream(side)              # the latent path's backward kernels
-        if staged:
-            # gradients of GP, likelihood, LSTM and decoder are final: their all-reduce runs under the encoder phase
-            self._ar(("start", "a", (self.rng_gp[0], self.rng_dec[1])))
-            outs, seeds = [], []
-            for (h, sk), (hd, skd) in zip(enc_out, enc_all):
-                for t, d in [(h, hd)] + list(zip(sk, skd)):
-                    if d.grad is not None:
-                        outs.append(t)
-                        seeds.append(d.grad)
-            torch.autograd.backward(outs, seeds)
-            self._ar(("start", "b", self.rng_enc), ("finish", "a"), ("finish", "b"))
-        else:
-            self._ar(("reduce", (self.rng_gp[0], self.rng_enc[1])))
-        self.frame_predictor_optimizer.step()
-        self.encoder_optimizer.step()
-        self.decoder_optimizer.step()
-        self.optimizer.step()
+        self._encoder_backward_and_step(
+            [(t, d.grad) for (h, sk), (hd, skd) in zip(enc_out, enc_all) for t, d in [(h, hd)] + list(zip(sk, skd))
+             if d.grad is not None] if staged else None)
         return mse_latent.detach(), loss.detach()
 
     def _finetune_dev(self, x):
@@ -670,7 +649,7 @@ class Trainer:
                 else:
                     h_pred = self.frame_predictor(h)
                     if i == 10:  # train.py:281: the one GP-sampled step of the qualitative rollout
-                        pred = self.likelihood(self.gp_layer(self._gp_in(h)))
+                        pred = self.likelihood(self.gp_layer(gp_input(self.gp_layer, h)))
                         z = pred.rsample(None if eps_by_sample is None else eps_by_sample[s])
                         x_in = self.decoder([z.transpose(0, 1), skip])
                     else:
