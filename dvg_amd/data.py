@@ -1,4 +1,5 @@
-"""Synthetic stand-ins for the datasets of the reference (no network, no torchvision here).
+"""The input pipeline: synthetic stand-ins for the datasets of the reference, and `make_batch_generator`, which also serves
+KTH / BAIR / UCF clips from `--data_root` (dvg_amd/datasets.py).
 
 `SyntheticMovingMNIST` follows the trajectory logic of data/moving_mnist.py:38-91 exactly —
 `num_digits` 32x32 sprites on a 64x64 canvas, start ~ randint(32), velocity ~ randint(-4,5),
@@ -12,6 +13,7 @@ import sys
 import numpy as np
 import torch
 
+from . import datasets
 from .utils import normalize_data
 
 
@@ -139,15 +141,40 @@ def synthetic_video(batch, seq_len, channels, res, seed=1) -> torch.Tensor:
     return torch.from_numpy(np.clip(drift, 0, 1, out=drift))
 
 
-def make_batch_generator(opt, seq_len, seed, device=None):
+def make_batch_generator(opt, seq_len, seed, device=None, train=True):
     """Yields `load()` callables: the host half of a batch has been drawn when the callable is yielded, calling it (on the
     thread that owns the GPU stream) puts the batch on the device as normalize_data's list of T x (B,C,H,W) frames.
-    smmnist: the host draws the integer trajectories, the device composites them (bit-identical to the host batch).
-    `--data_root` is NOT read: there are no dataset files (nor torchvision / network) in this environment.  smmnist is
-    the reference's trajectory generator over seeded in-repo sprites; every other dataset name must be acknowledged with
-    --synthetic_data, otherwise a reference command line would silently 'train' on noise."""
+    smmnist: the host draws the integer trajectories, the device composites them (bit-identical to the host batch); it is
+    the reference's trajectory generator over seeded in-repo sprites.
+    kth | bair | ucf: the `train` / test split under `--data_root` is indexed and decoded once into a device frame pool
+    (dvg_amd/datasets.py) BEFORE this returns - a missing tree is a SystemExit here, on the caller's thread; the host half
+    then draws `local_batch` clips like the reference's loaders, the callable uploads the B pool indices and gathers the
+    clips on the current stream (dvg_clip_gather_u8).  With --synthetic_data those names train on random textured clips of
+    their shape instead."""
+    if opt.dataset in datasets.REAL_DATASETS and not getattr(opt, 'synthetic_data', False):
+        return _clip_batches(opt, seq_len, seed, device or torch.device('cuda'), train)
+    return _synthetic_batches(opt, seq_len, seed, device)
+
+
+def _clip_batches(opt, seq_len, seed, device, train):
+    index = datasets.open_index(opt.dataset, opt.data_root, train, opt.image_width)
+    sampler = datasets.make_sampler(index, seq_len, seed)
+    pool = datasets.build_pool(index, opt.image_width, device, getattr(opt, 'data_threads', 5))
+    if opt.channels != pool.shape[3] and not (opt.channels == 1 and pool.shape[3] == 3):
+        raise SystemExit(f"dataset: --channels {opt.channels} from {opt.dataset} frames of {pool.shape[3]} channel(s) under "
+                         f"{opt.data_root!r}")
+
+    def batches():
+        from . import ops
+        while True:
+            first = np.array([sampler.draw()[0] for _ in range(opt.local_batch)], np.int64)
+            yield lambda first=first: list(ops.clip_gather(pool, first, seq_len, opt.channels).unbind(0))
+    return batches()
+
+
+def _synthetic_batches(opt, seq_len, seed, device):
     if opt.dataset != 'smmnist' and not getattr(opt, 'synthetic_data', False):
-        raise SystemExit(f"train.py: no loader for --dataset {opt.dataset} here (--data_root {opt.data_root!r} is not read). "
+        raise SystemExit(f"train.py: no loader for --dataset {opt.dataset} (kth | bair | ucf read --data_root). "
                          "Pass --synthetic_data to train on synthetic clips of that dataset's shape.")
     if opt.rank == 0:
         what = ("Moving-MNIST trajectories over synthetic sprites (not MNIST digits)" if opt.dataset == 'smmnist'

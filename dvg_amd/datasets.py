@@ -1,0 +1,225 @@
+"""KTH, BAIR and UCF clips from `--data_root`: the on-disk formats of the reference's loaders (data/kth.py, data/bair.py,
+data/ucf.py) indexed on the host, every indexed PNG decoded ONCE into a device-resident uint8 frame pool, and samplers that
+reproduce the reference's random draws.  A batch is then B pool indices: `ops.clip_gather` (dvg_clip_gather_u8) turns them
+into normalize_data's list of T x (B,C,H,W) float32 frames on the device.  Host code, no GPU at import.
+
+    KTH   <root>/processed/<class>/{train,test}_meta<S>x<S>.json   a list of {'vid', 'files': [[names...], ...]}; the frames
+          are <root>/processed/<class>/<vid>/<name> (kth.py:16-17,30-32,47-53)
+    UCF   the same tree with .pt metas read by torch.load and nine classes (ucf.py:17,31); ucf.py:13 sets `train = True`
+          whatever it is given, so the UCF test split IS the train split - kept
+    BAIR  <root>/processed_data/{train,test}/<d1>/<d2>/<i>.png, i = 0, 1, ... (bair.py:17-26,53)
+
+Deviation: the reference lists the BAIR directories with os.listdir, whose order depends on the file system; here they are
+listed SORTED, so the ordered test walk and the train draws name the same directories on every machine.
+
+Out of scope: the converters and download scripts that make these trees, a cache of the decoded pool on disk, and datasets
+larger than the device memory (the pool holds every indexed frame: BAIR at 64x64 is about 16 GB)."""
+from __future__ import annotations
+
+import json
+import os
+import random
+from concurrent.futures import ThreadPoolExecutor
+
+import numpy as np
+import torch
+
+KTH_CLASSES = ['boxing', 'handclapping', 'handwaving', 'jogging', 'running', 'walking']                      # kth.py:16-17
+UCF_CLASSES = ['BenchPress', 'BodyWeightSquats', 'CleanAndJerk', 'PullUps', 'PushUps', 'Shotput', 'TennisSwing', 'Lunges',
+               'Fencing']                                                                                    # ucf.py:17-18
+REAL_DATASETS = ('kth', 'bair', 'ucf')
+STAGING_BYTES = 256 << 20       # the pinned staging buffer of build_pool, at most
+MAX_DECODE_THREADS = 16
+
+
+def _need(path, what):
+    """A missing piece of the tree ends the program with its path, not with a traceback."""
+    if not os.path.exists(path):
+        raise SystemExit(f"dataset: {what} {path!r} does not exist (--data_root must hold the reference's processed tree)")
+    return path
+
+
+class ClipIndex:
+    """The sequences of one split: `sequences[i]` = the frame files of sequence i in order, `labels[i]` its class label
+    (-1: BAIR has none).  `bases[i]` = the pool index of its first frame once the frames are laid out sequence after
+    sequence (build_pool does).  KTH / UCF also keep `videos[c]` = per class, per video, the sequence ids: the nesting the
+    reference draws from."""
+
+    def __init__(self, dataset, split):
+        self.dataset, self.split = dataset, split
+        self.sequences, self.labels, self.videos = [], [], []
+
+    def _add(self, files, label):
+        self.sequences.append(files)
+        self.labels.append(label)
+        return len(self.sequences) - 1
+
+    @property
+    def lengths(self):
+        return np.array([len(s) for s in self.sequences], np.int64)
+
+    @property
+    def bases(self):
+        n = self.lengths
+        return np.cumsum(n) - n
+
+    @property
+    def n_frames(self):
+        return int(self.lengths.sum())
+
+
+def _meta_index(dataset, root, train, image_width, classes, load, ext):
+    base = _need(os.path.join(_need(root, "--data_root"), "processed"), "directory")
+    split = 'train' if train else 'test'
+    idx = ClipIndex(dataset, split)
+    for label, c in enumerate(classes):
+        cdir = _need(os.path.join(base, c), "class directory")
+        meta = load(_need(os.path.join(cdir, '%s_meta%dx%d.%s' % (split, image_width, image_width, ext)), "meta file"))
+        vids = []
+        for vid in meta:
+            vdir = os.path.join(cdir, vid['vid'])
+            vids.append([idx._add([os.path.join(vdir, f) for f in files], label) for files in vid['files']])
+        if not vids:
+            raise SystemExit(f"dataset: class {c!r} of the {dataset} {split} split under {base!r} lists no video")
+        idx.videos.append(vids)
+    return idx
+
+
+def kth_index(root, train, image_width=64):
+    def load(path):
+        with open(path) as f:
+            return json.load(f)
+    return _meta_index('kth', root, train, image_width, KTH_CLASSES, load, 'json')
+
+
+def ucf_index(root, train, image_width=64):
+    # ucf.py:13 `train = True`: both splits read the train metas
+    return _meta_index('ucf', root, True, image_width, UCF_CLASSES, lambda p: torch.load(p, weights_only=True), 'pt')
+
+
+def bair_index(root, train, image_width=64):
+    split = 'train' if train else 'test'
+    base = _need(os.path.join(_need(root, "--data_root"), "processed_data", split), "directory")
+    idx = ClipIndex('bair', split)
+    for d1 in sorted(os.listdir(base)):
+        for d2 in sorted(os.listdir(os.path.join(base, d1))):
+            d = os.path.join(base, d1, d2)
+            n = 0
+            while os.path.exists(os.path.join(d, '%d.png' % n)):
+                n += 1
+            idx._add([os.path.join(d, '%d.png' % i) for i in range(n)], -1)
+    if not idx.sequences:
+        raise SystemExit(f"dataset: no <d1>/<d2> directory under {base!r}")
+    return idx
+
+
+def open_index(dataset, root, train, image_width=64):
+    if dataset not in REAL_DATASETS:
+        raise SystemExit(f"dataset: no loader for {dataset!r} (kth | bair | ucf)")
+    return {'kth': kth_index, 'ucf': ucf_index, 'bair': bair_index}[dataset](root, train, image_width)
+
+
+class MetaSampler:
+    """KTH / UCF: get_sequence's draws in its order (kth.py:37-48, ucf.py:38-52).  Class, video and sequence come from a
+    np.random.RandomState(seed), drawn again while the sequence is shorter than the clip; the start frame from
+    random.Random(seed).randint(0, len - T).  The reference seeds the legacy GLOBAL generators with the first index it is
+    asked for (kth.py:58-62): `seed` plays that role, and the private generators here produce the same streams."""
+
+    def __init__(self, index, seq_len, seed):
+        self.index, self.seq_len = index, seq_len
+        self.np_rng, self.py_rng = np.random.RandomState(seed), random.Random(seed)
+        self.bases, self.lengths = index.bases, index.lengths
+        if not (self.lengths >= seq_len).any():
+            raise SystemExit(f"dataset: no {index.dataset} {index.split} sequence has {seq_len} frames")
+
+    def draw(self):
+        """(pool index of the clip's first frame, label)."""
+        vids = self.index.videos
+        while True:                                     # skip sequences that are too short
+            c = self.np_rng.randint(len(vids))
+            v = self.np_rng.randint(len(vids[c]))
+            s = vids[c][v][self.np_rng.randint(len(vids[c][v]))]
+            if self.lengths[s] - self.seq_len >= 0:
+                break
+        st = self.py_rng.randint(0, int(self.lengths[s]) - self.seq_len)
+        return int(self.bases[s]) + st, self.index.labels[s]
+
+
+class BairSampler:
+    """RobotPush.get_seq (bair.py:42-57): train draws np.random.randint(len(dirs)) from the generator seeded with the first
+    index, test walks the directories in order and wraps; a clip always starts at frame 0.  No label: -1."""
+
+    def __init__(self, index, seq_len, seed):
+        self.index, self.seq_len = index, seq_len
+        self.ordered = index.split == 'test'
+        self.np_rng = np.random.RandomState(seed)
+        self.bases, self.d = index.bases, 0
+        short = np.nonzero(index.lengths < seq_len)[0]
+        if short.size:
+            d = os.path.dirname(index.sequences[short[0]][0]) if index.sequences[short[0]] else "an empty directory"
+            raise SystemExit(f"dataset: {d!r} holds fewer than {seq_len} consecutive <i>.png frames")
+
+    def draw(self):
+        if self.ordered:
+            d = self.d
+            self.d = 0 if self.d == len(self.bases) - 1 else self.d + 1
+        else:
+            d = self.np_rng.randint(len(self.bases))
+        return int(self.bases[d]), -1
+
+
+def make_sampler(index, seq_len, seed):
+    return (BairSampler if index.dataset == 'bair' else MetaSampler)(index, seq_len, seed)
+
+
+def _decode(path, dst, image_width):
+    """One PNG into dst (H,W,pool_c) uint8: mode L as one channel, RGB interleaved; no resizing (nor does the reference)."""
+    from PIL import Image
+    try:
+        with Image.open(path) as im:
+            if im.size != (image_width, image_width):
+                raise SystemExit(f"dataset: {path!r} is {im.size[0]}x{im.size[1]}, not {image_width}x{image_width}")
+            if im.mode != ('L' if dst.shape[2] == 1 else 'RGB'):
+                raise SystemExit(f"dataset: {path!r} has mode {im.mode}, the pool holds {dst.shape[2]}-channel frames")
+            dst[...] = np.asarray(im).reshape(dst.shape)
+    except OSError as e:
+        raise SystemExit(f"dataset: cannot read {path!r}: {e}")
+
+
+def _pool_channels(path):
+    from PIL import Image
+    try:
+        with Image.open(path) as im:
+            if im.mode not in ('L', 'RGB'):
+                raise SystemExit(f"dataset: {path!r} has mode {im.mode}: only L and RGB PNGs are read")
+            return 1 if im.mode == 'L' else 3
+    except OSError as e:
+        raise SystemExit(f"dataset: cannot read {path!r}: {e}")
+
+
+def build_pool(index, image_width, device=None, threads=5):
+    """(n_frames, S, S, pool_c) uint8: every frame of `index`, sequence after sequence (sequence i starts at index.bases[i]).
+    Decoded with Pillow on min(threads, 16) threads.  For a GPU `device` the frames are decoded into a pinned staging
+    buffer of at most STAGING_BYTES and uploaded chunk by chunk into ONE device tensor; device None / cpu: a host tensor."""
+    files = [f for seq in index.sequences for f in seq]
+    if not files:
+        raise SystemExit(f"dataset: the {index.dataset} {index.split} split lists no frame")
+    pc = _pool_channels(files[0])
+    frame_bytes = image_width * image_width * pc
+    dev = torch.device(device) if device is not None else torch.device('cpu')
+    pool = torch.empty((len(files), image_width, image_width, pc), dtype=torch.uint8, device=dev)
+    workers = max(1, min(int(threads), MAX_DECODE_THREADS))
+    with ThreadPoolExecutor(workers) as ex:
+        if dev.type == 'cpu':
+            host = pool.numpy()
+            list(ex.map(lambda i: _decode(files[i], host[i], image_width), range(len(files))))
+            return pool
+        chunk = max(1, min(len(files), STAGING_BYTES // frame_bytes))
+        staging = torch.empty((chunk, image_width, image_width, pc), dtype=torch.uint8).pin_memory()
+        host = staging.numpy()
+        for a in range(0, len(files), chunk):
+            n = min(chunk, len(files) - a)
+            list(ex.map(lambda i: _decode(files[a + i], host[i], image_width), range(n)))
+            pool[a:a + n].copy_(staging[:n], non_blocking=True)
+            torch.cuda.current_stream(dev).synchronize()      # the staging buffer is written again by the next chunk
+    return pool

@@ -268,3 +268,28 @@ def moving_mnist_compose(sprites, ids, pos, seq_len, image_size):
     check(lib().dvg_moving_mnist_compose(_p(sprites), _p(ids), _p(pos), _p(out), sprites.shape[0], seq_len, b, nd,
                                          image_size, sprites.shape[1], _stream()), "dvg_moving_mnist_compose")
     return out
+
+
+def clip_gather(pool, first, T, C):
+    """(T,B,C,H,W) float32 clips = pool[first[b] + t] / 255 out of a device frame pool (n_frames,H,W,pool_c) uint8
+    (dvg_clip_gather_u8): what utils.normalize_data makes of the KTH / BAIR / UCF loaders' batches.  `first`: the B pool
+    indices of the clips' first frames - host int64 values (checked against the pool here, then uploaded on the current
+    stream) or an int64 device tensor (the kernel clamps what it reads)."""
+    if not pool.is_cuda or pool.dtype != torch.uint8 or pool.dim() != 4 or not pool.is_contiguous():
+        raise RuntimeError("clip_gather: pool must be a contiguous (n_frames,H,W,pool_c) uint8 GPU tensor - no CPU fallback")
+    n, h, w, pc = pool.shape
+    if not (isinstance(first, torch.Tensor) and first.is_cuda):
+        first = torch.as_tensor(first)
+        if first.dtype != torch.int64 or first.dim() != 1 or first.numel() == 0:
+            raise RuntimeError("clip_gather: first must be a non-empty 1-D int64 sequence")
+        if T < 1 or int(first.min()) < 0 or int(first.max()) + T > n:
+            raise RuntimeError(f"clip_gather: clips of {T} frames at [{int(first.min())}, {int(first.max())}] leave the "
+                               f"pool of {n} frames")
+        first = first.to(pool.device)
+    if first.dtype != torch.int64 or first.dim() != 1 or not first.is_contiguous() or first.device != pool.device:
+        raise RuntimeError("clip_gather: first must be a contiguous 1-D int64 tensor on the pool's device")
+    b = first.shape[0]
+    out = torch.empty((max(T, 0), b, C, h, w), device=pool.device, dtype=torch.float32)
+    _run("clip_gather", 0.0, float(T * b * h * w * pc) + 4.0 * out.numel(), lib().dvg_clip_gather_u8, _p(pool), _p(first),
+         _p(out), n, T, b, C, h, w, pc, _stream())
+    return out

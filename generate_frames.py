@@ -32,7 +32,7 @@ sys.path.insert(0, ROOT)
 
 import utils  # noqa: E402
 from dvg_amd import ops, viz  # noqa: E402
-from dvg_amd.data import SyntheticMovingMNIST, synthetic_video  # noqa: E402
+from dvg_amd.data import SyntheticMovingMNIST, make_batch_generator, synthetic_video  # noqa: E402
 from dvg_amd.rollout import (GraphedSampler, GraphedTrigger, condition, gp_input, posterior_from, sample_from, sample_rollout,  # noqa: E402
                              trigger_body, trigger_log, trigger_warmup)
 from gp_models import GaussianLikelihood, GPRegressionLayer1  # noqa: E402
@@ -73,7 +73,7 @@ def build_parser():
     p.add_argument('--gif_rows', type=int, default=1,
                    help='make_gifs: batch rows to write a GIF for (the reference returns after row 0, generate_frames.py:217)')
     p.add_argument('--synthetic_data', action='store_true',
-                   help='datasets other than smmnist: synthetic clips of the right shape (--data_root is not read)')
+                   help='kth | bair | ucf: synthetic clips of that shape instead of the test split under --data_root')
     return p
 
 
@@ -326,6 +326,11 @@ def synthetic_checkpoint(opt):
             'gp_layer': gp.state_dict(), 'opt': opt}
 
 
+def data_seed(seed):
+    """The seed of the test-split sampler (train.py draws its test batches from the same offset)."""
+    return seed + 7919
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     assert torch.cuda.is_available(), "generate_frames.py needs a GPU: the DVG hot path has no CPU fallback"
@@ -350,19 +355,23 @@ def main(argv=None):
     gen = Generator(opt, ckpt, device)
     dataset = getattr(opt, 'dataset', 'smmnist')
     if dataset != 'smmnist' and not args.synthetic_data:
-        raise SystemExit(f"generate_frames.py: no loader for dataset {dataset} here (--data_root {args.data_root!r} is not "
-                         "read). Pass --synthetic_data to roll out on synthetic clips of that dataset's shape.")
-    print("WARNING: synthetic data - %s; --data_root is ignored" %
-          ("Moving-MNIST trajectories over synthetic sprites (not MNIST digits)" if dataset == 'smmnist'
-           else f"random textured clips shaped like {dataset}"), file=sys.stderr)
-    if dataset == 'smmnist':
-        ds = SyntheticMovingMNIST(seq_len=opt.n_eval, image_size=opt.image_width, seed=opt.seed + 7919)
-        batches = (ds.batch(opt.batch_size) for _ in range(args.nbatches))
+        # the test split under --data_root (the command line's, not the checkpoint's), as generate_frames.py:89-104
+        opt.data_root, opt.data_threads, opt.synthetic_data = args.data_root, args.data_threads, False
+        opt.local_batch, opt.rank = opt.batch_size, 0
+        test_gen = make_batch_generator(opt, opt.n_eval, data_seed(opt.seed), device, train=False)
+        batches = (next(test_gen)() for _ in range(args.nbatches))
     else:
-        batches = (synthetic_video(opt.batch_size, opt.n_eval, opt.channels, opt.image_width, seed=opt.seed + k)
-                   for k in range(args.nbatches))
-    for i, seq in enumerate(batches):
-        test_x, _ = utils.normalize_data(opt, torch.cuda.FloatTensor, seq)
+        print("WARNING: synthetic data - %s; --data_root is ignored" %
+              ("Moving-MNIST trajectories over synthetic sprites (not MNIST digits)" if dataset == 'smmnist'
+               else f"random textured clips shaped like {dataset}"), file=sys.stderr)
+        if dataset == 'smmnist':
+            ds = SyntheticMovingMNIST(seq_len=opt.n_eval, image_size=opt.image_width, seed=opt.seed + 7919)
+            seqs = (ds.batch(opt.batch_size) for _ in range(args.nbatches))
+        else:
+            seqs = (synthetic_video(opt.batch_size, opt.n_eval, opt.channels, opt.image_width, seed=opt.seed + k)
+                    for k in range(args.nbatches))
+        batches = (utils.normalize_data(opt, torch.cuda.FloatTensor, seq)[0] for seq in seqs)
+    for i, test_x in enumerate(batches):
         if args.gp_trigger:
             res = gen.gp_trigger_gen(test_x, args.trigger_indices, total=opt.n_eval)
             torch.save(res, '%s/gen/gp_trigger_%d.pt' % (opt.log_dir, i))

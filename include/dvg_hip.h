@@ -584,6 +584,16 @@ int dvg_wgrad_thin(const float* inp_nchw, const float* dout_nhwc, float* partial
 int dvg_moving_mnist_compose(const float* sprites, const int* ids, const int* pos, float* out, int n_sprites, int T,
                              int B, int num_digits, int image_size, int digit_size, void* stream);
 
+/* A batch of clips gathered from a device-resident pool of decoded frames: replaces the per-frame `imread(f)/255.` loops of
+ * data/kth.py:52-56, data/bair.py:52-57, data/ucf.py:56-61 and the layout change of utils.normalize_data (utils.py:86-95).
+ * pool (n_frames,H,W,pool_c) uint8, interleaved as PNG decodes; first (B) DEVICE int64, the pool index of each clip's first
+ * frame (clamped to [0, n_frames - T] in the kernel); out (T,B,C,H,W): out[t,b,c,y,x] = (float)pool[first[b]+t,y,x,c] / 255.0f,
+ * a true division (bit-equal to float32(float64(v)/255.) for all 256 bytes).  C == pool_c (1 or 3), or C == 1 with
+ * pool_c == 3 (channel 0: kth.py:55).  W * pool_c % 16 == 0; pool offsets are 64-bit, out must stay below 2^31 elements.
+ * An addition within ABI 9. */
+int dvg_clip_gather_u8(const uint8_t* pool, const int64_t* first, float* out, int64_t n_frames, int T, int B, int C, int H,
+                       int W, int pool_c, void* stream);
+
 /* Evaluation metrics of utils.eval_seq (utils.py:220-234): per (sample, channel) image, SSIM as
  * skimage.measure.compare_ssim computes it with its defaults (7x7 uniform window, sample covariance, data range 2
  * for float images, mean over the valid window positions) and PSNR as compare_psnr (data range 1 for non-negative

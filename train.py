@@ -22,9 +22,9 @@ Added: data parallelism — launch with `python -m torch.distributed.run --nproc
 the KL weight does not change with the number of GPUs); every parameter's `.grad` is a view of one flat arena
 (dvg_amd/optim.py) whose ranges are averaged in place over RCCL, the decoder-side range while the encoder phase of the
 backward pass is still running (dvg_amd/parallel.py); BatchNorm statistics are per replica.
-Datasets are synthetic here (no network / files offline): `smmnist` = seeded Moving-MNIST trajectories with in-repo
-sprites; any other `--dataset` needs `--synthetic_data` (random textured clips of the right shape) and fails without
-it, because `--data_root` cannot be honoured.
+Datasets: `kth | bair | ucf` read the reference's processed tree under `--data_root` (dvg_amd/datasets.py: decoded once into
+a device frame pool, batches gathered by dvg_clip_gather_u8) - or, with `--synthetic_data`, train on random textured clips of
+that shape; `smmnist` = seeded Moving-MNIST trajectories with in-repo sprites (no MNIST files, no torchvision).
 """
 import argparse
 import importlib
@@ -57,7 +57,7 @@ def build_parser():
     p.add_argument('--model_dir', default='')
     p.add_argument('--name', default='')
     p.add_argument('--output_path', default='.')
-    p.add_argument('--data_root', default='path/to/data/')
+    p.add_argument('--data_root', default='path/to/data/', help='kth | bair | ucf: the root of the processed dataset tree')
     p.add_argument('--optimizer', default='adam')
     p.add_argument('--niter', type=int, default=601)
     p.add_argument('--seed', default=1, type=int)
@@ -93,7 +93,7 @@ def build_parser():
                         'B/N clips then train exactly like one process on B clips (default: per-replica statistics, as '
                         'DistributedDataParallel).  The collectives cannot be captured in a hipGraph: iterations run eager.')
     p.add_argument('--synthetic_data', action='store_true',
-                   help='datasets other than smmnist: train on synthetic clips of the right shape (--data_root is not read)')
+                   help='kth | bair | ucf: train on synthetic clips of that shape instead of reading --data_root')
     return p
 
 
@@ -723,7 +723,7 @@ def main(argv=None):
     tr = Trainer(opt, device)
     torch.manual_seed(opt.seed + 1000 * rank)   # from here on: per-rank randomness (GP samples)
     train_gen = BatchPrefetcher(make_batch_generator(opt, opt.n_past + opt.n_future, opt.seed + 17 * rank, device))
-    test_gen = make_batch_generator(opt, opt.n_eval, opt.seed + 7919 + 17 * rank, device)
+    test_gen = make_batch_generator(opt, opt.n_eval, opt.seed + 7919 + 17 * rank, device, train=False)
     # One rank: the iteration as one hipGraph.  Several ranks: a chain of hipGraphs cut at the gradient all-reduces, which
     # stay eager (SegmentedIteration).  Capturing the RCCL collectives inside ONE graph instead is NOT safe
     # on this stack: the c10d watchdog thread may query a collective's event while it is "recorded in a capturing stream"
