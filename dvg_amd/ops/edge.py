@@ -203,6 +203,28 @@ def eval_frames(gt, pred):
     return out[0].mean(1), out[1].mean(1)
 
 
+def eval_frames_finn(gt, pred):
+    """(ssim, psnr, mse) of predicted frames against the ground truth as utils.finn_eval_seq scores them (utils.py:236-256,
+    dvg_eval_frames_finn): 11x11 Gaussian-window SSIM and 10 log10(1 / mse) PSNR per channel, averaged over channels, and the
+    MSE of the whole frame.  gt / pred: NCHW -> three (N,) tensors, or (T,N,C,H,W) stacked frames -> three (T,N) tensors,
+    all time steps in ONE launch."""
+    _dev_f32(gt, "eval_frames_finn.gt")
+    _dev_f32(pred, "eval_frames_finn.pred")
+    if gt.shape != pred.shape or gt.dim() not in (4, 5):
+        raise RuntimeError(f"eval_frames_finn: shapes {tuple(gt.shape)} vs {tuple(pred.shape)}")
+    gt = gt if gt.is_contiguous() else gt.contiguous()
+    pred = pred if pred.is_contiguous() else pred.contiguous()
+    lead, (c, h, w) = tuple(gt.shape[:-3]), gt.shape[-3:]
+    n = gt.numel() // (c * h * w)
+    out = torch.empty((2, n, c), device=gt.device, dtype=torch.float32)
+    mse = torch.empty(n, device=gt.device, dtype=torch.float32)
+    _run("eval_frames_finn", 0.0, 8.0 * gt.numel(), lib().dvg_eval_frames_finn, _p(gt), _p(pred), _p(out[0]), _p(out[1]),
+         _p(mse), n, c, h, w, _stream())
+    if c == 1:          # the mean over one channel is that channel
+        return out[0].view(lead), out[1].view(lead), mse.view(lead)
+    return out[0].mean(1).view(lead), out[1].mean(1).view(lead), mse.view(lead)
+
+
 QUANT_TRUNC, QUANT_NEAREST = 0, 1                       # DVG_QUANT_*
 MOSAIC_BLACK, MOSAIC_RED, MOSAIC_GREEN = 0, 1, 2        # DVG_MOSAIC_* cell colours
 MOSAIC_SEL_NONE, MOSAIC_SEL_BEST, MOSAIC_SEL_PICK = 0, 1, 2

@@ -426,10 +426,17 @@ class GraphedSampler:
     (generate_frames.py:166-171: the draw at i % 15 == 0 is the loop's only source of randomness), so the prediction steps
     n_past ... t0 - 1 - the same kernels on the same inputs for every sample, like the conditioning frames - run ONCE per
     batch and every sample graph continues from the state they leave behind.  Results are bit-identical to the per-sample
-    loop (tests/test_gpu_rollouts.py); with no trigger step inside the rollout all samples are the prefix."""
+    loop (tests/test_gpu_rollouts.py); with no trigger step inside the rollout all samples are the prefix.
+
+    `metrics`: "skimage" (default) scores with utils.eval_seq's metrics, one ops.eval_frames per step; "finn" with
+    utils.finn_eval_seq's (ops.eval_frames_finn, one launch per captured step range), which adds the frames' MSE - `run()`
+    then fills its `mse` output as well.  The frames do not depend on it."""
 
     def __init__(self, encoder, decoder, frame_predictor, gp_layer, likelihood, x, n_past, n_eval,
-                 last_frame_skip=False, period=15, inflight=3, share_prefix=None):
+                 last_frame_skip=False, period=15, inflight=3, share_prefix=None, metrics="skimage"):
+        if metrics not in ("skimage", "finn"):
+            raise ValueError(f"GraphedSampler: metrics must be 'skimage' or 'finn', not {metrics!r}")
+        self.metrics = metrics
         # several sample chains in flight keep the board at its power cap: their graphs are captured with the energy-lean tiles
         # (ops.tile_policy; same results to fp32 rounding); one chain at a time keeps the latency tiles
         with ops.tile_policy(max(1, inflight) >= 2):
@@ -484,12 +491,18 @@ class GraphedSampler:
                 self.pre_graph, self.b["pre"], self._keep_p = graphs.capture(self._prefix)
             main_stream = skips.mark()    # written by graphs that replay on the main stream before any sample graph
             for ch in (() if self.t0 == n_eval else self.chains):
-                ch["graph"], (ch["frames"], ch["ssim"], ch["psnr"]), ch["keepalive"] = graphs.capture(lambda: self._body(ch))
+                ch["graph"], (ch["frames"], ch["ssim"], ch["psnr"], ch["mse"]), ch["keepalive"] = \
+                    graphs.capture(lambda: self._body(ch))
                 skips.drop_since(main_stream)
 
     def _metrics(self, frames, lo, hi):
+        """(ssim, psnr, mse), each (B, hi - lo), of the predicted frames lo ... hi - 1; mse is None unless metrics == "finn"
+        (utils.finn_eval_seq: one launch for the whole step range)."""
+        if self.metrics == "finn":
+            s, p, e = ops.eval_frames_finn(self.x[lo:hi], torch.stack(frames[lo:hi]))
+            return s.t(), p.t(), e.t()
         m = [ops.eval_frames(self.x[t], frames[t]) for t in range(lo, hi)]
-        return torch.stack([a for a, _ in m], 1), torch.stack([b for _, b in m], 1)
+        return torch.stack([a for a, _ in m], 1), torch.stack([b for _, b in m], 1), None
 
     def _condition(self) -> dict:
         """The conditioning state (rollout.condition) of the frames in self.x."""
@@ -503,19 +516,19 @@ class GraphedSampler:
         """The samples' steps n_past ... t0 - 1 from the conditioning state: frames, their metrics, the LSTM state after them."""
         st = self.b["state"]
         frames = sample_from(st, *self._mods, n_past=self.n_past, n_eval=self.t0, **self._kw)
-        ssim, psnr = self._metrics(frames, self.n_past, self.t0)
+        ssim, psnr, mse = self._metrics(frames, self.n_past, self.t0)
         return {"hidden": list(self._mods[2].hidden), "skip": st["skip"], "frames": frames, "stack": torch.stack(frames),
-                "ssim": ssim, "psnr": psnr}
+                "ssim": ssim, "psnr": psnr, "mse": mse}
 
     def _body(self, ch):
         """One sample from step t0 on: (frames t0 ... n_eval - 1 stacked - with the conditioning frames in front when there is
-        no shared prefix -, SSIM, PSNR of the predicted ones among them)."""
+        no shared prefix -, SSIM, PSNR and - Finn metrics only, else None - MSE of the predicted ones among them)."""
         if self.t0 == self.n_eval:       # no trigger step inside the rollout: every sample IS the prefix
-            return None, None, None
+            return None, None, None, None
         state = self.b["pre"] if self.share else self.b["state"]
         frames = sample_from(state, *self._mods, eps_by_step=ch["eps"], n_past=self.t0, n_eval=self.n_eval, **self._kw)
-        ssim, psnr = self._metrics(frames, self.t0, self.n_eval)
-        return torch.stack(frames[self.t0 if self.share else 0:]), ssim, psnr
+        ssim, psnr, mse = self._metrics(frames, self.t0, self.n_eval)
+        return torch.stack(frames[self.t0 if self.share else 0:]), ssim, psnr, mse
 
     def set_batch(self, x) -> None:
         """New frames (conditioning + ground truth), copied into the static buffer on the current stream."""
@@ -523,10 +536,14 @@ class GraphedSampler:
             self.x[i].copy_(t)
 
     def run(self, nsample: int, samples: torch.Tensor, ssim: torch.Tensor, psnr: torch.Tensor,
-            eps_by_sample: Optional[Sequence[Dict[int, torch.Tensor]]] = None) -> torch.Tensor:
+            eps_by_sample: Optional[Sequence[Dict[int, torch.Tensor]]] = None,
+            mse: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Draws `nsample` samples: samples[s] <- the n_eval frames (n_eval,B,C,H,W), ssim[:, s] / psnr[:, s] <- (B,T); returns
         the posterior rollout's frames (n_eval,B,C,H,W) - a static buffer the next run() overwrites.
-        eps_by_sample[s][i]: base sample of sample s at trigger step i (parity runs); None = torch's generator."""
+        eps_by_sample[s][i]: base sample of sample s at trigger step i (parity runs); None = torch's generator.
+        mse (metrics == "finn" only): mse[:, s] <- (B,T), the frames' mean squared error."""
+        if (mse is not None) != (self.metrics == "finn"):
+            raise ValueError("GraphedSampler.run: the mse output goes with metrics='finn', and only with it")
         cur = torch.cuda.current_stream()
         P = self.t0 - self.n_past
         self.cond_graph.replay()             # on the current stream: everything below waits for it
@@ -539,6 +556,8 @@ class GraphedSampler:
             samples[:, :self.t0].copy_(pre["stack"].unsqueeze(0).expand(nsample, *pre["stack"].shape))
             ssim[:, :, :P].copy_(pre["ssim"].unsqueeze(1).expand(-1, nsample, -1))
             psnr[:, :, :P].copy_(pre["psnr"].unsqueeze(1).expand(-1, nsample, -1))
+            if mse is not None:
+                mse[:, :, :P].copy_(pre["mse"].unsqueeze(1).expand(-1, nsample, -1))
             if self.t0 == self.n_eval:
                 cur.wait_stream(self.post_stream)
                 return self.b["post"]
@@ -557,6 +576,8 @@ class GraphedSampler:
                 samples[s, lo:].copy_(ch["frames"])
                 ssim[:, s, P:].copy_(ch["ssim"])
                 psnr[:, s, P:].copy_(ch["psnr"])
+                if mse is not None:
+                    mse[:, s, P:].copy_(ch["mse"])
         for ch in self.chains:
             cur.wait_stream(ch["stream"])
         cur.wait_stream(self.post_stream)

@@ -108,3 +108,15 @@ def save_gif_with_text(filename, inputs, text, duration=0.25):
     figs = [image_tensor([draw_text_tensor(ti, texti) for ti, texti in zip(tensor, txt)], padding=0)
             for tensor, txt in zip(inputs, text)]
     viz.write_gif(filename, _compose_figures(figs, viz.QUANT_TRUNC), duration)
+
+
+# ---- evaluation metrics ------------------------------------------------------------------------------------------------------
+def finn_eval_seq(gt, pred):
+    """utils.py:236-256: (mse, ssim, psnr), each a (bs, T) numpy array, of T predicted frames (bs,C,H,W) against the ground
+    truth - the SSIM / PSNR variant of Finn et al. (2016) and Babaeizadeh et al. (2017).  `gt` / `pred`: sequences of T device
+    tensors (or stacked (T,bs,C,H,W) tensors); computed by ONE launch of dvg_eval_frames_finn, then copied to the host."""
+    from . import ops
+    g = gt if torch.is_tensor(gt) else torch.stack(list(gt))
+    p = pred if torch.is_tensor(pred) else torch.stack(list(pred))
+    ssim, psnr, mse = ops.eval_frames_finn(g, p)
+    return tuple(v.t().double().cpu().numpy() for v in (mse, ssim, psnr))

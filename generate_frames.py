@@ -72,6 +72,10 @@ def build_parser():
     p.add_argument('--no_images', action='store_true', help='write the .pt tensors only, no GIF / PNG')
     p.add_argument('--gif_rows', type=int, default=1,
                    help='make_gifs: batch rows to write a GIF for (the reference returns after row 0, generate_frames.py:217)')
+    p.add_argument('--metrics', default='skimage', choices=('skimage', 'finn'),
+                   help="make_gifs: skimage = utils.eval_seq's 7x7 uniform-window SSIM and PSNR (the reference's script); finn = "
+                        "utils.finn_eval_seq's 11x11 Gaussian-window SSIM, PSNR and MSE, the variant KTH / BAIR results are "
+                        "published with")
     p.add_argument('--synthetic_data', action='store_true',
                    help='kth | bair | ucf: synthetic clips of that shape instead of the test split under --data_root')
     return p
@@ -105,6 +109,9 @@ class Generator:
         B, T = x[0].shape[0], opt.n_eval - opt.n_past
         ssim = torch.zeros(B, nsample, T, device=self.dev)
         psnr = torch.zeros(B, nsample, T, device=self.dev)
+        finn = getattr(opt, 'metrics', 'skimage') == 'finn'
+        mse = torch.zeros(B, nsample, T, device=self.dev) if finn else None
+        extra = {'mse': mse, 'metrics': 'finn'} if finn else {}
         all_gen = []
         inflight = getattr(opt, 'inflight', 3)
         if inflight > 0:
@@ -117,20 +124,21 @@ class Generator:
             def key():
                 vers = tuple(t._version for m in (self.encoder, self.decoder, self.frame_predictor, self.gp_layer, self.likelihood)
                              for t in list(m.parameters()) + list(m.buffers()))
-                return (tuple(x[0].shape), len(x), opt.n_past, opt.n_eval, bool(opt.last_frame_skip), inflight, share, vers)
+                return (tuple(x[0].shape), len(x), opt.n_past, opt.n_eval, bool(opt.last_frame_skip), inflight, share, finn, vers)
             if self._sampler_key != key():
                 self._sampler = GraphedSampler(self.encoder, self.decoder, self.frame_predictor, self.gp_layer,
                                                self.likelihood, x, opt.n_past, opt.n_eval, opt.last_frame_skip,
-                                               inflight=inflight, share_prefix=None if share else False)
+                                               inflight=inflight, share_prefix=None if share else False,
+                                               metrics='finn' if finn else 'skimage')
                 # the key AFTER the construction: the sampler's eager warm-up pass may be the GP layer's first call, which
                 # initialises its variational parameters in place (gp_models: variational_params_initialized); the graphs are
                 # captured after that pass, i.e. with the versions read here
                 self._sampler_key = key()
             self._sampler.set_batch(x)
             samples = torch.empty((nsample, opt.n_eval) + tuple(x[0].shape), device=self.dev)
-            post = self._sampler.run(nsample, samples, ssim, psnr, eps_by_sample).clone()
+            post = self._sampler.run(nsample, samples, ssim, psnr, eps_by_sample, mse=mse).clone()
             best = ssim.mean(2).argsort(1)[:, -1]
-            return {'posterior': post, 'samples': samples, 'ssim': ssim, 'psnr': psnr, 'best': best}
+            return {'posterior': post, 'samples': samples, 'ssim': ssim, 'psnr': psnr, 'best': best, **extra}
         # everything before the first predicted frame is the same for the posterior rollout and all nsample rollouts of this
         # batch (generate_frames.py:113-121 and :147-162 are the same computation): once per batch
         state = condition(self.encoder, self.frame_predictor, x, opt.n_past, opt.last_frame_skip, decoder=self.decoder)
@@ -140,12 +148,16 @@ class Generator:
             frames = sample_from(state, self.encoder, self.decoder, self.frame_predictor, self.gp_layer,
                                  self.likelihood, opt.n_past, opt.n_eval, opt.last_frame_skip,
                                  eps_by_step=None if eps_by_sample is None else eps_by_sample[s])
-            for t in range(T):   # utils.eval_seq (generate_frames.py:178) on device: dvg_eval_frames
-                ssim[:, s, t], psnr[:, s, t] = ops.eval_frames(x[opt.n_past + t], frames[opt.n_past + t])
+            if finn:             # utils.finn_eval_seq on device: dvg_eval_frames_finn, all steps in one launch
+                m = ops.eval_frames_finn(torch.stack(list(x[opt.n_past:opt.n_eval])), torch.stack(frames[opt.n_past:opt.n_eval]))
+                ssim[:, s], psnr[:, s], mse[:, s] = (v.t() for v in m)
+            else:
+                for t in range(T):   # utils.eval_seq (generate_frames.py:178) on device: dvg_eval_frames
+                    ssim[:, s, t], psnr[:, s, t] = ops.eval_frames(x[opt.n_past + t], frames[opt.n_past + t])
             all_gen.append(torch.stack(frames))
         best = ssim.mean(2).argsort(1)[:, -1]   # generate_frames.py:188-189,207: np.argsort(mean_ssim)[-1]
         return {'posterior': torch.stack(post), 'samples': torch.stack(all_gen), 'ssim': ssim, 'psnr': psnr,
-                'best': best}
+                'best': best, **extra}
 
     def write_gifs(self, x, res, idx, out_dir, name='lstm', rows=1):
         """generate_frames.py:185-217 on make_gifs' result: `<out_dir>/sample_<name>_<idx + i>.gif` for batch rows i < rows,
@@ -347,6 +359,7 @@ def main(argv=None):
         opt.n_eval, opt.n_future, opt.batch_size = args.n_eval, args.n_future, args.batch_size
         opt.log_dir = args.log_dir
         opt.inflight = args.inflight
+        opt.metrics = args.metrics
     os.makedirs('%s/gen/' % opt.log_dir, exist_ok=True)
     print("Random Seed: ", opt.seed)
     random.seed(opt.seed)
@@ -380,13 +393,20 @@ def main(argv=None):
                 gen.write_trigger_pngs(res, '%s/gen' % opt.log_dir)
         else:
             res = gen.make_gifs(test_x, args.nsample)
-            torch.save({'posterior': res['posterior'][:, 0].cpu(), 'best': res['best'].cpu(), 'psnr': res['psnr'].cpu(),
-                        'ssim': res['ssim'].cpu(),
-                        'best_sample_0': res['samples'][int(res['best'][0]), :, 0].cpu()},
-                       '%s/gen/sample_lstm_%d.pt' % (opt.log_dir, i))
+            saved = {'posterior': res['posterior'][:, 0].cpu(), 'best': res['best'].cpu(), 'psnr': res['psnr'].cpu(),
+                     'ssim': res['ssim'].cpu(),
+                     'best_sample_0': res['samples'][int(res['best'][0]), :, 0].cpu()}
+            if 'mse' in res:
+                saved.update(mse=res['mse'].cpu(), metrics=res['metrics'])
+            torch.save(saved, '%s/gen/sample_lstm_%d.pt' % (opt.log_dir, i))
             sel = res['best'].view(-1, 1, 1).expand(-1, 1, res['ssim'].shape[2])
-            print('batch %d: best-of-%d by mean SSIM: SSIM %.4f, PSNR %.3f dB' % (
-                i, args.nsample, float(res['ssim'].gather(1, sel).mean()), float(res['psnr'].gather(1, sel).mean())))
+            if 'mse' in res:
+                print('batch %d: best-of-%d by mean Finn SSIM (11x11 Gaussian window): SSIM %.4f, PSNR %.3f dB, MSE %.3e' % (
+                    i, args.nsample, float(res['ssim'].gather(1, sel).mean()), float(res['psnr'].gather(1, sel).mean()),
+                    float(res['mse'].gather(1, sel).mean())))
+            else:
+                print('batch %d: best-of-%d by mean SSIM: SSIM %.4f, PSNR %.3f dB' % (
+                    i, args.nsample, float(res['ssim'].gather(1, sel).mean()), float(res['psnr'].gather(1, sel).mean())))
             if not args.no_images:
                 gen.write_gifs(test_x, res, i, '%s/gen' % opt.log_dir, rows=args.gif_rows)
 

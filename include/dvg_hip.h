@@ -601,6 +601,18 @@ int dvg_clip_gather_u8(const uint8_t* pool, const int64_t* first, float* out, in
 int dvg_eval_frames(const float* gt, const float* pred, float* ssim, float* psnr, int n_images, int H, int W,
                     void* stream);
 
+/* Evaluation metrics of utils.finn_eval_seq (utils.py:236-301), the variant of Finn et al. (2016) / Babaeizadeh et al.
+ * (2017) that the KTH and BAIR curves are published with.  Per (frame, channel) image: SSIM under an 11x11 Gaussian window,
+ * sigma 1.5 (fspecial_gauss, :270-273), K1 = 0.01, K2 = 0.03, L = 1, mean over the (H-10)x(W-10) valid positions, -1 where
+ * that mean is NaN (:247-248); PSNR = 10 log10(1 / mse) with data range 1 whatever the ground truth's sign (finn_psnr,
+ * :259-261; +inf for identical images).  Per frame: the squared error over all C channels / (C*H*W) (mse_metric, :215-218).
+ * gt / pred: n_frames contiguous CxHxW fp32 frames - any number of them, so all time steps of a rollout are ONE launch;
+ * ssim / psnr: n_frames * C floats, mse: n_frames floats.  fp64 inside, fixed reduction order (bit-identical reruns).
+ * H, W >= 11; n_frames*C*H*W < 2^31; 11 row-filtered rows of 5 x (W-10) doubles must fit 150 KB of LDS (W <= 359).
+ * An addition within ABI 9. */
+int dvg_eval_frames_finn(const float* gt, const float* pred, float* ssim, float* psnr, float* mse, int n_frames, int C, int H,
+                         int W, void* stream);
+
 /* The reference's figures as uint8 RGB mosaics, composed on the device in ONE launch.  Replaces, at their call sites
  * generate_frames.py:185-217 (make_gifs -> utils.save_gif_with_text), :235-245 (plot_rec -> utils.save_tensors_image) and
  * train.py:291-335 (plot -> save_tensors_image + utils.save_gif), the chain utils.image_tensor (utils.py:104-150),

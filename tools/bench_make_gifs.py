@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """make_gifs (generate_frames.py:143-189) throughput: nsample rollouts of one batch + SSIM / PSNR + best-of-N, eager sample
-loop vs the replayed sample body with 1 / 3 samples in flight (GPU only)."""
+loop vs the replayed sample body with 1 / 3 samples in flight (GPU only).  --metrics finn scores with utils.finn_eval_seq's
+metric set instead of utils.eval_seq's."""
 import argparse
 import json
 import os
@@ -14,15 +15,22 @@ import generate_frames  # noqa: E402
 from dvg_amd.data import SyntheticMovingMNIST  # noqa: E402
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="dcgan")
     ap.add_argument("--nsample", type=int, default=30)
-    a = ap.parse_args()
+    ap.add_argument("--metrics", default="skimage", choices=("skimage", "finn"),
+                    help="the metric set scored per sample (generate_frames.py --metrics)")
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     dev = torch.device("cuda:0")
     for inflight in (0, 1, 3):
         opt = generate_frames.build_parser().parse_args(["--synthetic_ckpt", "--batch_size", "64", "--model", a.model,
-                                                         "--n_past", "10", "--n_eval", "20", "--inflight", str(inflight)])
+                                                         "--n_past", "10", "--n_eval", "20", "--inflight", str(inflight),
+                                                         "--metrics", a.metrics])
         torch.manual_seed(1)
         g = generate_frames.Generator(opt, generate_frames.synthetic_checkpoint(opt), dev)
         x = SyntheticMovingMNIST(seq_len=20, seed=1).batch_device(64, dev)
@@ -32,7 +40,7 @@ def main():
         g.make_gifs(x, a.nsample)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        print(json.dumps({"model": a.model, "inflight": inflight, "nsample": a.nsample, "s_per_batch": round(dt, 4),
+        print(json.dumps({"model": a.model, "metrics": a.metrics, "inflight": inflight, "nsample": a.nsample, "s_per_batch": round(dt, 4),
                           "predicted_frames_per_s": round(64 * 10 * a.nsample / dt, 1)}), flush=True)
 
 
