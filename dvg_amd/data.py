@@ -1,5 +1,5 @@
 """The input pipeline: synthetic stand-ins for the datasets of the reference, and `make_batch_generator`, which also serves
-KTH / BAIR / UCF clips from `--data_root` (dvg_amd/datasets.py).
+KTH / BAIR / UCF clips (dvg_amd/datasets.py) and Moving-MNIST over real MNIST digits (dvg_amd/mnist.py) from `--data_root`.
 
 `SyntheticMovingMNIST` follows the trajectory logic of data/moving_mnist.py:38-91 exactly —
 `num_digits` 32x32 sprites on a 64x64 canvas, start ~ randint(32), velocity ~ randint(-4,5),
@@ -8,12 +8,13 @@ sprites come from a seeded in-repo generator instead of MNIST.  Frames are (T,H,
 [0,1]; a batch is (B,T,H,W,1), which `utils.normalize_data` turns into T x (B,1,H,W)."""
 from __future__ import annotations
 
+import os
 import sys
 
 import numpy as np
 import torch
 
-from . import datasets
+from . import datasets, mnist
 from .utils import normalize_data
 
 
@@ -144,8 +145,11 @@ def synthetic_video(batch, seq_len, channels, res, seed=1) -> torch.Tensor:
 def make_batch_generator(opt, seq_len, seed, device=None, train=True):
     """Yields `load()` callables: the host half of a batch has been drawn when the callable is yielded, calling it (on the
     thread that owns the GPU stream) puts the batch on the device as normalize_data's list of T x (B,C,H,W) frames.
-    smmnist: the host draws the integer trajectories, the device composites them (bit-identical to the host batch); it is
-    the reference's trajectory generator over seeded in-repo sprites.
+    smmnist: the host draws the integer trajectories, the device composites them (bit-identical to the host batch).  With the
+    MNIST image files of both splits under `--data_root` (dvg_amd/mnist.py: <root>/MNIST/raw, <root>/raw or <root>, raw or .gz)
+    the wanted split is read, uploaded and scaled to 32x32 ONCE, before this returns (dvg_mnist_scale_u8); a batch is then the
+    reference's draws (mnist.MovingMnistSampler) and one dvg_moving_mnist_compose_u8 launch.  Without them, or with
+    --synthetic_data, it is the reference's trajectory generator over seeded in-repo sprites, and says so.
     kth | bair | ucf: the `train` / test split under `--data_root` is indexed and decoded once into a device frame pool
     (dvg_amd/datasets.py) BEFORE this returns - a missing tree is a SystemExit here, on the caller's thread; the host half
     then draws `local_batch` clips like the reference's loaders, the callable uploads the B pool indices and gathers the
@@ -153,7 +157,15 @@ def make_batch_generator(opt, seq_len, seed, device=None, train=True):
     their shape instead."""
     if opt.dataset in datasets.REAL_DATASETS and not getattr(opt, 'synthetic_data', False):
         return _clip_batches(opt, seq_len, seed, device or torch.device('cuda'), train)
-    return _synthetic_batches(opt, seq_len, seed, device)
+    tried = None
+    if opt.dataset == 'smmnist' and not getattr(opt, 'synthetic_data', False):
+        root = getattr(opt, 'data_root', None)
+        path = mnist.find_tree(root, train) if root else None
+        if path is not None:
+            return _mnist_batches(opt, seq_len, seed, device or torch.device('cuda'), path)
+        if root and os.path.isdir(root):
+            tried = [p for t in (True, False) for p in mnist.candidates(root, t)]
+    return _synthetic_batches(opt, seq_len, seed, device, tried)
 
 
 def _clip_batches(opt, seq_len, seed, device, train):
@@ -172,7 +184,23 @@ def _clip_batches(opt, seq_len, seed, device, train):
     return batches()
 
 
-def _synthetic_batches(opt, seq_len, seed, device):
+def _mnist_batches(opt, seq_len, seed, device, path):
+    from . import ops
+    try:
+        raw = mnist.read_idx_images(path)
+    except ValueError as e:
+        raise SystemExit(str(e))
+    sprites = ops.mnist_scale_u8(torch.from_numpy(raw.copy()).to(device), mnist.DIGIT_SIZE)      # the pool stays uint8
+    sampler = mnist.MovingMnistSampler(len(raw), seq_len, opt.num_digits, opt.image_width, seed)
+
+    def batches():
+        while True:
+            ids, pos = sampler.draw(opt.local_batch)
+            yield lambda ids=ids, pos=pos: list(ops.moving_mnist_compose_u8(sprites, ids, pos, seq_len, opt.image_width).unbind(0))
+    return batches()
+
+
+def _synthetic_batches(opt, seq_len, seed, device, mnist_tried=None):
     if opt.dataset != 'smmnist' and not getattr(opt, 'synthetic_data', False):
         raise SystemExit(f"train.py: no loader for --dataset {opt.dataset} (kth | bair | ucf read --data_root). "
                          "Pass --synthetic_data to train on synthetic clips of that dataset's shape.")
@@ -180,6 +208,8 @@ def _synthetic_batches(opt, seq_len, seed, device):
         what = ("Moving-MNIST trajectories over synthetic sprites (not MNIST digits)" if opt.dataset == 'smmnist'
                 else f"random textured clips shaped like {opt.dataset}")
         print(f"WARNING: synthetic data - {what}; --data_root is ignored", file=sys.stderr)
+        if mnist_tried:
+            print("         no MNIST image files of both splits under --data_root; tried: " + ", ".join(mnist_tried), file=sys.stderr)
     if opt.dataset == 'smmnist':
         ds = SyntheticMovingMNIST(seq_len=seq_len, num_digits=opt.num_digits, image_size=opt.image_width, seed=seed)
         while True:

@@ -315,3 +315,56 @@ def clip_gather(pool, first, T, C):
     _run("clip_gather", 0.0, float(T * b * h * w * pc) + 4.0 * out.numel(), lib().dvg_clip_gather_u8, _p(pool), _p(first),
          _p(out), n, T, b, C, h, w, pc, _stream())
     return out
+
+
+def mnist_scale_u8(raw, out_size=32, tables=None):
+    """(n,out,out) uint8 = Pillow's bilinear `resize((out, out))` of raw (n,s,s) uint8, bit for bit (dvg_mnist_scale_u8):
+    `transforms.Scale(32)` on a split's MNIST digits, once.  The coefficient tables come from dvg_amd/mnist.py and are uploaded
+    here; `tables` = (xmin, coef) of mnist.resize_tables already on the device spares the upload (a graph capture)."""
+    from .. import mnist
+    if not raw.is_cuda or raw.dtype != torch.uint8 or raw.dim() != 3 or raw.shape[1] != raw.shape[2] or not raw.is_contiguous() \
+            or raw.shape[0] == 0:
+        raise RuntimeError("mnist_scale_u8: raw must be a contiguous non-empty (n,s,s) uint8 GPU tensor - no CPU fallback")
+    n, s, _ = raw.shape
+    if s > out_size or out_size > 64:
+        raise RuntimeError(f"mnist_scale_u8: {s} -> {out_size}: only up-scaling to at most 64 is restated")
+    if tables is None:
+        tables = [torch.from_numpy(t).to(raw.device) for t in mnist.resize_tables(s, out_size)]
+    xmin, coef = tables
+    if any(t.dtype != torch.int32 or t.device != raw.device or not t.is_contiguous() for t in tables) or \
+            tuple(xmin.shape) != (out_size,) or tuple(coef.shape) != (out_size, mnist.TAPS):
+        raise RuntimeError("mnist_scale_u8: tables must be int32 (out,) and (out,3) tensors on raw's device")
+    out = torch.empty((n, out_size, out_size), device=raw.device, dtype=torch.uint8)
+    _run("mnist_scale_u8", 0.0, float(raw.numel() + out.numel()), lib().dvg_mnist_scale_u8, _p(raw), _p(out), n, s, out_size,
+         _p(xmin), _p(coef), _stream())
+    return out
+
+
+def moving_mnist_compose_u8(sprites, ids, pos, seq_len, image_size):
+    """(T,B,1,S,S) float32 frames from a uint8 digit pool (N,D,D), ids (B,ND) and pos (B,ND,T,2) = (sy,sx), int32
+    (dvg_moving_mnist_compose_u8).  ids / pos: host arrays (checked against the pool and the canvas here, then uploaded on the
+    current stream) or int32 device tensors (the kernel clamps ids and bounds-checks every access against pos)."""
+    if not sprites.is_cuda or sprites.dtype != torch.uint8 or sprites.dim() != 3 or sprites.shape[1] != sprites.shape[2] \
+            or not sprites.is_contiguous():
+        raise RuntimeError("moving_mnist_compose_u8: sprites must be a contiguous (N,D,D) uint8 GPU tensor - no CPU fallback")
+    n, d, _ = sprites.shape
+    if not (isinstance(ids, torch.Tensor) and ids.is_cuda):
+        ids, pos = torch.as_tensor(ids), torch.as_tensor(pos)
+        if ids.numel() == 0 or pos.numel() == 0 or int(ids.min()) < 0 or int(ids.max()) >= n:
+            raise RuntimeError(f"moving_mnist_compose_u8: ids outside the pool of {n} digits")
+        if int(pos.min()) < 0 or int(pos.max()) > image_size - d:
+            raise RuntimeError(f"moving_mnist_compose_u8: pos outside [0, {image_size - d}]: a digit would leave the canvas")
+        if ids.dtype != torch.int32 or pos.dtype != torch.int32:
+            raise RuntimeError("moving_mnist_compose_u8: ids / pos must be int32")
+        ids, pos = ids.to(sprites.device), pos.to(sprites.device)
+    if ids.dtype != torch.int32 or not isinstance(pos, torch.Tensor) or pos.dtype != torch.int32 or ids.dim() != 2 \
+            or ids.device != sprites.device or pos.device != sprites.device:
+        raise RuntimeError("moving_mnist_compose_u8: ids (B,ND) / pos must be int32 tensors on the pool's device")
+    ids, pos = ids.contiguous(), pos.contiguous()
+    b, nd = ids.shape
+    if tuple(pos.shape) != (b, nd, seq_len, 2):
+        raise RuntimeError(f"moving_mnist_compose_u8: pos shape {tuple(pos.shape)}")
+    out = torch.empty((seq_len, b, 1, image_size, image_size), device=sprites.device, dtype=torch.float32)
+    check(lib().dvg_moving_mnist_compose_u8(_p(sprites), _p(ids), _p(pos), _p(out), n, seq_len, b, nd, image_size, d,
+                                            _stream()), "dvg_moving_mnist_compose_u8")
+    return out

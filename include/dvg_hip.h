@@ -594,6 +594,23 @@ int dvg_moving_mnist_compose(const float* sprites, const int* ids, const int* po
 int dvg_clip_gather_u8(const uint8_t* pool, const int64_t* first, float* out, int64_t n_frames, int T, int B, int C, int H,
                        int W, int pool_c, void* stream);
 
+/* `transforms.Scale(out_size)` on the MNIST digits (data/moving_mnist.py:24-26): Pillow's 8-bit bilinear resize, bit for bit.
+ * raw (n,in_size,in_size) uint8 -> out (n,out_size,out_size) uint8, a horizontal pass into a uint8 intermediate, then a
+ * vertical pass; each output is clamp((2^21 + sum_k pixel[xmin[o] + k] * coef[o][k]) >> 22, 0, 255).  xmin (out_size) and coef
+ * (out_size,3) are DEVICE int32 tables shared by both passes: Pillow's filter bounds and its weights, normalised in double and
+ * rounded to 22-bit fixed point on the host (dvg_amd/mnist.py); the kernel clamps xmin and skips taps past the line.
+ * in_size <= out_size <= 64: only the up-scaling filter is restated.  An addition within ABI 9. */
+int dvg_mnist_scale_u8(const uint8_t* raw, uint8_t* out, int n, int in_size, int out_size, const int* xmin, const int* coef,
+                       void* stream);
+
+/* dvg_moving_mnist_compose from a uint8 digit pool (data/moving_mnist.py:86-90 + utils.normalize_data's layout, utils.py:86-95):
+ * sprites (n_sprites,D,D) uint8, a byte becomes float32 as `ToTensor` makes it, (float)v / 255.0f by a true division; digits are
+ * added in index order, the sum is clipped at 1, out (T,B,1,S,S) float32.  ids (B,num_digits) int32, clamped in the kernel; pos
+ * (B,num_digits,T,2) int32 = (sy,sx), every sprite access bounds-checked against it.  S % 4 == 0, out 16-byte aligned.
+ * An addition within ABI 9. */
+int dvg_moving_mnist_compose_u8(const uint8_t* sprites, const int* ids, const int* pos, float* out, int n_sprites, int T,
+                                int B, int num_digits, int image_size, int digit_size, void* stream);
+
 /* Evaluation metrics of utils.eval_seq (utils.py:220-234): per (sample, channel) image, SSIM as
  * skimage.measure.compare_ssim computes it with its defaults (7x7 uniform window, sample covariance, data range 2
  * for float images, mean over the valid window positions) and PSNR as compare_psnr (data range 1 for non-negative

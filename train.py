@@ -24,7 +24,9 @@ the KL weight does not change with the number of GPUs); every parameter's `.grad
 backward pass is still running (dvg_amd/parallel.py); BatchNorm statistics are per replica.
 Datasets: `kth | bair | ucf` read the reference's processed tree under `--data_root` (dvg_amd/datasets.py: decoded once into
 a device frame pool, batches gathered by dvg_clip_gather_u8) - or, with `--synthetic_data`, train on random textured clips of
-that shape; `smmnist` = seeded Moving-MNIST trajectories with in-repo sprites (no MNIST files, no torchvision).
+that shape; `smmnist` = the reference's Moving-MNIST over the MNIST IDX image files under `--data_root` (dvg_amd/mnist.py: no
+torchvision, no download; scaled to 32x32 once on the device, a batch is one dvg_moving_mnist_compose_u8 launch) - or, without
+those files or with `--synthetic_data`, seeded Moving-MNIST trajectories with in-repo sprites, announced by a warning.
 """
 import argparse
 import importlib
@@ -57,7 +59,9 @@ def build_parser():
     p.add_argument('--model_dir', default='')
     p.add_argument('--name', default='')
     p.add_argument('--output_path', default='.')
-    p.add_argument('--data_root', default='path/to/data/', help='kth | bair | ucf: the root of the processed dataset tree')
+    p.add_argument('--data_root', default='path/to/data/',
+                   help='kth | bair | ucf: the root of the processed dataset tree; smmnist: a directory holding the MNIST IDX '
+                        'image files (<root>/MNIST/raw, <root>/raw or <root>, raw or .gz)')
     p.add_argument('--optimizer', default='adam')
     p.add_argument('--niter', type=int, default=601)
     p.add_argument('--seed', default=1, type=int)
@@ -93,7 +97,8 @@ def build_parser():
                         'B/N clips then train exactly like one process on B clips (default: per-replica statistics, as '
                         'DistributedDataParallel).  The collectives cannot be captured in a hipGraph: iterations run eager.')
     p.add_argument('--synthetic_data', action='store_true',
-                   help='kth | bair | ucf: train on synthetic clips of that shape instead of reading --data_root')
+                   help='kth | bair | ucf: train on synthetic clips of that shape instead of reading --data_root; smmnist: '
+                        'the in-repo sprites even where --data_root holds MNIST')
     return p
 
 
