@@ -47,6 +47,14 @@ class SyntheticMovingMNIST:
     def __len__(self):
         return 10000
 
+    def position(self):
+        """Where the trajectory stream stands (see BatchStream): the generator's state; the sprites are rebuilt from the seed."""
+        return {"sampler": "SyntheticMovingMNIST", "rng": self.rng.bit_generator.state}
+
+    def restore(self, pos):
+        datasets.check_position(pos, "SyntheticMovingMNIST")
+        self.rng.bit_generator.state = pos["rng"]
+
     def _trajectory(self):
         """One sample's RNG draws in the order of moving_mnist.py:43-85: per digit the sprite index, the start and
         the velocity, then the per-frame bounce rules.  Returns (ids (num_digits,), pos (num_digits, T, 2) = (sy, sx))."""
@@ -142,6 +150,64 @@ def synthetic_video(batch, seq_len, channels, res, seed=1) -> torch.Tensor:
     return torch.from_numpy(np.clip(drift, 0, 1, out=drift))
 
 
+class _Batch:
+    """A drawn batch: calling it (on the thread that owns the GPU stream) puts it on the device; `position` is where the
+    sampler stood right after this batch's draws, i.e. where a run that has consumed this batch resumes."""
+    __slots__ = ("load", "position")
+
+    def __init__(self, load, position):
+        self.load, self.position = load, position
+
+    def __call__(self):
+        return self.load()
+
+
+class _Counter:
+    """The `seed + k` stream of the textured synthetic clips as a sampler: its position is k."""
+
+    def __init__(self):
+        self.k = 0
+
+    def position(self):
+        return {"sampler": "synthetic_video", "k": self.k}
+
+    def restore(self, pos):
+        datasets.check_position(pos, "synthetic_video")
+        self.k = int(pos["k"])
+
+
+class BatchStream:
+    """What make_batch_generator returns: an endless iterator of `load()` callables over one host sampler.  `draw()` makes the
+    host half of the next batch (integers only), `load(host)` the device half.  The sampler's state is taken right after every
+    draw and travels with the yielded callable (`.position`), because whoever sits in front (train_graphs.BatchPrefetcher) draws
+    ahead of what the training loop has consumed: the position of a RUN is that of the last batch it consumed, not the
+    sampler's.  `position()` is the position of the last batch handed out (before the first: the sampler's initial state);
+    `restore(position)` makes the next batch the one that followed that position in the run that saved it, bit for bit.
+    `first`: called once before the first draw (the synthetic path's warning / refusal, which stay lazy)."""
+
+    def __init__(self, sampler, draw, load, first=None):
+        self.sampler, self._draw, self._load, self._first = sampler, draw, load, first
+        self._pos = sampler.position()
+
+    def __iter__(self):
+        return self
+
+    def __next__(self):
+        if self._first is not None:
+            first, self._first = self._first, None
+            first()
+        host = self._draw()
+        self._pos = self.sampler.position()
+        return _Batch(lambda: self._load(host), self._pos)
+
+    def position(self):
+        return self._pos
+
+    def restore(self, pos):
+        self.sampler.restore(pos)
+        self._pos = self.sampler.position()
+
+
 def make_batch_generator(opt, seq_len, seed, device=None, train=True):
     """Yields `load()` callables: the host half of a batch has been drawn when the callable is yielded, calling it (on the
     thread that owns the GPU stream) puts the batch on the device as normalize_data's list of T x (B,C,H,W) frames.
@@ -154,7 +220,8 @@ def make_batch_generator(opt, seq_len, seed, device=None, train=True):
     (dvg_amd/datasets.py) BEFORE this returns - a missing tree is a SystemExit here, on the caller's thread; the host half
     then draws `local_batch` clips like the reference's loaders, the callable uploads the B pool indices and gathers the
     clips on the current stream (dvg_clip_gather_u8).  With --synthetic_data those names train on random textured clips of
-    their shape instead."""
+    their shape instead.
+    The result is a BatchStream: `position()` / `restore()` report and set where the stream stands (train.py --resume)."""
     if opt.dataset in datasets.REAL_DATASETS and not getattr(opt, 'synthetic_data', False):
         return _clip_batches(opt, seq_len, seed, device or torch.device('cuda'), train)
     tried = None
@@ -176,12 +243,10 @@ def _clip_batches(opt, seq_len, seed, device, train):
         raise SystemExit(f"dataset: --channels {opt.channels} from {opt.dataset} frames of {pool.shape[3]} channel(s) under "
                          f"{opt.data_root!r}")
 
-    def batches():
+    def load(first):
         from . import ops
-        while True:
-            first = np.array([sampler.draw()[0] for _ in range(opt.local_batch)], np.int64)
-            yield lambda first=first: list(ops.clip_gather(pool, first, seq_len, opt.channels).unbind(0))
-    return batches()
+        return list(ops.clip_gather(pool, first, seq_len, opt.channels).unbind(0))
+    return BatchStream(sampler, lambda: np.array([sampler.draw()[0] for _ in range(opt.local_batch)], np.int64), load)
 
 
 def _mnist_batches(opt, seq_len, seed, device, path):
@@ -193,30 +258,29 @@ def _mnist_batches(opt, seq_len, seed, device, path):
     sprites = ops.mnist_scale_u8(torch.from_numpy(raw.copy()).to(device), mnist.DIGIT_SIZE)      # the pool stays uint8
     sampler = mnist.MovingMnistSampler(len(raw), seq_len, opt.num_digits, opt.image_width, seed)
 
-    def batches():
-        while True:
-            ids, pos = sampler.draw(opt.local_batch)
-            yield lambda ids=ids, pos=pos: list(ops.moving_mnist_compose_u8(sprites, ids, pos, seq_len, opt.image_width).unbind(0))
-    return batches()
+    return BatchStream(sampler, lambda: sampler.draw(opt.local_batch),
+                       lambda h: list(ops.moving_mnist_compose_u8(sprites, h[0], h[1], seq_len, opt.image_width).unbind(0)))
 
 
 def _synthetic_batches(opt, seq_len, seed, device, mnist_tried=None):
-    if opt.dataset != 'smmnist' and not getattr(opt, 'synthetic_data', False):
-        raise SystemExit(f"train.py: no loader for --dataset {opt.dataset} (kth | bair | ucf read --data_root). "
-                         "Pass --synthetic_data to train on synthetic clips of that dataset's shape.")
-    if opt.rank == 0:
-        what = ("Moving-MNIST trajectories over synthetic sprites (not MNIST digits)" if opt.dataset == 'smmnist'
-                else f"random textured clips shaped like {opt.dataset}")
-        print(f"WARNING: synthetic data - {what}; --data_root is ignored", file=sys.stderr)
-        if mnist_tried:
-            print("         no MNIST image files of both splits under --data_root; tried: " + ", ".join(mnist_tried), file=sys.stderr)
+    def first():
+        if opt.dataset != 'smmnist' and not getattr(opt, 'synthetic_data', False):
+            raise SystemExit(f"train.py: no loader for --dataset {opt.dataset} (kth | bair | ucf read --data_root). "
+                             "Pass --synthetic_data to train on synthetic clips of that dataset's shape.")
+        if opt.rank == 0:
+            what = ("Moving-MNIST trajectories over synthetic sprites (not MNIST digits)" if opt.dataset == 'smmnist'
+                    else f"random textured clips shaped like {opt.dataset}")
+            print(f"WARNING: synthetic data - {what}; --data_root is ignored", file=sys.stderr)
+            if mnist_tried:
+                print("         no MNIST image files of both splits under --data_root; tried: " + ", ".join(mnist_tried), file=sys.stderr)
     if opt.dataset == 'smmnist':
         ds = SyntheticMovingMNIST(seq_len=seq_len, num_digits=opt.num_digits, image_size=opt.image_width, seed=seed)
-        while True:
-            ids, pos = ds.trajectories(opt.local_batch)
-            yield lambda ids=ids, pos=pos: ds.compose_device(ids, pos, device or torch.device('cuda'))
-    k = 0
-    while True:
-        seq = synthetic_video(opt.local_batch, seq_len, opt.channels, opt.image_width, seed=seed + k)
-        yield lambda seq=seq: normalize_data(opt, torch.cuda.FloatTensor, seq)[0]
-        k += 1
+        return BatchStream(ds, lambda: ds.trajectories(opt.local_batch),
+                           lambda h: ds.compose_device(h[0], h[1], device or torch.device('cuda')), first)
+    counter = _Counter()
+
+    def draw():
+        seq = synthetic_video(opt.local_batch, seq_len, opt.channels, opt.image_width, seed=seed + counter.k)
+        counter.k += 1
+        return seq
+    return BatchStream(counter, draw, lambda seq: normalize_data(opt, torch.cuda.FloatTensor, seq)[0], first)

@@ -144,6 +144,15 @@ class MetaSampler:
         st = self.py_rng.randint(0, int(self.lengths[s]) - self.seq_len)
         return int(self.bases[s]) + st, self.index.labels[s]
 
+    def position(self):
+        """Where both draw streams stand (data.BatchStream; train.py --resume)."""
+        return {"sampler": "MetaSampler", "np": self.np_rng.get_state(), "py": self.py_rng.getstate()}
+
+    def restore(self, pos):
+        check_position(pos, "MetaSampler")
+        self.np_rng.set_state(pos["np"])
+        self.py_rng.setstate(pos["py"])
+
 
 class BairSampler:
     """RobotPush.get_seq (bair.py:42-57): train draws np.random.randint(len(dirs)) from the generator seeded with the first
@@ -166,6 +175,23 @@ class BairSampler:
         else:
             d = self.np_rng.randint(len(self.bases))
         return int(self.bases[d]), -1
+
+    def position(self):
+        """The next directory of the ordered walk and the state of the random one (data.BatchStream; train.py --resume)."""
+        return {"sampler": "BairSampler", "ordered": self.ordered, "d": self.d, "np": self.np_rng.get_state()}
+
+    def restore(self, pos):
+        check_position(pos, "BairSampler")
+        if bool(pos["ordered"]) != self.ordered or not 0 <= int(pos["d"]) < len(self.bases):
+            raise SystemExit("data position: saved for another BAIR split or tree")
+        self.d = int(pos["d"])
+        self.np_rng.set_state(pos["np"])
+
+
+def check_position(pos, sampler):
+    if not isinstance(pos, dict) or pos.get("sampler") != sampler:
+        got = pos.get("sampler") if isinstance(pos, dict) else type(pos).__name__
+        raise SystemExit(f"data position: saved for {got}, this run draws from {sampler}")
 
 
 def make_sampler(index, seq_len, seed):

@@ -183,3 +183,13 @@ class MovingMnistSampler:
         for b in range(batch_size):
             self._clip(ids[b], pos[b])
         return ids, pos
+
+    def position(self):
+        """Where the draw stream stands (data.BatchStream; train.py --resume)."""
+        return {"sampler": "MovingMnistSampler", "np": self.rng.get_state()}
+
+    def restore(self, pos):
+        if not isinstance(pos, dict) or pos.get("sampler") != "MovingMnistSampler":
+            got = pos.get("sampler") if isinstance(pos, dict) else type(pos).__name__
+            raise SystemExit(f"data position: saved for {got}, this run draws from MovingMnistSampler")
+        self.rng.set_state(pos["np"])

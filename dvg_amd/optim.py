@@ -138,6 +138,33 @@ class FusedAdam(torch.optim.Optimizer):
         for gi, group in enumerate(self.param_groups):
             self._build(gi, group)
 
+    # ---- the host half of the state (train_state: the tensors are saved as whole arena buffers) ----------------------
+    def host_state(self) -> dict:
+        """Per group the hyper-parameters and the per-parameter step counts, as plain numbers."""
+        return {"param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
+                "steps": [[int(self.state[p]["step"]) for p in g["params"] if p.requires_grad] for g in self.param_groups]}
+
+    def load_host_state(self, hs: dict) -> None:
+        """The inverse of host_state(); parameters, gradients and moments are not touched (the caller wrote the arena).  A
+        captured graph's device step counts no longer describe this state: the graph is marked stale (check_graph_fresh raises
+        until begin_capture seeds `tdev` from the restored counts)."""
+        if len(hs["param_groups"]) != len(self.param_groups):
+            raise ValueError("FusedAdam: another number of parameter groups")
+        for g, saved, steps in zip(self.param_groups, hs["param_groups"], hs["steps"]):
+            params = [p for p in g["params"] if p.requires_grad]
+            if len(steps) != len(params):
+                raise ValueError("FusedAdam: another number of parameters in a group")
+            for k, v in saved.items():
+                g[k] = tuple(v) if k == "betas" else v
+            for p, t in zip(params, steps):
+                self.state[p]["step"] = torch.tensor(float(t))
+        for f in self._flat.values():
+            if f:
+                f.pop("ticked", None)
+                self._restore_grad_views(f)
+        if self._captured_groups:
+            self._graph_stale = True
+
     @torch.no_grad()
     def zero_grad(self, set_to_none: bool = False):
         """One fill per group; `p.grad` stays (or becomes again) the view of the flat gradient buffer.  Unlike

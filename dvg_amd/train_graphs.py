@@ -17,7 +17,8 @@ class GraphedIteration:
     GP prior initialisation and allocator warm-up happen there); the next call captures and replays; later calls replay.
     After each replay the version counters of all parameters and buffers are bumped (the graph writes them through raw
     pointers; the packed-weight / BN-fold caches key on versions) and the optimisers' host-side step counts advance.
-    A change of any learning rate (MultiStepLR, train.py:105-106) triggers a re-capture."""
+    A change of any learning rate (MultiStepLR, train.py:105-106) triggers a re-capture, and so does Trainer.load_state_dict
+    (the device-side Adam step counts are seeded from the restored host counts by begin_capture)."""
 
     def __init__(self, trainer, warmup: int = 2):
         self.tr, self.warmup = trainer, warmup
@@ -32,7 +33,8 @@ class GraphedIteration:
 
     def _signature(self, x):
         lrs = tuple(g['lr'] for o in self.tr.optimizers() for g in o.param_groups)
-        return lrs, tuple(tuple(t.shape) for t in x), self.tr.opt.ft, tuple(m.training for m in self.tr.modules)
+        return (lrs, tuple(tuple(t.shape) for t in x), self.tr.opt.ft, tuple(m.training for m in self.tr.modules),
+                getattr(self.tr, "state_loads", 0))     # Trainer.load_state_dict: another state behind the same pointers
 
     def _release(self):
         """Drop the captured graph(s) and everything they keep alive BEFORE a re-capture allocates a new private pool
@@ -179,21 +181,50 @@ class BatchPrefetcher:
     thread runs while the main thread waits (the wait releases the GIL); batches come out in the generator's order."""
 
     def __init__(self, gen, depth=2):
+        self.gen, self.depth = gen, depth
+        # where the CONSUMER stands: the position carried by the last batch handed out (data.BatchStream), not the generator's,
+        # which is up to `depth` + 1 batches further on
+        self._pos = gen.position() if hasattr(gen, "position") else None
+        self._start()
+
+    def _start(self):
         import queue
         import threading
-        self.gen, self.q = gen, queue.Queue(depth)
-        self.thread = threading.Thread(target=self._run, daemon=True)
+        self.q, self._stop = queue.Queue(self.depth), threading.Event()
+        self.thread = threading.Thread(target=self._run, args=(self.q, self._stop), daemon=True)
         self.thread.start()
 
     _END = object()
 
-    def _run(self):
+    def _run(self, q, stop):
         try:
             for item in self.gen:
-                self.q.put(item)
-            self.q.put(self._END)
+                q.put(item)
+                if stop.is_set():
+                    return
+            q.put(self._END)
         except BaseException as e:   # noqa: BLE001 - handed to the consumer
-            self.q.put(e)
+            q.put(e)
+
+    def position(self):
+        """The data position after the batches consumed so far (None in front of a generator that has none)."""
+        return self._pos
+
+    def restore(self, pos):
+        """Continue from `pos`: the thread is stopped (whatever it drew ahead is dropped), the generator restored, and a new
+        thread started.  The next batch is the one that followed `pos` in the run that saved it."""
+        import queue
+        self._stop.set()
+        while self.thread.is_alive():          # blocked in put(), or about to put: make room until it has seen the flag
+            try:
+                while True:
+                    self.q.get_nowait()
+            except queue.Empty:
+                pass
+            self.thread.join(0.002)
+        self.gen.restore(pos)
+        self._pos = self.gen.position()
+        self._start()
 
     def __iter__(self):
         return self
@@ -205,4 +236,5 @@ class BatchPrefetcher:
             raise StopIteration
         if isinstance(item, BaseException):
             raise item
+        self._pos = getattr(item, "position", self._pos)
         return item

@@ -27,6 +27,8 @@ a device frame pool, batches gathered by dvg_clip_gather_u8) - or, with `--synth
 that shape; `smmnist` = the reference's Moving-MNIST over the MNIST IDX image files under `--data_root` (dvg_amd/mnist.py: no
 torchvision, no download; scaled to 32x32 once on the device, a batch is one dvg_moving_mnist_compose_u8 launch) - or, without
 those files or with `--synthetic_data`, seeded Moving-MNIST trajectories with in-repo sprites, announced by a warning.
+`--resume PATH` continues a run exactly from the `train_state.pth` written beside `model.pth` (the reference's "load the trained
+model" section, :86, is empty and `--model_dir` is never read: both kept); dvg_amd/train_state.py, docs/DESIGN_NOTES_resume.md.
 """
 import argparse
 import importlib
@@ -43,7 +45,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 import utils  # noqa: E402
-from dvg_amd import fused, parallel, viz  # noqa: E402
+from dvg_amd import fused, parallel, train_state, viz  # noqa: E402
 from dvg_amd.data import SyntheticMovingMNIST, make_batch_generator, synthetic_video  # noqa: E402,F401
 from dvg_amd.models.gp_models import GaussianLikelihood, GPRegressionLayer1, VariationalELBO  # noqa: E402
 from dvg_amd.optim import FlatArena, FusedAdam, zero_grads  # noqa: E402
@@ -56,7 +58,10 @@ def build_parser():
     p.add_argument('--beta1', default=0.9, type=float)
     p.add_argument('--batch_size', default=50, type=int, help='GLOBAL batch size')
     p.add_argument('--log_dir', default='logs')
-    p.add_argument('--model_dir', default='')
+    p.add_argument('--model_dir', default='', help='accepted and unused, as in the reference; to continue a run: --resume')
+    p.add_argument('--resume', default='', metavar='PATH',
+                   help='continue exactly from a train_state.pth (or the directory that holds one; written beside model.pth) at '
+                        'the saved epoch; the other options must be those of the run that saved it (docs/DESIGN_NOTES_resume.md)')
     p.add_argument('--name', default='')
     p.add_argument('--output_path', default='.')
     p.add_argument('--data_root', default='path/to/data/',
@@ -627,7 +632,6 @@ class Trainer:
         self._iters = getattr(self, '_iters', 0) + 1
         return mse_ctrl, indices, temp_loss
 
-
     # ---- qualitative rollout of train.py:256-289; write_plot below turns its result into the figures of :291-335 ------
     @torch.no_grad()
     def plot(self, x, epoch, nsample=5, eps_by_sample=None):
@@ -685,6 +689,13 @@ class Trainer:
                     'likelihood': own(self.likelihood.state_dict()), 'gp_layer': own(self.gp_layer.state_dict()),
                     'gp_layer_optimizer': self.optimizer.state_dict(), 'opt': self.opt}, path)
 
+    # ---- the whole training state (--resume): dvg_amd/train_state.py, docs/DESIGN_NOTES_resume.md --------------------
+    def state_dict(self, epoch=0, train_gen=None, test_gen=None, shared=True):
+        return train_state.capture(self, epoch, train_gen, test_gen, shared)
+
+    def load_state_dict(self, sd, train_gen=None, test_gen=None, path="<state>"):
+        return train_state.restore(self, sd, train_gen, test_gen, path)
+
 
 def _detached_copy(module):
     """A deep copy of `module` whose parameters and buffers are fresh tensors with their OWN storage and no gradient
@@ -714,6 +725,7 @@ def main(argv=None):
     rank, world, local = parallel.init_distributed()
     opt.rank, opt.world = rank, world
     opt.local_batch = parallel.shard_batch(opt.batch_size, world)
+    state = train_state.open_resume(opt)    # --resume: read and checked against the options before anything is built
     if rank == 0:
         print("Random Seed: ", opt.seed)
     random.seed(opt.seed + rank)
@@ -739,7 +751,8 @@ def main(argv=None):
         step = GraphedIteration(tr)
     else:
         step = SegmentedIteration(tr)
-    for epoch in range(opt.niter):
+    first_epoch = train_state.resume(tr, state, train_gen, test_gen)
+    for epoch in range(first_epoch, opt.niter):
         tr.train_mode()
         tr.scheduler.step()   # before the epoch, as train.py:347
         epoch_mse = 0.0
@@ -767,6 +780,8 @@ def main(argv=None):
                            '%s/sample_%d.pt' % (opt.output_path, epoch))
                 tr.save('%s/model.pth' % opt.output_path)
                 opt.no_images or tr.write_plot(test_x, gen, best, epoch, opt.output_path)   # sample_<epoch>.png / .gif
+            if not opt.no_save:   # after everything of this epoch that draws random numbers; rank 0: the shared part as well
+                train_state.write(tr.state_dict(epoch + 1, train_gen, test_gen, shared=rank == 0), opt.output_path, rank, world)
         if epoch % 10 == 0 and rank == 0:
             print('log dir: %s' % opt.log_dir)
     if opt.print_param_checksum:   # tests: every rank must end with the same parameters
