@@ -80,6 +80,11 @@ _store = {}        # id(owner) -> (weakref(owner), {tag: (version_key(*sources),
 register("derived", _store.clear, lambda: [slot for _, slot in _store.values()])
 
 
+def drop_derived() -> None:
+    """Forget what `derived` holds and nothing else (the other registered caches stay)."""
+    _store.clear()
+
+
 def _forget(ref, key):
     if key in _store and _store[key][0] is ref:        # (the id may already belong to a new owner)
         del _store[key]

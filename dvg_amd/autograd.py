@@ -23,9 +23,8 @@ import os
 
 import torch
 
-from . import fused, ops
-from ._derived import derived
-from .ops import ACT_NONE, MODE_CONV3, MODE_CONV4S2, MODE_CONVT4S2
+from . import fused, ops, weights
+from .ops import ACT_NONE, MODE_CONV3, MODE_CONVT4S2
 
 DIRECT_PARAM_GRADS = True      # the backward kernels add parameter gradients straight into `.grad` (tests toggle it)
 
@@ -175,40 +174,6 @@ def _sink(p, needed=True):
     return g
 
 
-# Derived weights of the training path: a parameter is re-packed once per optimizer step (its `_version` changes),
-# not once per forward/backward call — train_model alone calls the encoder 2*S and the decoder 3*S times between two
-# optimizer steps (train.py:213-232).
-def _packed(weight, transposed=False, lo=None, hi=None, dim=0):
-    def build():
-        w = weight.detach()
-        if lo is not None:
-            w = _c(w[lo:hi] if dim == 0 else w[:, lo:hi])
-        return ops.pack_igemm_weight(w, transposed)
-
-    return derived(weight, ("wp", transposed, lo, hi, dim), (weight,), build)
-
-
-def _transposed(weight):
-    """Contiguous transpose of a 2-D parameter, cached per parameter version: the data gradients of Linear / LSTMCell are
-    NT GEMMs against W^T, and BPTT asked for the same transpose once per time step."""
-    return derived(weight, "T", (weight,), lambda: ops.transpose2d(weight.detach()))
-
-
-def _wino(weight, m, lo=None, hi=None, dgrad=False):
-    """Winograd-domain weights U (ops.winograd_weight) of a Conv2d weight for F(m x m, 3x3), cached per parameter version:
-    forward form, or - dgrad - of the flipped / transposed kernel (optionally of the input-channel slice [lo, hi)) whose
-    3x3 correlation with d(out) is the data gradient."""
-    def build():
-        w = weight.detach()
-        if lo is not None:
-            w = w[:, lo:hi]
-        if dgrad:
-            w = w.transpose(0, 1).flip(2, 3)
-        return ops.winograd_weight(w.contiguous(), m)
-
-    return derived(weight, ("wino", m, lo, hi, dgrad), (weight,), build)
-
-
 # Keep the forward's Winograd input transform V (2.25 x the layer input) for the weight gradient instead of recomputing it in
 # the backward pass: ~17 GB more live memory in a vgg_64 iteration at B = 64 (of 288), half of the weight gradient's operand
 # passes gone.  False: recompute.
@@ -224,23 +189,12 @@ def _conv3_raw(x, weight, b, need_stats, lo=None, hi=None, keep_v=None):
     if m:
         # keep_v: a dict from a caller whose backward will take the weight gradient of this conv
         want_v = keep_v is not None and m == 4 and SAVE_WINO_V and _wino_wgrad_applies(MODE_CONV3, x, None, cout, False)
-        u = ops.conv3x3_winograd(x, _wino(weight, m, lo, hi), None, b, act=ACT_NONE, return_v=want_v)
+        u = ops.conv3x3_winograd(x, weights.winograd(weight, m, lo, hi), None, b, act=ACT_NONE, return_v=want_v)
         if want_v:
             u, keep_v["v"] = u
         # (inside fused.bn_groups the statistics are per group right away: no second pass in fused.group_stats)
         return (u, ops.channel_stats(u.permute(0, 2, 3, 1).reshape(-1, cout), fused.bn_groups_now())) if need_stats else u
-    wp = _packed(weight) if lo is None else _packed(weight, False, lo, hi, 1)
-    return ops.conv3x3(x, None, wp, None, b, act=ACT_NONE, stats=need_stats)
-
-
-def _dgrad3(du, weight, lo, hi):
-    """Data gradient of a 3x3 conv w.r.t. its input channels [lo, hi): a 3x3 conv of d(out) with the flipped /
-    transposed kernel - Winograd when the shape qualifies."""
-    n, c, h, w = du.shape
-    m = fused.winograd_tile(n, c, h, w, hi - lo)
-    if m:
-        return ops.conv3x3_winograd(du, _wino(weight, m, lo, hi, dgrad=True), None, None, act=ACT_NONE)
-    return ops.conv3x3(du, None, _packed(weight, True, lo, hi, 1), None, None, act=ACT_NONE)
+    return fused.BLOCKS["conv3"].raw(x, None, fused.block_weight("conv3", weight, lo, hi), b, stats=need_stats)
 
 
 def _bn_forward(bn, u, stats, count, act, slope, pool):
@@ -258,17 +212,6 @@ def _bn_forward(bn, u, stats, count, act, slope, pool):
     return out, mean, invstd
 
 
-def _upconv_weights(weight, c1):
-    """K4 = W[:, :c1] (*) ones(2x2) as a ConvTranspose2d weight (C1, Cout, 4, 4) (fused.k4_weight: nearest-x2 upsampling +
-    3x3 conv == 4x4 stride-2 transposed conv), packed for the forward (transposed mode) and for the data gradient (the
-    adjoint: a plain 4x4 stride-2 conv with the same weight).  Cached per parameter version."""
-    def build():
-        k4 = fused.k4_weight(weight, c1)
-        return ops.pack_igemm_weight(k4, transposed=True), ops.pack_igemm_weight(k4, transposed=False)
-
-    return derived(weight, ("k4", c1), (weight,), build)
-
-
 class _ConvBlock(torch.autograd.Function):
     """conv (+fused up/cat) + BatchNorm + activation (+ max-pool).  kinds: conv3, conv3_first, conv4s2,
     conv4s2_first, convT4s2."""
@@ -284,35 +227,17 @@ class _ConvBlock(torch.autograd.Function):
         shared = cfg.get("shared")      # ops.SharedBlocks pattern: `addend` holds blocks shared by the groups of x's batch
         if shared is not None:
             addend = shared.like(addend)
-        if addend is not None:
+        blk = fused.BLOCKS[kind]
+        if addend is not None and kind == "conv3" and up and fused.UPCONV_AS_CONVT:
+            # x half of upsample + conv3x3 as the equivalent transposed conv: 4/9 of the MACs, forward and backward
+            r = ops.convT4x4s2(x, None, weights.k4_packed(weight, c1), None, b, act=ACT_NONE, stats=need_stats, addend=addend)
+        elif addend is not None:
             # x half of a concat conv; `addend` = conv(skip, W_skip) shared by the decoder calls of a step (_SkipHalf)
-            if kind == "conv3" and up and fused.UPCONV_AS_CONVT:
-                # upsample + conv3x3 as the equivalent transposed conv: 4/9 of the MACs, forward and backward
-                r = ops.convT4x4s2(x, None, _upconv_weights(weight, c1)[0], None, b, act=ACT_NONE, stats=need_stats,
-                                   addend=addend)
-            elif kind == "conv3":
-                r = ops.conv3x3(x, None, _packed(weight, False, 0, c1, 1), None, b, upsample=up, act=ACT_NONE,
-                                stats=need_stats, addend=addend)
-            elif kind == "convT4s2":
-                r = ops.convT4x4s2(x, None, _packed(weight, True, 0, c1, 0), None, b, act=ACT_NONE, stats=need_stats,
-                                   addend=addend)
-            else:
-                raise RuntimeError(kind)
+            r = blk.raw(x, None, fused.block_weight(kind, weight, 0, c1), b, up=up, stats=need_stats, addend=addend)
         elif kind == "conv3" and skip is None and not up:
             r = _conv3_raw(x, weight, b, need_stats, keep_v=keep if ctx.needs_input_grad[2] else None)
-        elif kind == "conv3":
-            wp = _packed(weight)
-            r = ops.conv3x3(x, skip, wp, None, b, upsample=up, act=ACT_NONE, stats=need_stats)
-        elif kind == "conv3_first":
-            r = ops.conv3x3_first(x, weight, None, b, act=ACT_NONE, stats=need_stats)
-        elif kind == "conv4s2":
-            r = ops.conv4x4s2(x, _packed(weight), None, b, act=ACT_NONE, stats=need_stats)
-        elif kind == "conv4s2_first":
-            r = ops.conv4x4s2_first(x, weight, None, b, act=ACT_NONE, stats=need_stats)
-        elif kind == "convT4s2":
-            r = ops.convT4x4s2(x, skip, _packed(weight, True), None, b, act=ACT_NONE, stats=need_stats)
         else:
-            raise RuntimeError(kind)
+            r = blk.raw(x, skip, fused.block_weight(kind, weight), b, up=up, stats=need_stats)
         u, st = r if need_stats else (r, None)
         n, _, h, w = u.shape
         out, mean, invstd = _bn_forward(bn, u, st, n * h * w, act, slope, pool)
@@ -365,6 +290,9 @@ class _ConvBlock(torch.autograd.Function):
         need_x, need_skip = ng[0], skip is not None and ng[1]
         dx = dskip = None
         c1 = x.shape[1]
+        blk = fused.BLOCKS[kind]
+        tr, kh, kw = blk.finish
+        ctot = weight.shape[blk.cat]
         if cfg["x_half"]:
             # gradient of the x half only; the skip half's dgrad / wgrad happen once per step in _SkipHalf.backward,
             # which receives du (d addend = du) summed over the decoder calls that shared it.  dW lands in the
@@ -379,59 +307,36 @@ class _ConvBlock(torch.autograd.Function):
                         ops.k4_to_w3(dk4, s_w, 0, beta_w)
                     _wgrad(MODE_CONVT4S2, x, None, du, False, q_w, fin, "k4")
                 if need_x:
-                    dx = ops.conv4x4s2(du, _upconv_weights(weight, c1)[1], None, None, act=ACT_NONE)
-            elif kind == "conv3":
-                if s_w is not None:
-                    _wgrad(MODE_CONV3, x, None, du, up, q_w,
-                           lambda part, s_w=s_w, beta_w=beta_w, ct=weight.shape[1]: ops.wgrad_finish(
-                               part, s_w, 0, 3, 3, ctot=ct, c_lo=0, beta=beta_w), "xh")
-                if need_x:
-                    dxu = _dgrad3(du, weight, 0, c1)
-                    dx = ops.upsample2x_bwd(dxu) if up else dxu
+                    dx = ops.conv4x4s2(du, weights.k4_packed(weight, c1, adjoint=True), None, None, act=ACT_NONE)
             else:
                 if s_w is not None:
-                    _wgrad(MODE_CONVT4S2, x, None, du, False, q_w,
-                           lambda part, s_w=s_w, beta_w=beta_w, ct=weight.shape[0]: ops.wgrad_finish(
-                               part, s_w, 1, 4, 4, ctot=ct, c_lo=0, beta=beta_w), "xh")
+                    _wgrad(blk.mode, x, None, du, up, q_w,
+                           lambda part, s_w=s_w, beta_w=beta_w: ops.wgrad_finish(part, s_w, tr, kh, kw, ctot=ctot, c_lo=0,
+                                                                                 beta=beta_w), "xh")
                 if need_x:
-                    dx = ops.conv4x4s2(du, _packed(weight, False, 0, c1, 0), None, None, act=ACT_NONE)
+                    dx = blk.dgrad(du, weight, 0, c1)
+                    dx = ops.upsample2x_bwd(dx) if up else dx
             d_add = None
             if ng[6] and holder is None:
                 # shared blocks (time-batched decoder calls): d(block) = sum of du over the groups that added it
                 d_add = ops.group_sum(du, cfg["shared"]) if cfg.get("shared") is not None else du
             return (dx, None, dW, dbias, dgamma, dbeta, d_add, None)
-        if kind == "conv3":
-            if s_w is not None:
-                _wgrad(MODE_CONV3, x, skip, du, up, q_w,
-                       lambda part, s_w=s_w, beta_w=beta_w: ops.wgrad_finish(part, s_w, 0, 3, 3, beta=beta_w), "full",
-                       v=ctx.wino_v)
-                ctx.wino_v = None
-            if need_x:  # dgrad = a 3x3 conv with the flipped / transposed weights (igemm or Winograd)
-                dxu = _dgrad3(du, weight, 0, c1)
-                dx = ops.upsample2x_bwd(dxu) if up else dxu
-            if need_skip:
-                dskip = _dgrad3(du, weight, c1, weight.shape[1])
-        elif kind == "conv4s2":
-            if s_w is not None:
-                _wgrad(MODE_CONV4S2, x, None, du, False, q_w,
-                       lambda part, s_w=s_w, beta_w=beta_w: ops.wgrad_finish(part, s_w, 0, 4, 4, beta=beta_w), "full")
-            if need_x:
-                dx = ops.convT4x4s2(du, None, _packed(weight, True), None, None, act=ACT_NONE)
-        elif kind == "convT4s2":
-            if s_w is not None:
-                _wgrad(MODE_CONVT4S2, x, skip, du, False, q_w,
-                       lambda part, s_w=s_w, beta_w=beta_w: ops.wgrad_finish(part, s_w, 1, 4, 4, beta=beta_w), "full")
-            if need_x:
-                dx = ops.conv4x4s2(du, _packed(weight, False, 0, c1, 0), None, None, act=ACT_NONE)
-            if need_skip:
-                dskip = ops.conv4x4s2(du, _packed(weight, False, c1, weight.shape[0], 0), None, None, act=ACT_NONE)
-        elif kind in ("conv3_first", "conv4s2_first"):
+        if blk.mode is None:               # the layers on the raw frame
             if need_x:
                 raise RuntimeError("gradients w.r.t. the input frames are not part of the DVG training path")
             if s_w is not None:
-                ops.wgrad_thin(x, du, 3 if kind == "conv3_first" else 4, out=s_w, beta=beta_w)
-        else:
-            raise RuntimeError(kind)
+                ops.wgrad_thin(x, du, kh, out=s_w, beta=beta_w)
+            return None, None, dW, dbias, dgamma, dbeta, None, None
+        if s_w is not None:
+            _wgrad(blk.mode, x, skip, du, up, q_w,
+                   lambda part, s_w=s_w, beta_w=beta_w: ops.wgrad_finish(part, s_w, tr, kh, kw, beta=beta_w), "full",
+                   v=ctx.wino_v)
+            ctx.wino_v = None
+        if need_x:      # (conv3: a 3x3 conv with the flipped / transposed weights, igemm or Winograd)
+            dx = blk.dgrad(du, weight, 0, c1)
+            dx = ops.upsample2x_bwd(dx) if up else dx
+        if need_skip:
+            dskip = blk.dgrad(du, weight, c1, ctot)
         return dx, dskip, dW, dbias, dgamma, dbeta, None, None
 
 
@@ -445,10 +350,11 @@ class _SkipHalf(torch.autograd.Function):
     def forward(ctx, skip, weight, cfg):
         kind, c1 = cfg["kind"], cfg["c1"]
         keep = {}
+        ctot = weight.shape[fused.BLOCKS[kind].cat]
         if kind == "conv3":
-            s = _conv3_raw(skip, weight, None, False, c1, weight.shape[1], keep_v=keep if ctx.needs_input_grad[1] else None)
+            s = _conv3_raw(skip, weight, None, False, c1, ctot, keep_v=keep if ctx.needs_input_grad[1] else None)
         else:
-            s = ops.convT4x4s2(skip, None, _packed(weight, True, c1, weight.shape[0], 0), None, None, act=ACT_NONE)
+            s = fused.BLOCKS[kind].raw(skip, None, fused.block_weight(kind, weight, c1, ctot), None)
         ctx.save_for_backward(skip, weight)
         ctx.param = weight
         ctx.cfg = cfg
@@ -470,22 +376,17 @@ class _SkipHalf(torch.autograd.Function):
         q_w = s_w
         if s_w is None and ctx.needs_input_grad[1]:
             s_w = dW = torch.zeros_like(weight, memory_format=torch.contiguous_format)
+        blk = fused.BLOCKS[kind]
+        tr, kh, kw = blk.finish
+        ctot = weight.shape[blk.cat]
         dskip = None
-        if kind == "conv3":     # the channel slice [c1, Ctot) of the weight's gradient
-            if s_w is not None:
-                _wgrad(MODE_CONV3, skip, None, ds, False, q_w,
-                       lambda part, s_w=s_w, ct=weight.shape[1]: ops.wgrad_finish(part, s_w, 0, 3, 3, ctot=ct, c_lo=c1,
-                                                                                  beta=1.0), "sk", v=ctx.wino_v)
-                ctx.wino_v = None
-            if ctx.needs_input_grad[0]:
-                dskip = _dgrad3(ds, weight, c1, weight.shape[1])
-        else:
-            if s_w is not None:
-                _wgrad(MODE_CONVT4S2, skip, None, ds, False, q_w,
-                       lambda part, s_w=s_w, ct=weight.shape[0]: ops.wgrad_finish(part, s_w, 1, 4, 4, ctot=ct, c_lo=c1,
-                                                                                  beta=1.0), "sk")
-            if ctx.needs_input_grad[0]:
-                dskip = ops.conv4x4s2(ds, _packed(weight, False, c1, weight.shape[0], 0), None, None, act=ACT_NONE)
+        if s_w is not None:     # the channel slice [c1, Ctot) of the weight's gradient
+            _wgrad(blk.mode, skip, None, ds, False, q_w,
+                   lambda part, s_w=s_w: ops.wgrad_finish(part, s_w, tr, kh, kw, ctot=ctot, c_lo=c1, beta=1.0), "sk",
+                   v=ctx.wino_v)
+            ctx.wino_v = None
+        if ctx.needs_input_grad[0]:
+            dskip = blk.dgrad(ds, weight, c1, ctot)
         return dskip, dW, None
 
 
@@ -559,24 +460,23 @@ class _DenseBlock(torch.autograd.Function):
         kind, bn, act, slope = cfg["kind"], cfg["bn"], cfg["act"], cfg["slope"]
         b = bias.detach() if bias is not None else None
         w = weight.detach()
+        gw = weights.gemm_operand(weight, kind)      # head: [dim][K]; stem: [N_out][dim]
         if kind == "head":
             n, c, h, wd = x.shape
             a = x.permute(0, 2, 3, 1).reshape(n, h * wd * c)
-            gw = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()  # [dim][K]
             u2 = ops.gemm_nt(a, gw, None, b, act=ACT_NONE, splitk=max(1, min(64, a.shape[1] // 128)))
             rows, ch = n, w.shape[0]
         else:
             dim, cout, kh, kw = w.shape
             a = _c(x.reshape(-1, dim))
             n = a.shape[0]
-            gw = w.permute(2, 3, 1, 0).reshape(kh * kw * cout, dim).contiguous()  # [N_out][dim]
             u2 = ops.gemm_nt(a, gw, None, b, act=ACT_NONE, period=cout).view(n * kh * kw, cout)
             rows, ch = n * kh * kw, cout
         u4 = u2.view(rows, 1, 1, ch).permute(0, 3, 1, 2)
         st = ops.channel_stats(u2, fused.bn_groups_now()) if bn.training else None
         y4, mean, invstd = _bn_forward(bn, u4, st, rows, act, slope, False)
-        ctx.save_for_backward(a, gw, gamma, u4, y4, mean, invstd)
-        ctx.params = (bias, gamma, beta)
+        ctx.save_for_backward(a, weight, gamma, u4, y4, mean, invstd)     # (weight: so that a step before backward() raises)
+        ctx.params = (weight, bias, gamma, beta)
         groups = mean.shape[0] if mean.dim() == 2 else 1
         ctx.cfg = dict(cfg, train=bn.training, rows=rows, ch=ch, xshape=tuple(x.shape), wshape=tuple(w.shape),
                        has_bias=bias is not None, count=rows // groups)
@@ -586,14 +486,14 @@ class _DenseBlock(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dy):
-        a, gw, gamma, u4, y4, mean, invstd = ctx.saved_tensors
+        a, _, gamma, u4, y4, mean, invstd = ctx.saved_tensors
         cfg = ctx.cfg
         rows, ch, kind = cfg["rows"], cfg["ch"], cfg["kind"]
         if kind == "head":
             dy4 = _c(dy).view(rows, 1, 1, ch).permute(0, 3, 1, 2)
         else:
             dy4 = ops.to_nhwc(dy).permute(0, 2, 3, 1).reshape(rows, 1, 1, ch).permute(0, 3, 1, 2)
-        p_b, p_g, p_be = ctx.params
+        p_w, p_b, p_g, p_be = ctx.params
         ng = ctx.needs_input_grad
         s_g, s_be = _sink(p_g, ng[3]), _sink(p_be, ng[4])
         s_b = _sink(p_b, ng[2]) if cfg["has_bias"] else None
@@ -608,7 +508,7 @@ class _DenseBlock(torch.autograd.Function):
             dW = dgw.view(ch, h, wd, c).permute(0, 3, 1, 2).contiguous()
             dx = None
             if ctx.needs_input_grad[0]:
-                da = ops.gemm_nt(du, ops.transpose2d(gw), None, None)   # [N][K]
+                da = ops.gemm_nt(du, weights.gemm_operand(p_w, "head_T"), None, None)   # [N][K]
                 dx = da.view(n, h, wd, c).permute(0, 3, 1, 2)
         else:
             dim, cout, kh, kw = cfg["wshape"]
@@ -618,7 +518,7 @@ class _DenseBlock(torch.autograd.Function):
             dW = dgw.view(kh, kw, cout, dim).permute(3, 2, 0, 1).contiguous()
             dx = None
             if ctx.needs_input_grad[0]:
-                dx = ops.gemm_nt(du, ops.transpose2d(gw), None, None).view(cfg["xshape"])
+                dx = ops.gemm_nt(du, weights.gemm_operand(p_w, "stem_T"), None, None).view(cfg["xshape"])
         return dx, dW, (dbias if cfg["has_bias"] else None), dgamma, dbeta, None
 
 

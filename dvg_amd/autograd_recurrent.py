@@ -7,7 +7,7 @@ from __future__ import annotations
 import torch
 
 from . import autograd as _ag
-from . import ops
+from . import ops, weights
 from ._derived import zero_state
 from .ops import ACT_NONE
 
@@ -25,7 +25,7 @@ class _Linear(torch.autograd.Function):
     def backward(ctx, dy):
         x, weight, y = ctx.saved_tensors
         dpre = ops.act_bwd(dy, y, ctx.act) if ctx.act != ACT_NONE else _ag._c(dy)
-        dx = ops.gemm_nt(dpre, _ag._transposed(ctx.params[0]), None, None) if ctx.needs_input_grad[0] else None
+        dx = ops.gemm_nt(dpre, weights.transposed(ctx.params[0]), None, None) if ctx.needs_input_grad[0] else None
         s_w = _ag._sink(ctx.params[0], ctx.needs_input_grad[1])
         s_b0 = _ag._sink(ctx.params[1], ctx.needs_input_grad[2]) if ctx.has_bias else None
         if _ag.DENSE_BATCH > 1 and s_w is not None and (s_b0 is not None or not ctx.has_bias):
@@ -54,8 +54,8 @@ class _LSTMCell(torch.autograd.Function):
     def backward(ctx, dh2, dc2):
         x, h, c, w_ih, w_hh, gates, c2 = ctx.saved_tensors
         dG, dc = ops.lstm_gates_bwd(dh2, dc2, gates, c, c2)
-        dx = ops.gemm_nt(dG, _ag._transposed(ctx.params[0]), None, None) if ctx.needs_input_grad[0] else None
-        dh = ops.gemm_nt(dG, _ag._transposed(ctx.params[1]), None, None) if ctx.needs_input_grad[1] else None
+        dx = ops.gemm_nt(dG, weights.transposed(ctx.params[0]), None, None) if ctx.needs_input_grad[0] else None
+        dh = ops.gemm_nt(dG, weights.transposed(ctx.params[1]), None, None) if ctx.needs_input_grad[1] else None
         ng = ctx.needs_input_grad
         sinks = [_ag._sink(p, n) for p, n in zip(ctx.params, ng[3:7])]
         if _ag.DENSE_BATCH > 1 and all(t is not None for t in sinks):
@@ -159,12 +159,12 @@ class _LSTMSequence(torch.autograd.Function):
         dpre = ops.act_bwd(_ag._c(dy), y, ops.ACT_TANH)
         top = saved[4 * (L - 1) + 1]
         acc_wb(len(params) - 2, dpre, top, [len(params) - 1])
-        dh_all = ops.gemm_nt(dpre, _ag._transposed(params[-2]), None, None)          # d h^L_t for every t, (S*B, H)
+        dh_all = ops.gemm_nt(dpre, weights.transposed(params[-2]), None, None)          # d h^L_t for every t, (S*B, H)
         dev = x.device
         for l in reversed(range(L)):
             inp, hs, cs, gs = saved[4 * l: 4 * l + 4]
             wih, whh = params[2 + 4 * l], params[3 + 4 * l]
-            whh_t = _ag._transposed(whh)                                              # [H][4H]
+            whh_t = weights.transposed(whh)                                              # [H][4H]
             dG = torch.empty((S * B, 4 * H), device=dev)
             dcb = [torch.empty((B, H), device=dev), torch.empty((B, H), device=dev)]
             dhb = [torch.empty((B, H), device=dev), torch.empty((B, H), device=dev)]
@@ -179,10 +179,10 @@ class _LSTMSequence(torch.autograd.Function):
             if S > 1:                           # h_{-1} = 0: the first step contributes nothing to dW_hh
                 acc_wb(3 + 4 * l, dG[B:], hs[:(S - 1) * B])
             if l > 0 or pg[0] or pg[1] or ng[0]:
-                dh_all = ops.gemm_nt(dG, _ag._transposed(wih), None, None)          # gradient w.r.t. this layer's input sequence
+                dh_all = ops.gemm_nt(dG, weights.transposed(wih), None, None)          # gradient w.r.t. this layer's input sequence
         de = dh_all
         acc_wb(0, de, x, [1])
-        dx = ops.gemm_nt(de, _ag._transposed(params[0]), None, None) if ng[0] else None
+        dx = ops.gemm_nt(de, weights.transposed(params[0]), None, None) if ng[0] else None
         return (dx, None) + tuple(grads)
 
 

@@ -14,21 +14,19 @@ BN + activation (+ 2x2 max-pool) in one elementwise pass.
 """
 from __future__ import annotations
 
+import collections
+import contextlib
+import functools
 import os
+import types
 import weakref
 
 import torch
 import torch.nn as nn
 
-from . import _derived, ops
+from . import _derived, ops, weights
 from ._derived import derived, version_key as _ver
-from .ops import ACT_LRELU, ACT_NONE, ACT_SIGMOID, ACT_TANH
-
-
-def packed_weight(conv: nn.Module) -> torch.Tensor:
-    """[taps][Cout][Cin] repack of a Conv2d / ConvTranspose2d weight, cached per parameter version."""
-    return derived(conv, "wp", (conv.weight,),
-                   lambda: ops.pack_igemm_weight(conv.weight, transposed=isinstance(conv, nn.ConvTranspose2d)))
+from .ops import ACT_LRELU, ACT_NONE, ACT_SIGMOID, ACT_TANH, MODE_CONV3, MODE_CONV4S2, MODE_CONVT4S2
 
 
 # Winograd F(m x m, 3x3) for the eval-mode 3x3 layers (ops.conv3x3_winograd): 4x (m = 4) / 2.25x (m = 2) fewer
@@ -69,50 +67,10 @@ def winograd_tile(n, c, h, w, cout) -> int:
     return 0
 
 
-def winograd_weight(conv: nn.Module, m: int) -> torch.Tensor:
-    """U = G g G^T in the batched-GEMM layout, cached per parameter version and tile size."""
-    return derived(conv, ("wino", m), (conv.weight,), lambda: ops.winograd_weight(conv.weight, m))
-
-
 # x half of a decoder block's upsample + concat conv in Winograd F(4x4) form when the skip half is hoisted (eval-mode
 # rollouts); UPCONV_WINOGRAD = False: the transposed-conv (K4) form (module attribute; an environment switch until r06)
 UPCONV_WINOGRAD = True
 _UPCONV_WINO_MAX = 16     # largest output map side that takes this form (32 x 32 measured slower than the K4 transposed form)
-
-
-def _winograd_weight_x(conv: nn.Module, c1: int) -> torch.Tensor:
-    """U = G g G^T of the x half W[:, :c1] of a concat conv (F(4x4,3x3)), cached per parameter version."""
-    return derived(conv, ("wino_x", c1), (conv.weight,),
-                   lambda: ops.winograd_weight(conv.weight.detach()[:, :c1].contiguous(), 4))
-
-
-def gemm_weight(conv: nn.Module, kind: str) -> torch.Tensor:
-    """Weights of the two dense ends as [N][K] GEMM operands in NHWC flatten order.
-
-    kind == "head": Conv2d(512,dim,4,1,0) on a 4x4 map (vgg_64.py:44):
-        W[n][ (h*4+w)*512 + c ] = w[n][c][h][w]
-    kind == "stem": ConvTranspose2d(dim,512,4,1,0) on a 1x1 map (vgg_64.py:65):
-        W[ (h*4+w)*512 + c ][k] = w[k][c][h][w]
-    kind == "stem_t": the same transposed to [KP][N], rows zero-padded to KP in {96, 128} (dvg_stem_gemm), or None
-        when dim > 128 / N % 32 != 0.
-    """
-    def build():
-        w = conv.weight.detach()
-        if kind == "head":
-            n, c, kh, kw = w.shape
-            gw = w.permute(0, 2, 3, 1).reshape(n, kh * kw * c).contiguous()
-        elif kind == "stem_t":
-            k, c, kh, kw = w.shape
-            gw = None
-            if k <= 128 and (kh * kw * c) % 32 == 0:
-                gw = torch.zeros((96 if k <= 96 else 128, kh * kw * c), device=w.device, dtype=torch.float32)
-                gw[:k] = w.permute(0, 2, 3, 1).reshape(k, kh * kw * c)
-        else:
-            k, c, kh, kw = w.shape
-            gw = w.permute(2, 3, 1, 0).reshape(kh * kw * c, k).contiguous()
-        return gw
-
-    return derived(conv, "gw" + kind, (conv.weight,), build)
 
 
 def folded_affine(conv: nn.Module, bn: nn.BatchNorm2d):
@@ -140,33 +98,107 @@ def _no_shared(skip, who):
         raise RuntimeError(f"{who}: shared skip blocks (time-batched decoder calls) are a training-path operand (autograd)")
 
 
+def _bias(conv):
+    return conv.bias.detach() if conv.bias is not None else None
+
+
+# ---- the five kinds of conv block ----------------------------------------------------------------------------------------
+# What differs from kind to kind, stated once; the no-grad train-mode blocks and the skip hoisting below and
+# autograd._ConvBlock / _SkipHalf read it.
+#   raw(x, skip, w, bias, up=, stats=, addend=)  the conv alone: raw accumulators (+ bias), on request with the statistics
+#                                                epilogue; w = block_weight(kind, weight[, lo, hi])
+#   mode, finish    the weight gradient: ops.conv_wgrad_partial_multi's MODE_* and ops.wgrad_finish's (transposed, kh, kw);
+#                   mode None (the layers on the raw frame): ops.wgrad_thin with kernel size finish[1], weight read as it is
+#   cat             the weight axis that cat([x, skip]) runs along: 1 for a Conv2d, 0 for a ConvTranspose2d
+#   dgrad(du, weight, lo, hi)   the data gradient w.r.t. the input channels [lo, hi): x is [0, C1), skip [C1, C)
+Block = collections.namedtuple("Block", "raw mode finish cat dgrad")
+
+
+def _raw_conv3(x, skip, wp, b, *, up=False, stats=False, addend=None):
+    return ops.conv3x3(x, skip, wp, None, b, upsample=up, act=ACT_NONE, stats=stats, addend=addend)
+
+
+def _raw_convT4s2(x, skip, wp, b, *, up=False, stats=False, addend=None):
+    if up:
+        raise RuntimeError("convT4s2: no fused upsampling")
+    return ops.convT4x4s2(x, skip, wp, None, b, act=ACT_NONE, stats=stats, addend=addend)
+
+
+def _raw_plain(name):
+    def raw(x, skip, w, b, *, up=False, stats=False, addend=None):
+        if skip is not None or up or addend is not None:
+            raise RuntimeError(f"{name}: neither a concat conv nor an upsampling one")
+        return getattr(ops, name)(x, w, None, b, act=ACT_NONE, stats=stats)
+    return raw
+
+
+def _dgrad_conv3(du, weight, lo, hi):
+    """A 3x3 conv of d(out) with the flipped / transposed kernel - Winograd when the shape qualifies."""
+    n, c, h, w = du.shape
+    m = winograd_tile(n, c, h, w, hi - lo)
+    if m:
+        return ops.conv3x3_winograd(du, weights.winograd(weight, m, lo, hi, dgrad=True), None, None, act=ACT_NONE)
+    return ops.conv3x3(du, None, weights.packed(weight, True, lo, hi, 1), None, None, act=ACT_NONE)
+
+
+def _dgrad_conv4s2(du, weight, lo, hi):
+    return ops.convT4x4s2(du, None, weights.packed(weight, True, lo, hi, 1), None, None, act=ACT_NONE)
+
+
+def _dgrad_convT4s2(du, weight, lo, hi):
+    return ops.conv4x4s2(du, weights.packed(weight, False, lo, hi, 0), None, None, act=ACT_NONE)
+
+
+BLOCKS = {
+    "conv3": Block(_raw_conv3, MODE_CONV3, (0, 3, 3), 1, _dgrad_conv3),
+    "conv4s2": Block(_raw_plain("conv4x4s2"), MODE_CONV4S2, (0, 4, 4), 1, _dgrad_conv4s2),
+    "convT4s2": Block(_raw_convT4s2, MODE_CONVT4S2, (1, 4, 4), 0, _dgrad_convT4s2),
+    "conv3_first": Block(_raw_plain("conv3x3_first"), None, (0, 3, 3), 1, None),
+    "conv4s2_first": Block(_raw_plain("conv4x4s2_first"), None, (0, 4, 4), 1, None),
+}
+
+
+def block_weight(kind, weight, lo=None, hi=None):
+    """The form of `weight` - of its input channels [lo, hi) - that BLOCKS[kind].raw reads."""
+    blk = BLOCKS[kind]
+    return weight if blk.mode is None else weights.packed(weight, bool(blk.finish[0]), lo, hi, blk.cat)
+
+
+def _skip_half(kind, skip, ps):
+    """S = conv(skip, W_skip), raw accumulators; ps: the packed skip half of the weight."""
+    return BLOCKS[kind].raw(skip, None, ps, None)
+
+
 # A train-mode forward pass that stands for k identical reference passes (train.py encodes every middle frame of a
 # sequence twice per closure: as step i's target and as step i+1's input - same weights, same batch, same outputs):
 # k momentum updates with the same batch statistics equal ONE update with momentum 1 - (1 - m)^k, and
 # num_batches_tracked advances by k.  Set by train.Trainer through `bn_passes(k)`.
-_BN_PASSES = 1
+# (This and the scoped settings further down live in one holder: a `with` form sets its fields and puts the former values back
+# on exit.)
+_scope = types.SimpleNamespace(passes=1, groups=None, trace=None, share=None)
 
 
-class bn_passes:
-    def __init__(self, k: int):
-        self.k = int(k)
-
-    def __enter__(self):
-        global _BN_PASSES
-        self.prev, _BN_PASSES = _BN_PASSES, self.k
-
-    def __exit__(self, *exc):
-        global _BN_PASSES
-        _BN_PASSES = self.prev
+@contextlib.contextmanager
+def _scoped(result=None, **fields):
+    prev = {k: getattr(_scope, k) for k in fields}
+    vars(_scope).update(fields)
+    try:
+        yield result
+    finally:
+        vars(_scope).update(prev)
 
 
-def bn_momentum(bn) -> float:
+def bn_passes(k: int):
+    return _scoped(passes=int(k))
+
+
+def bn_momentum(bn, passes=None) -> float:
     m = bn.momentum if bn.momentum is not None else 0.1
-    return 1.0 - (1.0 - m) ** _BN_PASSES
+    return 1.0 - (1.0 - m) ** (_scope.passes if passes is None else passes)
 
 
 def bn_passes_now() -> int:
-    return _BN_PASSES
+    return _scope.passes
 
 
 # Time-batched training (train.py:213-232 is teacher-forced: the encoder calls of a closure - and, once the latent chain has
@@ -175,25 +207,15 @@ def bn_passes_now() -> int:
 # advance group after group in the reference's call order.  `bn_groups(G, (p_first, p_mid, p_last))`: the number of groups
 # and how many reference passes the first / a middle / the last group stands for (see bn_passes: a middle frame of a
 # sequence is encoded twice per closure).  Inside it `bn_passes` must be 1.
-_BN_GROUPS = None
 _GROUP_STATS_RECOMPUTE = False      # tests set it: always take the dvg_channel_stats pass
 
 
-class bn_groups:
-    def __init__(self, groups: int, passes=(1, 1, 1)):
-        self.val = (int(groups),) + tuple(int(k) for k in passes) if groups > 1 else None
-
-    def __enter__(self):
-        global _BN_GROUPS
-        self.prev, _BN_GROUPS = _BN_GROUPS, self.val
-
-    def __exit__(self, *exc):
-        global _BN_GROUPS
-        _BN_GROUPS = self.prev
+def bn_groups(groups: int, passes=(1, 1, 1)):
+    return _scoped(groups=(int(groups),) + tuple(int(k) for k in passes) if groups > 1 else None)
 
 
 def bn_groups_now() -> int:
-    return _BN_GROUPS[0] if _BN_GROUPS else 1
+    return _scope.groups[0] if _scope.groups else 1
 
 
 def group_stats(st, u):
@@ -223,32 +245,16 @@ def bn_counter(bn):
 # in between, train.py:175-198 then :146-172), so train.Trainer reuses those encodings and REPLAYS the running-statistic
 # updates of the second set of passes from the recorded per-call statistics: the same dvg_bn_finalize launches on the
 # same inputs in the same order - bit-identical buffers, none of the convolutions.
-_BN_TRACE = None
-
-
-class bn_trace:
-    def __enter__(self):
-        global _BN_TRACE
-        self.prev, self.entries = _BN_TRACE, []
-        _BN_TRACE = self.entries
-        return self
-
-    def __exit__(self, *exc):
-        global _BN_TRACE
-        _BN_TRACE = self.prev
+def bn_trace():
+    """`with bn_trace() as trace`: trace.entries lists the BatchNorm updates of the train-mode passes run inside."""
+    trace = types.SimpleNamespace(entries=[])
+    return _scoped(trace, trace=trace.entries)
 
 
 def replay_bn_trace(entries) -> None:
-    global _BN_TRACE, _BN_GROUPS
-    prev, _BN_TRACE = _BN_TRACE, None
-    prev_g = _BN_GROUPS
-    try:
-        for bn, stats, count, passes, groups in entries:
-            _BN_GROUPS = groups
-            with bn_passes(passes):
-                _train_bn(bn, stats, count, synced=True)     # (recorded AFTER the cross-rank reduction: no collective here)
-    finally:
-        _BN_TRACE, _BN_GROUPS = prev, prev_g
+    for bn, stats, count, passes, groups in entries:
+        with _scoped(trace=None, groups=groups, passes=passes):
+            _train_bn(bn, stats, count, synced=True)     # (recorded AFTER the cross-rank reduction: no collective here)
 
 
 # ---- synchronised BatchNorm (train.py --sync_bn; SURVEY 8(e)'s "SyncBN variant") -------------------------------------------
@@ -279,29 +285,25 @@ def sync_bn_world() -> int:
 def _train_bn(bn: nn.BatchNorm2d, stats, count, save=False, synced=False):
     """count = elements per channel of the WHOLE (local) batch; with groups every group has count / G of them.
     sync-BN: `stats` becomes the all-reduced sums (two fp32 rows, hi + lo, per group) and `count` the global count (`synced`: that has happened)."""
+    grouped, passes = _scope.groups, _scope.passes
+    g = grouped[0] if grouped else 1
     if _SYNC_BN is not None and not synced:
-        stats = ops.sync_partial_rows(stats, _BN_GROUPS[0] if _BN_GROUPS else 1)
+        stats = ops.sync_partial_rows(stats, g)
         count = count * _SYNC_BN[2]
-    if _BN_TRACE is not None:
-        _BN_TRACE.append((bn, stats, count, _BN_PASSES, _BN_GROUPS))
-    if _BN_GROUPS is not None:
-        g, p0, p1, p2 = _BN_GROUPS
-        if _BN_PASSES != 1 or count % g:
+    if _scope.trace is not None:
+        _scope.trace.append((bn, stats, count, passes, grouped))
+    if grouped:
+        _, p0, p1, p2 = grouped
+        if passes != 1 or count % g:
             raise RuntimeError("grouped BatchNorm: bn_passes must be 1 and the groups must divide the batch")
-        m = bn.momentum if bn.momentum is not None else 0.1
-        mom = tuple(1.0 - (1.0 - m) ** k for k in (p0, p1, p2))
-        return ops.bn_finalize(stats, bn.weight.detach() if bn.weight is not None else None,
-                               bn.bias.detach() if bn.bias is not None else None,
-                               bn.running_mean if bn.track_running_stats else None,
-                               bn.running_var if bn.track_running_stats else None, count // g, bn.eps, 0.0, save=save,
-                               num_batches_tracked=bn_counter(bn), passes=p0 + p2 + (g - 2) * p1, groups=g,
-                               group_momenta=mom)
-    res = ops.bn_finalize(stats, bn.weight.detach() if bn.weight is not None else None,
-                          bn.bias.detach() if bn.bias is not None else None,
-                          bn.running_mean if bn.track_running_stats else None,
-                          bn.running_var if bn.track_running_stats else None, count, bn.eps,
-                          bn_momentum(bn), save=save, num_batches_tracked=bn_counter(bn), passes=_BN_PASSES)
-    return res
+        momentum, passes, momenta = 0.0, p0 + p2 + (g - 2) * p1, tuple(bn_momentum(bn, k) for k in (p0, p1, p2))
+    else:
+        momentum, momenta = bn_momentum(bn), None
+    return ops.bn_finalize(stats, bn.weight.detach() if bn.weight is not None else None,
+                           bn.bias.detach() if bn.bias is not None else None,
+                           bn.running_mean if bn.track_running_stats else None,
+                           bn.running_var if bn.track_running_stats else None, count // g, bn.eps, momentum, save=save,
+                           num_batches_tracked=bn_counter(bn), passes=passes, groups=g, group_momenta=momenta)
 
 
 # --------------------------------------------------------------------------------------
@@ -316,7 +318,7 @@ def _train_bn(bn: nn.BatchNorm2d, stats, count, save=False, synced=False):
 # as `addend` - identical maths up to fp32 summation order, half the K loop.  A skip that changes on every call
 # (training, last_frame_skip) never gets there and pays nothing.  DVG_SKIP_HOIST=0 disables it.
 SKIP_HOIST = os.environ.get("DVG_SKIP_HOIST", "1") != "0"
-# x half of an upsample + 3x3 conv as the equivalent 4x4 stride-2 transposed conv (see _upconv_packed); 0 disables
+# x half of an upsample + 3x3 conv as the equivalent 4x4 stride-2 transposed conv (see weights.k4_packed); 0 disables
 UPCONV_AS_CONVT = os.environ.get("DVG_UPCONV_AS_CONVT", "1") != "0"
 _skip_seen = {}      # (id(conv), id(skip)) -> [weakref(skip), skip._version, weight key, sightings, S or None]
 
@@ -344,57 +346,16 @@ def declare_frozen_skips(skips) -> None:
         _frozen[id(s)] = (weakref.ref(s), s._version)
 
 
-def _split_packed(conv, c1: int):
-    """Packed weights of the x half and the skip half of a concat conv, cached per parameter version."""
-    def build():
-        w = conv.weight.detach()
-        tr = isinstance(conv, nn.ConvTranspose2d)
-        wx, wsk = (w[:c1], w[c1:]) if tr else (w[:, :c1], w[:, c1:])
-        return ops.pack_igemm_weight(wx.contiguous(), transposed=tr), ops.pack_igemm_weight(wsk.contiguous(), transposed=tr)
-
-    return derived(conv, ("wp_split", c1), (conv.weight,), build)
-
-
-_SHARE_SCOPE = None   # dict while inside share_skip_halves(), else None
-
-
-class share_skip_halves:
+def share_skip_halves():
     """Training-side twin of the rollout hoisting: inside this scope the decoder calls that receive the SAME skip
     tensors share one skip half per concat block, forward and backward (autograd._SkipHalf).  train.Trainer opens one
     scope per time step around the three decoder calls of train.py:227-231."""
-
-    def __enter__(self):
-        global _SHARE_SCOPE
-        self.prev, _SHARE_SCOPE = _SHARE_SCOPE, {}
-        return self
-
-    def __exit__(self, *exc):
-        global _SHARE_SCOPE
-        _SHARE_SCOPE = self.prev
+    return _scoped(share={})
 
 
 def skip_share_scope():
-    return _SHARE_SCOPE
-
-
-def k4_weight(weight, c1: int) -> torch.Tensor:
-    """nearest-x2 upsampling followed by a 3x3 conv (pad 1) IS a stride-2 transposed conv with the 4x4 kernel
-    K4 = W (*) ones(2x2): of the 9 taps of an output pixel only 4 distinct low-resolution inputs contribute.  Returns K4
-    of the x half W[:, :c1] of a Conv2d weight in ConvTranspose2d layout (C1, Cout, 4, 4).  Tap t (0..2) of the 3x3
-    kernel lands on k = 2 - t and k = 3 - t of the 4-tap kernel, per axis."""
-    w = weight.detach()[:, :c1]                           # (Cout, C1, 3, 3)
-    k4 = torch.zeros((w.shape[0], c1, 4, 4), device=w.device, dtype=torch.float32)
-    for ty in range(3):
-        for tx in range(3):
-            k4[:, :, 2 - ty:4 - ty, 2 - tx:4 - tx] += w[:, :, ty:ty + 1, tx:tx + 1]
-    return k4.permute(1, 0, 2, 3).contiguous()
-
-
-def _upconv_packed(conv, c1: int):
-    """The packed K4 (k4_weight) of the x half of a concat conv, cached per parameter version: the x half of every decoder
-    block's first conv (vgg_64.py:98-105) then runs on the CONVT4S2 igemm mode with 4/9 of the MACs."""
-    return derived(conv, ("k4", c1), (conv.weight,),
-                   lambda: ops.pack_igemm_weight(k4_weight(conv.weight, c1), transposed=True))
+    """The dict of the innermost share_skip_halves() scope, or None outside one."""
+    return _scope.share
 
 
 def precompute_skip_half(conv, skip, kind: str) -> None:
@@ -403,13 +364,8 @@ def precompute_skip_half(conv, skip, kind: str) -> None:
     first decoder call finds S ready.  kind: "conv3" (vgg blocks) | "convT4s2" (dcgan blocks)."""
     if not SKIP_HOIST or skip is None:
         return
-    tr = isinstance(conv, nn.ConvTranspose2d)
-    c1 = (conv.weight.shape[0] if tr else conv.weight.shape[1]) - skip.shape[1]
-    _, ps = _split_packed(conv, c1)
-    if kind == "conv3":
-        s = ops.conv3x3(skip, None, ps, None, None, act=ACT_NONE)
-    else:
-        s = ops.convT4x4s2(skip, None, ps, None, None, act=ACT_NONE)
+    ctot = conv.weight.shape[BLOCKS[kind].cat]
+    s = _skip_half(kind, skip, block_weight(kind, conv.weight, ctot - skip.shape[1], ctot))
     _skip_seen[(id(conv), id(skip))] = [weakref.ref(skip), skip._version, _ver(conv.weight), 1, s]
 
 
@@ -434,7 +390,7 @@ def _hoisted_skip(conv, x, skip, partial_fn, force=False):
             return None                    # first sighting of an undeclared skip: the ordinary fused concat conv
     else:
         ent[3] += 1
-    px, ps = _split_packed(conv, x.shape[1])
+    px, ps = weights.split_packed(conv.weight, x.shape[1], isinstance(conv, nn.ConvTranspose2d))
     if ent[4] is None:
         ent[4] = partial_fn(ps)            # second sighting: S = conv(skip, W_skip), raw accumulators
     return px, ent[4]
@@ -502,6 +458,30 @@ def _chain_up_to(next_up, n, c, h, w, stem=False) -> bool:
             and ((h, w) == (4, 4) if stem else ops.winograd_up_chain_ok(n, c, h, w)) and _hoist_ready(conv_n, skip_n))
 
 
+def _hand_over(next_conv, next_up, n, c, h, w, pool=False):
+    """What an F(4x4) layer with an (n,c,h,w) output hands to its only consumer instead of the activation: True - the input
+    transform of next_conv (through this layer's 2x2 max-pool with `pool`), "up" - that of next_up's conv through the
+    upsampling, False - nothing, it writes the activation."""
+    if _chain_to(next_conv, n, c, h, w, pool):
+        return True
+    return "up" if not pool and _chain_up_to(next_up, n, c, h, w) else False
+
+
+def _bn_act_train(bn, u, st, *, act, slope=0.2, pool=False):
+    """Tail of every no-grad train-mode block: batch statistics of the raw conv output u (NHWC; st: its partial statistics
+    rows) finalised on device - running statistics updated - then BN + activation (+ max-pool) in place."""
+    n, _, h, w = u.shape
+    sc, sh = _train_bn(bn, group_stats(st, u), n * h * w)
+    return ops.bn_act_apply(u, sc, sh, act=act, slope=slope, pool=pool, inplace=True)
+
+
+def _train_block(kind, conv, bn, x, skip=None, *, up=False, act, slope, pool=False):
+    """A conv block in train mode without autograd: the direct kernel with the statistics epilogue, also where the shape
+    would qualify for Winograd (the autograd forward differs there: autograd._conv3_raw)."""
+    u, st = BLOCKS[kind].raw(x, skip, block_weight(kind, conv.weight), _bias(conv), up=up, stats=True)
+    return _bn_act_train(bn, u, st, act=act, slope=slope, pool=pool)
+
+
 def conv3_bn_act(conv, bn, x, skip=None, *, upsample=False, pool=False, act=ACT_LRELU, slope=0.2, next_conv=None, y_from=0,
                  next_up=None):
     """vgg_layer (vgg_64.py:5-15) with optional fused cat/upsample on the input and
@@ -517,15 +497,14 @@ def conv3_bn_act(conv, bn, x, skip=None, *, upsample=False, pool=False, act=ACT_
     if isinstance(x, ops.WinoV) and x.up:
         # first conv of a decoder block fed by the previous block's last layer through the upsampling (_chain_up_to held there)
         hs = None if (bn.training or not upsample or pool) else \
-            _hoisted_skip(conv, x, skip, lambda ps: ops.conv3x3(skip, None, ps, None, None, act=ACT_NONE), force=True)
+            _hoisted_skip(conv, x, skip, functools.partial(_skip_half, "conv3", skip), force=True)
         if hs is None:
             raise RuntimeError("conv3_bn_act: an upsampled WinoV needs the eval-mode concat conv with its skip half hoisted")
         sc, sh = folded_affine(conv, bn)
         n, c1, h, w = x.shape
         cout = conv.weight.shape[0]
-        to_v = _chain_to(next_conv, n, cout, h, w)
-        return ops.conv3x3_winograd(x, _winograd_weight_x(conv, c1), sc, sh, act=act, slope=slope, upsample=True,
-                                    addend=hs[1], to_v=to_v)
+        return ops.conv3x3_winograd(x, weights.winograd(conv.weight, 4, 0, c1), sc, sh, act=act, slope=slope, upsample=True,
+                                    addend=hs[1], to_v=_hand_over(next_conv, None, n, cout, h, w))
     if isinstance(x, ops.WinoV):
         if bn.training or skip is not None or upsample:
             raise RuntimeError("conv3_bn_act: a WinoV input needs an eval-mode plain 3x3 layer")
@@ -534,11 +513,8 @@ def conv3_bn_act(conv, bn, x, skip=None, *, upsample=False, pool=False, act=ACT_
         cout = conv.weight.shape[0]
         if winograd_tile(n, c, h, w, cout) != 4:
             raise RuntimeError("conv3_bn_act: WinoV handed to a layer that is not F(4x4,3x3)")
-        to_v = _chain_to(next_conv, n, cout, h, w, pool)
-        if not to_v and not pool and _chain_up_to(next_up, n, cout, h, w):
-            to_v = "up"
-        return ops.conv3x3_winograd(x, winograd_weight(conv, 4), sc, sh, act=act, slope=slope, pool=pool, to_v=to_v,
-                                    y_from=y_from)
+        return ops.conv3x3_winograd(x, weights.winograd(conv.weight, 4), sc, sh, act=act, slope=slope, pool=pool,
+                                    to_v=_hand_over(next_conv, next_up, n, cout, h, w, pool), y_from=y_from)
     if _needs_grad(x, skip, conv.weight, bn.weight):
         from .autograd import conv_block_autograd
         return conv_block_autograd("conv3", conv, bn, x, skip, upsample=upsample, pool=pool, act=act, slope=slope)
@@ -546,7 +522,7 @@ def conv3_bn_act(conv, bn, x, skip=None, *, upsample=False, pool=False, act=ACT_
     if not bn.training:
         sc, sh = folded_affine(conv, bn)
         if not pool:
-            hs = _hoisted_skip(conv, x, skip, lambda ps: ops.conv3x3(skip, None, ps, None, None, act=ACT_NONE))
+            hs = _hoisted_skip(conv, x, skip, functools.partial(_skip_half, "conv3", skip))
             if hs is not None:
                 if upsample and UPCONV_WINOGRAD:
                     # x half of upsample + concat conv in Winograd form: the input transform reads x through the nearest-x2
@@ -558,29 +534,24 @@ def conv3_bn_act(conv, bn, x, skip=None, *, upsample=False, pool=False, act=ACT_
                     # measured per layer pair at B = 64 (tools/_exp_up.py; this layer + the next one, K4 form -> Winograd form):
                     # 8x8 139.8 -> 125.8 us, 16x16 145.2 -> 134.4 us, 32x32 (K = 128: bandwidth-bound GEMM) 174.7 -> 189.5 us
                     if 2 * hx_ <= _UPCONV_WINO_MAX and winograd_tile(n_, c1_, 2 * hx_, 2 * wx_, cout_) == 4:
-                        to_v = not torch.is_grad_enabled() and _chain_to(next_conv, n_, cout_, 2 * hx_, 2 * wx_)
-                        return ops.conv3x3_winograd(x, _winograd_weight_x(conv, c1_), sc, sh, act=act, slope=slope,
+                        to_v = not torch.is_grad_enabled() and _hand_over(next_conv, None, n_, cout_, 2 * hx_, 2 * wx_)
+                        return ops.conv3x3_winograd(x, weights.winograd(conv.weight, 4, 0, c1_), sc, sh, act=act, slope=slope,
                                                     upsample=True, addend=hs[1], to_v=to_v)
                 if upsample and UPCONV_AS_CONVT:
-                    return ops.convT4x4s2(x, None, _upconv_packed(conv, x.shape[1]), sc, sh, act=act, slope=slope,
+                    return ops.convT4x4s2(x, None, weights.k4_packed(conv.weight, x.shape[1]), sc, sh, act=act, slope=slope,
                                           addend=hs[1])
                 return ops.conv3x3(x, None, hs[0], sc, sh, upsample=upsample, act=act, slope=slope, addend=hs[1])
         if skip is None and not upsample:
-            m = winograd_tile(x.shape[0], x.shape[1], x.shape[2], x.shape[3], conv.weight.shape[0])
+            n, c, h, w = x.shape
+            cout = conv.weight.shape[0]
+            m = winograd_tile(n, c, h, w, cout)
             if m:
-                to_v = m == 4 and not torch.is_grad_enabled() and \
-                    _chain_to(next_conv, x.shape[0], conv.weight.shape[0], x.shape[2], x.shape[3], pool)
-                if m == 4 and not to_v and not pool and _chain_up_to(next_up, x.shape[0], conv.weight.shape[0], x.shape[2], x.shape[3]):
-                    to_v = "up"
-                return ops.conv3x3_winograd(x, winograd_weight(conv, m), sc, sh, act=act, slope=slope, pool=pool, to_v=to_v,
-                                            y_from=y_from)
-        return _from(ops.conv3x3(x, skip, packed_weight(conv), sc, sh, upsample=upsample, act=act, slope=slope, pool=pool), y_from)
-    wp = packed_weight(conv)
-    u, st = ops.conv3x3(x, skip, wp, None, conv.bias.detach() if conv.bias is not None else None, upsample=upsample,
-                        act=ACT_NONE, stats=True)
-    n, _, h, w = u.shape
-    sc, sh = _train_bn(bn, group_stats(st, u), n * h * w)
-    return ops.bn_act_apply(u, sc, sh, act=act, slope=slope, pool=pool, inplace=True)
+                to_v = m == 4 and not torch.is_grad_enabled() and _hand_over(next_conv, next_up, n, cout, h, w, pool)
+                return ops.conv3x3_winograd(x, weights.winograd(conv.weight, m), sc, sh, act=act, slope=slope, pool=pool,
+                                            to_v=to_v, y_from=y_from)
+        return _from(ops.conv3x3(x, skip, weights.packed(conv.weight), sc, sh, upsample=upsample, act=act, slope=slope,
+                                 pool=pool), y_from)
+    return _train_block("conv3", conv, bn, x, skip, up=upsample, act=act, slope=slope, pool=pool)
 
 
 def conv3_first_bn_act(conv, bn, x_nchw, *, act=ACT_LRELU, slope=0.2):
@@ -591,11 +562,7 @@ def conv3_first_bn_act(conv, bn, x_nchw, *, act=ACT_LRELU, slope=0.2):
     if not bn.training:
         sc, sh = folded_affine(conv, bn)
         return ops.conv3x3_first(x_nchw, conv.weight, sc, sh, act=act, slope=slope)
-    u, st = ops.conv3x3_first(x_nchw, conv.weight, None, conv.bias.detach() if conv.bias is not None else None,
-                              act=ACT_NONE, stats=True)
-    n, _, h, w = u.shape
-    sc, sh = _train_bn(bn, group_stats(st, u), n * h * w)
-    return ops.bn_act_apply(u, sc, sh, act=act, slope=slope, inplace=True)
+    return _train_block("conv3_first", conv, bn, x_nchw, act=act, slope=slope)
 
 
 # eval mode: the encoder's first stage vgg_layer(1, 64) -> vgg_layer(64, C) (+ pool) as one launch (FIRST_PAIR = False: two; module attribute, an environment switch until r06)
@@ -614,8 +581,8 @@ def conv3_first_pair(conv0, bn0, conv1, bn1, x_nchw, *, pool=False, slope=0.2, y
     y_from: as conv3_bn_act."""
     sc0, sh0 = folded_affine(conv0, bn0)
     sc1, sh1 = folded_affine(conv1, bn1)
-    w_t = derived(conv0, "w_t9x64", (conv0.weight,), lambda: conv0.weight.detach().reshape(64, 9).t().contiguous())  # [tap][channel]
-    return ops.conv3x3_first_pair(x_nchw, w_t, sc0, sh0, packed_weight(conv1), sc1, sh1, slope=slope, pool=pool, y_from=y_from)
+    return ops.conv3x3_first_pair(x_nchw, weights.first_pair_taps(conv0.weight), sc0, sh0, weights.packed(conv1.weight), sc1, sh1,
+                                  slope=slope, pool=pool, y_from=y_from)
 
 
 def conv4s2_bn_act(conv, bn, x, *, act=ACT_LRELU, slope=0.2):
@@ -623,15 +590,10 @@ def conv4s2_bn_act(conv, bn, x, *, act=ACT_LRELU, slope=0.2):
     if _needs_grad(x, conv.weight, bn.weight):
         from .autograd import conv_block_autograd
         return conv_block_autograd("conv4s2", conv, bn, x, None, act=act, slope=slope)
-    wp = packed_weight(conv)
     if not bn.training:
         sc, sh = folded_affine(conv, bn)
-        return ops.conv4x4s2(x, wp, sc, sh, act=act, slope=slope)
-    u, st = ops.conv4x4s2(x, wp, None, conv.bias.detach() if conv.bias is not None else None, act=ACT_NONE,
-                          stats=True)
-    n, _, h, w = u.shape
-    sc, sh = _train_bn(bn, group_stats(st, u), n * h * w)
-    return ops.bn_act_apply(u, sc, sh, act=act, slope=slope, inplace=True)
+        return ops.conv4x4s2(x, weights.packed(conv.weight), sc, sh, act=act, slope=slope)
+    return _train_block("conv4s2", conv, bn, x, act=act, slope=slope)
 
 
 def conv4s2_first_bn_act(conv, bn, x_nchw, *, act=ACT_LRELU, slope=0.2):
@@ -642,11 +604,7 @@ def conv4s2_first_bn_act(conv, bn, x_nchw, *, act=ACT_LRELU, slope=0.2):
     if not bn.training:
         sc, sh = folded_affine(conv, bn)
         return ops.conv4x4s2_first(x_nchw, conv.weight, sc, sh, act=act, slope=slope)
-    u, st = ops.conv4x4s2_first(x_nchw, conv.weight, None, conv.bias.detach() if conv.bias is not None else None,
-                                act=ACT_NONE, stats=True)
-    n, _, h, w = u.shape
-    sc, sh = _train_bn(bn, group_stats(st, u), n * h * w)
-    return ops.bn_act_apply(u, sc, sh, act=act, slope=slope, inplace=True)
+    return _train_block("conv4s2_first", conv, bn, x_nchw, act=act, slope=slope)
 
 
 def convT4s2_bn_act(conv, bn, x, skip=None, *, act=ACT_LRELU, slope=0.2):
@@ -657,16 +615,11 @@ def convT4s2_bn_act(conv, bn, x, skip=None, *, act=ACT_LRELU, slope=0.2):
     _no_shared(skip, "convT4s2_bn_act")
     if not bn.training:
         sc, sh = folded_affine(conv, bn)
-        hs = _hoisted_skip(conv, x, skip, lambda ps: ops.convT4x4s2(skip, None, ps, None, None, act=ACT_NONE))
+        hs = _hoisted_skip(conv, x, skip, functools.partial(_skip_half, "convT4s2", skip))
         if hs is not None:
             return ops.convT4x4s2(x, None, hs[0], sc, sh, act=act, slope=slope, addend=hs[1])
-        return ops.convT4x4s2(x, skip, packed_weight(conv), sc, sh, act=act, slope=slope)
-    wp = packed_weight(conv)
-    u, st = ops.convT4x4s2(x, skip, wp, None, conv.bias.detach() if conv.bias is not None else None, act=ACT_NONE,
-                           stats=True)
-    n, _, h, w = u.shape
-    sc, sh = _train_bn(bn, group_stats(st, u), n * h * w)
-    return ops.bn_act_apply(u, sc, sh, act=act, slope=slope, inplace=True)
+        return ops.convT4x4s2(x, skip, weights.packed(conv.weight, True), sc, sh, act=act, slope=slope)
+    return _train_block("convT4s2", conv, bn, x, skip, act=act, slope=slope)
 
 
 def head_bn_tanh(conv, bn, x):
@@ -677,17 +630,16 @@ def head_bn_tanh(conv, bn, x):
     n, c, h, w = x.shape
     if (h, w) != tuple(conv.kernel_size):
         raise RuntimeError(f"encoder head expects a {conv.kernel_size} map, got {(h, w)}")
-    gw = gemm_weight(conv, "head")
+    gw = weights.gemm_operand(conv.weight, "head")
     a = x.permute(0, 2, 3, 1).reshape(n, h * w * c)  # NHWC buffer viewed as [N][K]; no copy
     k = a.shape[1]
     splitk = max(1, min(64, k // 128))
     if not bn.training:
         sc, sh = folded_affine(conv, bn)
         return ops.gemm_nt(a, gw, sc, sh, act=ACT_TANH, splitk=splitk)
-    u = ops.gemm_nt(a, gw, None, conv.bias.detach() if conv.bias is not None else None, act=ACT_NONE, splitk=splitk)
-    st = ops.channel_stats(u, bn_groups_now())
-    sc, sh = _train_bn(bn, st, n)
-    return ops.bn_act_apply(_as_nhwc_vec(u), sc, sh, act=ACT_TANH, inplace=True).reshape(n, u.shape[1])
+    u = ops.gemm_nt(a, gw, None, _bias(conv), act=ACT_NONE, splitk=splitk)
+    u4 = u.view(n, 1, 1, u.shape[1]).permute(0, 3, 1, 2)            # [N][dim] as an NHWC 1x1 map
+    return _bn_act_train(bn, u4, ops.channel_stats(u, bn_groups_now()), act=ACT_TANH).reshape(n, u.shape[1])
 
 
 def stem_bn_act(conv, bn, vec, *, act=ACT_LRELU, slope=0.2, next_up=None):
@@ -700,10 +652,10 @@ def stem_bn_act(conv, bn, vec, *, act=ACT_LRELU, slope=0.2, next_up=None):
     dim, cout, kh, kw = conv.weight.shape
     vec = vec.reshape(-1, dim)
     n = vec.shape[0]
-    gw = gemm_weight(conv, "stem")
+    gw = weights.gemm_operand(conv.weight, "stem")
     if not bn.training:
         sc, sh = folded_affine(conv, bn)
-        wt = gemm_weight(conv, "stem_t")
+        wt = weights.gemm_operand(conv.weight, "stem_t")
         if wt is not None and (kh, kw) == (4, 4) and cout % 16 == 0 and _chain_up_to(next_up, n, cout, 4, 4, stem=True):
             return ops.stem_up_winograd_input(vec, wt, dim, sc, sh, cout, act=act, slope=slope)
     out = ops.nhwc_empty(n, cout, kh, kw, vec.device)
@@ -714,16 +666,8 @@ def stem_bn_act(conv, bn, vec, *, act=ACT_LRELU, slope=0.2, next_up=None):
         else:
             ops.gemm_nt(vec, gw, sc, sh, act=act, slope=slope, period=cout, out=out2d)
         return out
-    ops.gemm_nt(vec, gw, None, conv.bias.detach() if conv.bias is not None else None, act=ACT_NONE, period=cout,
-                out=out2d)
-    st = ops.channel_stats(out2d.view(n * kh * kw, cout), bn_groups_now())
-    sc, sh = _train_bn(bn, st, n * kh * kw)
-    return ops.bn_act_apply(out, sc, sh, act=act, slope=slope, inplace=True)
-
-
-def _as_nhwc_vec(u2d):
-    n, c = u2d.shape
-    return u2d.view(n, 1, 1, c).permute(0, 3, 1, 2)
+    ops.gemm_nt(vec, gw, None, _bias(conv), act=ACT_NONE, period=cout, out=out2d)
+    return _bn_act_train(bn, out, ops.channel_stats(out2d.view(n * kh * kw, cout), bn_groups_now()), act=act, slope=slope)
 
 
 def convT3_last(conv, x, *, act=ACT_SIGMOID):
@@ -731,8 +675,7 @@ def convT3_last(conv, x, *, act=ACT_SIGMOID):
     if _needs_grad(x, conv.weight):
         from .autograd import last_layer_autograd
         return last_layer_autograd("convT3", conv, x, None, act=act)
-    return ops.convT_last_two_step(x, None, conv.weight, conv.bias.detach() if conv.bias is not None else None,
-                                   conv.weight.shape[1], 3, act=act)
+    return ops.convT_last_two_step(x, None, conv.weight, _bias(conv), conv.weight.shape[1], 3, act=act)
 
 
 def convT4s2_last(conv, x, skip, *, act=ACT_TANH):
@@ -741,5 +684,4 @@ def convT4s2_last(conv, x, skip, *, act=ACT_TANH):
         from .autograd import last_layer_autograd
         return last_layer_autograd("convT4s2", conv, x, skip, act=act)
     _no_shared(skip, "convT4s2_last")
-    return ops.convT_last_two_step(x, skip, conv.weight, conv.bias.detach() if conv.bias is not None else None,
-                                   conv.weight.shape[1], 4, act=act)
+    return ops.convT_last_two_step(x, skip, conv.weight, _bias(conv), conv.weight.shape[1], 4, act=act)

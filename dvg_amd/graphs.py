@@ -6,7 +6,10 @@ GraphedTrigger / GraphedSampler, train_graphs.GraphedIteration / SegmentedIterat
    after it - eager code must not read what lives in a graph's private pool (`skip_scope`);
 3. the capture uses the thread-local error mode (`CAPTURE_KW`, `capturing`);
 4. right after the capture the holder takes `snapshot_eager_caches()` and keeps it as long as the graph lives (`capture`);
-5. a capture that raises drops every version-keyed cache and the deferred weight-gradient queues (`capturing`).
+5. a capture that raises drops every version-keyed cache and the deferred weight-gradient queues (`capturing`);
+6. a graph that STEPS parameters (train_graphs) builds every parameter-derived tensor itself: what an eager call derived from
+   the current parameter version is forgotten before the capture (`drop_parameter_forms`).  Inside the capture a form is
+   rebuilt after every optimiser step because `FusedAdam.step` advances the parameters' version counters while capturing too.
 
 Host only: no kernel is launched from here."""
 from __future__ import annotations
@@ -54,6 +57,15 @@ def drop_version_keyed_caches() -> None:
     from . import autograd as ag
     ag.drop_deferred_wgrads()
     _derived.drop_all()
+
+
+def drop_parameter_forms() -> None:
+    """Forget the tensors derived from parameters (packed / transposed / Winograd-domain weights, GEMM-operand forms, folds)
+    before the capture of a graph that steps those parameters.  A form is built once per parameter version whoever asks, so
+    the closure that opens a training iteration finds the forms that the last closure of the previous iteration built from
+    the same version; captured, it would record no build and every replay would read the weights of the eager warm-up.
+    After this, each form's build is recorded in the graph ahead of its first use."""
+    _derived.drop_derived()
 
 
 def snapshot_eager_caches() -> list:

@@ -51,6 +51,7 @@ class GraphedIteration:
         for o in tr.optimizers():
             o.begin_capture()
         torch.cuda.synchronize()
+        graphs.drop_parameter_forms()                # every replay re-derives the weight forms from the stepped parameters
         self._record()
         for o in tr.optimizers():
             o.end_capture()                          # every group a captured zero_grads() ticked was stepped in the capture

@@ -171,7 +171,7 @@ def test_lstm_folded_first_cell_and_state_only_step():
 def test_decoder_stem_kernel_matches_generic_gemm(family):
     """Eval-mode decoder stem through dvg_stem_gemm (transposed, zero-padded weight) against the generic small-M GEMM."""
     import importlib
-    from dvg_amd import fused, ops
+    from dvg_amd import fused, ops, weights
     mod = importlib.import_module(f"dvg_amd.models.{family}_64")
     dec = mod.decoder(90, 1)
     dec.load_state_dict(params.fill_state_dict(dec.state_dict(), 77, params.decoder_transposed_keys(dec.state_dict(), family)))
@@ -182,7 +182,7 @@ def test_decoder_stem_kernel_matches_generic_gemm(family):
         with torch.no_grad():
             got = fused.stem_bn_act(conv, bn, vec)
             sc, sh = fused.folded_affine(conv, bn)
-            ref = ops.gemm_nt(vec, fused.gemm_weight(conv, "stem"), sc, sh, act=ops.ACT_LRELU, slope=0.2, period=512)
+            ref = ops.gemm_nt(vec, weights.gemm_operand(conv.weight, "stem"), sc, sh, act=ops.ACT_LRELU, slope=0.2, period=512)
         assert got.shape == (B, 512, 4, 4)
         assert rel_err(got.permute(0, 2, 3, 1).reshape(B, -1), ref) < 1e-5
 

@@ -34,7 +34,7 @@ def test_upsample_conv3x3_winograd_with_hoisted_skip_half(N, H, C1, Cout):
     u = ops.winograd_weight(d(w), 4)
     y = ops.conv3x3_winograd(nhwc(x), u, d(sc), d(sh), upsample=True, addend=nhwc(S))
     assert y.shape == (N, Cout, 2 * H, 2 * H) and rel_err(y, ref) < 1e-4, rel_err(y, ref)
-    # the form it replaces (fused._upconv_packed): same result up to fp32 summation order
+    # the form it replaces (weights.k4_packed): same result up to fp32 summation order
     k4 = torch.zeros((Cout, C1, 4, 4))
     for ty in range(3):
         for tx in range(3):

@@ -288,8 +288,8 @@ def test_hoist_ready_and_hoisted_skip_agree_across_evictions(monkeypatch):
     declaration, second sighting, weight change, dead skips), and where the entry is evicted between the two calls (the
     64-entry bound) the consumer's `force=True` still yields the skip half instead of raising.  Host logic only: the packing
     and the conv launch are stubbed."""
-    from dvg_amd import fused
-    monkeypatch.setattr(fused, "_split_packed", lambda conv, c1: ("px", "ps"))
+    from dvg_amd import fused, weights
+    monkeypatch.setattr(weights, "split_packed", lambda weight, c1, transposed=False: ("px", "ps"))
     calls = []
     part = lambda ps: calls.append(ps) or "S"      # noqa: E731
     fused.clear_skip_hoist_cache()
@@ -524,8 +524,9 @@ def test_derived_rebuilds_on_version_or_pointer_change_and_dies_with_its_owner()
 def test_every_module_level_cache_is_registered_dropped_and_snapshotted(monkeypatch):
     """The registry of _derived: graphs.snapshot_eager_caches() holds every tensor of every registered cache,
     graphs.drop_version_keyed_caches() empties every one of them and the deferred weight-gradient queues.  The names are
-    listed literally: a new module-level cache means a new name here."""
-    from dvg_amd import _derived, fused, graphs, ops
+    listed literally: a new module-level cache means a new name here.  (One object per form whoever asks, one build per
+    parameter version: tests/test_weights_host.py.)"""
+    from dvg_amd import _derived, fused, graphs, ops, weights
     from dvg_amd import autograd as ag
     from dvg_amd.ops import edge
     assert set(_derived.registered()) == {"derived", "zero_state", "splitk_ws", "group_maps", "skip_proj", "loss_weights",
@@ -542,14 +543,18 @@ def test_every_module_level_cache_is_registered_dropped_and_snapshotted(monkeypa
     monkeypatch.setattr(edge, "pixel_proj", lambda x, wm: t())
     monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: False)       # (asks the device otherwise)
     conv, bn, lin = torch.nn.Conv2d(8, 4, 3, 1, 1), torch.nn.BatchNorm2d(4), torch.nn.Linear(3, 2)
-    last = torch.nn.ConvTranspose2d(8, 1, 3, 1, 1)
-    # "derived": the sites of fused, autograd and ops.edge, stub builders where the real one launches a kernel
-    got = [fused.packed_weight(conv), fused.winograd_weight(conv, 4), fused._winograd_weight_x(conv, 4),
-           fused.gemm_weight(conv, "head"), *fused.folded_affine(conv, bn), *fused._split_packed(conv, 4),
-           fused._upconv_packed(conv, 4), ag._packed(conv.weight), ag._transposed(lin.weight), ag._wino(conv.weight, 4),
-           *ag._upconv_weights(conv.weight, 4), ops._last_wmat_cached(last.weight, 4, 8, 9)]
-    assert fused.packed_weight(conv) is got[0] and ag._transposed(lin.weight) is got[10]
-    k4 = fused.k4_weight(conv.weight.double(), 4).double()      # K4 = W (*) ones(2x2): every tap lands 4 times
+    last, pair, convt = torch.nn.ConvTranspose2d(8, 1, 3, 1, 1), torch.nn.Conv2d(1, 64, 3, 1, 1), torch.nn.ConvTranspose2d(8, 4, 4, 2, 1)
+    big = torch.nn.ConvTranspose2d(200, 8, 4)
+    w, wt = conv.weight, convt.weight
+    # "derived": the sites of weights, fused.folded_affine and ops.edge, stub builders where the real one launches a kernel
+    got = [weights.packed(w), *weights.split_packed(w, 4), weights.k4_packed(w, 4), weights.packed(wt, True),
+           *weights.split_packed(wt, 4, True), weights.k4_packed(w, 4, adjoint=True), weights.packed(w, True, 0, 4, 1), weights.winograd(w, 4), weights.winograd(w, 4, 0, 4), weights.winograd(w, 4, 4, 8, dgrad=True),
+           weights.transposed(lin.weight), weights.gemm_operand(w, "head"), weights.gemm_operand(wt, "stem"),
+           weights.gemm_operand(wt, "stem_t"), weights.gemm_operand(w, "head_T"), weights.first_pair_taps(pair.weight),
+           *fused.folded_affine(conv, bn), ops._last_wmat_cached(last.weight, 4, 8, 9)]
+    assert weights.packed(w) is got[0] and weights.transposed(lin.weight) is got[12] and len({id(g) for g in got}) == len(got)
+    assert weights.gemm_operand(big.weight, "stem_t") is None         # (dim > 128: no dvg_stem_gemm form)
+    k4 = weights.k4_weight(conv.weight.double(), 4).double()      # K4 = W (*) ones(2x2): every tap lands 4 times
     assert k4.shape == (4, 4, 4, 4) and torch.allclose(k4.sum((2, 3)), 4 * conv.weight.detach().double()[:, :4].sum((2, 3)).t(), rtol=1e-5, atol=1e-7)
     # the plain caches, one entry each
     z = _derived.zero_state(2, 3, torch.device("cpu"))
@@ -574,7 +579,9 @@ def test_every_module_level_cache_is_registered_dropped_and_snapshotted(monkeypa
         assert len(cache) == 0, name
     assert graphs.snapshot_eager_caches() == []
     assert not ag._wgrad_queues and not ag._dense_queues and ag._wgrad_flush_queued is False
-    assert fused.packed_weight(conv) is not got[0]                # rebuilt on demand
+    assert weights.packed(conv.weight) is not got[0]              # rebuilt on demand
+    z, _ = _derived.zero_state(2, 3, torch.device("cpu")), graphs.drop_parameter_forms()     # before a training capture: the derived forms only
+    assert len(_derived._store) == 0 and _derived.zero_state(2, 3, torch.device("cpu")) is z
     graphs.drop_version_keyed_caches()
 
 

@@ -14,7 +14,7 @@ from dvg_amd._lib import LIB_PATH  # noqa: E402
 
 LAYERS = [("c4s2", 32, 64, 0, 128), ("c4s2", 16, 128, 0, 256), ("c4s2", 8, 256, 0, 512),
           ("cT", 4, 512, 512, 256), ("cT", 8, 256, 256, 128), ("cT", 16, 128, 128, 64),
-          # x halves of the vgg_64 decoder's upsample convs (as transposed convs, fused._upconv_packed)
+          # x halves of the vgg_64 decoder's upsample convs (as transposed convs, weights.k4_packed)
           ("cT", 4, 512, 0, 512), ("cT", 8, 256, 0, 256), ("cT", 16, 128, 0, 128), ("cT", 32, 64, 0, 64)]
 WARM_S = float(os.environ.get("DIAG_WARM_S", "0.3"))
 

@@ -122,7 +122,8 @@ def main():
                         fused.WINOGRAD_LAYER_OVERRIDE.pop(k_, None)
             return inner
         if "dgrad_direct16" in diag:
-            ag._dgrad3 = with_direct16(ag._dgrad3)
+            blk = fused.BLOCKS["conv3"]
+            fused.BLOCKS["conv3"] = blk._replace(dgrad=with_direct16(blk.dgrad))
         if "fwd_direct16" in diag:
             ag._conv3_raw = with_direct16(ag._conv3_raw)
     if "lockstep" in diag and world > 1:
