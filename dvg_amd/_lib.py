@@ -61,6 +61,7 @@ SIGNATURES = {
     "dvg_moving_mnist_compose_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "dvg_eval_frames": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "dvg_eval_frames_finn": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "dvg_pairwise_frame_mse": (_i, [_p, _p, _i, _l, _i, _l, _i, _p]),
     "dvg_frame_mosaic": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _p] + [_i] * 9 + [_p, _i, _p, _i, _i, _p, _i, _i, _i, _i, _p, _p]),
     "dvg_adam_step": (_i, [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p, _p]),
     "dvg_pixel_proj": (_i, [_p, _p, _p, _l, _i, _i, _p]),

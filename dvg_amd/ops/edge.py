@@ -225,6 +225,28 @@ def eval_frames_finn(gt, pred):
     return out[0].mean(1).view(lead), out[1].mean(1).view(lead), mse.view(lead)
 
 
+def pairwise_frame_mse(samples, lo=None, hi=None):
+    """(hi - lo, B, S, S) mean squared differences BETWEEN the S samples of every frame (dvg_pairwise_frame_mse): entry
+    [t, b, i, j] = mean over C*H*W of (samples[i, lo + t, b] - samples[j, lo + t, b])^2, computed as differences (identical
+    frames give exactly 0; symmetric bit for bit; zero diagonal).  samples: the (S,T,B,C,H,W) tensor make_gifs returns,
+    contiguous; [lo, hi) a step range (default: all T).  The range is scored where it lies: the strides go to the kernel."""
+    _dev_f32(samples, "pairwise_frame_mse.samples")
+    if samples.dim() != 6 or samples.numel() == 0 or not samples.is_contiguous():
+        raise RuntimeError(f"pairwise_frame_mse: samples {tuple(samples.shape)} must be a contiguous non-empty (S,T,B,C,H,W) tensor")
+    s, t, b = samples.shape[:3]
+    d = samples[0, 0, 0].numel()
+    lo, hi = 0 if lo is None else int(lo), t if hi is None else int(hi)
+    if not 0 <= lo < hi <= t:
+        raise RuntimeError(f"pairwise_frame_mse: step range [{lo}, {hi}) of {t} steps")
+    if d >= 1 << 31 or (hi - lo) * b >= 1 << 31:
+        raise RuntimeError(f"pairwise_frame_mse: {hi - lo}x{b} frames of {d} floats exceed the kernel's 32-bit counts")
+    out = torch.empty((hi - lo, b, s, s), device=samples.device, dtype=torch.float32)
+    n = (hi - lo) * b
+    _run("pairwise_frame_mse", 3.0 * n * d * (s * (s - 1) // 2), 4.0 * n * d * s + 4.0 * out.numel(),
+         lib().dvg_pairwise_frame_mse, _p(samples[0, lo]), _p(out), s, t * b * d, n, d, d, _stream())
+    return out
+
+
 QUANT_TRUNC, QUANT_NEAREST = 0, 1                       # DVG_QUANT_*
 MOSAIC_BLACK, MOSAIC_RED, MOSAIC_GREEN = 0, 1, 2        # DVG_MOSAIC_* cell colours
 MOSAIC_SEL_NONE, MOSAIC_SEL_BEST, MOSAIC_SEL_PICK = 0, 1, 2

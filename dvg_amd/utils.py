@@ -120,3 +120,23 @@ def finn_eval_seq(gt, pred):
     p = pred if torch.is_tensor(pred) else torch.stack(list(pred))
     ssim, psnr, mse = ops.eval_frames_finn(g, p)
     return tuple(v.t().double().cpu().numpy() for v in (mse, ssim, psnr))
+
+
+def sample_diversity(samples, n_past):
+    """How different the samples of make_gifs are from each other, per batch row and predicted step.  samples: the
+    (S,T,B,C,H,W) device tensor of make_gifs; the steps n_past ... T - 1 are scored (ops.pairwise_frame_mse, on the device;
+    every reduction of its fp32 matrix in fp64).  The reference has no counterpart: it compares samples with the ground truth only.
+      pair_mse    (B, T_pred) float64: the mean of the S (S - 1) / 2 pairwise MSEs (0 for S = 1)
+      pair_psnr   (B, T_pred) float64: 10 log10(1 / pair_mse), +inf where pair_mse is 0
+      distinct    (B, T_pred) int64: samples s with D[s, j] > 0 for every j < s = different frames among the samples (a sample
+                  holding a NaN compares > 0 with nothing and is not counted)
+      matrix_last (B, S, S) float32: the last predicted step's matrix"""
+    from . import ops
+    m = ops.pairwise_frame_mse(samples, n_past, samples.shape[1])            # (T_pred, B, S, S)
+    s = m.shape[-1]
+    pair_mse = (m.double().sum((-1, -2)) / max(s * (s - 1), 1)).t()         # symmetric, zero diagonal: every pair twice
+    pair_psnr = 10.0 * torch.log10(1.0 / pair_mse)
+    first = (m > 0) | torch.ones(s, s, dtype=torch.bool, device=m.device).triu()   # [s, j]: j >= s, or s differs from j
+    distinct = first.all(-1).sum(-1).t()
+    return {"pair_mse": pair_mse.contiguous(), "pair_psnr": pair_psnr.contiguous(), "distinct": distinct.contiguous(),
+            "matrix_last": m[-1]}

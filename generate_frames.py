@@ -77,6 +77,10 @@ def build_parser():
                    help="make_gifs: skimage = utils.eval_seq's 7x7 uniform-window SSIM and PSNR (the reference's script); finn = "
                         "utils.finn_eval_seq's 11x11 Gaussian-window SSIM, PSNR and MSE, the variant KTH / BAIR results are "
                         "published with")
+    p.add_argument('--diversity', action='store_true',
+                   help='make_gifs: also measure how different the samples are from EACH OTHER (utils.sample_diversity: mean '
+                        'pairwise MSE / PSNR between samples and the number of distinct samples, per predicted step); printed per '
+                        'batch and saved as `diversity`.  Ignored with --gp_trigger')
     p.add_argument('--synthetic_data', action='store_true',
                    help='kth | bair | ucf: synthetic clips of that shape instead of the test split under --data_root; smmnist: '
                         'the in-repo sprites even where --data_root holds MNIST')
@@ -105,8 +109,16 @@ class Generator:
         return self.likelihood(self.gp_layer(gp_input(self.gp_layer, h)))
 
     @torch.no_grad()
-    def make_gifs(self, x, nsample, eps_by_sample=None):
-        """`eps_by_sample[s][i]`: the N(0,1) base sample (D,B) of sample s at trigger step i (parity runs); None = torch RNG."""
+    def make_gifs(self, x, nsample, eps_by_sample=None, diversity=False):
+        """`eps_by_sample[s][i]`: the N(0,1) base sample (D,B) of sample s at trigger step i (parity runs); None = torch RNG.
+        diversity: also return utils.sample_diversity of the samples as `diversity` (computed after the sampler has run, from
+        the returned tensor; nothing about the rollouts or the other keys changes)."""
+        res = self._make_gifs(x, nsample, eps_by_sample)
+        if diversity:
+            res['diversity'] = utils.sample_diversity(res['samples'], self.opt.n_past)
+        return res
+
+    def _make_gifs(self, x, nsample, eps_by_sample):
         opt = self.opt
         B, T = x[0].shape[0], opt.n_eval - opt.n_past
         ssim = torch.zeros(B, nsample, T, device=self.dev)
@@ -389,6 +401,8 @@ def main(argv=None):
             seqs = (synthetic_video(opt.batch_size, opt.n_eval, opt.channels, opt.image_width, seed=opt.seed + k)
                     for k in range(args.nbatches))
         batches = (utils.normalize_data(opt, torch.cuda.FloatTensor, seq)[0] for seq in seqs)
+    if args.diversity and args.gp_trigger:
+        print("WARNING: --diversity scores make_gifs' samples; ignored with --gp_trigger", file=sys.stderr)
     for i, test_x in enumerate(batches):
         if args.gp_trigger:
             res = gen.gp_trigger_gen(test_x, args.trigger_indices, total=opt.n_eval)
@@ -397,12 +411,14 @@ def main(argv=None):
             if not args.no_images:
                 gen.write_trigger_pngs(res, '%s/gen' % opt.log_dir)
         else:
-            res = gen.make_gifs(test_x, args.nsample)
+            res = gen.make_gifs(test_x, args.nsample, diversity=args.diversity)
             saved = {'posterior': res['posterior'][:, 0].cpu(), 'best': res['best'].cpu(), 'psnr': res['psnr'].cpu(),
                      'ssim': res['ssim'].cpu(),
                      'best_sample_0': res['samples'][int(res['best'][0]), :, 0].cpu()}
             if 'mse' in res:
                 saved.update(mse=res['mse'].cpu(), metrics=res['metrics'])
+            if 'diversity' in res:
+                saved['diversity'] = {k: v.cpu() for k, v in res['diversity'].items()}
             torch.save(saved, '%s/gen/sample_lstm_%d.pt' % (opt.log_dir, i))
             sel = res['best'].view(-1, 1, 1).expand(-1, 1, res['ssim'].shape[2])
             if 'mse' in res:
@@ -412,6 +428,12 @@ def main(argv=None):
             else:
                 print('batch %d: best-of-%d by mean SSIM: SSIM %.4f, PSNR %.3f dB' % (
                     i, args.nsample, float(res['ssim'].gather(1, sel).mean()), float(res['psnr'].gather(1, sel).mean())))
+            if 'diversity' in res:
+                dv = res['diversity']
+                print('batch %d: between the %d samples: pairwise MSE %.3e, PSNR %.3f dB over the predicted steps; distinct '
+                      'samples at the last step %.1f/%d' % (i, args.nsample, float(dv['pair_mse'].mean()),
+                                                            float(10.0 * torch.log10(1.0 / dv['pair_mse'].mean())),
+                                                            float(dv['distinct'][:, -1].double().mean()), args.nsample))
             if not args.no_images:
                 gen.write_gifs(test_x, res, i, '%s/gen' % opt.log_dir, rows=args.gif_rows)
 

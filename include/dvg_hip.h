@@ -630,6 +630,15 @@ int dvg_eval_frames(const float* gt, const float* pred, float* ssim, float* psnr
 int dvg_eval_frames_finn(const float* gt, const float* pred, float* ssim, float* psnr, float* mse, int n_frames, int C, int H,
                          int W, void* stream);
 
+/* Sample diversity: out[f][i][j] = (1/D) sum_d (x[i,f,d] - x[j,f,d])^2, (frames, S, S) fp32, BETWEEN the S rollouts of the sample
+ * loop generate_frames.py:147-183; the reference computes nothing of the kind (it scores samples against the ground truth, :178).
+ * Sample s of frame f: D = C*H*W contiguous floats at samples + s * sample_stride + f * frame_stride (strides in floats, >= D).
+ * Direct form, fp32 differences squared (no norm expansion, no MFMA): identical frames give exactly 0; zero diagonal; i < j is
+ * computed once and written twice.  fp32 sums over <= 256 consecutive elements, added and divided in fp64; fixed order, no atomics.
+ * A NaN in sample i fills row / column i of its frame only.  S, frames, D >= 1; no allocation.  An addition within ABI 9. */
+int dvg_pairwise_frame_mse(const float* samples, float* out, int S, long sample_stride, int frames, long frame_stride, int D,
+                           void* stream);
+
 /* The reference's figures as uint8 RGB mosaics, composed on the device in ONE launch.  Replaces, at their call sites
  * generate_frames.py:185-217 (make_gifs -> utils.save_gif_with_text), :235-245 (plot_rec -> utils.save_tensors_image) and
  * train.py:291-335 (plot -> save_tensors_image + utils.save_gif), the chain utils.image_tensor (utils.py:104-150),

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """make_gifs (generate_frames.py:143-189) throughput: nsample rollouts of one batch + SSIM / PSNR + best-of-N, eager sample
 loop vs the replayed sample body with 1 / 3 samples in flight (GPU only).  --metrics finn scores with utils.finn_eval_seq's
-metric set instead of utils.eval_seq's."""
+metric set instead of utils.eval_seq's; --diversity adds utils.sample_diversity (pairwise MSE between the samples) to every batch."""
 import argparse
 import json
 import os
@@ -21,6 +21,7 @@ def build_parser():
     ap.add_argument("--nsample", type=int, default=30)
     ap.add_argument("--metrics", default="skimage", choices=("skimage", "finn"),
                     help="the metric set scored per sample (generate_frames.py --metrics)")
+    ap.add_argument("--diversity", action="store_true", help="also score the samples against each other (generate_frames.py --diversity)")
     return ap
 
 
@@ -34,13 +35,13 @@ def main(argv=None):
         torch.manual_seed(1)
         g = generate_frames.Generator(opt, generate_frames.synthetic_checkpoint(opt), dev)
         x = SyntheticMovingMNIST(seq_len=20, seed=1).batch_device(64, dev)
-        g.make_gifs(x, 3)
+        g.make_gifs(x, 3, diversity=a.diversity)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        g.make_gifs(x, a.nsample)
+        g.make_gifs(x, a.nsample, diversity=a.diversity)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        print(json.dumps({"model": a.model, "metrics": a.metrics, "inflight": inflight, "nsample": a.nsample, "s_per_batch": round(dt, 4),
+        print(json.dumps({"model": a.model, "metrics": a.metrics, "diversity": a.diversity, "inflight": inflight, "nsample": a.nsample, "s_per_batch": round(dt, 4),
                           "predicted_frames_per_s": round(64 * 10 * a.nsample / dt, 1)}), flush=True)
 
 
