@@ -119,6 +119,10 @@ SIGNATURES = {
     "dvg_nchw_to_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "dvg_nhwc_to_nchw": (_i, [_p, _p, _i, _i, _i, _i, _p]),
     "dvg_zero_tick": (_i, [_p, _l, _p, _p, _p, _p, _p]),
+    "dvg_grad_sumsq_blocks": (_i, [_l]),
+    "dvg_grad_sumsq": (_i, [_p, _l, _p, _p]),
+    "dvg_grad_guard_finish": (_i, [_p, _i, _d, _i, _p, _p, _p]),
+    "dvg_adam_step_guarded": (_i, [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p, _p, _p, _p]),
     "dvg_frame_losses_blocks": (_i, [_l]),
     "dvg_frame_losses": (_i, [_p, _p, _p, _p, _l, _i, _i, _p, _p, _p]),
     "dvg_mse_sum_grad": (_i, [_p, _p, _p, _p, _l, _f, _p]),

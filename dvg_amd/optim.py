@@ -116,6 +116,7 @@ class FusedAdam(torch.optim.Optimizer):
         views of the flat moment buffers (of the shared arena under train.Trainer), and torch.save writes the whole storage
         behind a view - the GP optimiser's entry of a checkpoint (train.py:385) would carry the Adam moments of every
         module (+2 x all parameter bytes)."""
+        self.sync_step_counts()
         sd = super().state_dict()
         sd["state"] = {k: {n: (t.detach().clone() if torch.is_tensor(t) else t) for n, t in st.items()}
                        for k, st in sd["state"].items()}
@@ -133,6 +134,8 @@ class FusedAdam(torch.optim.Optimizer):
                     self.state[p] = {"step": torch.tensor(float(st["step"])),
                                      "exp_avg": f["m"][o:o + p.numel()].view(p.shape),
                                      "exp_avg_sq": f["v"][o:o + p.numel()].view(p.shape)}
+                if "skips" in f:
+                    f["skips"].zero_()           # the loaded counts are counts of applied steps (as load_host_state)
             return
         self._flat.clear()
         for gi, group in enumerate(self.param_groups):
@@ -141,6 +144,7 @@ class FusedAdam(torch.optim.Optimizer):
     # ---- the host half of the state (train_state: the tensors are saved as whole arena buffers) ----------------------
     def host_state(self) -> dict:
         """Per group the hyper-parameters and the per-parameter step counts, as plain numbers."""
+        self.sync_step_counts()
         return {"param_groups": [{k: v for k, v in g.items() if k != "params"} for g in self.param_groups],
                 "steps": [[int(self.state[p]["step"]) for p in g["params"] if p.requires_grad] for g in self.param_groups]}
 
@@ -161,6 +165,8 @@ class FusedAdam(torch.optim.Optimizer):
         for f in self._flat.values():
             if f:
                 f.pop("ticked", None)
+                if "skips" in f:
+                    f["skips"].zero_()           # the restored counts are counts of applied steps
                 self._restore_grad_views(f)
         if self._captured_groups:
             self._graph_stale = True
@@ -195,6 +201,7 @@ class FusedAdam(torch.optim.Optimizer):
         next.  An EAGER step() in between advances the host count only (it passes the count as an argument), so a replay
         after it would apply stale bias corrections: step() marks the captured graph stale and after_graph_replay() raises.
         Re-capture (begin_capture again) to continue with graphs after eager steps."""
+        self.sync_step_counts()      # guarded steps that were skipped: the host counts become the counts of applied steps
         self._captured_groups = []
         self._graph_stale = False
         for gi, f in self._flat.items():
@@ -230,8 +237,76 @@ class FusedAdam(torch.optim.Optimizer):
                 self.state[p]["step"] += 1
 
     # ---- step ---------------------------------------------------------------------------------------
+    def _skips(self, f) -> torch.Tensor:
+        """The group's device-side count of guarded steps that were skipped since the last sync_step_counts(); made on the
+        first guarded step (an optimiser that is never guarded owns no such tensor)."""
+        if "skips" not in f:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("FusedAdam: the first guarded step of a group cannot be inside a hipGraph capture "
+                                   "(GradGuard.attach the optimisers, or run one eager guarded step, first)")
+            f["skips"] = torch.zeros(1, dtype=torch.int32, device=f["p"].device)
+        return f["skips"]
+
+    def sync_step_counts(self) -> None:
+        """A guarded step that was skipped (dvg_adam_step_guarded: non-finite gradients under GradGuard.skip_nonfinite) touched
+        nothing, but its step had already been counted: by the zero_grads() tick on the device, by step() / after_graph_replay()
+        on the host.  The kernel corrects for that with the group's `skips` counter; here the counter is read (ONE
+        synchronisation for all groups, never inside an iteration), subtracted from the host counts - and from the device
+        count a captured graph holds - and zeroed, so that state_dict() / host_state() save the number of steps applied.
+        Does nothing, and does not synchronise, for an optimiser that was never stepped with a guard."""
+        fl = [(gi, f) for gi, f in self._flat.items() if f and "skips" in f]
+        if not fl:
+            return
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedAdam.sync_step_counts: cannot read the skip counters during a hipGraph capture")
+        ks = torch.cat([f["skips"] for _, f in fl]).tolist()
+        for (gi, f), k in zip(fl, ks):
+            if not k:
+                continue
+            for p in f["params"]:
+                self.state[p]["step"] -= k
+            if gi in self._captured_groups:
+                f["tdev"].sub_(k)
+            f["skips"].zero_()
+
+    def _adopt_stray_grads(self, f) -> None:
+        """Gradients normally ARE the views of the flat buffer; one that was re-created (module.zero_grad() sets None) is
+        copied in and `p.grad` re-pointed."""
+        stray = [(gv, p.grad) for p, gv in zip(f["params"], f["gviews"])
+                 if p.grad is not gv and p.grad.data_ptr() != gv.data_ptr()]
+        if stray:
+            torch._foreach_copy_([s[0] for s in stray], [s[1] for s in stray])
+            for p, gv in zip(f["params"], f["gviews"]):
+                p.grad = gv
+
     @torch.no_grad()
-    def step(self, closure=None):
+    def guard_spans(self):
+        """What a guarded step of this optimiser is about to apply: (arena or None, lo, hi, flat gradient) per group that has
+        gradients, with every gradient in its flat buffer.  A partially used group raises: the guard's norm is taken over whole
+        flat ranges, and the per-parameter launches of step() have no guarded form."""
+        spans = []
+        for gi, group in enumerate(self.param_groups):
+            f = self._flat.get(gi)
+            if f is None or [id(p) for p in f.get("params", [])] != [id(p) for p in group["params"] if p.requires_grad]:
+                if self.arena is not None and f is not None:
+                    raise RuntimeError("FusedAdam: the parameters of an arena-backed group cannot change")
+                f = self._build(gi, group)
+            if not f:
+                continue
+            have = [p.grad is not None for p in f["params"]]
+            if not any(have):
+                continue
+            if not all(have) or len({int(self.state[p]["step"]) for p in f["params"]}) != 1:
+                raise RuntimeError(f"FusedAdam: group {gi} is partially used (parameters without a gradient, or with different "
+                                   "step counts): it cannot be stepped with a gradient guard")
+            self._adopt_stray_grads(f)
+            self._skips(f)
+            spans.append((self.arena, f["lo"], f["hi"], f["g"]))
+        return spans
+
+    @torch.no_grad()
+    def step(self, closure=None, guard=None):
+        """`guard`: a GradGuard whose `stat` the launches of this call obey (guarded_step has just filled it)."""
         loss = None
         if closure is not None:
             with torch.enable_grad():
@@ -253,14 +328,8 @@ class FusedAdam(torch.optim.Optimizer):
             capturing = torch.cuda.is_current_stream_capturing()
             if all(have) and len(steps) == 1:
                 # the whole group in one launch; the step count lives on the device so that a captured hipGraph
-                # (train.GraphedIteration) applies fresh bias corrections at every replay.  Gradients normally ARE the
-                # views of the flat buffer; a gradient that was re-created (module.zero_grad() sets None) is copied in.
-                stray = [(gv, p.grad) for p, gv in zip(f["params"], f["gviews"])
-                         if p.grad is not gv and p.grad.data_ptr() != gv.data_ptr()]
-                if stray:
-                    torch._foreach_copy_([s[0] for s in stray], [s[1] for s in stray])
-                    for p, gv in zip(f["params"], f["gviews"]):
-                        p.grad = gv
+                # (train.GraphedIteration) applies fresh bias corrections at every replay.
+                self._adopt_stray_grads(f)
                 t = steps.pop() + 1
                 if capturing:
                     # the count lives on the device (begin_capture synchronised it): advanced by the zero_grads() launch of
@@ -273,8 +342,11 @@ class FusedAdam(torch.optim.Optimizer):
                     f.pop("ticked", None)
                     if gi in self._captured_groups:  # a captured graph holds this group's device count: now behind the host's
                         self._graph_stale = True
-                check(lib().dvg_adam_step(ops._p(f["p"]), ops._p(f["g"]), ops._p(f["m"]), ops._p(f["v"]),
-                                          f["p"].numel(), *hyper, t, ops._p(tdev), ops._stream()), "dvg_adam_step")
+                if guard is None:
+                    check(lib().dvg_adam_step(ops._p(f["p"]), ops._p(f["g"]), ops._p(f["m"]), ops._p(f["v"]),
+                                              f["p"].numel(), *hyper, t, ops._p(tdev), ops._stream()), "dvg_adam_step")
+                else:
+                    ops.adam_step_guarded(f["p"], f["g"], f["m"], f["v"], *hyper, t, tdev, guard.stat, self._skips(f))
                 touched = f["params"]
                 if capturing:
                     self._captured_groups.append(gi)
@@ -283,6 +355,8 @@ class FusedAdam(torch.optim.Optimizer):
                 # (no moment decay, no step count) - one launch per parameter that has one
                 if capturing:
                     raise RuntimeError("FusedAdam: a partially used parameter group cannot be captured in a hipGraph")
+                if guard is not None:
+                    raise RuntimeError(f"FusedAdam: group {gi} is partially used: it cannot be stepped with a gradient guard")
                 touched = [p for p in f["params"] if p.grad is not None]
                 for p, gv in zip(f["params"], f["gviews"]):
                     if p.grad is None:
@@ -333,3 +407,113 @@ def zero_grads(optimizers) -> None:
                 s_[3]["ticked"] = True
             s_[4]._restore_grad_views(s_[3])
         i += 1
+
+
+class GradGuard:
+    """Gradient-norm clipping and the skip of a non-finite step, decided on the device (train.py --clip_grad_norm /
+    --skip_nonfinite; docs/DESIGN_NOTES_gradguard.md).  Owns the three device buffers the kernels of grad_guard.hip share:
+
+      partials  fp64 partial sums of squares (dvg_grad_sumsq), sized on first use
+      stat      4 floats: norm of the last step site, its clip factor, its skip flag, the largest finite norm since the last read
+      counters  3 ints: step sites, clipped, skipped since the last read
+
+    max_norm <= 0: no clipping (the factor is 1).  skip_nonfinite: a site whose norm is not finite - some gradient is Inf or NaN -
+    changes no parameter, no moment and no effective step count."""
+
+    def __init__(self, max_norm: float, skip_nonfinite: bool, device):
+        if max_norm != max_norm or max_norm < 0:
+            raise ValueError("GradGuard: max_norm must be >= 0 (0 = no clipping)")
+        self.max_norm, self.skip_nonfinite, self.device = float(max_norm), bool(skip_nonfinite), torch.device(device)
+        self.stat = torch.tensor([0.0, 1.0, 0.0, 0.0], dtype=torch.float32, device=self.device)
+        self.counters = torch.zeros(3, dtype=torch.int32, device=self.device)
+        self.partials = None
+
+    def reserve(self, nblocks: int) -> torch.Tensor:
+        if self.partials is None or self.partials.numel() < nblocks:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("GradGuard: the partial-sum buffer cannot grow during a hipGraph capture (GradGuard.attach "
+                                   "the optimisers, or run one eager guarded step, first)")
+            self.partials = torch.zeros(nblocks, dtype=torch.float64, device=self.device)
+        return self.partials
+
+    def attach(self, optimizers) -> None:
+        """Everything a guarded step of `optimizers` allocates, now: the partial sums for all their groups and the groups' skip
+        counters.  Needed only when the FIRST guarded step is captured in a hipGraph."""
+        n = 0
+        for o in optimizers:
+            for f in o._flat.values():
+                if f:
+                    o._skips(f)
+                    n += ops.grad_sumsq_blocks(f["g"].numel())
+        if n:
+            self.reserve(n)
+
+    def read_and_reset(self) -> dict:
+        """The numbers since the last call - {"max", "last", "sites", "clipped", "skipped"} - read from the device (this
+        synchronises: once per epoch, never inside an iteration); the counters and the maximum start again from zero."""
+        st, ct = self.stat.tolist(), self.counters.tolist()
+        self.counters.zero_()
+        self.stat[3:].zero_()
+        return {"max": st[3], "last": st[0], "sites": ct[0], "clipped": ct[1], "skipped": ct[2]}
+
+    def epoch_line(self) -> str:
+        """train.py's line after `train frames/s` (reads and resets)."""
+        d = self.read_and_reset()
+        return ('     grad norm: max %.4g last %.4g  clipped %d  skipped %d  of %d steps'
+                % (d["max"], d["last"], d["clipped"], d["skipped"], d["sites"]))
+
+
+def guard_options(opt):
+    """(max_norm, skip_nonfinite) when train.py's --clip_grad_norm / --skip_nonfinite ask for a gradient guard, None when
+    neither does (an options object from before the flags has neither attribute).  Host only."""
+    c = float(getattr(opt, "clip_grad_norm", 0.0) or 0.0)
+    skip = bool(getattr(opt, "skip_nonfinite", False))
+    if c != c or c < 0:
+        raise SystemExit("train.py: --clip_grad_norm must be >= 0")
+    return (c, skip) if (c > 0 or skip) else None
+
+
+def make_guard(opt, device, optimizers):
+    """The GradGuard the options ask for, with everything a guarded step of `optimizers` allocates made now (the first
+    guarded step may then be captured in a hipGraph); None - no object, no launch - without the flags."""
+    go = guard_options(opt)
+    if go is None:
+        return None
+    guard = GradGuard(go[0], go[1], device)
+    guard.attach(optimizers)
+    return guard
+
+
+@torch.no_grad()
+def guarded_step(optimizers, guard: Optional[GradGuard]) -> None:
+    """`o.step()` for every FusedAdam in `optimizers` under ONE verdict of `guard` about ALL the gradients they are about to
+    apply: the sum of squares of every flat range (adjacent ranges of a shared arena as one), the decision kernel, then the
+    guarded Adam launches - on the current stream, in order, eagerly or inside a hipGraph capture.  With several ranks call it
+    after the all-reduce of these ranges has finished: every rank then reduces the same bits in the same order.
+    guard = None: the plain steps, nothing else."""
+    if guard is None:
+        for o in optimizers:
+            o.step()
+        return
+    spans = []
+    for o in optimizers:
+        if not isinstance(o, FusedAdam):
+            raise RuntimeError("guarded_step: FusedAdam optimisers expected")
+        spans += o.guard_spans()
+    if not spans:
+        return
+    shared = sorted((s_ for s_ in spans if s_[0] is not None), key=lambda s_: (id(s_[0]), s_[1]))
+    ranges = []                                            # flat gradient tensors, adjacent arena ranges merged
+    for arena, lo, hi, _ in shared:
+        if ranges and ranges[-1][0] is arena and ranges[-1][2] == lo:
+            ranges[-1][2] = hi
+        else:
+            ranges.append([arena, lo, hi])
+    flats = [a.g[lo:hi] for a, lo, hi in ranges] + [s_[3] for s_ in spans if s_[0] is None]
+    partials = guard.reserve(sum(ops.grad_sumsq_blocks(g.numel()) for g in flats))
+    slot = 0
+    for g in flats:
+        slot += ops.grad_sumsq(g, partials, slot)
+    ops.grad_guard_finish(partials, slot, guard.max_norm, guard.skip_nonfinite, guard.stat, guard.counters)
+    for o in optimizers:
+        o.step(guard=guard)

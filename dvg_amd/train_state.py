@@ -7,7 +7,8 @@ One process: `<output_path>/train_state.pth` holds everything.  Several ranks: r
 moments and step counts, scheduler, epoch) to `train_state.pth`, every rank what differs between replicas (BatchNorm buffers,
 random streams, data positions) to `train_state.rank<r>.pth` beside it.
 
-Host only: no kernel is launched from here."""
+Host only: no kernel is launched from here (with a gradient guard, capture() first has the optimisers fold their skip counters
+into the step counts: FusedAdam.sync_step_counts, one read of a few device ints)."""
 from __future__ import annotations
 
 import os
@@ -138,6 +139,23 @@ def set_random_streams(rng: dict, device) -> None:
     np.random.set_state(rng["numpy"])
 
 
+def detached_copy(module):
+    """A deep copy of `module` whose parameters and buffers are fresh tensors with their OWN storage and no gradient
+    (copy.deepcopy alone clones the whole storage behind every arena view, and would copy `.grad` as well).  Trainer.save's
+    helper; it lives here, beside the other code that writes training state, because train.py is held to 800 lines
+    (tests/test_host_logic.py) and the gradient-guard flags needed the room."""
+    import copy
+    memo = {}
+    for p in module.parameters():
+        memo[id(p)] = torch.nn.Parameter(p.detach().clone(), requires_grad=p.requires_grad)
+    for b in module.buffers():
+        memo[id(b)] = b.detach().clone()
+    hidden = getattr(module, "hidden", None)
+    if hidden is not None:         # lstm.hidden: the recurrent state of the last sequence, may carry an autograd graph
+        memo[id(hidden)] = [(h.detach().clone(), c.detach().clone()) for h, c in hidden]
+    return copy.deepcopy(module, memo)
+
+
 # ---- what the state of a train.Trainer is -----------------------------------------------------------------------------------
 def named_optimizers(tr):
     return (("gp", tr.optimizer), ("frame_predictor", tr.frame_predictor_optimizer), ("decoder", tr.decoder_optimizer),
@@ -176,6 +194,8 @@ def capture(tr, epoch=0, train_gen=None, test_gen=None, shared=True) -> dict:
             "data": {"train": train_gen.position() if train_gen is not None else None,
                      "test": test_gen.position() if test_gen is not None else None}}
     sd = {"format": FORMAT, "epoch": int(epoch), RANK_KEY: mine}
+    for _, o in named_optimizers(tr):    # steps a gradient guard skipped are not steps: the counts of steps really applied
+        o.sync_step_counts()             # (every rank: the host counts stay the same on all of them)
     if shared:
         lo, hi = tr.rng_gp
         a = tr.arena

@@ -56,53 +56,40 @@ long dvg_stream_capture_id(void* stream);
  * Weight re-layout (one launch per parameter, cached by the caller).
  * ------------------------------------------------------------------ */
 
-/* Conv2d weight (Cout,Cin,KH,KW) [vgg_64.py:8, dcgan_64.py:8] ->
- * packed [KH*KW][Cout][Cin] (Cin contiguous = implicit-GEMM K order).     */
-int dvg_pack_conv_weight(const float* w_oihw, float* w_packed, int cout, int cin,
-                         int kh, int kw, void* stream);
+/* Conv2d weight (Cout,Cin,KH,KW) [vgg_64.py:8, dcgan_64.py:8] -> packed [KH*KW][Cout][Cin] (Cin contiguous = implicit-GEMM K). */
+int dvg_pack_conv_weight(const float* w_oihw, float* w_packed, int cout, int cin, int kh, int kw, void* stream);
 
-/* ConvTranspose2d weight (Cin,Cout,KH,KW) [vgg_64.py:88, dcgan_64.py:20,76]
- * -> packed [KH*KW][Cout][Cin] with the kernel spatially FLIPPED, i.e. the
- * weight of the equivalent direct correlation.                             */
-int dvg_pack_convT_weight(const float* w_iohw, float* w_packed, int cin, int cout,
-                          int kh, int kw, void* stream);
+/* ConvTranspose2d weight (Cin,Cout,KH,KW) [vgg_64.py:88, dcgan_64.py:20,76] -> packed [KH*KW][Cout][Cin] with the kernel
+ * spatially FLIPPED, i.e. the weight of the equivalent direct correlation.                             */
+int dvg_pack_convT_weight(const float* w_iohw, float* w_packed, int cin, int cout, int kh, int kw, void* stream);
 
 /* Inverse of the two packs (used by the backward pass to scatter dW back). */
-int dvg_unpack_conv_weight(const float* w_packed, float* w_oihw, int cout, int cin,
-                           int kh, int kw, void* stream);
-int dvg_unpack_convT_weight(const float* w_packed, float* w_iohw, int cin, int cout,
-                            int kh, int kw, void* stream);
+int dvg_unpack_conv_weight(const float* w_packed, float* w_oihw, int cout, int cin, int kh, int kw, void* stream);
+int dvg_unpack_convT_weight(const float* w_packed, float* w_iohw, int cin, int cout, int kh, int kw, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Encoder / decoder blocks
  * ------------------------------------------------------------------ */
 
-/* vgg_layer = Conv2d(nin,nout,3,1,1)+BatchNorm2d+LeakyReLU(0.2)  (vgg_64.py:5-15)
- * as ONE fp32-MFMA implicit GEMM (M = N*H*W pixels, N = Cout, K = 9*Cin):
+/* vgg_layer = Conv2d(nin,nout,3,1,1)+BatchNorm2d+LeakyReLU(0.2)  (vgg_64.py:5-15) as ONE fp32-MFMA implicit GEMM
+ * (M = N*H*W pixels, N = Cout, K = 9*Cin):
  *
  *   u        = conv3x3(in) + 0            (bias is folded into `shift`)
  *   y        = act(u * scale[c] + shift[c])
  *   y_pool   = maxpool2x2(y)              (optional; nn.MaxPool2d(2,2) vgg_64.py:49)
  *
- * `in` is either `x` (N,H,W,C1) or, when `upsample_x` != 0, the channel concat
- *   cat([nearest_up2(x), skip], C)   (vgg_64.py:93,98-105)
- * with x given at (N,H/2,W/2,C1) and skip at (N,H,W,C2); the concat and the
- * up-sampling are done by the tile loader and never materialised.
- * With skip == NULL, C2 must be 0.  When upsample_x == 0 and skip != NULL the
+ * `in` is either `x` (N,H,W,C1) or, when `upsample_x` != 0, the channel concat cat([nearest_up2(x), skip], C)
+ * (vgg_64.py:93,98-105) with x given at (N,H/2,W/2,C1) and skip at (N,H,W,C2); the concat and the up-sampling are done by
+ * the tile loader and never materialised.  With skip == NULL, C2 must be 0.  When upsample_x == 0 and skip != NULL the
  * input is cat([x, skip]) at full resolution.
+ * scale/shift: [Cout] (eval-mode BN folded with the conv bias); either may be NULL (=1 / =0).
  *
- * scale/shift: [Cout] (eval-mode BN folded with the conv bias); either may be
- * NULL (=1 / =0).
+ * stats (optional, train-mode BN): float[rows][2][Cout] with rows = dvg_conv_stats_rows_v2(...); every workgroup writes the
+ * per-channel sum(u') and sum(u'^2) of its own pixel tile, where u' = u*scale+shift BEFORE the activation (callers pass
+ * scale=NULL, shift=bias, act=NONE to obtain the raw conv output and its statistics).  Deterministic (no atomics);
+ * dvg_bn_finalize reduces the rows.
  *
- * stats (optional, train-mode BN): float[rows][2][Cout] with
- * rows = dvg_conv_stats_rows_v2(...); every workgroup writes the
- * per-channel sum(u') and sum(u'^2) of its own pixel tile, where
- * u' = u*scale+shift BEFORE the activation (callers pass scale=NULL,
- * shift=bias, act=NONE to obtain the raw conv output and its statistics).
- * Deterministic (no atomics); dvg_bn_finalize reduces the rows.
- *
- * Requirements: C1 % 32 == 0, C2 % 32 == 0, Cout % 64 == 0, H % 8 == 0,
- * W % 8 == 0, all pointers 16-byte aligned.                                 */
+ * Requirements: C1 % 32 == 0, C2 % 32 == 0, Cout % 64 == 0, H % 8 == 0, W % 8 == 0, all pointers 16-byte aligned.       */
 #define DVG_MODE_CONV3 0
 #define DVG_MODE_CONV4S2 1
 #define DVG_MODE_CONVT4S2 2
@@ -793,6 +780,19 @@ int dvg_mse_sum_grad(const float* a, const float* b, float* sum, float* da, long
  * and the device-side Adam step counts t0..t3 (NULL: none) advanced by one in the same launch (dvg_adam_step's step_dev): a
  * captured iteration needs no one-element increment launch per optimiser step.  ABI 8.                                   */
 int dvg_zero_tick(float* g, long n, int* t0, int* t1, int* t2, int* t3, void* stream);
+
+/* Gradient guard (train.py --clip_grad_norm / --skip_nonfinite here; the reference's optimizer.step() calls train.py:171,196,245
+ * apply whatever backward() left); semantics in docs/DESIGN_NOTES_gradguard.md.  dvg_grad_sumsq: partials[b] = fp64 sum of exact
+ * squares of floats [16384 b, 16384 (b + 1)) of g[0:n], fixed order, no atomics; n % 4 == 0, g 16-byte aligned;
+ * dvg_grad_sumsq_blocks(n) slots, a function of n alone.  dvg_grad_guard_finish: stat = {norm, clip factor, `skip` && sum not finite,
+ * max finite norm}, counters += {1, clipped, skipped}.  dvg_adam_step_guarded: dvg_adam_step on g * stat[1] (same bits for 1);
+ * stat[2] != 0: only *skips_dev += 1; else the step count minus *skips_dev.  Additions within ABI 9.                        */
+int dvg_grad_sumsq_blocks(long n);
+int dvg_grad_sumsq(const float* g, long n, double* partials, void* stream);
+int dvg_grad_guard_finish(const double* partials, int nblocks, double max_norm, int skip, float* stat, int* counters, void* stream);
+int dvg_adam_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1,
+                          float beta2, float eps, float weight_decay, int step, const int* step_dev, const float* stat,
+                          int* skips_dev, void* stream);
 
 #ifdef __cplusplus
 }

@@ -30,10 +30,13 @@ def main():
                          "DVG_FORCE_ALLREDUCE=1 a 1-rank RCCL group is created so that the collectives really run")
     ap.add_argument("--channels", type=int, default=1)
     ap.add_argument("--image_width", type=int, default=64)
+    ap.add_argument("--clip_grad_norm", type=float, default=0.0, help="train.py's flag: the gradient guard's clip threshold")
+    ap.add_argument("--skip_nonfinite", action="store_true", help="train.py's flag: skip step sites with Inf / NaN gradients")
     a = ap.parse_args()
     o = train.build_parser().parse_args(["--model", a.model, "--batch_size", str(a.batch), "--n_past", str(a.n_past),
                                          "--n_future", str(a.n_future), "--no_save", "--channels", str(a.channels),
-                                         "--image_width", str(a.image_width)])
+                                         "--image_width", str(a.image_width), "--clip_grad_norm", repr(a.clip_grad_norm)] +
+                                        (["--skip_nonfinite"] if a.skip_nonfinite else []))
     o.ft, o.rank, o.world, o.local_batch = not a.no_ft, 0, 1, a.batch
     if os.environ.get("DVG_FORCE_ALLREDUCE") == "1":
         import torch.distributed as dist
@@ -80,7 +83,7 @@ def main():
     agg = timer.summary()
     tot = sum(v["ms"] for v in agg.values())
     out = {"launch": ("hipGraph segments (%d) + eager all-reduces" % g.n_segments) if a.segmented else
-           "hipGraph replay" if a.graph else "eager", "model": f"{a.model}_{a.image_width}", "channels": a.channels, "batch": a.batch, "T": a.n_past + a.n_future, "ms_per_iter": round(dt * 1e3, 1),
+           "hipGraph replay" if a.graph else "eager", "grad_guard": tr.guard is not None, "model": f"{a.model}_{a.image_width}", "channels": a.channels, "batch": a.batch, "T": a.n_past + a.n_future, "ms_per_iter": round(dt * 1e3, 1),
            "train_frames_per_s": round(a.batch * (a.n_past + a.n_future - 1) / dt, 1),
            "peak_mem_GB": round(torch.cuda.max_memory_allocated() / 2**30, 1), "timed_kernel_ms": round(tot, 1),
            "kernels": {k: {"n": v["launches"], "ms": round(v["ms"], 1),

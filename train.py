@@ -48,8 +48,9 @@ import utils  # noqa: E402
 from dvg_amd import fused, parallel, train_state, viz  # noqa: E402
 from dvg_amd.data import SyntheticMovingMNIST, make_batch_generator, synthetic_video  # noqa: E402,F401
 from dvg_amd.models.gp_models import GaussianLikelihood, GPRegressionLayer1, VariationalELBO  # noqa: E402
-from dvg_amd.optim import FlatArena, FusedAdam, zero_grads  # noqa: E402
+from dvg_amd.optim import FlatArena, FusedAdam, guard_options, guarded_step, make_guard, zero_grads  # noqa: E402,F401
 from dvg_amd.rollout import frames_as_batch, gp_input  # noqa: E402
+from dvg_amd.train_state import detached_copy as _detached_copy  # noqa: E402
 
 
 def build_parser():
@@ -104,6 +105,11 @@ def build_parser():
     p.add_argument('--synthetic_data', action='store_true',
                    help='kth | bair | ucf: train on synthetic clips of that shape instead of reading --data_root; smmnist: '
                         'the in-repo sprites even where --data_root holds MNIST')
+    p.add_argument('--clip_grad_norm', default=0.0, type=float, metavar='C',   # docs/DESIGN_NOTES_gradguard.md
+                   help='limit the L2 norm of ALL gradients that step together after one backward pass to C, by the factor '
+                        'min(1, C / (norm + 1e-6)) of torch\'s clip_grad_norm_; decided on the device, also in a hipGraph (0 = off)')
+    p.add_argument('--skip_nonfinite', action='store_true',
+                   help='skip such a step when a gradient is Inf or NaN: no parameter, Adam moment or step count changes')
     return p
 
 
@@ -191,6 +197,13 @@ class Trainer:
         self.rng_dec = self.decoder_optimizer.flat_range(0)
         self.rng_enc = self.encoder_optimizer.flat_range(0)
         assert self.rng_gp[1] == self.rng_fp[0] and self.rng_fp[1] == self.rng_dec[0] and self.rng_dec[1] == self.rng_enc[0]
+        # --clip_grad_norm / --skip_nonfinite: one device-side verdict per step site (_step); None = every site steps as ever
+        self.guard = make_guard(opt, device, self.optimizers())
+
+    def _step(self, optimizers):
+        """A step site: the optimisers that step together after one backward pass (with several ranks: after the all-reduce
+        of their ranges).  With a guard, ONE norm over all their gradients decides the clip factor or the skip."""
+        guarded_step(optimizers, self.guard)
 
     # ---- data-parallel switches / statistics (bench.py's training leg) --------------------------
     def _ar(self, *actions):
@@ -365,7 +378,7 @@ class Trainer:
                 elbo.backward(gneg)
                 if not defer_step:
                     self._ar(("reduce", self.rng_gp))
-                    self.optimizer.step()
+                    self._step([self.optimizer])
                 return loss
             max_ll = -elbo
         else:
@@ -382,7 +395,7 @@ class Trainer:
         loss.backward()
         if not defer_step:
             self._ar(("reduce", self.rng_gp))
-            self.optimizer.step()
+            self._step([self.optimizer])
         return loss.detach()
 
     def _train_fp_dev(self, x, defer_step=False):
@@ -414,7 +427,7 @@ class Trainer:
                 pred.backward(d_pred)
                 if not defer_step:
                     self._ar(("reduce", self.rng_fp))
-                    self.frame_predictor_optimizer.step()
+                    self._step([self.frame_predictor_optimizer])
                 return mse_latent
             d = pred - hcat[1:]
             mse_latent = (d * d).sum() / float(hcat[0].numel())                # sum over the steps of nn.MSELoss (mean)
@@ -428,7 +441,7 @@ class Trainer:
         mse_latent.backward()
         if not defer_step:
             self._ar(("reduce", self.rng_fp))
-            self.frame_predictor_optimizer.step()
+            self._step([self.frame_predictor_optimizer])
         return mse_latent.detach()
 
     def _train_model_batched(self, x):
@@ -530,10 +543,7 @@ class Trainer:
             self._ar(("start", "b", self.rng_enc), ("finish", "a"), ("finish", "b"))
         else:
             self._ar(("reduce", (self.rng_gp[0], self.rng_enc[1])))
-        self.frame_predictor_optimizer.step()
-        self.encoder_optimizer.step()
-        self.decoder_optimizer.step()
-        self.optimizer.step()
+        self._step([self.frame_predictor_optimizer, self.encoder_optimizer, self.decoder_optimizer, self.optimizer])
 
     def _train_model_dev(self, x):
         opt = self.opt
@@ -613,8 +623,7 @@ class Trainer:
         fp = self._train_fp_dev(x, defer_step=True)
         gp = self._train_gp_dev(x, defer_step=True)
         self._ar(("reduce", (self.rng_gp[0], self.rng_fp[1])))
-        self.frame_predictor_optimizer.step()
-        self.optimizer.step()
+        self._step([self.frame_predictor_optimizer, self.optimizer])
         return fp, gp
 
     def finetune_temporal_encoders(self, x):
@@ -697,21 +706,6 @@ class Trainer:
         return train_state.restore(self, sd, train_gen, test_gen, path)
 
 
-def _detached_copy(module):
-    """A deep copy of `module` whose parameters and buffers are fresh tensors with their OWN storage and no gradient
-    (copy.deepcopy alone clones the whole storage behind every arena view, and would copy `.grad` as well)."""
-    import copy
-    memo = {}
-    for p in module.parameters():
-        memo[id(p)] = torch.nn.Parameter(p.detach().clone(), requires_grad=p.requires_grad)
-    for b in module.buffers():
-        memo[id(b)] = b.detach().clone()
-    hidden = getattr(module, "hidden", None)
-    if hidden is not None:         # lstm.hidden: the recurrent state of the last sequence, may carry an autograd graph
-        memo[id(hidden)] = [(h.detach().clone(), c.detach().clone()) for h, c in hidden]
-    return copy.deepcopy(module, memo)
-
-
 # hipGraph replay of the iteration and the batch prefetcher: dvg_amd/train_graphs.py (r06; re-exported for `train.<name>`)
 from dvg_amd.train_graphs import BatchPrefetcher, GraphedIteration, SegmentedIteration  # noqa: E402,F401
 
@@ -768,6 +762,9 @@ def main(argv=None):
             print('[%02d] mse loss: %.5f (%d) %.5f' % (epoch, epoch_mse / opt.epoch_size,
                                                        epoch * opt.epoch_size * opt.batch_size, indices))
             print('     train frames/s: %.1f' % fps)
+        if tr.guard is not None:   # the one read of the guard's device counters: per epoch, outside the iterations
+            line = tr.guard.epoch_line()
+            rank == 0 and print(line)
         if epoch % opt.save_every == 0:
             tr.frame_predictor.eval()
             tr.gp_layer.eval()
