@@ -123,6 +123,8 @@ SIGNATURES = {
     "dvg_grad_sumsq": (_i, [_p, _l, _p, _p]),
     "dvg_grad_guard_finish": (_i, [_p, _i, _d, _i, _p, _p, _p]),
     "dvg_adam_step_guarded": (_i, [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p, _p, _p, _p]),
+    "dvg_ema_update_blocks": (_i, [_l]),
+    "dvg_ema_update": (_i, [_p, _p, _l, _d, _p, _p, _p]),
     "dvg_frame_losses_blocks": (_i, [_l]),
     "dvg_frame_losses": (_i, [_p, _p, _p, _p, _l, _i, _i, _p, _p, _p]),
     "dvg_mse_sum_grad": (_i, [_p, _p, _p, _p, _l, _f, _p]),

@@ -42,4 +42,5 @@ from .backward import (  # noqa: F401
     winograd_wgrad_partial_multi, wgrad_finish, k4_to_w3, conv_wgrad, wgrad_thin, act_bwd, upsample2x_bwd,
 )
 from .guard import grad_sumsq_blocks, grad_sumsq, grad_guard_finish, adam_step_guarded  # noqa: F401
+from .ema import ema_update_blocks, ema_update  # noqa: F401
 from .._lib import check, lib  # noqa: F401

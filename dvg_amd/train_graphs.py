@@ -68,6 +68,7 @@ class GraphedIteration:
         fp = gp = None
         if tr.opt.ft:
             fp, gp = tr._finetune_dev(self.static_x)
+        tr.ema is None or tr.ema.update()      # --ema_decay: once per iteration, after the last step site (the last segment)
         self.outs = (mse_latent, loss, fp, gp)
 
     def __call__(self, x):

@@ -156,6 +156,22 @@ def detached_copy(module):
     return copy.deepcopy(module, memo)
 
 
+def owned_state_dict(sd):
+    """`sd` (a module's state_dict) with every tensor cloned into its own storage; keeps the module version info torch's
+    state_dict carries (and load_state_dict reads)."""
+    out = type(sd)((k, v.detach().clone() if torch.is_tensor(v) else v) for k, v in sd.items())
+    if hasattr(sd, "_metadata"):
+        out._metadata = sd._metadata
+    return out
+
+
+def checkpoint(tr) -> dict:
+    """train.py:380-388: whole-module pickles + GP / likelihood / GP-optimiser state dicts (Trainer.save writes it)."""
+    return {'encoder': detached_copy(tr.encoder), 'decoder': detached_copy(tr.decoder),
+            'frame_predictor': detached_copy(tr.frame_predictor), 'likelihood': owned_state_dict(tr.likelihood.state_dict()),
+            'gp_layer': owned_state_dict(tr.gp_layer.state_dict()), 'gp_layer_optimizer': tr.optimizer.state_dict(), 'opt': tr.opt}
+
+
 # ---- what the state of a train.Trainer is -----------------------------------------------------------------------------------
 def named_optimizers(tr):
     return (("gp", tr.optimizer), ("frame_predictor", tr.frame_predictor_optimizer), ("decoder", tr.decoder_optimizer),
@@ -206,6 +222,10 @@ def capture(tr, epoch=0, train_gen=None, test_gen=None, shared=True) -> dict:
                          "g_gp": a.g[lo:hi].detach().clone(), "g_gp_range": (lo, hi)},
                   optimizers={name: o.host_state() for name, o in named_optimizers(tr)},
                   scheduler=tr.scheduler.state_dict())
+        ema = getattr(tr, "ema", None)
+        if ema is not None:      # --ema_decay: the average and its count of updates (dvg_amd/ema.py); no key without the flag
+            st = ema.state()
+            sd["arena"]["e"], sd["ema"] = st["e"], st["ema"]
     return sd
 
 
@@ -221,6 +241,13 @@ def restore(tr, sd, train_gen=None, test_gen=None, path="<state>") -> int:
         getattr(a, name).copy_(saved[name])
     lo, hi = saved["g_gp_range"]
     a.g[lo:hi].copy_(saved["g_gp"])
+    ema = getattr(tr, "ema", None)
+    if ema is not None:          # the decay of THIS run applies; a state without an average restarts it from the restored weights
+        ema.load_state(saved.get("e"), sd.get("ema"))
+        if "e" not in saved and tr.rank == 0:
+            print(f"{path}: no weight average in the file: --ema_decay restarts it from the restored weights", flush=True)
+    elif "e" in saved and tr.rank == 0:
+        print(f"{path}: the weight average in the file is ignored: this run has no --ema_decay", flush=True)
     for name, o in named_optimizers(tr):
         o.load_host_state(sd["optimizers"][name])      # step counts (begin_capture seeds the device counts from them), lr
     tr.scheduler.load_state_dict(sd["scheduler"])

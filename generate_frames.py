@@ -2,7 +2,8 @@
 """generate_frames.py — counterpart of the reference's generate_frames.py on the MI355X kernel library.
 
 Same flags (generate_frames.py:17-41).  Loads `<model_dir>/<dataset>.pth` (falls back to the
-`model.pth` that train.py writes — the reference's two scripts disagree on the filename),
+`model.pth` that train.py writes — the reference's two scripts disagree on the filename; `--ema`: the averaged
+weights of train.py --ema_decay, `<dataset>_ema.pth` else `model_ema.pth`),
 takes `opt` from the checkpoint (:44), forces n_eval / n_future / batch_size like :47-49 unless
 overridden, and runs either
 
@@ -65,6 +66,8 @@ def build_parser():
     p.add_argument('--nbatches', type=int, default=5)
     p.add_argument('--trigger_indices', type=int, default=None, help='GPtrigger_gen: how many batch indices')
     p.add_argument('--synthetic_ckpt', action='store_true')
+    p.add_argument('--ema', action='store_true',
+                   help='load the averaged weights: <model_dir>/<dataset>_ema.pth, else <model_dir>/model_ema.pth (train.py --ema_decay)')
     p.add_argument('--inflight', type=int, default=3,
                    help='make_gifs: samples of a batch drawn at once (one hipGraph + stream each); 0 = eager loop, one at a time')
     p.add_argument('--no_share_prefix', action='store_true',
@@ -366,7 +369,10 @@ def main(argv=None):
         opt = args
     else:
         path = '%s/%s.pth' % (args.model_dir, args.dataset)
-        if not os.path.exists(path):
+        if args.ema:      # the averaged weights train.py --ema_decay wrote (same container); a missing file is a one-line exit
+            from dvg_amd.ema import checkpoint_path
+            path = checkpoint_path(args.model_dir, args.dataset)
+        elif not os.path.exists(path):
             path = '%s/model.pth' % args.model_dir
         ckpt = torch.load(path, map_location='cpu', weights_only=False)
         opt = ckpt['opt']
@@ -436,6 +442,7 @@ def main(argv=None):
                                                             float(dv['distinct'][:, -1].double().mean()), args.nsample))
             if not args.no_images:
                 gen.write_gifs(test_x, res, i, '%s/gen' % opt.log_dir, rows=args.gif_rows)
+    return gen
 
 
 if __name__ == '__main__':

@@ -1,27 +1,23 @@
 /*
- * dvg_hip.h — C ABI of libdvg_hip.so, the MI355X (gfx950) kernel library behind
- * the DVG frame-prediction hot path.
+ * dvg_hip.h — C ABI of libdvg_hip.so, the MI355X (gfx950) kernel library behind the DVG frame-prediction hot path.
  *
- * The reference (shgaurav1/DVG) has no FFI / plugin boundary of its own: every
- * device op is an implicit torch.nn / gpytorch call.  Each entry
- * point below therefore names the reference *call site* it replaces.  Citations
- * are file:line into the reference tree.
+ * The reference (shgaurav1/DVG) has no FFI / plugin boundary of its own: every device op is an implicit torch.nn / gpytorch
+ * call.  Each entry point below therefore names the reference *call site* it replaces.  Citations are
+ * file:line into the reference tree.
  *
  * Conventions
  *   - every pointer is a DEVICE pointer to fp32 data unless stated otherwise;
- *   - activations are NHWC ("channels last"): x[n][y][x][c]; the Python side
- *     exposes them as (N,C,H,W) torch tensors with channels_last strides;
+ *   - activations are NHWC ("channels last"): x[n][y][x][c]; the Python side exposes them as (N,C,H,W) torch tensors with
+ *     channels_last strides;
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream);
- *   - every function returns 0 on success, a DVG_ERR_* code otherwise and never
- *     throws; dvg_last_error() gives a thread-local message;
- *   - all shape checks happen on the host BEFORE a kernel is launched: a call
- *     that fails a check launches nothing.
+ *   - every function returns 0 on success, a DVG_ERR_* code otherwise and never throws; dvg_last_error() gives a thread-local
+ *     message;
+ *   - all shape checks happen on the host BEFORE a kernel is launched: a call that fails a check launches nothing.
  *   - no function allocates, frees or synchronises: graph-capture safe;
- *   - threading: ONE host thread per process drives the library (the reference's own
- *     contract, SURVEY.md 8(b) "Threading"; data parallelism is one process per GPU).  The
- *     first launch of each conv kernel instantiation raises its dynamic-LDS limit through an
- *     unsynchronised function-local flag (conv_igemm2.hip `attr_set`), and the debug hooks
- *     at the end of this file are plain globals.
+ *   - threading: ONE host thread per process drives the library (the reference's own contract, SURVEY.md 8(b) "Threading"; data
+ *     parallelism is one process per GPU).  The first launch of each conv kernel instantiation raises its dynamic-LDS limit
+ *     through an unsynchronised function-local flag (conv_igemm2.hip `attr_set`), and the debug hooks at the end of this file
+ *     are plain globals.
  */
 #ifndef DVG_HIP_H
 #define DVG_HIP_H
@@ -55,7 +51,6 @@ long dvg_stream_capture_id(void* stream);
 /* ------------------------------------------------------------------ *
  * Weight re-layout (one launch per parameter, cached by the caller).
  * ------------------------------------------------------------------ */
-
 /* Conv2d weight (Cout,Cin,KH,KW) [vgg_64.py:8, dcgan_64.py:8] -> packed [KH*KW][Cout][Cin] (Cin contiguous = implicit-GEMM K). */
 int dvg_pack_conv_weight(const float* w_oihw, float* w_packed, int cout, int cin, int kh, int kw, void* stream);
 
@@ -70,7 +65,6 @@ int dvg_unpack_convT_weight(const float* w_packed, float* w_iohw, int cin, int c
 /* ------------------------------------------------------------------ *
  * Encoder / decoder blocks
  * ------------------------------------------------------------------ */
-
 /* vgg_layer = Conv2d(nin,nout,3,1,1)+BatchNorm2d+LeakyReLU(0.2)  (vgg_64.py:5-15) as ONE fp32-MFMA implicit GEMM
  * (M = N*H*W pixels, N = Cout, K = 9*Cin):
  *
@@ -93,8 +87,8 @@ int dvg_unpack_convT_weight(const float* w_packed, float* w_iohw, int cin, int c
 #define DVG_MODE_CONV3 0
 #define DVG_MODE_CONV4S2 1
 #define DVG_MODE_CONVT4S2 2
-/* rows of the `stats` partial buffer of the first-layer kernels (ks = 3 or 4); -1 if the
- * shape is unsupported.  (The implicit-GEMM convs: dvg_conv_stats_rows_v2 below.)          */
+/* rows of the `stats` partial buffer of the first-layer kernels (ks = 3 or 4); -1 if the shape is unsupported.  (The
+ * implicit-GEMM convs: dvg_conv_stats_rows_v2 below.)                                                                     */
 int dvg_conv_first_stats_rows(int ks, int N, int H, int W);
 
 /* The three implicit-GEMM convs (conv_igemm2.hip; the "_v2" suffix is historical: the first
@@ -732,10 +726,9 @@ int dvg_nchw_to_nhwc(const float* x, float* y, int N, int C, int H, int W, void*
 int dvg_nhwc_to_nchw(const float* x, float* y, int N, int C, int H, int W, void* stream);
 
 /* ------------------------------------------------------------------ *
- * Debug hooks (tools/diag_*.py).  Not part of the product path: they hand the next launches of
- * one kernel family a device buffer that every workgroup fills with clock64()/wall_clock64()
- * phase stamps.  buf == NULL (the default) disables stamping; the kernels then pay one
- * uniform branch.  Not thread-safe: set, launch, synchronise, reset from ONE host thread.
+ * Debug hooks (tools/diag_*.py).  Not part of the product path: they hand the next launches of one kernel family a device
+ * buffer that every workgroup fills with clock64()/wall_clock64() phase stamps.  buf == NULL (the default) disables stamping;
+ * the kernels then pay one uniform branch.  Not thread-safe: set, launch, synchronise, reset from ONE host thread.
  * ------------------------------------------------------------------ */
 void dvg_debug_set_clockbuf(void* buf, unsigned records);        /* conv_igemm2 kernels: 8 x u64 per workgroup */
 void dvg_debug_set_gp_clockbuf(void* buf, unsigned records);     /* gp_predict_kernel: 12 x u64 per workgroup  */
@@ -790,9 +783,16 @@ int dvg_zero_tick(float* g, long n, int* t0, int* t1, int* t2, int* t3, void* st
 int dvg_grad_sumsq_blocks(long n);
 int dvg_grad_sumsq(const float* g, long n, double* partials, void* stream);
 int dvg_grad_guard_finish(const double* partials, int nblocks, double max_norm, int skip, float* stat, int* counters, void* stream);
-int dvg_adam_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1,
-                          float beta2, float eps, float weight_decay, int step, const int* step_dev, const float* stat,
-                          int* skips_dev, void* stream);
+int dvg_adam_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1, float beta2,
+                          float eps, float weight_decay, int step, const int* step_dev, const float* stat, int* skips_dev, void* stream);
+
+/* Exponential moving average of a flat parameter range (train.py --ema_decay here; docs/DESIGN_NOTES_ema.md).  No reference
+ * counterpart: it follows the optimiser steps of the reference's train.py:242-245.  ema = fmaf(w, param - ema, ema), w = (float)(1 -
+ * min(decay, (1 + k) / (10 + k))) formed in fp64 in the kernel from k = *updates_dev, the updates already applied (read, never
+ * written).  Workgroup b writes partials[2b] = sum (param - ema')^2, partials[2b + 1] = sum param^2 over floats [8192 b, 8192 (b + 1)),
+ * fp64, fixed order; dvg_ema_update_blocks(n) pairs.  n % 4 == 0, 16-byte aligned, ema != param, decay in [0, 1).  Within ABI 9. */
+int dvg_ema_update_blocks(long n);
+int dvg_ema_update(float* ema, const float* param, long n, double decay, const int* updates_dev, double* partials, void* stream);
 
 #ifdef __cplusplus
 }

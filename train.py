@@ -29,6 +29,8 @@ torchvision, no download; scaled to 32x32 once on the device, a batch is one dvg
 those files or with `--synthetic_data`, seeded Moving-MNIST trajectories with in-repo sprites, announced by a warning.
 `--resume PATH` continues a run exactly from the `train_state.pth` written beside `model.pth` (the reference's "load the trained
 model" section, :86, is empty and `--model_dir` is never read: both kept); dvg_amd/train_state.py, docs/DESIGN_NOTES_resume.md.
+`--ema_decay D` keeps an exponential moving average of all weights on the device, one launch per iteration inside the captured
+graph, and writes `model_ema.pth` beside `model.pth` (dvg_amd/ema.py, docs/DESIGN_NOTES_ema.md).
 """
 import argparse
 import importlib
@@ -45,7 +47,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 import utils  # noqa: E402
-from dvg_amd import fused, parallel, train_state, viz  # noqa: E402
+from dvg_amd import ema as weight_ema, fused, parallel, train_state, viz  # noqa: E402
 from dvg_amd.data import SyntheticMovingMNIST, make_batch_generator, synthetic_video  # noqa: E402,F401
 from dvg_amd.models.gp_models import GaussianLikelihood, GPRegressionLayer1, VariationalELBO  # noqa: E402
 from dvg_amd.optim import FlatArena, FusedAdam, guard_options, guarded_step, make_guard, zero_grads  # noqa: E402,F401
@@ -110,6 +112,7 @@ def build_parser():
                         'min(1, C / (norm + 1e-6)) of torch\'s clip_grad_norm_; decided on the device, also in a hipGraph (0 = off)')
     p.add_argument('--skip_nonfinite', action='store_true',
                    help='skip such a step when a gradient is Inf or NaN: no parameter, Adam moment or step count changes')
+    weight_ema.add_arguments(p)   # --ema_decay
     return p
 
 
@@ -199,6 +202,8 @@ class Trainer:
         assert self.rng_gp[1] == self.rng_fp[0] and self.rng_fp[1] == self.rng_dec[0] and self.rng_dec[1] == self.rng_enc[0]
         # --clip_grad_norm / --skip_nonfinite: one device-side verdict per step site (_step); None = every site steps as ever
         self.guard = make_guard(opt, device, self.optimizers())
+        # --ema_decay: an averaged copy of arena.p (after the broadcast above), moved once per iteration; None = nothing exists
+        self.ema = weight_ema.make_average(opt, self.arena)
 
     def _step(self, optimizers):
         """A step site: the optimisers that step together after one backward pass (with several ranks: after the all-reduce
@@ -638,6 +643,7 @@ class Trainer:
         opt.ft.  Returns (mse_ctrl, indices, temp_loss) as Python floats."""
         mse_ctrl, indices = self.train_model(x)
         temp_loss = self.finetune_temporal_encoders(x) if self.opt.ft else 0
+        self.ema is None or self.ema.update()   # after the last step site of the iteration
         self._iters = getattr(self, '_iters', 0) + 1
         return mse_ctrl, indices, temp_loss
 
@@ -688,15 +694,7 @@ class Trainer:
         its storage: the live parameters, gradients and Adam moments are views of the shared FlatArena, and torch.save
         writes the whole storage behind a view (a checkpoint would carry the arena instead of the GP's moments, and loading
         only ck['encoder'] would pin all of it)."""
-        def own(sd):
-            out = type(sd)((k, v.detach().clone() if torch.is_tensor(v) else v) for k, v in sd.items())
-            if hasattr(sd, "_metadata"):          # module version info torch's state_dict carries (and load_state_dict reads)
-                out._metadata = sd._metadata
-            return out
-        torch.save({'encoder': _detached_copy(self.encoder), 'decoder': _detached_copy(self.decoder),
-                    'frame_predictor': _detached_copy(self.frame_predictor),
-                    'likelihood': own(self.likelihood.state_dict()), 'gp_layer': own(self.gp_layer.state_dict()),
-                    'gp_layer_optimizer': self.optimizer.state_dict(), 'opt': self.opt}, path)
+        torch.save(train_state.checkpoint(self), path)
 
     # ---- the whole training state (--resume): dvg_amd/train_state.py, docs/DESIGN_NOTES_resume.md --------------------
     def state_dict(self, epoch=0, train_gen=None, test_gen=None, shared=True):
@@ -765,6 +763,7 @@ def main(argv=None):
         if tr.guard is not None:   # the one read of the guard's device counters: per epoch, outside the iterations
             line = tr.guard.epoch_line()
             rank == 0 and print(line)
+        weight_ema.print_epoch_line(tr.ema, rank)   # --ema_decay: every rank reads its own counters, rank 0 prints
         if epoch % opt.save_every == 0:
             tr.frame_predictor.eval()
             tr.gp_layer.eval()
@@ -776,16 +775,14 @@ def main(argv=None):
                 torch.save({'gen': gen[:, :, :min(opt.local_batch, 10)].cpu(), 'best': best.cpu()},
                            '%s/sample_%d.pt' % (opt.output_path, epoch))
                 tr.save('%s/model.pth' % opt.output_path)
+                tr.ema is None or tr.ema.save(tr, '%s/%s' % (opt.output_path, weight_ema.FILE))   # model_ema.pth
                 opt.no_images or tr.write_plot(test_x, gen, best, epoch, opt.output_path)   # sample_<epoch>.png / .gif
             if not opt.no_save:   # after everything of this epoch that draws random numbers; rank 0: the shared part as well
                 train_state.write(tr.state_dict(epoch + 1, train_gen, test_gen, shared=rank == 0), opt.output_path, rank, world)
         if epoch % 10 == 0 and rank == 0:
             print('log dir: %s' % opt.log_dir)
     if opt.print_param_checksum:   # tests: every rank must end with the same parameters
-        mods = (tr.encoder, tr.decoder, tr.frame_predictor, tr.gp_layer, tr.likelihood)
-        cs = sum(float(p.detach().double().sum()) for m in mods for p in m.parameters())
-        ab = sum(float(p.detach().double().abs().sum()) for m in mods for p in m.parameters())
-        print('rank %d param checksum %.17g %.17g' % (rank, cs, ab), flush=True)
+        weight_ema.print_checksums(tr, rank)
     if world > 1:
         torch.distributed.barrier()
         torch.distributed.destroy_process_group()
