@@ -57,6 +57,7 @@ SIGNATURES = {
     "dvg_convT4x4s2_last": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
     "dvg_moving_mnist_compose": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "dvg_clip_gather_u8": (_i, [_p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _p]),
+    "dvg_clip_gather_aug_u8": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _p]),
     "dvg_mnist_scale_u8": (_i, [_p, _p, _i, _i, _i, _p, _p, _p]),
     "dvg_moving_mnist_compose_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "dvg_eval_frames": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),

@@ -185,9 +185,14 @@ class BatchStream:
     `restore(position)` makes the next batch the one that followed that position in the run that saved it, bit for bit.
     `first`: called once before the first draw (the synthetic path's warning / refusal, which stay lazy)."""
 
-    def __init__(self, sampler, draw, load, first=None):
-        self.sampler, self._draw, self._load, self._first = sampler, draw, load, first
-        self._pos = sampler.position()
+    def __init__(self, sampler, draw, load, first=None, augmenter=None):
+        self.sampler, self._draw, self._load, self._first, self.augmenter = sampler, draw, load, first, augmenter
+        self._pos = self._position()
+
+    def _position(self):
+        """The sampler's position; with `--augment` it also carries the augmenter's, under "augment"."""
+        pos = self.sampler.position()
+        return pos if self.augmenter is None else dict(pos, augment=self.augmenter.position())
 
     def __iter__(self):
         return self
@@ -197,15 +202,23 @@ class BatchStream:
             first, self._first = self._first, None
             first()
         host = self._draw()
-        self._pos = self.sampler.position()
+        self._pos = self._position()
         return _Batch(lambda: self._load(host), self._pos)
 
     def position(self):
         return self._pos
 
     def restore(self, pos):
+        saved = pos.get("augment") if isinstance(pos, dict) else None
+        if self.augmenter is None and saved is not None:
+            raise SystemExit(f"data position: saved with --augment {saved.get('spec')!r}, this run has no --augment")
+        if self.augmenter is not None and saved is None:
+            raise SystemExit(f"data position: saved without --augment, this run has --augment {self.augmenter.spec!r}")
+        if self.augmenter is not None:
+            self.augmenter.restore(saved)
+            pos = {k: v for k, v in pos.items() if k != "augment"}
         self.sampler.restore(pos)
-        self._pos = self.sampler.position()
+        self._pos = self._position()
 
 
 def make_batch_generator(opt, seq_len, seed, device=None, train=True):
@@ -220,7 +233,9 @@ def make_batch_generator(opt, seq_len, seed, device=None, train=True):
     (dvg_amd/datasets.py) BEFORE this returns - a missing tree is a SystemExit here, on the caller's thread; the host half
     then draws `local_batch` clips like the reference's loaders, the callable uploads the B pool indices and gathers the
     clips on the current stream (dvg_clip_gather_u8).  With --synthetic_data those names train on random textured clips of
-    their shape instead.
+    their shape instead.  `opt.augment` (train.py --augment; docs/DESIGN_NOTES_augment.md) applies to the TRAIN split of these
+    three only: the host also draws per-clip flip / reverse / shift / jitter parameters (datasets.ClipAugmenter) and the gather
+    is dvg_clip_gather_aug_u8; `train=False` ignores it.
     The result is a BatchStream: `position()` / `restore()` report and set where the stream stands (train.py --resume)."""
     if opt.dataset in datasets.REAL_DATASETS and not getattr(opt, 'synthetic_data', False):
         return _clip_batches(opt, seq_len, seed, device or torch.device('cuda'), train)
@@ -243,10 +258,23 @@ def _clip_batches(opt, seq_len, seed, device, train):
         raise SystemExit(f"dataset: --channels {opt.channels} from {opt.dataset} frames of {pool.shape[3]} channel(s) under "
                          f"{opt.data_root!r}")
 
+    def firsts():
+        return np.array([sampler.draw()[0] for _ in range(opt.local_batch)], np.int64)
+
     def load(first):
         from . import ops
         return list(ops.clip_gather(pool, first, seq_len, opt.channels).unbind(0))
-    return BatchStream(sampler, lambda: np.array([sampler.draw()[0] for _ in range(opt.local_batch)], np.int64), load)
+    cfg = datasets.parse_augment(getattr(opt, 'augment', '') or '')
+    if not train or not datasets.augment_spec(cfg):       # the test split is never augmented; no --augment: the path above, as ever
+        return BatchStream(sampler, firsts, load)
+    # --augment (train split): the host half of a batch is (first, geom, photo), the device half still one upload and one
+    # launch.  The augmenter draws from its own generator, after the sampler's draws of the batch: the clips stay the same
+    augmenter = datasets.ClipAugmenter(cfg, seed ^ datasets.AUGMENT_SEED_XOR)
+
+    def load_aug(host):
+        from . import ops
+        return list(ops.clip_gather_aug(pool, host[0], host[1], host[2], seq_len, opt.channels).unbind(0))
+    return BatchStream(sampler, lambda: (firsts(), *augmenter.draw(opt.local_batch)), load_aug, augmenter=augmenter)
 
 
 def _mnist_batches(opt, seq_len, seed, device, path):

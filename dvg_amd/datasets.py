@@ -198,6 +198,110 @@ def make_sampler(index, seq_len, seed):
     return (BairSampler if index.dataset == 'bair' else MetaSampler)(index, seq_len, seed)
 
 
+# ---- --augment: per-clip augmentation parameters, drawn on the host, applied by ops.clip_gather_aug -----------------------------
+AUGMENT_SEED_XOR = 0x5A17C11B   # data._clip_batches: the augmenter's seed = the generator's seed ^ this
+MAX_SHIFT = 16                  # DVG_CLIP_MAX_SHIFT of dvg_amd/csrc/clips.hip
+MAX_JITTER = 0.5
+
+
+def parse_augment(spec):
+    """'hflip,reverse,shift=N,jitter=G' (any subset, any order; N an integer in 1..16, 0 < G <= 0.5) ->
+    {'hflip': bool, 'reverse': bool, 'shift': N or 0, 'jitter': G or 0.0}.  '' = no augmentation.  An unknown word, a duplicate
+    or a value out of range ends the program naming it."""
+    cfg = {'hflip': False, 'reverse': False, 'shift': 0, 'jitter': 0.0}
+    seen = set()
+    for word in [w.strip() for w in str(spec).split(',')] if str(spec).strip() else []:
+        name, eq, value = word.partition('=')
+        if name not in cfg or (name in ('hflip', 'reverse')) == bool(eq):
+            raise SystemExit(f"--augment: unknown word {word!r} (hflip | reverse | shift=N | jitter=G)")
+        if name in seen:
+            raise SystemExit(f"--augment: {name!r} is given twice")
+        seen.add(name)
+        if name == 'shift':
+            if not value.isdigit() or not 1 <= int(value) <= MAX_SHIFT:
+                raise SystemExit(f"--augment: {word!r}: the shift is an integer in 1..{MAX_SHIFT}")
+            cfg['shift'] = int(value)
+        elif name == 'jitter':
+            try:
+                cfg['jitter'] = float(value)
+            except ValueError:
+                cfg['jitter'] = float('nan')
+            if not 0.0 < cfg['jitter'] <= MAX_JITTER:           # a NaN, parsed or not a number at all, fails this as well
+                raise SystemExit(f"--augment: {word!r}: the jitter is a number in (0, {MAX_JITTER}]")
+        else:
+            cfg[name] = True
+    return cfg
+
+
+def augment_spec(cfg):
+    """The canonical spec string of a parsed one: the fixed order hflip, reverse, shift, jitter ('' = nothing enabled)."""
+    words = [n for n in ('hflip', 'reverse') if cfg[n]]
+    words += ['shift=%d' % cfg['shift']] if cfg['shift'] else []
+    words += ['jitter=%s' % repr(float(cfg['jitter']))] if cfg['jitter'] else []
+    return ','.join(words)
+
+
+def add_arguments(p) -> None:
+    """train.py's `--augment` option (as ema.add_arguments: the option lives with what it configures)."""
+    p.add_argument('--augment', default='', metavar='LIST',   # docs/DESIGN_NOTES_augment.md
+                   help='kth | bair | ucf from --data_root, train split only: a comma list of hflip, reverse, shift=N (1..16 pixels, '
+                        'edge-replicated) and jitter=G (0 < G <= 0.5: contrast and brightness); parameters are drawn per clip and '
+                        'applied on the device inside the gather (default: none)')
+
+
+def check_augment(opt) -> str:
+    """train.py: the canonical form of `--augment` ('' = off).  It augments clips that are gathered from a frame pool: the
+    Moving-MNIST and synthetic streams draw a new clip for every batch, there is nothing to augment."""
+    spec = augment_spec(parse_augment(opt.augment))
+    if spec and (opt.dataset not in REAL_DATASETS or opt.synthetic_data):
+        raise SystemExit(f"train.py --augment: applies to kth | bair | ucf clips read from --data_root, not to "
+                         f"{'--synthetic_data' if opt.synthetic_data else '--dataset ' + opt.dataset}")
+    return spec
+
+
+class ClipAugmenter:
+    """The draws of `--augment`: one private np.random.RandomState(seed), apart from the samplers' generators, so the clips a
+    run selects are the same with and without augmentation.  Per clip in batch order, and only for the enabled transforms, in
+    this order: hflip = randint(2); reverse = randint(2); dy = randint(-N, N + 1), then dx; c = 1 + uniform(-G, G), then
+    b = uniform(-G, G) / 2.  gain = float32(c), bias = float32(0.5 - 0.5 * c + b): contrast about mid-grey plus brightness,
+    computed in float64 and rounded once.  Parameters are per CLIP, not per frame: the motion stays coherent."""
+
+    def __init__(self, spec, seed):
+        self.cfg = spec if isinstance(spec, dict) else parse_augment(spec)
+        self.spec = augment_spec(self.cfg)
+        self.rng = np.random.RandomState(seed)
+
+    def draw(self, B):
+        """(geom (B,4) int32 [hflip, reverse, dy, dx], photo (B,2) float32 [gain, bias]); disabled: 0, 0, 0, 0 and 1.0, 0.0."""
+        cfg, rng = self.cfg, self.rng
+        geom = np.zeros((B, 4), np.int32)
+        photo = np.tile(np.array([1.0, 0.0], np.float32), (B, 1))
+        N, G = cfg['shift'], cfg['jitter']
+        for i in range(B):
+            if cfg['hflip']:
+                geom[i, 0] = rng.randint(2)
+            if cfg['reverse']:
+                geom[i, 1] = rng.randint(2)
+            if N:
+                geom[i, 2] = rng.randint(-N, N + 1)
+                geom[i, 3] = rng.randint(-N, N + 1)
+            if G:
+                c = 1.0 + rng.uniform(-G, G)
+                b = rng.uniform(-G, G) / 2.0
+                photo[i, 0] = np.float32(c)
+                photo[i, 1] = np.float32(0.5 - 0.5 * c + b)
+        return geom, photo
+
+    def position(self):
+        return {"spec": self.spec, "np": self.rng.get_state()}
+
+    def restore(self, pos):
+        got = pos.get("spec") if isinstance(pos, dict) else None
+        if got != self.spec:
+            raise SystemExit(f"data position: saved with --augment {got!r}, this run has --augment {self.spec!r}")
+        self.rng.set_state(pos["np"])
+
+
 def _decode(path, dst, image_width):
     """One PNG into dst (H,W,pool_c) uint8: mode L as one channel, RGB interleaved; no resizing (nor does the reference)."""
     from PIL import Image

@@ -23,7 +23,8 @@ from .winograd import (  # noqa: F401
 from .edge import (  # noqa: F401
     conv3x3_first, first_pair_ok, conv3x3_first_pair, convT3x3_last, conv4x4s2_first, convT4x4s2_last, pixel_proj,
     _SKIP_PROJ_CACHE, clear_skip_proj_cache, _cached_skip_proj, _last_wmat, _last_wmat_cached,
-    precompute_skip_proj, convT_last_two_step, eval_frames, eval_frames_finn, pairwise_frame_mse, moving_mnist_compose, clip_gather, mnist_scale_u8, moving_mnist_compose_u8, frame_mosaic, QUANT_TRUNC, QUANT_NEAREST,
+    precompute_skip_proj, convT_last_two_step, eval_frames, eval_frames_finn, pairwise_frame_mse, moving_mnist_compose, clip_gather, clip_gather_aug, CLIP_MAX_SHIFT,
+    mnist_scale_u8, moving_mnist_compose_u8, frame_mosaic, QUANT_TRUNC, QUANT_NEAREST,
     MOSAIC_BLACK, MOSAIC_RED, MOSAIC_GREEN, MOSAIC_SEL_NONE, MOSAIC_SEL_BEST, MOSAIC_SEL_PICK, MOSAIC_CELL_INTS,
 )
 from .dense import (  # noqa: F401

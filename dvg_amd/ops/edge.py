@@ -3,6 +3,7 @@ pair, the last transposed conv as projection + gather (with the loop-invariant s
 compositing."""
 from __future__ import annotations
 
+import numpy as np
 import torch
 
 from .._derived import derived, register
@@ -336,6 +337,72 @@ def clip_gather(pool, first, T, C):
     out = torch.empty((max(T, 0), b, C, h, w), device=pool.device, dtype=torch.float32)
     _run("clip_gather", 0.0, float(T * b * h * w * pc) + 4.0 * out.numel(), lib().dvg_clip_gather_u8, _p(pool), _p(first),
          _p(out), n, T, b, C, h, w, pc, _stream())
+    return out
+
+
+CLIP_MAX_SHIFT = 16     # DVG_CLIP_MAX_SHIFT of clips.hip: the kernel clamps dy / dx to it
+
+
+def clip_gather_aug(pool, first, geom, photo, T, C):
+    """`clip_gather` with per-clip augmentation (dvg_clip_gather_aug_u8): geom (B,4) int32 = [hflip, reverse, dy, dx], photo
+    (B,2) float32 = [gain, bias]; out[t,b,c,y,x] = clip(gain * v + bias, 0, 1) of v = pool[first[b] + ts, sy, sx, c] / 255 with
+    ts = T-1-t under reverse, sx from W-1-x under hflip, and the shift (dy, dx) with edge replication.  Identity parameters give
+    clip_gather's bits.  Host arrays are range-checked here (first against the pool, |dy|, |dx| <= 16, finite gain / bias); when
+    all three are host arrays they travel as ONE buffer - a batch stays one upload and one launch.  An int64 / int32 / float32
+    device tensor is passed through: the kernel clamps what it reads."""
+    if not pool.is_cuda or pool.dtype != torch.uint8 or pool.dim() != 4 or not pool.is_contiguous():
+        raise RuntimeError("clip_gather_aug: pool must be a contiguous (n_frames,H,W,pool_c) uint8 GPU tensor - no CPU fallback")
+    n, h, w, pc = pool.shape
+
+    def on_device(t):
+        return isinstance(t, torch.Tensor) and t.is_cuda
+
+    def host_array(t):      # numpy arrays, CPU tensors and sequences alike, without a copy where there is an array already
+        return np.ascontiguousarray(t.numpy() if isinstance(t, torch.Tensor) else t)
+    # the checks of host arrays run in numpy: a handful of one-element torch ops per batch cost more than the launch
+    host = {}
+    if not on_device(first):
+        f = host_array(first)
+        if f.dtype != np.int64 or f.ndim != 1 or f.size == 0:
+            raise RuntimeError("clip_gather_aug: first must be a non-empty 1-D int64 sequence")
+        if T < 1 or int(f.min()) < 0 or int(f.max()) + T > n:
+            raise RuntimeError(f"clip_gather_aug: clips of {T} frames at [{int(f.min())}, {int(f.max())}] leave the pool of "
+                               f"{n} frames")
+        host["first"] = f
+    if not on_device(geom):
+        g = host_array(geom)
+        if g.dtype != np.int32 or g.ndim != 2 or g.shape[1] != 4 or g.size == 0:
+            raise RuntimeError("clip_gather_aug: geom must be a non-empty (B,4) int32 array [hflip, reverse, dy, dx]")
+        if int(g[:, 2:].min()) < -CLIP_MAX_SHIFT or int(g[:, 2:].max()) > CLIP_MAX_SHIFT:
+            raise RuntimeError(f"clip_gather_aug: a shift (dy, dx) beyond +-{CLIP_MAX_SHIFT} pixels")
+        host["geom"] = g
+    if not on_device(photo):
+        ph = host_array(photo)
+        if ph.dtype != np.float32 or ph.ndim != 2 or ph.shape[1] != 2 or ph.size == 0:
+            raise RuntimeError("clip_gather_aug: photo must be a non-empty (B,2) float32 array [gain, bias]")
+        if not np.isfinite(ph).all():
+            raise RuntimeError("clip_gather_aug: gain / bias must be finite")
+        host["photo"] = ph
+    if len(host) == 3:      # one buffer, one upload: first (8 B bytes) | geom (16 B) | photo (8 B), each part 8-byte aligned
+        a, b_ = host["first"].nbytes, host["first"].nbytes + host["geom"].nbytes
+        buf = np.empty(b_ + host["photo"].nbytes, np.uint8)
+        buf[:a], buf[a:b_], buf[b_:] = (host[k].reshape(-1).view(np.uint8) for k in ("first", "geom", "photo"))
+        packed = torch.from_numpy(buf).to(pool.device)
+        first, geom, photo = packed[:a].view(torch.int64), packed[a:b_].view(torch.int32).view(-1, 4), \
+            packed[b_:].view(torch.float32).view(-1, 2)
+    else:
+        first, geom, photo = (torch.from_numpy(host[k]).to(pool.device) if k in host else t
+                              for k, t in (("first", first), ("geom", geom), ("photo", photo)))
+    if first.dtype != torch.int64 or first.dim() != 1 or not first.is_contiguous() or first.device != pool.device:
+        raise RuntimeError("clip_gather_aug: first must be a contiguous 1-D int64 tensor on the pool's device")
+    b = first.shape[0]
+    if geom.dtype != torch.int32 or tuple(geom.shape) != (b, 4) or not geom.is_contiguous() or geom.device != pool.device:
+        raise RuntimeError(f"clip_gather_aug: geom must be a contiguous ({b},4) int32 tensor on the pool's device")
+    if photo.dtype != torch.float32 or tuple(photo.shape) != (b, 2) or not photo.is_contiguous() or photo.device != pool.device:
+        raise RuntimeError(f"clip_gather_aug: photo must be a contiguous ({b},2) float32 tensor on the pool's device")
+    out = torch.empty((max(T, 0), b, C, h, w), device=pool.device, dtype=torch.float32)
+    _run("clip_gather_aug", 0.0, float(T * b * h * w * pc) + 4.0 * out.numel(), lib().dvg_clip_gather_aug_u8, _p(pool), _p(first),
+         _p(geom), _p(photo), _p(out), n, T, b, C, h, w, pc, _stream())
     return out
 
 

@@ -1,17 +1,13 @@
 /*
  * dvg_hip.h — C ABI of libdvg_hip.so, the MI355X (gfx950) kernel library behind the DVG frame-prediction hot path.
- *
  * The reference (shgaurav1/DVG) has no FFI / plugin boundary of its own: every device op is an implicit torch.nn / gpytorch
  * call.  Each entry point below therefore names the reference *call site* it replaces.  Citations are
  * file:line into the reference tree.
- *
  * Conventions
  *   - every pointer is a DEVICE pointer to fp32 data unless stated otherwise;
- *   - activations are NHWC ("channels last"): x[n][y][x][c]; the Python side exposes them as (N,C,H,W) torch tensors with
- *     channels_last strides;
+ *   - activations are NHWC ("channels last"): x[n][y][x][c]; Python exposes them as (N,C,H,W) tensors with channels_last strides;
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream);
- *   - every function returns 0 on success, a DVG_ERR_* code otherwise and never throws; dvg_last_error() gives a thread-local
- *     message;
+ *   - every function returns 0 on success, else a DVG_ERR_* code, and never throws; dvg_last_error(): a thread-local message;
  *   - all shape checks happen on the host BEFORE a kernel is launched: a call that fails a check launches nothing.
  *   - no function allocates, frees or synchronises: graph-capture safe;
  *   - threading: ONE host thread per process drives the library (the reference's own contract, SURVEY.md 8(b) "Threading"; data
@@ -571,9 +567,15 @@ int dvg_moving_mnist_compose(const float* sprites, const int* ids, const int* po
  * frame (clamped to [0, n_frames - T] in the kernel); out (T,B,C,H,W): out[t,b,c,y,x] = (float)pool[first[b]+t,y,x,c] / 255.0f,
  * a true division (bit-equal to float32(float64(v)/255.) for all 256 bytes).  C == pool_c (1 or 3), or C == 1 with
  * pool_c == 3 (channel 0: kth.py:55).  W * pool_c % 16 == 0; pool offsets are 64-bit, out must stay below 2^31 elements.
- * An addition within ABI 9. */
+ * dvg_clip_gather_aug_u8 adds per-clip augmentation, which the reference's loaders (the lines cited above) do not have: geom (B,4)
+ * DEVICE int32 [hflip, reverse, dy, dx], photo (B,2) DEVICE float [gain, bias], 4-byte aligned; W <= 1024.  It reads frame
+ * first[b] + (reverse ? T-1-t : t) at row clamp(y + dy, 0, H-1), column clamp((hflip ? W-1-x : x) + dx, 0, W-1) (edge replicate)
+ * and writes min(max(gain * v + bias, 0), 1), the multiply and the add rounded separately (no FMA): identity parameters give
+ * dvg_clip_gather_u8's bits.  dy / dx are clamped to +-16, hflip / reverse read as != 0.  Additions within ABI 9. */
 int dvg_clip_gather_u8(const uint8_t* pool, const int64_t* first, float* out, int64_t n_frames, int T, int B, int C, int H,
                        int W, int pool_c, void* stream);
+int dvg_clip_gather_aug_u8(const uint8_t* pool, const int64_t* first, const int32_t* geom, const float* photo, float* out,
+                           int64_t n_frames, int T, int B, int C, int H, int W, int pool_c, void* stream);
 
 /* `transforms.Scale(out_size)` on the MNIST digits (data/moving_mnist.py:24-26): Pillow's 8-bit bilinear resize, bit for bit.
  * raw (n,in_size,in_size) uint8 -> out (n,out_size,out_size) uint8, a horizontal pass into a uint8 intermediate, then a
@@ -587,8 +589,7 @@ int dvg_mnist_scale_u8(const uint8_t* raw, uint8_t* out, int n, int in_size, int
 /* dvg_moving_mnist_compose from a uint8 digit pool (data/moving_mnist.py:86-90 + utils.normalize_data's layout, utils.py:86-95):
  * sprites (n_sprites,D,D) uint8, a byte becomes float32 as `ToTensor` makes it, (float)v / 255.0f by a true division; digits are
  * added in index order, the sum is clipped at 1, out (T,B,1,S,S) float32.  ids (B,num_digits) int32, clamped in the kernel; pos
- * (B,num_digits,T,2) int32 = (sy,sx), every sprite access bounds-checked against it.  S % 4 == 0, out 16-byte aligned.
- * An addition within ABI 9. */
+ * (B,num_digits,T,2) int32 = (sy,sx), every sprite access bounds-checked against it.  S % 4 == 0, out 16-byte aligned.  ABI 9. */
 int dvg_moving_mnist_compose_u8(const uint8_t* sprites, const int* ids, const int* pos, float* out, int n_sprites, int T,
                                 int B, int num_digits, int image_size, int digit_size, void* stream);
 
@@ -606,8 +607,7 @@ int dvg_eval_frames(const float* gt, const float* pred, float* ssim, float* psnr
  * :259-261; +inf for identical images).  Per frame: the squared error over all C channels / (C*H*W) (mse_metric, :215-218).
  * gt / pred: n_frames contiguous CxHxW fp32 frames - any number of them, so all time steps of a rollout are ONE launch;
  * ssim / psnr: n_frames * C floats, mse: n_frames floats.  fp64 inside, fixed reduction order (bit-identical reruns).
- * H, W >= 11; n_frames*C*H*W < 2^31; 11 row-filtered rows of 5 x (W-10) doubles must fit 150 KB of LDS (W <= 359).
- * An addition within ABI 9. */
+ * H, W >= 11; n_frames*C*H*W < 2^31; 11 row-filtered rows of 5 x (W-10) doubles must fit 150 KB of LDS (W <= 359).  ABI 9. */
 int dvg_eval_frames_finn(const float* gt, const float* pred, float* ssim, float* psnr, float* mse, int n_frames, int C, int H,
                          int W, void* stream);
 

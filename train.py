@@ -31,6 +31,8 @@ those files or with `--synthetic_data`, seeded Moving-MNIST trajectories with in
 model" section, :86, is empty and `--model_dir` is never read: both kept); dvg_amd/train_state.py, docs/DESIGN_NOTES_resume.md.
 `--ema_decay D` keeps an exponential moving average of all weights on the device, one launch per iteration inside the captured
 graph, and writes `model_ema.pth` beside `model.pth` (dvg_amd/ema.py, docs/DESIGN_NOTES_ema.md).
+`--augment LIST` (kth | bair | ucf, train split): flip / reverse / shift / jitter per clip, applied inside the gather
+(dvg_clip_gather_aug_u8; dvg_amd/datasets.py ClipAugmenter, docs/DESIGN_NOTES_augment.md).
 """
 import argparse
 import importlib
@@ -47,7 +49,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 import utils  # noqa: E402
-from dvg_amd import ema as weight_ema, fused, parallel, train_state, viz  # noqa: E402
+from dvg_amd import datasets, ema as weight_ema, fused, parallel, train_state, viz  # noqa: E402
 from dvg_amd.data import SyntheticMovingMNIST, make_batch_generator, synthetic_video  # noqa: E402,F401
 from dvg_amd.models.gp_models import GaussianLikelihood, GPRegressionLayer1, VariationalELBO  # noqa: E402
 from dvg_amd.optim import FlatArena, FusedAdam, guard_options, guarded_step, make_guard, zero_grads  # noqa: E402,F401
@@ -113,6 +115,7 @@ def build_parser():
     p.add_argument('--skip_nonfinite', action='store_true',
                    help='skip such a step when a gradient is Inf or NaN: no parameter, Adam moment or step count changes')
     weight_ema.add_arguments(p)   # --ema_decay
+    datasets.add_arguments(p)     # --augment
     return p
 
 
@@ -711,6 +714,7 @@ from dvg_amd.train_graphs import BatchPrefetcher, GraphedIteration, SegmentedIte
 def main(argv=None):
     opt = build_parser().parse_args(argv)
     opt.ft = not opt.no_ft
+    opt.augment = datasets.check_augment(opt)   # --augment: parsed and refused before anything is built
     if hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
         # the latent path of an eager iteration runs on a second stream on purpose (autograd.JOIN_STREAMS joins them)
         torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
@@ -720,6 +724,8 @@ def main(argv=None):
     state = train_state.open_resume(opt)    # --resume: read and checked against the options before anything is built
     if rank == 0:
         print("Random Seed: ", opt.seed)
+        if opt.augment:
+            print(f"augment: {opt.augment} (train split only)")
     random.seed(opt.seed + rank)
     np.random.seed(opt.seed + rank)
     torch.manual_seed(opt.seed)          # identical init on every rank (also broadcast below)
