@@ -575,49 +575,89 @@ __global__ __launch_bounds__(256) void wgrad_thin_kernel(const float* __restrict
     }
 }
 
-static inline unsigned grid_for(long n, int block = 256, int cap = 4096) {
-    long g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (unsigned)g;
-}
-
-
 // ------------------------------------------------------------------------------------
 // Fused Adam over a flat parameter group (train.py:95-106: torch.optim.Adam(lr=0.002), default betas / eps):
 //   g' = g + wd p;  m = b1 m + (1-b1) g';  v = b2 v + (1-b2) g'^2;
 //   p -= (lr / bc1) * m / (sqrt(v) / sqrt(bc2) + eps)        bc1 = 1 - b1^t, bc2 = 1 - b2^t
 // (torch.optim.Adam's arithmetic, non-amsgrad).  One launch per group instead of the foreach chain.
 // ------------------------------------------------------------------------------------
+struct AdamCoef {
+    float b1, b2, eps, wd, lr_over_bc1, inv_sqrt_bc2;
+};
+
+// the coefficients of step t (t >= 1: the steps really applied)
+__device__ __forceinline__ AdamCoef adam_coef(float lr, float b1, float b2, float eps, float wd, int t) {
+    const double bc1 = 1.0 - pow((double)b1, (double)t), bc2 = 1.0 - pow((double)b2, (double)t);
+    return {b1, b2, eps, wd, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2))};
+}
+
+// One element - p[e], m[e], v[e] of a 16-byte piece held in registers, or of the arrays themselves (the tail): the ONLY place
+// the update is written.  (An index, not references: a vector element does not bind to one.)
+template <typename V, typename I>
+__device__ __forceinline__ void adam_element(V& p, float g, V& m, V& v, const AdamCoef& c, I e) {
+    const float gg = g + c.wd * p[e];
+    const float mm = c.b1 * m[e] + (1.f - c.b1) * gg, vv = c.b2 * v[e] + (1.f - c.b2) * gg * gg;
+    m[e] = mm;
+    v[e] = vv;
+    p[e] -= c.lr_over_bc1 * mm / (sqrtf(vv) * c.inv_sqrt_bc2 + c.eps);
+}
+
+// a * b rounded on its own: never contracted into an add that follows (HIP's __fmul_rn is a plain product, which the default
+// -ffp-contract=fast-honor-pragmas does fuse)
+__device__ __forceinline__ float gg_mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+    return a * b;
+}
+
 __global__ void adam_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
                                  float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
                                  const int* __restrict__ step_dev, int step_host) {
     // the step count may live in device memory (a captured hipGraph replays with a fresh count every iteration)
-    const int t = step_dev ? *step_dev : step_host;
-    const double bc1 = 1.0 - pow((double)b1, (double)t), bc2 = 1.0 - pow((double)b2, (double)t);
-    const float lr_over_bc1 = (float)((double)lr / bc1), inv_sqrt_bc2 = (float)(1.0 / sqrt(bc2));
+    const AdamCoef c = adam_coef(lr, b1, b2, eps, wd, step_dev ? *step_dev : step_host);
     const long n4 = n >> 2;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         f32x4 pv = reinterpret_cast<f32x4*>(p)[i], mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
         const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float gg = gv[e] + wd * pv[e];
-            mv[e] = b1 * mv[e] + (1.f - b1) * gg;
-            vv[e] = b2 * vv[e] + (1.f - b2) * gg * gg;
-            pv[e] -= lr_over_bc1 * mv[e] / (sqrtf(vv[e]) * inv_sqrt_bc2 + eps);
-        }
+        for (int e = 0; e < 4; ++e) adam_element(pv, gv[e], mv, vv, c, e);
         reinterpret_cast<f32x4*>(p)[i] = pv;
         reinterpret_cast<f32x4*>(m)[i] = mv;
         reinterpret_cast<f32x4*>(v)[i] = vv;
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {   // tail
         const long i = (n4 << 2) + threadIdx.x;
-        const float gg = g[i] + wd * p[i];
-        const float mm = b1 * m[i] + (1.f - b1) * gg, vv = b2 * v[i] + (1.f - b2) * gg * gg;
-        m[i] = mm;
-        v[i] = vv;
-        p[i] -= lr_over_bc1 * mm / (sqrtf(vv) * inv_sqrt_bc2 + eps);
+        adam_element(p, g[i], m, v, c, i);
+    }
+}
+
+// adam_step_kernel under the verdict of grad_guard.hip (train.py --clip_grad_norm / --skip_nonfinite): the gradient is scaled
+// by stat[1] as it is read, nothing is touched when stat[2] != 0, and the steps skipped so far do not count.  The product
+// g * scale is rounded on its own (gg_mul_rn), so scale = 1 leaves every later operation - the weight-decay multiply-add
+// included - with the operands adam_step_kernel has: the same bits.
+__global__ void adam_step_guarded_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                         float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
+                                         const int* __restrict__ step_dev, int step_host, const float* __restrict__ stat,
+                                         int* __restrict__ skips_dev) {
+    if (stat[2] != 0.f) {            // uniform over the grid; this launch does not read *skips_dev
+        if (blockIdx.x == 0 && threadIdx.x == 0) *skips_dev += 1;
+        return;
+    }
+    const float scale = stat[1];
+    // the counts (device or host) were advanced for the skipped steps too: the bias corrections use the steps really applied
+    const AdamCoef c = adam_coef(lr, b1, b2, eps, wd, (step_dev ? *step_dev : step_host) - *skips_dev);
+    const long n4 = n >> 2;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        f32x4 pv = reinterpret_cast<f32x4*>(p)[i], mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
+        const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) adam_element(pv, gg_mul_rn(gv[e], scale), mv, vv, c, e);
+        reinterpret_cast<f32x4*>(p)[i] = pv;
+        reinterpret_cast<f32x4*>(m)[i] = mv;
+        reinterpret_cast<f32x4*>(v)[i] = vv;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {   // tail
+        const long i = (n4 << 2) + threadIdx.x;
+        adam_element(p, gg_mul_rn(g[i], scale), m, v, c, i);
     }
 }
 
@@ -745,10 +785,10 @@ extern "C" int dvg_affine3_apply(const float* dp, const float* u, const float* A
                      aligned16(Cc) && aligned16(sum);
     DVG_REQUIRE(sum_mode == 0 || vec, DVG_ERR_ALIGN, "dvg_affine3_apply: the sum output needs C %% 4 == 0 and 16-byte alignment");
     if (vec)
-        hipLaunchKernelGGL(affine3_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, dp, u, A, B, Cc,
-                           du, n / 4, C / 4, sum, sum_mode, per_group / 4);
+        hipLaunchKernelGGL(affine3_kernel, dim3(grid_for(n / 4, 256, 4096)), dim3(256), 0, (hipStream_t)stream, dp, u, A, B,
+                           Cc, du, n / 4, C / 4, sum, sum_mode, per_group / 4);
     else
-        hipLaunchKernelGGL(affine3_scalar_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, dp, u, A, B,
+        hipLaunchKernelGGL(affine3_scalar_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, dp, u, A, B,
                            Cc, du, n, C, per_group);
     return check_launch("dvg_affine3_apply");
 }
@@ -770,7 +810,7 @@ extern "C" int dvg_group_sum(const float* src, const int* map, float* dst, int g
 extern "C" int dvg_act_bwd(const float* dy, const float* y, float* dpre, long n, int act, float slope, void* stream) {
     DVG_REQUIRE(dy && y && dpre, DVG_ERR_NULL, "dvg_act_bwd: NULL pointer");
     DVG_REQUIRE(n > 0 && act >= 0 && act <= 3, DVG_ERR_SHAPE, "dvg_act_bwd: bad args");
-    hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, dy, y, dpre, n, act,
+    hipLaunchKernelGGL(act_bwd_kernel, dim3(grid_for(n, 256, 4096)), dim3(256), 0, (hipStream_t)stream, dy, y, dpre, n, act,
                        slope);
     return check_launch("dvg_act_bwd");
 }
@@ -779,7 +819,7 @@ extern "C" int dvg_upsample2x_bwd(const float* dxu, float* dx, int N, int H, int
     DVG_REQUIRE(dxu && dx, DVG_ERR_NULL, "dvg_upsample2x_bwd: NULL pointer");
     DVG_REQUIRE(N > 0 && H > 0 && W > 0 && C > 0 && C % 4 == 0, DVG_ERR_SHAPE, "dvg_upsample2x_bwd: bad shape");
     DVG_REQUIRE(aligned16(dxu) && aligned16(dx), DVG_ERR_ALIGN, "dvg_upsample2x_bwd: alignment");
-    hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3(grid_for((long)N * H * W * (C / 4))), dim3(256), 0,
+    hipLaunchKernelGGL(upsample2x_bwd_kernel, dim3(grid_for((long)N * H * W * (C / 4), 256, 4096)), dim3(256), 0,
                        (hipStream_t)stream, dxu, dx, N, H, W, C / 4);
     return check_launch("dvg_upsample2x_bwd");
 }
@@ -816,8 +856,8 @@ extern "C" int dvg_k4_to_w3(const float* dk4_packed, float* dw, int cout, int c1
                             void* stream) {
     DVG_REQUIRE(dk4_packed && dw, DVG_ERR_NULL, "dvg_k4_to_w3: NULL pointer");
     DVG_REQUIRE(cout > 0 && c1 > 0 && c_lo >= 0 && c_lo + c1 <= ctot, DVG_ERR_SHAPE, "dvg_k4_to_w3: bad shape");
-    hipLaunchKernelGGL(k4_to_w3_kernel, dim3(grid_for((long)9 * cout * c1)), dim3(256), 0, (hipStream_t)stream, dk4_packed, dw,
-                       cout, c1, ctot, c_lo, beta);
+    hipLaunchKernelGGL(k4_to_w3_kernel, dim3(grid_for((long)9 * cout * c1, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
+                       dk4_packed, dw, cout, c1, ctot, c_lo, beta);
     return check_launch("dvg_k4_to_w3");
 }
 
@@ -835,7 +875,7 @@ extern "C" int dvg_lstm_gates_bwd(const float* dh, const float* dc, const float*
     DVG_REQUIRE(gates && c_prev && c_new && dG && dc_prev, DVG_ERR_NULL, "dvg_lstm_gates_bwd: NULL pointer");
     DVG_REQUIRE(dh || dc, DVG_ERR_NULL, "dvg_lstm_gates_bwd: no incoming gradient");
     DVG_REQUIRE(B > 0 && H > 0, DVG_ERR_SHAPE, "dvg_lstm_gates_bwd: bad shape");
-    hipLaunchKernelGGL(lstm_gates_bwd_kernel, dim3(grid_for((long)B * H)), dim3(256), 0, (hipStream_t)stream, dh, dc,
+    hipLaunchKernelGGL(lstm_gates_bwd_kernel, dim3(grid_for((long)B * H, 256, 4096)), dim3(256), 0, (hipStream_t)stream, dh, dc,
                        gates, c_prev, c_new, dG, dc_prev, B, H);
     return check_launch("dvg_lstm_gates_bwd");
 }
@@ -869,9 +909,25 @@ extern "C" int dvg_adam_step(float* param, const float* grad, float* exp_avg, fl
     DVG_REQUIRE(n > 0 && (step >= 1 || step_dev != nullptr), DVG_ERR_SHAPE, "dvg_adam_step: n=%ld step=%d", n, step);
     DVG_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq), DVG_ERR_ALIGN,
                 "dvg_adam_step: buffers must be 16-byte aligned");
-    hipLaunchKernelGGL(adam_step_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, param, grad,
+    hipLaunchKernelGGL(adam_step_kernel, dim3(grid_for((n + 3) / 4, 256, 4096)), dim3(256), 0, (hipStream_t)stream, param, grad,
                        exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step_dev, step);
     return check_launch("dvg_adam_step");
+}
+
+// dvg_adam_step under the verdict of dvg_grad_guard_finish: the gradient times stat[1], or nothing at all when stat[2] != 0
+// (then *skips_dev is advanced).
+extern "C" int dvg_adam_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr,
+                                     float beta1, float beta2, float eps, float weight_decay, int step, const int* step_dev,
+                                     const float* stat, int* skips_dev, void* stream) {
+    DVG_REQUIRE(param && grad && exp_avg && exp_avg_sq && stat && skips_dev, DVG_ERR_NULL, "dvg_adam_step_guarded: NULL pointer");
+    DVG_REQUIRE(n > 0 && (step >= 1 || step_dev != nullptr), DVG_ERR_SHAPE, "dvg_adam_step_guarded: n=%ld step=%d", n, step);
+    DVG_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq), DVG_ERR_ALIGN,
+                "dvg_adam_step_guarded: buffers must be 16-byte aligned");
+    DVG_REQUIRE(aligned_to<4>(stat) && aligned_to<4>(skips_dev) && aligned_to<4>(step_dev), DVG_ERR_ALIGN,
+                "dvg_adam_step_guarded: stat, skips_dev and step_dev must be 4-byte aligned");
+    hipLaunchKernelGGL(adam_step_guarded_kernel, dim3(grid_for((n + 3) / 4, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
+                       param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step_dev, step, stat, skips_dev);
+    return check_launch("dvg_adam_step_guarded");
 }
 
 // g[0:n] = 0 and *t_k += 1 for the non-NULL step counters (see zero_tick_kernel): optimizer.zero_grad() of adjacent groups of
@@ -879,6 +935,7 @@ extern "C" int dvg_adam_step(float* param, const float* grad, float* exp_avg, fl
 extern "C" int dvg_zero_tick(float* g, long n, int* t0, int* t1, int* t2, int* t3, void* stream) {
     DVG_REQUIRE(g, DVG_ERR_NULL, "dvg_zero_tick: NULL pointer");
     DVG_REQUIRE(n > 0 && aligned16(g), DVG_ERR_SHAPE, "dvg_zero_tick: n > 0 and a 16-byte aligned buffer needed");
-    hipLaunchKernelGGL(zero_tick_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, g, n, t0, t1, t2, t3);
+    hipLaunchKernelGGL(zero_tick_kernel, dim3(grid_for((n + 3) / 4, 256, 4096)), dim3(256), 0, (hipStream_t)stream, g, n, t0,
+                       t1, t2, t3);
     return check_launch("dvg_zero_tick");
 }

@@ -210,7 +210,7 @@ extern "C" int dvg_clip_gather_aug_u8(const uint8_t* pool, const int64_t* first,
     DVG_REQUIRE((long)T * B * C * H * W < (1L << 31) && (long)H * W * pool_c < (1L << 31), DVG_ERR_SHAPE,
                 "dvg_clip_gather_aug_u8: %dx%dx%dx%dx%d output elements exceed the 32-bit offsets of the kernel", T, B, C, H, W);
     DVG_REQUIRE(aligned16(pool) && aligned16(out), DVG_ERR_ALIGN, "dvg_clip_gather_aug_u8: pool / out not 16-byte aligned");
-    DVG_REQUIRE((reinterpret_cast<uintptr_t>(geom) & 3u) == 0 && (reinterpret_cast<uintptr_t>(photo) & 3u) == 0, DVG_ERR_ALIGN,
+    DVG_REQUIRE(aligned_to<4>(geom) && aligned_to<4>(photo), DVG_ERR_ALIGN,
                 "dvg_clip_gather_aug_u8: geom / photo not 4-byte aligned");
     // W * pool_c % 16 == 0 with pool_c in {1, 3} makes W a multiple of 16: whole float4 groups and whole 16-byte chunks per row
     const unsigned rpt = (unsigned)(CLIP_TILE_PX / W);                         // >= 1: W <= CLIP_TILE_PX

@@ -779,7 +779,7 @@ extern "C" int dvg_lstm_cell_x(const float* x, int ldx, int Kx, const float* h, 
     DVG_REQUIRE(Kx > 0 && Kx <= 128 && Kx % 2 == 0 && ldx >= Kx && ldx % 2 == 0 && Kxp >= Kx && Kxp % 4 == 0,
                 DVG_ERR_SHAPE, "dvg_lstm_cell_x: Kx=%d (even, <= 128), ldx=%d (even), Kxp=%d (multiple of 4)", Kx, ldx, Kxp);
     DVG_REQUIRE(h_out != h && c_out != c, DVG_ERR_SHAPE, "dvg_lstm_cell_x: in-place state update");
-    DVG_REQUIRE(aligned16(h) && aligned16(w_x) && aligned16(w_hh) && (reinterpret_cast<uintptr_t>(x) & 7u) == 0,
+    DVG_REQUIRE(aligned16(h) && aligned16(w_x) && aligned16(w_hh) && aligned_to<8>(x),
                 DVG_ERR_ALIGN, "dvg_lstm_cell_x: alignment");
     dim3 grid(H / 2, (B + 31) / 32);
     hipLaunchKernelGGL(lstm_cell_x_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, ldx, Kx, h, c, w_x, Kxp, w_hh, bias,

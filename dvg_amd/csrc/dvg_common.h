@@ -11,7 +11,20 @@ namespace dvg {
 char* err_buf();
 int fail(int code, const char* fmt, ...);
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
+template <unsigned N>
+inline bool aligned_to(const void* p) {
+    static_assert(N && !(N & (N - 1)), "a power of two");
+    return (reinterpret_cast<uintptr_t>(p) & (N - 1)) == 0;      // NULL counts as aligned (optional pointers)
+}
+inline bool aligned16(const void* p) { return aligned_to<16>(p); }
+
+// Workgroups for a grid-stride kernel over n items.  No default cap: the launchers do not agree on one (2048, 4096, 8192).
+inline unsigned grid_for(long n, int block, int cap) {
+    long g = (n + block - 1) / block;
+    if (g < 1) g = 1;
+    if (g > cap) g = cap;
+    return (unsigned)g;
+}
 
 // Checks the launch that was just issued; no sync.
 inline int check_launch(const char* what) {
@@ -107,6 +120,71 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
     const unsigned q = nwg >> 3, r = nwg & 7u, xcd = bid & 7u;
     const unsigned base = xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q;
     return base + (bid >> 3);
+}
+
+// ---- deterministic sums over a wave and over a workgroup ---------------------------------------------------------------------
+// Every kernel that uses these promises the same bits on every launch, and saved training states, the --resume tests and the
+// determinism tests compare bits: neither the tree inside a wave nor the order in which the wave sums are combined may change
+// silently.  The two orders are historical, not chosen; each call site keeps the one it was written with.
+//   SUM_WAVE_ORDER  ((0 + r0) + r1) + r2 ... left to right over the NT / 64 waves: gp.hip (gp_predict, gp_train_bwd, gp_elbo),
+//                   grad_guard.hip (grad_sumsq, grad_guard_finish), ema.hip (ema_update).  The leading + 0 is gp.hip's loop; the
+//                   wave sums of grad_guard.hip and ema.hip are sums of squares from + 0, never - 0, so it changes none of their bits.
+//   SUM_PAIRWISE    (r0 + r1) + (r2 + r3), four waves: finn_metrics.hip (eval_frames_finn) and eval_frames_kernel,
+//                   frame_losses_kernel in misc_kernels.hip.
+// One-wave kernels (gp_var_norms, gp_trigger_step, gp_trigger_replay) use wave_sum alone.
+
+// The xor butterfly, offsets 32 ... 1: EVERY lane ends with the wave's sum.  Lane 0's value is also what the halving tree
+// `v += __shfl_down(v, off)` leaves in lane 0 (grad_guard.hip and ema.hip were written with that one): at every level lane 0 adds
+// its own value and lane `off`'s, and those two hold the same partial sums under either idiom - fp addition is commutative.
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+__device__ __forceinline__ float wave_min(float v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v = fminf(v, __shfl_xor(v, off));
+    return v;
+}
+
+enum SumOrder { SUM_WAVE_ORDER, SUM_PAIRWISE };
+
+// v[q] = the sum of v[q] over the workgroup's NT threads, for Q quantities under ONE pair of barriers; every thread gets the
+// totals and every thread must call it.  `red`: Q * NT / 64 values of LDS.  The leading barrier lets a kernel call it again and
+// again on the same `red` (a thread may still be reading the previous call's wave sums).
+template <int NT, SumOrder ORDER = SUM_WAVE_ORDER, int Q, typename T>
+__device__ __forceinline__ void block_sum(T (&v)[Q], T* red) {
+    constexpr int NW = NT / 64;
+    static_assert(NT % 64 == 0 && (ORDER == SUM_WAVE_ORDER || NW == 4), "whole waves; the pairwise order is written for four");
+#pragma unroll
+    for (int q = 0; q < Q; ++q) v[q] = wave_sum(v[q]);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+        for (int q = 0; q < Q; ++q) red[q * NW + (threadIdx.x >> 6)] = v[q];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int q = 0; q < Q; ++q) {
+        const T* r = red + q * NW;
+        if constexpr (ORDER == SUM_PAIRWISE) {
+            v[q] = (r[0] + r[1]) + (r[2] + r[3]);
+        } else {
+            T t = T(0.);
+#pragma unroll
+            for (int w = 0; w < NW; ++w) t += r[w];
+            v[q] = t;
+        }
+    }
+}
+
+template <int NT, SumOrder ORDER = SUM_WAVE_ORDER, typename T>
+__device__ __forceinline__ T block_sum(T v, T* red) {
+    T a[1] = {v};
+    block_sum<NT, ORDER>(a, red);
+    return a[0];
 }
 
 }  // namespace dvg

@@ -16,8 +16,9 @@
 //
 // Order, as grad_sumsq_kernel: workgroup b owns the fixed chunk [b * EMA_CHUNK, (b + 1) * EMA_CHUNK) - no grid-stride loop, the
 // number of partial pairs is a function of n alone (dvg_ema_update_blocks).  A thread adds its 16-byte pieces in index order into
-// four fp64 sums per quantity (one per vector lane), those as (s0 + s1) + (s2 + s3), the 64 lanes of a wave by a halving tree of
-// cross-lane moves, the four waves through LDS in wave order.  No atomics: the same input gives the same bits on every launch.
+// four fp64 sums per quantity (one per vector lane), those as (s0 + s1) + (s2 + s3), the 64 lanes of a wave and then the four
+// waves through LDS in wave order by block_sum (dvg_common.h), both quantities under one pair of barriers.  No atomics: the
+// same input gives the same bits on every launch.
 //
 // HBM-bound at 12 bytes per float (read p, read e, write e).  A thread issues all its loads of BOTH arrays - 2 x 8 x 16 bytes -
 // before the first is consumed: 64 KiB per workgroup, the amount grad_sumsq_kernel keeps in flight.
@@ -28,13 +29,6 @@ namespace dvg {
 constexpr int EMA_THREADS = 256;
 constexpr int EMA_PIECES = 8;                                     // 16-byte loads per thread and array
 constexpr long EMA_CHUNK = (long)EMA_THREADS * EMA_PIECES * 4;    // 8 192 floats per workgroup
-
-// lane 0 of every wave ends with the wave's sum; always the same tree
-__device__ __forceinline__ double ema_wave_sum(double s) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) s += __shfl_down(s, off, 64);
-    return s;
-}
 
 // One workgroup's chunk.  FULL: every 16-byte piece of the chunk is inside the range - straight-line code, no index test.  Else
 // (the last workgroup of a range that is no multiple of the chunk): a piece past the end is loaded from the last valid piece
@@ -81,28 +75,21 @@ __device__ __forceinline__ void ema_chunk(f32x4* __restrict__ e4, const f32x4* _
 __global__ __launch_bounds__(EMA_THREADS) void ema_update_kernel(float* __restrict__ ema, const float* __restrict__ param,
                                                                   long n4, double decay, const int* __restrict__ updates_dev,
                                                                   double* __restrict__ partials) {
-    __shared__ double red[2][4];
+    __shared__ double red[2 * 4];
     const double k = (double)*updates_dev;           // updates already applied; read, never written here
     const double warm = (1.0 + k) / (10.0 + k);
     const float w = (float)(1.0 - (decay < warm ? decay : warm));
     f32x4* e4 = reinterpret_cast<f32x4*>(ema);
     const f32x4* p4 = reinterpret_cast<const f32x4*>(param);
-    double lag, sq;
+    double s[2];                                             // lag, sum of squares
     if (((long)blockIdx.x + 1) * (EMA_CHUNK / 4) <= n4)      // uniform over the workgroup
-        ema_chunk<true>(e4, p4, n4, w, lag, sq);
+        ema_chunk<true>(e4, p4, n4, w, s[0], s[1]);
     else
-        ema_chunk<false>(e4, p4, n4, w, lag, sq);
-    lag = ema_wave_sum(lag);
-    sq = ema_wave_sum(sq);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    if (lane == 0) {
-        red[0][wave] = lag;
-        red[1][wave] = sq;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {                          // the four waves in wave order
-        partials[2 * (long)blockIdx.x] = ((red[0][0] + red[0][1]) + red[0][2]) + red[0][3];
-        partials[2 * (long)blockIdx.x + 1] = ((red[1][0] + red[1][1]) + red[1][2]) + red[1][3];
+        ema_chunk<false>(e4, p4, n4, w, s[0], s[1]);
+    block_sum<EMA_THREADS>(s, red);
+    if (threadIdx.x == 0) {
+        partials[2 * (long)blockIdx.x] = s[0];
+        partials[2 * (long)blockIdx.x + 1] = s[1];
     }
 }
 
@@ -122,9 +109,8 @@ extern "C" int dvg_ema_update(float* ema, const float* param, long n, double dec
     DVG_REQUIRE(n > 0 && n % 4 == 0 && dvg_ema_update_blocks(n) > 0, DVG_ERR_SHAPE,
                 "dvg_ema_update: n = %ld must be a positive multiple of 4", n);
     DVG_REQUIRE(decay >= 0.0 && decay < 1.0, DVG_ERR_SHAPE, "dvg_ema_update: decay = %g must be in [0, 1)", decay);   // NaN fails
-    DVG_REQUIRE(aligned16(ema) && aligned16(param) && (reinterpret_cast<uintptr_t>(partials) & 7u) == 0 &&
-                    (reinterpret_cast<uintptr_t>(updates_dev) & 3u) == 0,
-                DVG_ERR_ALIGN, "dvg_ema_update: ema and param must be 16-byte, partials 8-byte, updates_dev 4-byte aligned");
+    DVG_REQUIRE(aligned16(ema) && aligned16(param) && aligned_to<8>(partials) && aligned_to<4>(updates_dev), DVG_ERR_ALIGN,
+                "dvg_ema_update: ema and param must be 16-byte, partials 8-byte, updates_dev 4-byte aligned");
     DVG_REQUIRE(ema != param, DVG_ERR_SHAPE, "dvg_ema_update: ema and param are the same buffer");
     hipLaunchKernelGGL(ema_update_kernel, dim3((unsigned)dvg_ema_update_blocks(n)), dim3(EMA_THREADS), 0, (hipStream_t)stream,
                        ema, param, n >> 2, decay, updates_dev, partials);

@@ -16,8 +16,8 @@
 // 64x64 (two workgroups per CU) and 142 KB at 128x128; the 10 halo rows of a strip are filtered again by the next one
 // (x1.5 on the row pass at 20 output rows per strip).  Wider images get fewer rows per strip, down to the window's 11.
 //
-// Order.  Every lane sums its window positions in index order, the 64 lanes of a wave combine by xor-shuffles, lane 0 of the
-// workgroup adds the four wave sums in a fixed tree: two launches give the same bits.  No atomics.
+// Order.  Every lane sums its window positions in index order, the 64 lanes of a wave and then the four wave sums combine in a
+// fixed tree (block_sum, pairwise: dvg_common.h): two launches give the same bits.  No atomics.
 #include <cmath>
 
 #include "dvg_common.h"
@@ -31,16 +31,6 @@ constexpr size_t FINN_LDS_MAX = 150 * 1024;    // like eval_frames_kernel's tile
 struct FinnTaps {
     double g[FINN_WIN];                        // exp(-i^2 / (2 sigma^2)) / sum, i = -5 ... 5
 };
-
-// sum over the workgroup's 256 lanes, fixed order; every lane must call it
-__device__ __forceinline__ double finn_block_sum(double v, double* red) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
-    __syncthreads();                           // red may still be read from the previous call
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
 
 // utils.py:300-301 at one window position.  No contraction: with identical images 2 mu_x mu_y and mu_x^2 + mu_y^2 (and the
 // two variance sums) must round alike, so that the ratio is exactly 1.
@@ -62,7 +52,7 @@ __device__ __forceinline__ double finn_sq_err(const float* __restrict__ a, const
 }
 
 // One workgroup per (frame, channel) image.  ssim / psnr: [n_frames * C]; mse: [n_frames], written by the workgroup of the
-// frame's channel 0, which also sums the squared error of the frame's other channels (channel order, each reduced as above).
+// frame's channel 0, which also sums the squared error of the frame's other channels (channel order, each reduced alike).
 __global__ __launch_bounds__(256) void eval_frames_finn_kernel(const float* __restrict__ gt, const float* __restrict__ pred,
                                                                float* __restrict__ ssim, float* __restrict__ psnr,
                                                                float* __restrict__ mse, int C, int H, int W, int rows_in,
@@ -104,12 +94,13 @@ __global__ __launch_bounds__(256) void eval_frames_finn_kernel(const float* __re
         }
         __syncthreads();                       // the next strip overwrites the planes
     }
-    const double s = finn_block_sum(ssum, red);
-    const double e = finn_block_sum(finn_sq_err(X, Y, HW), red);
+    const double s = block_sum<256, SUM_PAIRWISE>(ssum, red);
+    const double e = block_sum<256, SUM_PAIRWISE>(finn_sq_err(X, Y, HW), red);
     double frame_se = e;
     const int c = blockIdx.x % C;
     if (c == 0)
-        for (int k = 1; k < C; ++k) frame_se += finn_block_sum(finn_sq_err(X + (size_t)k * HW, Y + (size_t)k * HW, HW), red);
+        for (int k = 1; k < C; ++k)
+            frame_se += block_sum<256, SUM_PAIRWISE>(finn_sq_err(X + (size_t)k * HW, Y + (size_t)k * HW, HW), red);
     if (threadIdx.x == 0) {
         const double m = s / ((double)Ho * Wo);
         ssim[blockIdx.x] = m != m ? -1.f : (float)m;                       // utils.py:247-248: a NaN mean counts as -1

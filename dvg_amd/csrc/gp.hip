@@ -192,20 +192,6 @@ __device__ void block_cholesky(T* A, int n, int ld, int tid) {
     }
 }
 
-template <int NT, typename T>
-__device__ __forceinline__ T block_sum(T v, T* scratch, int tid) {
-    // NT threads; scratch >= NT / 64 floats; fixed summation order
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    __syncthreads();
-    if ((tid & 63) == 0) scratch[tid >> 6] = v;
-    __syncthreads();
-    T t = T(0.);
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) t += scratch[w];
-    return t;
-}
-
 // Blocked forward substitution L X = R in place (R = X [M][ncol], row stride LB; L lower, row stride LM): per block of 8
 // rows one thread per column solves the 8x8 triangle, then all 256 threads subtract the block's contribution from the
 // rows below.  One thread per column walking all M rows serially took 49 K cycles (M = 40, 65 columns).
@@ -392,7 +378,7 @@ __global__ __launch_bounds__(NT) void gp_predict_kernel(const GpParams p) {
             part -= T(2.) * log_t(L[i * LM + i]);
             part -= T(2.) * log_t(abs_t(Ls[i * LM + i]));
         }
-        const T tot = block_sum<NT, T>(part, red, tid);
+        const T tot = block_sum<NT>(part, red);
         if (tid < ns) p.kl[d + tid * p.Dp] = T(0.5) * (tot - (T)M);    // the same value for every step of the workgroup
     }
 
@@ -753,10 +739,10 @@ __global__ __launch_bounds__(NT) void gp_train_bwd_kernel(const GpBwdParams p) {
         p.dz[(size_t)wg * M + i] = acc * il2;
     }
     GP_STAMP(8)
-    const T ds_tot = block_sum<NT, T>(ds_acc, red, tid);
-    const T dl_tot = block_sum<NT, T>(dl_acc, red, tid);
-    const T dc_tot = block_sum<NT, T>(dc_part, red, tid);
-    const T dsdir_tot = block_sum<NT, T>(ds_part, red, tid);
+    const T ds_tot = block_sum<NT>(ds_acc, red);
+    const T dl_tot = block_sum<NT>(dl_acc, red);
+    const T dc_tot = block_sum<NT>(dc_part, red);
+    const T dsdir_tot = block_sum<NT>(ds_part, red);
     if (tid == 0) {
         p.ds[wg] = ds_tot / s + dsdir_tot;
         p.dell[wg] = dl_tot * il3;
@@ -793,7 +779,7 @@ __global__ __launch_bounds__(256) void gp_elbo_kernel(const GpElboParams p) {
         const float r = p.target[d * p.t_sd + b * p.t_sb] - p.mean[(size_t)d * B + b];
         acc += fmaf(r, r, p.var[(size_t)d * B + b]);
     }
-    const float tot = block_sum<256, float>(acc, red, tid);     // fixed order: deterministic
+    const float tot = block_sum<256>(acc, red);     // fixed order: deterministic
     if (!BWD) {
         if (tid == 0)
             p.elbo[d] = -0.5f * tot / (nz * (float)B) - 0.5f * logf(nz) - 0.9189385332046727f - p.kl[d] * p.inv_num_data;

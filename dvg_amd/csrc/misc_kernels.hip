@@ -264,13 +264,6 @@ __global__ void bn_act_pool_kernel(const float* __restrict__ u, const float* __r
     }
 }
 
-static inline unsigned grid_for(long n, int block = 256, int cap = 2048) {
-    long g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (unsigned)g;
-}
-
 
 // ------------------------------------------------------------------------------------
 // eval_frames: SSIM and PSNR of one predicted channel image against its ground truth, as utils.eval_seq
@@ -286,7 +279,7 @@ __global__ __launch_bounds__(256) void eval_frames_kernel(const float* __restric
     extern __shared__ __attribute__((aligned(16))) float img[];   // [2][H*W]
     float* X = img;
     float* Y = img + H * W;
-    __shared__ double red[3 * 4];
+    __shared__ double red[2 * 4];
     __shared__ float redmin[4];
     const size_t base = (size_t)blockIdx.x * H * W;
     double se = 0.0;
@@ -323,21 +316,12 @@ __global__ __launch_bounds__(256) void eval_frames_kernel(const float* __restric
         ssum += ((2.0 * ux * uy + C1) * (2.0 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2));
     }
     // workgroup reduction (fixed order)
-    for (int off = 32; off > 0; off >>= 1) {
-        ssum += __shfl_xor(ssum, off);
-        se += __shfl_xor(se, off);
-        mn = fminf(mn, __shfl_xor(mn, off));
-    }
-    const int wave = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) {
-        red[wave] = ssum;
-        red[4 + wave] = se;
-        redmin[wave] = mn;
-    }
-    __syncthreads();
+    mn = wave_min(mn);
+    if ((threadIdx.x & 63) == 0) redmin[threadIdx.x >> 6] = mn;
+    double sums[2] = {ssum, se};
+    block_sum<256, SUM_PAIRWISE>(sums, red);             // its barriers publish redmin as well
     if (threadIdx.x == 0) {
-        const double s = (red[0] + red[1]) + (red[2] + red[3]);
-        const double e = (red[4] + red[5]) + (red[6] + red[7]);
+        const double s = sums[0], e = sums[1];
         const float m = fminf(fminf(redmin[0], redmin[1]), fminf(redmin[2], redmin[3]));
         ssim[blockIdx.x] = (float)(s / ((double)Ho * Wo));
         const double range = m >= 0.f ? 1.0 : 2.0;
@@ -385,8 +369,7 @@ __global__ __launch_bounds__(64) void gp_var_norms_kernel(const float* __restric
         const double v = (double)var[(size_t)d * B + b];
         s += v * v;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+    s = wave_sum(s);
     if (lane == 0) norms[b] = (float)sqrt(s);
 }
 
@@ -404,16 +387,14 @@ __global__ __launch_bounds__(64) void gp_var_norms_kernel(const float* __restric
 // the slid window's statistics and the decision, one wave: lane i < W holds window element w; returns value > threshold
 __device__ __forceinline__ bool trigger_window_decide(int lane, float w, int W, float coef, float value, float& thr_out) {
     double m = lane < W ? (double)w : 0.0;
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) m += __shfl_xor(m, o);
+    m = wave_sum(m);
     const float mean = (float)(m / W);
     double q = 0.0;
     if (lane < W) {
         const float dlt = w - mean;                      // float32 like `x - x.mean()` on a float32 array
         q = (double)dlt * (double)dlt;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) q += __shfl_xor(q, o);
+    q = wave_sum(q);
     const float sd = (float)sqrt((double)(float)(q / W));
     thr_out = mean + coef * sd;                          // float32 product, float32 sum (NumPy 2 scalar promotion)
     return value > thr_out;
@@ -428,8 +409,7 @@ __global__ __launch_bounds__(64) void gp_trigger_step_kernel(const float* __rest
         const double v = (double)var[(size_t)d * B + col];
         s += v * v;
     }
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+    s = wave_sum(s);
     const float value = (float)sqrt(s);
     // the slid window: lane i holds element i
     float w = 0.f;
@@ -507,7 +487,7 @@ template <int K>
 __global__ __launch_bounds__(256) void frame_losses_kernel(const float* __restrict__ pred, const float* __restrict__ target,
                                                            float* __restrict__ dpred, float* __restrict__ partial, long n4, int S,
                                                            const float* __restrict__ w) {
-    __shared__ float red[4][K];
+    __shared__ float red[K * 4];
     const long total = (long)S * n4;
     float acc[K];
     float w2[K];
@@ -530,16 +510,11 @@ __global__ __launch_bounds__(256) void frame_losses_kernel(const float* __restri
             reinterpret_cast<f32x4*>(dpred)[j] = g;
         }
     }
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    block_sum<256, SUM_PAIRWISE>(acc, red);
+    if (threadIdx.x == 0) {
 #pragma unroll
-    for (int k = 0; k < K; ++k) {
-        float v = acc[k];
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-        if (lane == 0) red[wave][k] = v;
+        for (int k = 0; k < K; ++k) partial[(size_t)blockIdx.x * K + k] = acc[k];
     }
-    __syncthreads();
-    if (threadIdx.x < K) partial[(size_t)blockIdx.x * K + threadIdx.x] = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
 }
 
 __global__ __launch_bounds__(256) void frame_losses_finish_kernel(const float* __restrict__ partial, int blocks, int K,
@@ -601,7 +576,7 @@ extern "C" long dvg_stream_capture_id(void* stream) {
         DVG_REQUIRE(src && dst, DVG_ERR_NULL, #NAME ": NULL pointer");                                          \
         DVG_REQUIRE(cout > 0 && cin > 0 && kh > 0 && kw > 0, DVG_ERR_SHAPE, #NAME ": bad shape");               \
         const long total = (long)cout * cin * kh * kw;                                                          \
-        hipLaunchKernelGGL((pack_weight_kernel<TR, UN>), dim3(grid_for(total)), dim3(256), 0, (hipStream_t)stream, \
+        hipLaunchKernelGGL((pack_weight_kernel<TR, UN>), dim3(grid_for(total, 256, 2048)), dim3(256), 0, (hipStream_t)stream, \
                            src, dst, cout, cin, kh, kw);                                                        \
         return check_launch(#NAME);                                                                             \
     }

@@ -160,13 +160,6 @@ __global__ __launch_bounds__(256) void frame_mosaic_kernel(MosaicArgs a, unsigne
     }
 }
 
-static inline unsigned grid_for(long n, int block = 256, int cap = 2048) {
-    long g = (n + block - 1) / block;
-    if (g < 1) g = 1;
-    if (g > cap) g = cap;
-    return (unsigned)g;
-}
-
 }  // namespace dvg
 
 using namespace dvg;
@@ -211,7 +204,7 @@ extern "C" int dvg_frame_mosaic(const float* src0, long n0, const float* src1, l
     a.GH = (unsigned)GH, a.GW = (unsigned)GW;
     const long n_pix = (long)F * GH * GW;
     // grid sized to the chip: 256 CUs x 8 workgroups of 256 threads, a grid-stride loop over the rest
-    hipLaunchKernelGGL(frame_mosaic_kernel, dim3(grid_for((n_pix + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a,
+    hipLaunchKernelGGL(frame_mosaic_kernel, dim3(grid_for((n_pix + 3) / 4, 256, 2048)), dim3(256), 0, (hipStream_t)stream, a,
                        (unsigned)n_pix);
     return check_launch("dvg_frame_mosaic");
 }

@@ -40,8 +40,8 @@ from .gp import (  # noqa: F401
 )
 from .backward import (  # noqa: F401
     _LOSS_W, frame_losses, mse_sum_grad, conv_wgrad_partial, conv_wgrad_partial_multi, winograd_wgrad_ok,
-    winograd_wgrad_partial_multi, wgrad_finish, k4_to_w3, conv_wgrad, wgrad_thin, act_bwd, upsample2x_bwd,
+    winograd_wgrad_partial_multi, wgrad_finish, k4_to_w3, conv_wgrad, wgrad_thin, act_bwd, upsample2x_bwd, adam_step, adam_step_guarded,
 )
-from .guard import grad_sumsq_blocks, grad_sumsq, grad_guard_finish, adam_step_guarded  # noqa: F401
+from .guard import grad_sumsq_blocks, grad_sumsq, grad_guard_finish  # noqa: F401
 from .ema import ema_update_blocks, ema_update  # noqa: F401
 from .._lib import check, lib  # noqa: F401

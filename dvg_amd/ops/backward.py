@@ -1,5 +1,5 @@
 """Training-only wrappers: fused frame losses, weight gradients (dense, multi-use, Winograd form), their finishing
-kernels, activation / upsampling backward."""
+kernels, activation / upsampling backward, the Adam step."""
 from __future__ import annotations
 
 import torch
@@ -246,3 +246,30 @@ def upsample2x_bwd(dxu):
     dx = nhwc_empty(n, c, h2 // 2, w2 // 2, dxu.device)
     check(lib().dvg_upsample2x_bwd(_p(dxu), _p(dx), n, h2 // 2, w2 // 2, c, _stream()), "upsample2x_bwd")
     return dx
+
+
+def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, step_dev, stat=None, skips_dev=None) -> None:
+    """One Adam step over the buffers p, g, m, v (a flat group, or one parameter's views of it); `step_dev`: the device-side
+    step count, None = `step`.  With `stat` (a GradGuard's 4 floats) and `skips_dev` (one device int) the guarded form,
+    dvg_adam_step_guarded: the gradient times stat[1], nothing when stat[2] != 0 (then skips_dev is advanced); without them
+    dvg_adam_step."""
+    guarded = stat is not None or skips_dev is not None
+    name = "adam_step_guarded" if guarded else "adam_step"
+    for which, t in (("p", p), ("g", g), ("m", m), ("v", v)):
+        _dev_f32(t, f"{name}.{which}")
+        if not t.is_contiguous() or t.numel() != p.numel() or t.device != p.device:
+            raise RuntimeError(f"{name}: {which} must be contiguous, on p's device and of p's size")
+    stat_ok = not guarded or (stat is not None and skips_dev is not None and stat.dtype == torch.float32 and stat.numel() == 4
+                              and stat.device == p.device and stat.is_contiguous())
+    ints = [t for t in (step_dev, skips_dev) if t is not None]
+    if not stat_ok or any(t.dtype != torch.int32 or t.numel() != 1 or t.device != p.device for t in ints):
+        raise RuntimeError(f"{name}: 4 fp32 stat values and one-element int32 counters on p's device expected")
+    args = (_p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
+            int(step), _p(step_dev))
+    if guarded:
+        check(lib().dvg_adam_step_guarded(*args, _p(stat), _p(skips_dev), _stream()), name)
+    else:
+        check(lib().dvg_adam_step(*args, _stream()), name)
+
+
+adam_step_guarded = adam_step    # the name tools and tests call the guarded form by

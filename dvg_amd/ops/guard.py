@@ -1,6 +1,6 @@
 """Wrappers of the gradient-guard entry points (grad_guard.hip): the fp64 sum of squares of a flat gradient range in fixed
-chunks, the one-workgroup decision kernel, and the Adam step that applies its verdict.  dvg_amd/optim.py (GradGuard,
-guarded_step) is the caller."""
+chunks and the one-workgroup decision kernel (the Adam step that applies its verdict: ops.adam_step).  dvg_amd/optim.py
+(GradGuard, guarded_step) is the caller."""
 from __future__ import annotations
 
 import torch
@@ -38,19 +38,3 @@ def grad_guard_finish(partials: torch.Tensor, nblocks: int, max_norm: float, ski
         raise RuntimeError("grad_guard_finish: fp64 partials, 4 fp32 stat values and 3 int32 counters on one GPU expected")
     check(lib().dvg_grad_guard_finish(_p(partials), int(nblocks), float(max_norm), int(bool(skip_nonfinite)), _p(stat),
                                       _p(counters), _stream()), "grad_guard_finish")
-
-
-def adam_step_guarded(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, step_dev, stat, skips_dev) -> None:
-    """dvg_adam_step_guarded over the flat buffers p, g, m, v: the gradient times stat[1], nothing when stat[2] != 0 (then
-    skips_dev, one device int, is advanced); `step_dev`: the device-side step count, None = `step`."""
-    for name, t in (("p", p), ("g", g), ("m", m), ("v", v)):
-        _dev_f32(t, "adam_step_guarded." + name)
-        if not t.is_contiguous() or t.numel() != p.numel() or t.device != p.device:
-            raise RuntimeError(f"adam_step_guarded: {name} must be contiguous, on p's device and of p's size")
-    ints = [skips_dev] if step_dev is None else [skips_dev, step_dev]
-    if (stat.dtype != torch.float32 or stat.numel() != 4 or stat.device != p.device or not stat.is_contiguous()
-            or any(t.dtype != torch.int32 or t.numel() != 1 or t.device != p.device for t in ints)):
-        raise RuntimeError("adam_step_guarded: 4 fp32 stat values and one-element int32 counters on p's device expected")
-    check(lib().dvg_adam_step_guarded(_p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps),
-                                      float(weight_decay), int(step), _p(step_dev), _p(stat), _p(skips_dev), _stream()),
-          "adam_step_guarded")

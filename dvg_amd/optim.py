@@ -279,12 +279,9 @@ class FusedAdam(torch.optim.Optimizer):
             for p, gv in zip(f["params"], f["gviews"]):
                 p.grad = gv
 
-    @torch.no_grad()
-    def guard_spans(self):
-        """What a guarded step of this optimiser is about to apply: (arena or None, lo, hi, flat gradient) per group that has
-        gradients, with every gradient in its flat buffer.  A partially used group raises: the guard's norm is taken over whole
-        flat ranges, and the per-parameter launches of step() have no guarded form."""
-        spans = []
+    def _groups_with_grads(self):
+        """(gi, group, flat record, [parameter has a gradient]) for every group that has gradients; a group whose parameters
+        changed since its flat record was made is rebuilt first."""
         for gi, group in enumerate(self.param_groups):
             f = self._flat.get(gi)
             if f is None or [id(p) for p in f.get("params", [])] != [id(p) for p in group["params"] if p.requires_grad]:
@@ -294,8 +291,16 @@ class FusedAdam(torch.optim.Optimizer):
             if not f:
                 continue
             have = [p.grad is not None for p in f["params"]]
-            if not any(have):
-                continue
+            if any(have):
+                yield gi, group, f, have
+
+    @torch.no_grad()
+    def guard_spans(self):
+        """What a guarded step of this optimiser is about to apply: (arena or None, lo, hi, flat gradient) per group that has
+        gradients, with every gradient in its flat buffer.  A partially used group raises: the guard's norm is taken over whole
+        flat ranges, and the per-parameter launches of step() have no guarded form."""
+        spans = []
+        for gi, group, f, have in self._groups_with_grads():
             if not all(have) or len({int(self.state[p]["step"]) for p in f["params"]}) != 1:
                 raise RuntimeError(f"FusedAdam: group {gi} is partially used (parameters without a gradient, or with different "
                                    "step counts): it cannot be stepped with a gradient guard")
@@ -311,17 +316,7 @@ class FusedAdam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        for gi, group in enumerate(self.param_groups):
-            f = self._flat.get(gi)
-            if f is None or [id(p) for p in f.get("params", [])] != [id(p) for p in group["params"] if p.requires_grad]:
-                if self.arena is not None and f is not None:
-                    raise RuntimeError("FusedAdam: the parameters of an arena-backed group cannot change")
-                f = self._build(gi, group)
-            if not f:
-                continue
-            have = [p.grad is not None for p in f["params"]]
-            if not any(have):
-                continue
+        for gi, group, f, have in self._groups_with_grads():
             b1, b2 = group["betas"]
             hyper = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]))
             steps = {int(self.state[p]["step"]) for p in f["params"]}
@@ -342,11 +337,8 @@ class FusedAdam(torch.optim.Optimizer):
                     f.pop("ticked", None)
                     if gi in self._captured_groups:  # a captured graph holds this group's device count: now behind the host's
                         self._graph_stale = True
-                if guard is None:
-                    check(lib().dvg_adam_step(ops._p(f["p"]), ops._p(f["g"]), ops._p(f["m"]), ops._p(f["v"]),
-                                              f["p"].numel(), *hyper, t, ops._p(tdev), ops._stream()), "dvg_adam_step")
-                else:
-                    ops.adam_step_guarded(f["p"], f["g"], f["m"], f["v"], *hyper, t, tdev, guard.stat, self._skips(f))
+                stat, skips = (None, None) if guard is None else (guard.stat, self._skips(f))
+                ops.adam_step(f["p"], f["g"], f["m"], f["v"], *hyper, t, tdev, stat, skips)
                 touched = f["params"]
                 if capturing:
                     self._captured_groups.append(gi)
@@ -364,9 +356,7 @@ class FusedAdam(torch.optim.Optimizer):
                     st = self.state[p]
                     if p.grad is not gv and p.grad.data_ptr() != gv.data_ptr():
                         gv.copy_(p.grad)
-                    check(lib().dvg_adam_step(ops._p(p), ops._p(gv), ops._p(st["exp_avg"]), ops._p(st["exp_avg_sq"]),
-                                              p.numel(), *hyper, int(st["step"]) + 1, None, ops._stream()),
-                          "dvg_adam_step")
+                    ops.adam_step(p, gv, st["exp_avg"], st["exp_avg_sq"], *hyper, int(st["step"]) + 1, None)
             for p in touched:
                 # the kernel wrote through raw pointers; also while capturing, so that code captured AFTER this step
                 # re-packs its weights instead of reusing the packs from before the step
@@ -411,7 +401,7 @@ def zero_grads(optimizers) -> None:
 
 class GradGuard:
     """Gradient-norm clipping and the skip of a non-finite step, decided on the device (train.py --clip_grad_norm /
-    --skip_nonfinite; docs/DESIGN_NOTES_gradguard.md).  Owns the three device buffers the kernels of grad_guard.hip share:
+    --skip_nonfinite; docs/DESIGN_NOTES_gradguard.md).  Owns the three device buffers the guard's kernels share:
 
       partials  fp64 partial sums of squares (dvg_grad_sumsq), sized on first use
       stat      4 floats: norm of the last step site, its clip factor, its skip flag, the largest finite norm since the last read
