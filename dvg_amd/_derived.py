@@ -85,6 +85,19 @@ def drop_derived() -> None:
     _store.clear()
 
 
+def derived_mark() -> dict:
+    """What `derived` holds now, entry by entry (the tensors are referenced, not copied): for derived_restore."""
+    return {k: (ref, dict(slot)) for k, (ref, slot) in _store.items()}
+
+
+def derived_restore(mark: dict) -> None:
+    """Make `derived` hold what it held at `mark` again: entries built since are forgotten, entries replaced since come back.
+    For a pass that must leave no trace while the parameters stay what they are (validate.Validator.run): every entry that
+    comes back is as valid for its key as it was at the mark."""
+    _store.clear()
+    _store.update({k: (ref, dict(slot)) for k, (ref, slot) in mark.items() if ref() is not None})
+
+
 def _forget(ref, key):
     if key in _store and _store[key][0] is ref:        # (the id may already belong to a new owner)
         del _store[key]

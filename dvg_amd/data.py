@@ -253,7 +253,7 @@ def make_batch_generator(opt, seq_len, seed, device=None, train=True):
 def _clip_batches(opt, seq_len, seed, device, train):
     index = datasets.open_index(opt.dataset, opt.data_root, train, opt.image_width)
     sampler = datasets.make_sampler(index, seq_len, seed)
-    pool = datasets.build_pool(index, opt.image_width, device, getattr(opt, 'data_threads', 5))
+    pool = datasets.shared_pool(index, opt.data_root, opt.image_width, device, getattr(opt, 'data_threads', 5))
     if opt.channels != pool.shape[3] and not (opt.channels == 1 and pool.shape[3] == 3):
         raise SystemExit(f"dataset: --channels {opt.channels} from {opt.dataset} frames of {pool.shape[3]} channel(s) under "
                          f"{opt.data_root!r}")

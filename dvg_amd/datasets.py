@@ -327,6 +327,21 @@ def _pool_channels(path):
         raise SystemExit(f"dataset: cannot read {path!r}: {e}")
 
 
+_pools = {}     # (dataset, root, split, width, device) -> the pool build_pool made: the streams of one split share it
+
+
+def shared_pool(index, root, image_width, device=None, threads=5):
+    """build_pool(index, ...), once per (dataset, root, split, width, device) and process: train.py's test stream and its
+    validation stream (--val_every) read the test split from ONE frame pool.  The pool is read only."""
+    dev = torch.device(device) if device is not None else torch.device('cpu')
+    if dev.type == 'cuda' and dev.index is None:
+        dev = torch.device('cuda', torch.cuda.current_device())
+    key = (index.dataset, os.path.abspath(root), index.split, int(image_width), str(dev))
+    if key not in _pools:
+        _pools[key] = build_pool(index, image_width, dev, threads)
+    return _pools[key]
+
+
 def build_pool(index, image_width, device=None, threads=5):
     """(n_frames, S, S, pool_c) uint8: every frame of `index`, sequence after sequence (sequence i starts at index.bases[i]).
     Decoded with Pillow on min(threads, 16) threads.  For a GPU `device` the frames are decoded into a pinned staging

@@ -226,6 +226,9 @@ def capture(tr, epoch=0, train_gen=None, test_gen=None, shared=True) -> dict:
         if ema is not None:      # --ema_decay: the average and its count of updates (dvg_amd/ema.py); no key without the flag
             st = ema.state()
             sd["arena"]["e"], sd["ema"] = st["e"], st["ema"]
+        val = getattr(tr, "validation", None)
+        if val is not None:      # --val_every: the history and the best scores (dvg_amd/validate.py); no key without the flag
+            sd["validation"] = val.state()
     return sd
 
 
@@ -248,6 +251,11 @@ def restore(tr, sd, train_gen=None, test_gen=None, path="<state>") -> int:
             print(f"{path}: no weight average in the file: --ema_decay restarts it from the restored weights", flush=True)
     elif "e" in saved and tr.rank == 0:
         print(f"{path}: the weight average in the file is ignored: this run has no --ema_decay", flush=True)
+    val = getattr(tr, "validation", None)
+    if val is not None:          # a state without validations starts an empty history
+        val.load_state(sd.get("validation"))
+    elif "validation" in sd and tr.rank == 0 and not getattr(tr.opt, "val_every", 0):
+        print(f"{path}: the validation history in the file is ignored: this run has no --val_every", flush=True)
     for name, o in named_optimizers(tr):
         o.load_host_state(sd["optimizers"][name])      # step counts (begin_capture seeds the device counts from them), lr
     tr.scheduler.load_state_dict(sd["scheduler"])

@@ -68,6 +68,8 @@ def build_parser():
     p.add_argument('--synthetic_ckpt', action='store_true')
     p.add_argument('--ema', action='store_true',
                    help='load the averaged weights: <model_dir>/<dataset>_ema.pth, else <model_dir>/model_ema.pth (train.py --ema_decay)')
+    p.add_argument('--best', action='store_true',
+                   help='load the best checkpoint of train.py --val_every: <model_dir>/model_best.pth, with --ema model_ema_best.pth')
     p.add_argument('--inflight', type=int, default=3,
                    help='make_gifs: samples of a batch drawn at once (one hipGraph + stream each); 0 = eager loop, one at a time')
     p.add_argument('--no_share_prefix', action='store_true',
@@ -369,7 +371,10 @@ def main(argv=None):
         opt = args
     else:
         path = '%s/%s.pth' % (args.model_dir, args.dataset)
-        if args.ema:      # the averaged weights train.py --ema_decay wrote (same container); a missing file is a one-line exit
+        if args.best:     # the checkpoint train.py --val_every kept (dvg_amd/validate.py); a missing file is a one-line exit
+            from dvg_amd.validate import best_checkpoint_path
+            path = best_checkpoint_path(args.model_dir, args.ema)
+        elif args.ema:    # the averaged weights train.py --ema_decay wrote (same container); a missing file is a one-line exit
             from dvg_amd.ema import checkpoint_path
             path = checkpoint_path(args.model_dir, args.dataset)
         elif not os.path.exists(path):

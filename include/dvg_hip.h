@@ -327,7 +327,6 @@ int dvg_bn_act_apply(const float* u, const float* scale, const float* shift, flo
 /* ------------------------------------------------------------------ *
  * Dense ends and the recurrent predictor
  * ------------------------------------------------------------------ */
-
 /* out[m][n] = act( (sum_k a[m][k]*w[n][k]) * scale[n % period] + shift[n % period] )
  * Small-M GEMM used for: encoder head Conv2d(512,dim,4,1,0)+BN+Tanh on the 4x4
  * map (vgg_64.py:44-48; K = 8192), decoder stem ConvTranspose2d(dim,512,4,1,0)
@@ -335,10 +334,9 @@ int dvg_bn_act_apply(const float* u, const float* scale, const float* shift, flo
  * 53-55.  a [M][K] (row stride lda), w [N][K], out [M][N] (row stride ldo).
  * scale/shift may be NULL.  `workspace` must hold M*N*splitk floats when
  * splitk > 1 (NULL allowed when splitk == 1).                                  */
-int dvg_gemm_nt_bias_act(const float* a, const float* w, const float* scale,
-                         const float* shift, float* out, float* workspace, int M,
-                         int N, int K, int lda, int ldo, int period, int splitk,
-                         int act, float slope, int accumulate /* out += result */, void* stream);
+int dvg_gemm_nt_bias_act(const float* a, const float* w, const float* scale, const float* shift, float* out, float* workspace,
+                         int M, int N, int K, int lda, int ldo, int period, int splitk, int act, float slope,
+                         int accumulate /* out += result */, void* stream);
 
 /* One nn.LSTMCell step (lstm.py:51,68-70; gate order i,f,g,o):
  *   g = W_ih x + b_ih + W_hh h + b_hh ; c' = sig(f)*c + sig(i)*tanh(g~) ;
@@ -347,10 +345,8 @@ int dvg_gemm_nt_bias_act(const float* a, const float* w, const float* scale,
  * In-place state update (h_out == h, c_out == c) is NOT allowed (every
  * workgroup reads all of h).  gates_out (optional, [B][4H]) receives the
  * post-activation gates (i,f,g~,o) for the backward pass.  H % 64 == 0.       */
-int dvg_lstm_cell(const float* x, const float* h, const float* c, const float* w_ih,
-                  const float* w_hh, const float* b_ih, const float* b_hh,
-                  float* h_out, float* c_out, float* gates_out, int B, int H,
-                  void* stream);
+int dvg_lstm_cell(const float* x, const float* h, const float* c, const float* w_ih, const float* w_hh, const float* b_ih,
+                  const float* b_hh, float* h_out, float* c_out, float* gates_out, int B, int H, void* stream);
 
 /* Teacher-forced training (train.py:213-222: every step of a closure feeds the encoding of a GROUND-TRUTH frame to the
  * predictor, so the inputs of all S steps exist before the recurrence starts).  r04: the input halves of both cells, the
@@ -665,31 +661,28 @@ int dvg_frame_mosaic(const float* src0, long n0, const float* src1, long n1, con
 int dvg_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1,
                   float beta2, float eps, float weight_decay, int step, const int* step_dev, void* stream);
 
-/* nn.LSTMCell backward, elementwise part: gate pre-activation gradients dG [B][4H] and
- * dc_prev [B][H] from dh', dc' (either may be NULL), the saved activated gates, c, c'.
- * The GEMM parts (dx = dG W_ih, dW_ih = dG^T x, ...) go through dvg_gemm_nt_bias_act. */
+/* nn.LSTMCell backward, elementwise part: gate pre-activation gradients dG [B][4H] and dc_prev [B][H] from dh', dc' (either may
+ * be NULL), the saved activated gates, c, c'.  The GEMM parts (dx = dG W_ih, dW_ih = dG^T x, ...) go through dvg_gemm_nt_bias_act. */
 /* out[m][n] (+)= sum_r a[r][m] b[r][n] (a [R][M], b [R][N], row strides lda / ldb / ldo): dW = dY^T X of nn.Linear / nn.LSTMCell
  * (lstm.py:50-55) over the R = steps x batch rows of a BPTT pass in ONE launch, no transposed copies; colsum0 / colsum1
  * (NULL = none) receive the column sums of a - the bias gradient(s) - overwritten or, colsum_accumulate, added to.  ABI 8. */
 int dvg_gemm_tn(const float* a, const float* b, float* out, float* colsum0, float* colsum1, int R, int M, int N,
                 int lda, int ldb, int ldo, int accumulate, int colsum_accumulate, void* stream);
-int dvg_lstm_gates_bwd(const float* dh, const float* dc, const float* gates, const float* c_prev,
-                       const float* c_new, float* dG, float* dc_prev, int B, int H, void* stream);
+int dvg_lstm_gates_bwd(const float* dh, const float* dc, const float* gates, const float* c_prev, const float* c_new, float* dG,
+                       float* dc_prev, int B, int H, void* stream);
 
-/* Train-mode GP backward (gradients of dvg_gp_predict(train_mode=1) outputs mean / var
- * (without likelihood noise) / kl): upstream gmean [D][B], gvar [D][B], gkl [D] (any may
- * be NULL = zero) -> dh [B][D], dz [D][M], dm [D][M], dls [D][M][M] (lower), dc, ds, dell
- * [D] w.r.t. the soft-plus'ed hyper-parameters.  One workgroup per latent dim, all in LDS.  fp64 inside, fp32 I/O
+/* Train-mode GP backward (gradients of dvg_gp_predict(train_mode=1) outputs mean / var (without likelihood noise) / kl): upstream
+ * gmean [D][B], gvar [D][B], gkl [D] (any may be NULL = zero) -> dh [B][D], dz [D][M], dm [D][M], dls [D][M][M] (lower), dc, ds,
+ * dell [D] w.r.t. the soft-plus'ed hyper-parameters.  One workgroup per latent dim, all in LDS.  fp64 inside, fp32 I/O
  * (ABI 6).  r04: the data points are processed in chunks of dvg_gp_bwd_chunk(B, M) so that the fp64 working set fits the
  * 160 KB of LDS for every B <= 128 at M <= 40 (M = 40: one pass up to B = 71, two chunks of 64 at B = 128; until r03 B > 71
  * fell back to fp32 arithmetic); dvg_gp_bwd_precision still returns 32 where not even small chunks fit (M = 64, B > 40). */
 int dvg_gp_bwd_precision(int B, int M);
 size_t dvg_gp_bwd_lds_bytes(int B, int M);
 int dvg_gp_bwd_chunk(int B, int M);
-int dvg_gp_train_bwd(const float* h, const float* z, const float* var_mean, const float* chol_var,
-                     const float* mean_const, const float* outputscale, const float* lengthscale,
-                     const float* gmean, const float* gvar, const float* gkl, float* dh, float* dz,
-                     float* dm, float* dls, float* dc, float* ds, float* dell, int B, int D, int M,
+int dvg_gp_train_bwd(const float* h, const float* z, const float* var_mean, const float* chol_var, const float* mean_const,
+                     const float* outputscale, const float* lengthscale, const float* gmean, const float* gvar, const float* gkl,
+                     float* dh, float* dz, float* dm, float* dls, float* dc, float* ds, float* dell, int B, int D, int M,
                      float jitter, int param_period /* ABI 8, as dvg_gp_predict */,
                      int step_group /* ABI 8, as dvg_gp_predict.  The PARAMETER gradients are written per workgroup:
                                        dz, dm [G * P][M], dls [G * P][M][M], dc, ds, dell [G * P] with P = param_period (or D)
@@ -711,17 +704,14 @@ int dvg_sum_steps_multi(const float* const* src, float* const* dst, const long* 
 int dvg_gp_elbo(const float* mean, const float* var, const float* kl, const float* target, long t_stride_d,
                 long t_stride_b, const float* raw_noise, float* elbo, int B, int D, int num_data,
                 int noise_period /* ABI 8; 0 = D: workgroup d reads raw_noise[d % noise_period] */, void* stream);
-int dvg_gp_elbo_bwd(const float* mean, const float* var, const float* kl, const float* target, long t_stride_d,
-                    long t_stride_b, const float* raw_noise, const float* gelbo, float* gmean, float* gvar,
-                    float* gkl, float* gtarget, float* graw_noise, int B, int D, int num_data, int noise_period,
-                    void* stream);
+int dvg_gp_elbo_bwd(const float* mean, const float* var, const float* kl, const float* target, long t_stride_d, long t_stride_b,
+                    const float* raw_noise, const float* gelbo, float* gmean, float* gvar, float* gkl, float* gtarget,
+                    float* graw_noise, int B, int D, int num_data, int noise_period, void* stream);
 
 /* ------------------------------------------------------------------ *
  * Small elementwise helpers on the path
  * ------------------------------------------------------------------ */
-
-/* (N,C,H,W) contiguous -> NHWC and back (skip tensors handed to / taken from
- * callers that insist on contiguous NCHW).                                    */
+/* (N,C,H,W) contiguous -> NHWC and back (skip tensors handed to / taken from callers that insist on contiguous NCHW). */
 int dvg_nchw_to_nhwc(const float* x, float* y, int N, int C, int H, int W, void* stream);
 int dvg_nhwc_to_nchw(const float* x, float* y, int N, int C, int H, int W, void* stream);
 
@@ -793,6 +783,16 @@ int dvg_adam_step_guarded(float* param, const float* grad, float* exp_avg, float
  * fp64, fixed order; dvg_ema_update_blocks(n) pairs.  n % 4 == 0, 16-byte aligned, ema != param, decay in [0, 1).  Within ABI 9. */
 int dvg_ema_update_blocks(long n);
 int dvg_ema_update(float* ema, const float* param, long n, double decay, const int* updates_dev, double* partials, void* stream);
+
+/* The reduction of a validation pass (train.py --val_every here; docs/DESIGN_NOTES_validation.md).  No reference counterpart: its
+ * train.py scores nothing.  ssim / psnr / mse: (B, S, T) fp32, the layout make_gifs fills (batch row, sample, predicted step).
+ * best[b] (int[B], may be NULL) = the sample with the largest fp64 sum over t, from 0.0 with t ascending, of ssim[b, s, t]: a NaN sum
+ * loses, ties go to the lowest s, all NaN gives 0.  acc (double[2][3][T][2]: track, metric ssim / psnr / mse, step, {sum, sum of
+ * squares}) and cnt (long long[2][3][T]) are ADDED to, K batches = K launches: track 0 takes v = metric[b, best[b], t] if finite,
+ * track 1 the fp64 mean u over the finite metric[b, s, t], s ascending, if there is one.  fp64, fixed order, no atomics; the result
+ * does not depend on the launch.  B, S, T >= 1, B*S*T < 2^31; no allocation.  An addition within ABI 9. */
+int dvg_val_accumulate(const float* ssim, const float* psnr, const float* mse, int B, int S, int T, double* acc, long long* cnt,
+                       int* best, void* stream);
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,8 @@ model" section, :86, is empty and `--model_dir` is never read: both kept); dvg_a
 graph, and writes `model_ema.pth` beside `model.pth` (dvg_amd/ema.py, docs/DESIGN_NOTES_ema.md).
 `--augment LIST` (kth | bair | ucf, train split): flip / reverse / shift / jitter per clip, applied inside the gather
 (dvg_clip_gather_aug_u8; dvg_amd/datasets.py ClipAugmenter, docs/DESIGN_NOTES_augment.md).
+`--val_every N` scores a fixed set of held-out clips every N epochs on rank 0 (eval-mode rollouts, Finn metrics, dvg_val_accumulate),
+logs them to `val_log.jsonl` and keeps `model_best.pth` (dvg_amd/validate.py, docs/DESIGN_NOTES_validation.md).
 """
 import argparse
 import importlib
@@ -49,7 +51,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 import utils  # noqa: E402
-from dvg_amd import datasets, ema as weight_ema, fused, parallel, train_state, viz  # noqa: E402
+from dvg_amd import datasets, ema as weight_ema, fused, parallel, train_state, validate, viz  # noqa: E402
 from dvg_amd.data import SyntheticMovingMNIST, make_batch_generator, synthetic_video  # noqa: E402,F401
 from dvg_amd.models.gp_models import GaussianLikelihood, GPRegressionLayer1, VariationalELBO  # noqa: E402
 from dvg_amd.optim import FlatArena, FusedAdam, guard_options, guarded_step, make_guard, zero_grads  # noqa: E402,F401
@@ -114,8 +116,8 @@ def build_parser():
                         'min(1, C / (norm + 1e-6)) of torch\'s clip_grad_norm_; decided on the device, also in a hipGraph (0 = off)')
     p.add_argument('--skip_nonfinite', action='store_true',
                    help='skip such a step when a gradient is Inf or NaN: no parameter, Adam moment or step count changes')
-    weight_ema.add_arguments(p)   # --ema_decay
-    datasets.add_arguments(p)     # --augment
+    for mod in (weight_ema, datasets, validate):   # --ema_decay, --augment, --val_every / --val_batches / --val_nsample
+        mod.add_arguments(p)
     return p
 
 
@@ -207,6 +209,7 @@ class Trainer:
         self.guard = make_guard(opt, device, self.optimizers())
         # --ema_decay: an averaged copy of arena.p (after the broadcast above), moved once per iteration; None = nothing exists
         self.ema = weight_ema.make_average(opt, self.arena)
+        self.validation = validate.make(opt, device)   # --val_every, rank 0: the held-out stream and the history; else None
 
     def _step(self, optimizers):
         """A step site: the optimisers that step together after one backward pass (with several ranks: after the all-reduce
@@ -733,8 +736,7 @@ def main(argv=None):
     torch.cuda.set_device(local)
     device = torch.device('cuda', local)
     torch.cuda.manual_seed_all(opt.seed)
-    if rank == 0:
-        print(opt)
+    rank == 0 and print(opt)
     tr = Trainer(opt, device)
     torch.manual_seed(opt.seed + 1000 * rank)   # from here on: per-rank randomness (GP samples)
     train_gen = BatchPrefetcher(make_batch_generator(opt, opt.n_past + opt.n_future, opt.seed + 17 * rank, device))
@@ -754,8 +756,7 @@ def main(argv=None):
         tr.train_mode()
         tr.scheduler.step()   # before the epoch, as train.py:347
         epoch_mse = 0.0
-        t0 = time.time()
-        indices = 0.0
+        t0, indices = time.time(), 0.0
         for i in range(opt.epoch_size):
             x = next(train_gen)()
             mse_ctrl, indices, temp_loss = step(x)
@@ -783,10 +784,10 @@ def main(argv=None):
                 tr.save('%s/model.pth' % opt.output_path)
                 tr.ema is None or tr.ema.save(tr, '%s/%s' % (opt.output_path, weight_ema.FILE))   # model_ema.pth
                 opt.no_images or tr.write_plot(test_x, gen, best, epoch, opt.output_path)   # sample_<epoch>.png / .gif
-            if not opt.no_save:   # after everything of this epoch that draws random numbers; rank 0: the shared part as well
-                train_state.write(tr.state_dict(epoch + 1, train_gen, test_gen, shared=rank == 0), opt.output_path, rank, world)
-        if epoch % 10 == 0 and rank == 0:
-            print('log dir: %s' % opt.log_dir)
+        validate.after_epoch(tr, epoch)   # --val_every (rank 0): after the checkpoint, before the state that carries its history
+        if epoch % opt.save_every == 0 and not opt.no_save:   # after all of this epoch that draws random numbers; rank 0: the shared part too
+            train_state.write(tr.state_dict(epoch + 1, train_gen, test_gen, shared=rank == 0), opt.output_path, rank, world)
+        epoch % 10 == 0 and rank == 0 and print('log dir: %s' % opt.log_dir)
     if opt.print_param_checksum:   # tests: every rank must end with the same parameters
         weight_ema.print_checksums(tr, rank)
     if world > 1:
