@@ -585,10 +585,10 @@ struct AdamCoef {
     float b1, b2, eps, wd, lr_over_bc1, inv_sqrt_bc2;
 };
 
-// the coefficients of step t (t >= 1: the steps really applied)
-__device__ __forceinline__ AdamCoef adam_coef(float lr, float b1, float b2, float eps, float wd, int t) {
+// the coefficients of step t (t >= 1: the steps really applied); lr: the rate of the launch, already in fp64
+__device__ __forceinline__ AdamCoef adam_coef(double lr, float b1, float b2, float eps, float wd, int t) {
     const double bc1 = 1.0 - pow((double)b1, (double)t), bc2 = 1.0 - pow((double)b2, (double)t);
-    return {b1, b2, eps, wd, (float)((double)lr / bc1), (float)(1.0 / sqrt(bc2))};
+    return {b1, b2, eps, wd, (float)(lr / bc1), (float)(1.0 / sqrt(bc2))};
 }
 
 // One element - p[e], m[e], v[e] of a 16-byte piece held in registers, or of the arrays themselves (the tail): the ONLY place
@@ -609,25 +609,32 @@ __device__ __forceinline__ float gg_mul_rn(float a, float b) {
     return a * b;
 }
 
-__global__ void adam_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                 float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
-                                 const int* __restrict__ step_dev, int step_host) {
-    // the step count may live in device memory (a captured hipGraph replays with a fresh count every iteration)
-    const AdamCoef c = adam_coef(lr, b1, b2, eps, wd, step_dev ? *step_dev : step_host);
+// The grid-stride loop over the 16-byte pieces and the tail, of all three Adam kernels: the ONLY place the sweep is written.
+// SCALED: the gradient times `scale` as it is read, the product rounded on its own; else the gradient as it is.
+template <bool SCALED>
+__device__ __forceinline__ void adam_sweep(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                           float* __restrict__ v, long n, const AdamCoef& c, float scale) {
     const long n4 = n >> 2;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
         f32x4 pv = reinterpret_cast<f32x4*>(p)[i], mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
         const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
 #pragma unroll
-        for (int e = 0; e < 4; ++e) adam_element(pv, gv[e], mv, vv, c, e);
+        for (int e = 0; e < 4; ++e) adam_element(pv, SCALED ? gg_mul_rn(gv[e], scale) : gv[e], mv, vv, c, e);
         reinterpret_cast<f32x4*>(p)[i] = pv;
         reinterpret_cast<f32x4*>(m)[i] = mv;
         reinterpret_cast<f32x4*>(v)[i] = vv;
     }
     if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {   // tail
         const long i = (n4 << 2) + threadIdx.x;
-        adam_element(p, g[i], m, v, c, i);
+        adam_element(p, SCALED ? gg_mul_rn(g[i], scale) : g[i], m, v, c, i);
     }
+}
+
+__global__ void adam_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                 float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
+                                 const int* __restrict__ step_dev, int step_host) {
+    // the step count may live in device memory (a captured hipGraph replays with a fresh count every iteration)
+    adam_sweep<false>(p, g, m, v, n, adam_coef((double)lr, b1, b2, eps, wd, step_dev ? *step_dev : step_host), 1.f);
 }
 
 // adam_step_kernel under the verdict of grad_guard.hip (train.py --clip_grad_norm / --skip_nonfinite): the gradient is scaled
@@ -642,23 +649,29 @@ __global__ void adam_step_guarded_kernel(float* __restrict__ p, const float* __r
         if (blockIdx.x == 0 && threadIdx.x == 0) *skips_dev += 1;
         return;
     }
-    const float scale = stat[1];
     // the counts (device or host) were advanced for the skipped steps too: the bias corrections use the steps really applied
-    const AdamCoef c = adam_coef(lr, b1, b2, eps, wd, (step_dev ? *step_dev : step_host) - *skips_dev);
-    const long n4 = n >> 2;
-    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
-        f32x4 pv = reinterpret_cast<f32x4*>(p)[i], mv = reinterpret_cast<f32x4*>(m)[i], vv = reinterpret_cast<f32x4*>(v)[i];
-        const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) adam_element(pv, gg_mul_rn(gv[e], scale), mv, vv, c, e);
-        reinterpret_cast<f32x4*>(p)[i] = pv;
-        reinterpret_cast<f32x4*>(m)[i] = mv;
-        reinterpret_cast<f32x4*>(v)[i] = vv;
+    adam_sweep<true>(p, g, m, v, n, adam_coef((double)lr, b1, b2, eps, wd, (step_dev ? *step_dev : step_host) - *skips_dev),
+                     stat[1]);
+}
+
+// Either of the two kernels above - stat == NULL: adam_step_kernel, else adam_step_guarded_kernel - at the rate lr * *lr_scale_dev
+// (train.py --lr_schedule: dvg_lr_schedule_tick wrote the multiplier of this iteration; every step site of the iteration reads the
+// same value).  The product is formed in fp64, before the division by bc1, and rounded to fp32 once with it.  With
+// *lr_scale_dev == 1 it is (double)lr exactly, so every operand is the one the kernels above have: the same bits.
+__global__ void adam_step_scheduled_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                           float* __restrict__ v, long n, float lr, float b1, float b2, float eps, float wd,
+                                           const int* __restrict__ step_dev, int step_host, const float* __restrict__ stat,
+                                           int* __restrict__ skips_dev, const float* __restrict__ lr_scale_dev) {
+    if (stat != nullptr && stat[2] != 0.f) {   // uniform over the grid, as above
+        if (blockIdx.x == 0 && threadIdx.x == 0) *skips_dev += 1;
+        return;
     }
-    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {   // tail
-        const long i = (n4 << 2) + threadIdx.x;
-        adam_element(p, gg_mul_rn(g[i], scale), m, v, c, i);
-    }
+    const int t = (step_dev ? *step_dev : step_host) - (stat != nullptr ? *skips_dev : 0);
+    const AdamCoef c = adam_coef((double)lr * (double)*lr_scale_dev, b1, b2, eps, wd, t);
+    if (stat != nullptr)
+        adam_sweep<true>(p, g, m, v, n, c, stat[1]);
+    else
+        adam_sweep<false>(p, g, m, v, n, c, 1.f);
 }
 
 // zero_grad of one or several ADJACENT parameter groups of the gradient arena as one fill, and the device-side step counts
@@ -928,6 +941,24 @@ extern "C" int dvg_adam_step_guarded(float* param, const float* grad, float* exp
     hipLaunchKernelGGL(adam_step_guarded_kernel, dim3(grid_for((n + 3) / 4, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
                        param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step_dev, step, stat, skips_dev);
     return check_launch("dvg_adam_step_guarded");
+}
+
+// dvg_adam_step (stat == skips_dev == NULL) or dvg_adam_step_guarded (both given) at the rate lr * *lr_scale_dev.
+extern "C" int dvg_adam_step_scheduled(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr,
+                                       float beta1, float beta2, float eps, float weight_decay, int step, const int* step_dev,
+                                       const float* stat, int* skips_dev, const float* lr_scale_dev, void* stream) {
+    DVG_REQUIRE(param && grad && exp_avg && exp_avg_sq && lr_scale_dev, DVG_ERR_NULL, "dvg_adam_step_scheduled: NULL pointer");
+    DVG_REQUIRE((stat == nullptr) == (skips_dev == nullptr), DVG_ERR_NULL,
+                "dvg_adam_step_scheduled: stat and skips_dev go together (both NULL: unguarded)");
+    DVG_REQUIRE(n > 0 && (step >= 1 || step_dev != nullptr), DVG_ERR_SHAPE, "dvg_adam_step_scheduled: n=%ld step=%d", n, step);
+    DVG_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(exp_avg) && aligned16(exp_avg_sq), DVG_ERR_ALIGN,
+                "dvg_adam_step_scheduled: buffers must be 16-byte aligned");
+    DVG_REQUIRE(aligned_to<4>(stat) && aligned_to<4>(skips_dev) && aligned_to<4>(step_dev) && aligned_to<4>(lr_scale_dev),
+                DVG_ERR_ALIGN, "dvg_adam_step_scheduled: stat, skips_dev, step_dev and lr_scale_dev must be 4-byte aligned");
+    hipLaunchKernelGGL(adam_step_scheduled_kernel, dim3(grid_for((n + 3) / 4, 256, 4096)), dim3(256), 0, (hipStream_t)stream,
+                       param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step_dev, step, stat, skips_dev,
+                       lr_scale_dev);
+    return check_launch("dvg_adam_step_scheduled");
 }
 
 // g[0:n] = 0 and *t_k += 1 for the non-NULL step counters (see zero_tick_kernel): optimizer.zero_grad() of adjacent groups of

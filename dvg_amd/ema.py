@@ -53,7 +53,7 @@ class WeightAverage:
         return {"updates": k, "decay_eff": effective_decay(self.decay, max(k - 1, 0)), "lag": lag}
 
     def epoch_line(self) -> str:
-        """train.py's line after the gradient guard's (reads the device)."""
+        """train.py's line after the gradient guard's (reads the device; every rank reads the same bits, rank 0 prints)."""
         d = self.read_lag()
         return '     ema: decay %.6g (effective %.6g)  updates %d  lag |p-ema|/|p| %.3e' % (self.decay, d["decay_eff"],
                                                                                            d["updates"], d["lag"])
@@ -133,14 +133,6 @@ def make_average(opt, arena):
     """The WeightAverage the options ask for; None - no buffer, no launch - without the flag."""
     d = ema_options(opt)
     return None if d is None else WeightAverage(d, arena)
-
-
-def print_epoch_line(average, rank) -> None:
-    """After the guard's line: every rank reads (the same bits everywhere), rank 0 prints."""
-    if average is not None:
-        line = average.epoch_line()
-        if rank == 0:
-            print(line)
 
 
 def print_checksums(tr, rank) -> None:

@@ -44,5 +44,6 @@ from .backward import (  # noqa: F401
 )
 from .guard import grad_sumsq_blocks, grad_sumsq, grad_guard_finish  # noqa: F401
 from .ema import ema_update_blocks, ema_update  # noqa: F401
+from .lr_schedule import LR_KINDS, lr_schedule_tick  # noqa: F401
 from .validate import val_accumulators, val_accumulate  # noqa: F401
 from .._lib import check, lib  # noqa: F401

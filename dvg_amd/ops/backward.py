@@ -248,13 +248,14 @@ def upsample2x_bwd(dxu):
     return dx
 
 
-def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, step_dev, stat=None, skips_dev=None) -> None:
+def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, step_dev, stat=None, skips_dev=None, lr_scale=None) -> None:
     """One Adam step over the buffers p, g, m, v (a flat group, or one parameter's views of it); `step_dev`: the device-side
     step count, None = `step`.  With `stat` (a GradGuard's 4 floats) and `skips_dev` (one device int) the guarded form,
     dvg_adam_step_guarded: the gradient times stat[1], nothing when stat[2] != 0 (then skips_dev is advanced); without them
-    dvg_adam_step."""
+    dvg_adam_step.  With `lr_scale` (one device float, an LrSchedule's multiplier) either of the two at the rate lr * lr_scale[0],
+    dvg_adam_step_scheduled; it is picked only then."""
     guarded = stat is not None or skips_dev is not None
-    name = "adam_step_guarded" if guarded else "adam_step"
+    name = "adam_step_scheduled" if lr_scale is not None else "adam_step_guarded" if guarded else "adam_step"
     for which, t in (("p", p), ("g", g), ("m", m), ("v", v)):
         _dev_f32(t, f"{name}.{which}")
         if not t.is_contiguous() or t.numel() != p.numel() or t.device != p.device:
@@ -264,9 +265,13 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, step_dev, s
     ints = [t for t in (step_dev, skips_dev) if t is not None]
     if not stat_ok or any(t.dtype != torch.int32 or t.numel() != 1 or t.device != p.device for t in ints):
         raise RuntimeError(f"{name}: 4 fp32 stat values and one-element int32 counters on p's device expected")
+    if lr_scale is not None and (lr_scale.dtype != torch.float32 or lr_scale.numel() != 1 or lr_scale.device != p.device):
+        raise RuntimeError(f"{name}: lr_scale must be one fp32 value on p's device")
     args = (_p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(beta1), float(beta2), float(eps), float(weight_decay),
             int(step), _p(step_dev))
-    if guarded:
+    if lr_scale is not None:
+        check(lib().dvg_adam_step_scheduled(*args, _p(stat), _p(skips_dev), _p(lr_scale), _stream()), name)
+    elif guarded:
         check(lib().dvg_adam_step_guarded(*args, _p(stat), _p(skips_dev), _stream()), name)
     else:
         check(lib().dvg_adam_step(*args, _stream()), name)

@@ -55,6 +55,9 @@ class FusedAdam(torch.optim.Optimizer):
         self.arena = arena
         self._flat = {}   # group index -> dict(p, g, m, v, params, offsets, gviews, tdev, lo, hi)
         self._captured_groups = []   # groups stepped while a hipGraph was being captured (see after_graph_replay)
+        # one device fp32 (an lr_schedule.LrSchedule's multiplier) every launch of step() multiplies its group's rate with, read on
+        # the device (dvg_adam_step_scheduled); None: the rate is param_groups[...]['lr'] and the launches are the unscheduled ones
+        self.lr_scale: Optional[torch.Tensor] = None
         if all(p.is_cuda for g in self.param_groups for p in g["params"]):
             for gi, group in enumerate(self.param_groups):   # flat storage right away: p.grad are views from the start
                 self._build(gi, group)
@@ -338,7 +341,7 @@ class FusedAdam(torch.optim.Optimizer):
                     if gi in self._captured_groups:  # a captured graph holds this group's device count: now behind the host's
                         self._graph_stale = True
                 stat, skips = (None, None) if guard is None else (guard.stat, self._skips(f))
-                ops.adam_step(f["p"], f["g"], f["m"], f["v"], *hyper, t, tdev, stat, skips)
+                ops.adam_step(f["p"], f["g"], f["m"], f["v"], *hyper, t, tdev, stat, skips, self.lr_scale)
                 touched = f["params"]
                 if capturing:
                     self._captured_groups.append(gi)
@@ -356,7 +359,7 @@ class FusedAdam(torch.optim.Optimizer):
                     st = self.state[p]
                     if p.grad is not gv and p.grad.data_ptr() != gv.data_ptr():
                         gv.copy_(p.grad)
-                    ops.adam_step(p, gv, st["exp_avg"], st["exp_avg_sq"], *hyper, int(st["step"]) + 1, None)
+                    ops.adam_step(p, gv, st["exp_avg"], st["exp_avg_sq"], *hyper, int(st["step"]) + 1, None, lr_scale=self.lr_scale)
             for p in touched:
                 # the kernel wrote through raw pointers; also while capturing, so that code captured AFTER this step
                 # re-packs its weights instead of reusing the packs from before the step
@@ -451,6 +454,14 @@ class GradGuard:
         d = self.read_and_reset()
         return ('     grad norm: max %.4g last %.4g  clipped %d  skipped %d  of %d steps'
                 % (d["max"], d["last"], d["clipped"], d["skipped"], d["sites"]))
+
+
+def add_arguments(parser) -> None:
+    parser.add_argument('--clip_grad_norm', default=0.0, type=float, metavar='C',   # docs/DESIGN_NOTES_gradguard.md
+                        help='limit the L2 norm of ALL gradients that step together after one backward pass to C, by the factor '
+                             'min(1, C / (norm + 1e-6)) of torch\'s clip_grad_norm_; decided on the device, also in a hipGraph (0 = off)')
+    parser.add_argument('--skip_nonfinite', action='store_true',
+                        help='skip such a step when a gradient is Inf or NaN: no parameter, Adam moment or step count changes')
 
 
 def guard_options(opt):

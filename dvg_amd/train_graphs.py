@@ -17,7 +17,8 @@ class GraphedIteration:
     GP prior initialisation and allocator warm-up happen there); the next call captures and replays; later calls replay.
     After each replay the version counters of all parameters and buffers are bumped (the graph writes them through raw
     pointers; the packed-weight / BN-fold caches key on versions) and the optimisers' host-side step counts advance.
-    A change of any learning rate (MultiStepLR, train.py:105-106) triggers a re-capture, and so does Trainer.load_state_dict
+    A change of any learning rate (MultiStepLR, train.py:105-106) triggers a re-capture - `--lr_schedule` changes none: its multiplier
+    lives on the device (dvg_amd/lr_schedule.py) -, and so does Trainer.load_state_dict
     (the device-side Adam step counts are seeded from the restored host counts by begin_capture)."""
 
     def __init__(self, trainer, warmup: int = 2):
@@ -64,6 +65,7 @@ class GraphedIteration:
 
     def _body(self):
         tr = self.tr
+        tr.lr_schedule is None or tr.lr_schedule.tick()   # --lr_schedule: first, as Trainer.iteration (the first segment)
         mse_latent, loss = tr._train_model_dev(self.static_x)
         fp = gp = None
         if tr.opt.ft:

@@ -226,6 +226,9 @@ def capture(tr, epoch=0, train_gen=None, test_gen=None, shared=True) -> dict:
         if ema is not None:      # --ema_decay: the average and its count of updates (dvg_amd/ema.py); no key without the flag
             st = ema.state()
             sd["arena"]["e"], sd["ema"] = st["e"], st["ema"]
+        sched = getattr(tr, "lr_schedule", None)
+        if sched is not None:    # --lr_schedule: the spec and the count of iterations (dvg_amd/lr_schedule.py); no key without the flag
+            sd["lr_schedule"] = sched.state()
         val = getattr(tr, "validation", None)
         if val is not None:      # --val_every: the history and the best scores (dvg_amd/validate.py); no key without the flag
             sd["validation"] = val.state()
@@ -259,6 +262,9 @@ def restore(tr, sd, train_gen=None, test_gen=None, path="<state>") -> int:
     for name, o in named_optimizers(tr):
         o.load_host_state(sd["optimizers"][name])      # step counts (begin_capture seeds the device counts from them), lr
     tr.scheduler.load_state_dict(sd["scheduler"])
+    from . import lr_schedule    # --lr_schedule: the count of iterations, a state from before the flag counts from its global step
+    lr_schedule.restore(getattr(tr, "lr_schedule", None), sd, path, sd.get("global_step", global_step(tr)), tr.rank,
+                        tr.encoder_optimizer.param_groups[0]["lr"])
     mine = sd[RANK_KEY]
     buffers = dict(named_buffers(tr))
     if set(buffers) != set(mine["buffers"]):

@@ -87,23 +87,20 @@ int dvg_unpack_convT_weight(const float* w_packed, float* w_iohw, int cin, int c
  * implicit-GEMM convs: dvg_conv_stats_rows_v2 below.)                                                                     */
 int dvg_conv_first_stats_rows(int ks, int N, int H, int W);
 
-/* The three implicit-GEMM convs (conv_igemm2.hip; the "_v2" suffix is historical: the first
- * schedule and its un-suffixed entry points were retired in ABI 3).  Weights are packed by
- * dvg_pack_conv_weight_k16 (transposed != 0: ConvTranspose2d weight (Cin,Cout,KH,KW), flipped) into
- * Cin/16 * KH*KW * Cout rows of dvg_packed_row_floats() floats, [Cin/16][Cout/64][tap slot][64][row]
- * (a 4x4 transposed pack orders the slots by OUTPUT parity: it feeds dvg_convT4x4s2_bn_act_v2; a 4x4
- * plain pack orders them by INPUT parity (r05): it feeds dvg_conv4x4s2_bn_act_v2, which runs one stage per
- * parity and needs N * H * W * Cin < 2^31; a 3x3 pack feeds dvg_conv3x3_bn_act_v2), and `stats` has
- * dvg_conv_stats_rows_v2(...) rows.  C1, C2 multiples of 16; Cout multiple of 64.
+/* The three implicit-GEMM convs (conv_igemm2.hip; the "_v2" suffix is historical: the first schedule and its un-suffixed entry
+ * points were retired in ABI 3).  Weights are packed by dvg_pack_conv_weight_k16 (transposed != 0: ConvTranspose2d weight
+ * (Cin,Cout,KH,KW), flipped) into Cin/16 * KH*KW * Cout rows of dvg_packed_row_floats() floats,
+ * [Cin/16][Cout/64][tap slot][64][row] (a 4x4 transposed pack orders the slots by OUTPUT parity: it feeds dvg_convT4x4s2_bn_act_v2;
+ * a 4x4 plain pack orders them by INPUT parity (r05): it feeds dvg_conv4x4s2_bn_act_v2, which runs one stage per parity and needs
+ * N * H * W * Cin < 2^31; a 3x3 pack feeds dvg_conv3x3_bn_act_v2), and `stats` has dvg_conv_stats_rows_v2(...) rows.
+ * C1, C2 multiples of 16; Cout multiple of 64.
  *
- * ABI 7 - arithmetic of the implicit-GEMM kernels.  dvg_mfma_mode() == 1 (the default build): every fp32
- * operand is split EXACTLY into three bf16 terms (8 + 8 + 8 significant bits; activations when a tile is
- * staged in LDS, weights when they are packed: a packed row is 3 x 16 bf16 = 24 floats) and a K = 16 slab
- * of the product is six v_mfma_f32_32x32x16_bf16 with fp32 accumulation; the dropped cross terms are
- * below 2^-24 |a||b|, under the rounding of one fp32 product, and the measured error against fp64 is
- * that of the f32 MFMA or below.  dvg_mfma_mode() == 0 (library built with -DDVG_BF16X3=0): the native
- * v_mfma_f32_32x32x2_f32, packed rows of 16 floats.  Callers size packed buffers with
- * dvg_packed_row_floats() and are otherwise unaffected.                                          */
+ * ABI 7 - arithmetic of the implicit-GEMM kernels.  dvg_mfma_mode() == 1 (the default build): every fp32 operand is split EXACTLY
+ * into three bf16 terms (8 + 8 + 8 significant bits; activations when a tile is staged in LDS, weights when they are packed: a
+ * packed row is 3 x 16 bf16 = 24 floats) and a K = 16 slab of the product is six v_mfma_f32_32x32x16_bf16 with fp32 accumulation;
+ * the dropped cross terms are below 2^-24 |a||b|, under the rounding of one fp32 product, and the measured error against fp64 is
+ * that of the f32 MFMA or below.  dvg_mfma_mode() == 0 (library built with -DDVG_BF16X3=0): the native v_mfma_f32_32x32x2_f32,
+ * packed rows of 16 floats.  Callers size packed buffers with dvg_packed_row_floats() and are otherwise unaffected. */
 int dvg_mfma_mode(void);
 int dvg_packed_row_floats(void);
 /* ABI 9 - which BUILD of the library is loaded: a static string "abi=9 bf16x3=1 variant= src=<12 hex digits>".  `src` =
@@ -123,49 +120,42 @@ const char* dvg_build_info(void);
  * launches (or the hipGraph capture) it shall apply to.  The reference has no counterpart (cuDNN picks its own algorithms).   */
 void dvg_set_tile_policy(int energy);
 int dvg_tile_policy(void);
-int dvg_pack_conv_weight_k16(const float* w, float* w_packed, int cout, int cin, int kh, int kw,
-                             int transposed, void* stream);
-/* Split-K: when a layer would launch < 384 workgroups (deep, narrow layers; small per-GPU batches) and the caller
- * supplies `workspace` (>= dvg_conv_splitk_v2(...) * N*Ho*Wo*Cout floats), K is split over workgroups, raw partial
- * tiles go to the workspace and a finish kernel applies scale/shift/act (+pool, +statistics).  workspace may be
- * NULL (no split).  `stats` then has dvg_conv_stats_rows_v2(..., pool, with_workspace) rows.
- * `addend` (may be NULL): raw pre-scale partial sums in y's NHWC shape, y = act((conv + addend) * scale + shift).
- * It carries the skip half of a decoder block's first conv, cat([up(d), skip]) (vgg_64.py:98-105, dcgan_64.py:84-86),
- * when the skip tensor is loop-invariant over the steps of a rollout (generate_frames.py:154-157): the caller
- * computes conv(skip, W[:, C1:]) once with scale = shift = NULL, act = NONE and then runs only the x half per step.
- * Statistics (train-mode BatchNorm) are taken over conv + addend; excludes the pooled output.                 */
+int dvg_pack_conv_weight_k16(const float* w, float* w_packed, int cout, int cin, int kh, int kw, int transposed, void* stream);
+/* Split-K: when a layer would launch < 384 workgroups (deep, narrow layers; small per-GPU batches) and the caller supplies
+ * `workspace` (>= dvg_conv_splitk_v2(...) * N*Ho*Wo*Cout floats), K is split over workgroups, raw partial tiles go to the
+ * workspace and a finish kernel applies scale/shift/act (+pool, +statistics).  workspace may be NULL (no split).  `stats` then
+ * has dvg_conv_stats_rows_v2(..., pool, with_workspace) rows.  `addend` (may be NULL): raw pre-scale partial sums in y's NHWC
+ * shape, y = act((conv + addend) * scale + shift).  It carries the skip half of a decoder block's first conv, cat([up(d), skip])
+ * (vgg_64.py:98-105, dcgan_64.py:84-86), when the skip tensor is loop-invariant over the steps of a rollout
+ * (generate_frames.py:154-157): the caller computes conv(skip, W[:, C1:]) once with scale = shift = NULL, act = NONE and then
+ * runs only the x half per step.  Statistics (train-mode BatchNorm) are taken over conv + addend; excludes the pooled output. */
 int dvg_conv_splitk_v2(int mode, int N, int H, int W, int Cin, int Cout);
 int dvg_conv_stats_rows_v2(int mode, int N, int H, int W, int Cin, int Cout, int pool, int with_workspace);
-int dvg_conv3x3_bn_act_v2(const float* x, const float* skip, const float* w_k16,
-                          const float* scale, const float* shift, float* y, float* y_pool,
-                          float* stats, int N, int H, int W, int C1, int C2, int Cout,
-                          int upsample_x, int act, float slope, float* workspace,
-                          long workspace_floats, const float* addend,
+int dvg_conv3x3_bn_act_v2(const float* x, const float* skip, const float* w_k16, const float* scale, const float* shift, float* y,
+                          float* y_pool, float* stats, int N, int H, int W, int C1, int C2, int Cout, int upsample_x, int act,
+                          float slope, float* workspace, long workspace_floats, const float* addend,
                           /* ABI 6, time-batched decoder calls (train.py:227-231): the images form groups of addend_block;
                            * group g = n / addend_block adds block addend_map[g] (device ints) of an addend made of
                            * addend_block-image blocks - the skip half shared by the three decoder calls of a time step
                            * and, once the skip is frozen, by every later step.  NULL: image n adds addend image n.     */
                           const int* addend_map, int addend_block, void* stream);
-/* dcgan_conv = Conv2d(nin,nout,4,2,1)+BN+LReLU (dcgan_64.py:4-14): K = 16*Cin,
- * x NHWC (N,H,W,Cin) -> y NHWC (N,H/2,W/2,Cout).                                          */
+/* dcgan_conv = Conv2d(nin,nout,4,2,1)+BN+LReLU (dcgan_64.py:4-14): K = 16*Cin, x NHWC (N,H,W,Cin) -> y NHWC (N,H/2,W/2,Cout). */
 /* vgg_64's first stage in eval mode, c1 = vgg_layer(1, 64) -> vgg_layer(64, Cout) (vgg_64.py:23-26, 49), as ONE launch: the
  * second layer's implicit GEMM computes its input tile from the frame patch under it, so the 64-channel activation between
  * the two layers (67 MB at B = 64) is never written or read.  frame (N,1,H,W) NCHW; w0 = the first layer's (64,1,3,3) weight
- * transposed to [9 taps][64 channels]; scale0 / shift0 = the first
- * layer's folded BatchNorm (64 each; LeakyReLU `slope`); w1_k16 / scale1 / shift1 / y / y_pool / act as in
- * dvg_conv3x3_bn_act_v2 with C1 = 64.  H % 8 == 0, W % 16 == 0, N * H/8 * W/16 * Cout/64 >= 512.                          */
+ * transposed to [9 taps][64 channels]; scale0 / shift0 = the first layer's folded BatchNorm (64 each; LeakyReLU `slope`);
+ * w1_k16 / scale1 / shift1 / y / y_pool / act as in dvg_conv3x3_bn_act_v2 with C1 = 64.  H % 8 == 0, W % 16 == 0,
+ * N * H/8 * W/16 * Cout/64 >= 512.                                                                                        */
 int dvg_conv3x3_first_pair(const float* frame, const float* w0, const float* scale0, const float* shift0,
                            const float* w1_k16, const float* scale1, const float* shift1, float* y, float* y_pool,
                            int N, int H, int W, int Cout, int act, float slope,
                            int y_from /* ABI 8: y holds the images [y_from, N) only - see dvg_winograd_output_pool_input */,
                            void* stream);
-int dvg_conv4x4s2_bn_act_v2(const float* x, const float* w_k16, const float* scale,
-                            const float* shift, float* y, float* stats, int N, int H, int W,
-                            int Cin, int Cout, int act, float slope, float* workspace,
-                            long workspace_floats, void* stream);
-/* dcgan_upconv = ConvTranspose2d(nin,nout,4,2,1)+BN+LReLU on cat([x, skip])
- * (dcgan_64.py:16-26,84-87) as four parity-class implicit GEMMs (K = 4*Cin).
- * x NHWC (N,H,W,C1), skip NHWC (N,H,W,C2) or NULL; y NHWC (N,2H,2W,Cout).                 */
+int dvg_conv4x4s2_bn_act_v2(const float* x, const float* w_k16, const float* scale, const float* shift, float* y, float* stats,
+                            int N, int H, int W, int Cin, int Cout, int act, float slope, float* workspace, long workspace_floats,
+                            void* stream);
+/* dcgan_upconv = ConvTranspose2d(nin,nout,4,2,1)+BN+LReLU on cat([x, skip]) (dcgan_64.py:16-26,84-87) as four parity-class
+ * implicit GEMMs (K = 4*Cin).  x NHWC (N,H,W,C1), skip NHWC (N,H,W,C2) or NULL; y NHWC (N,2H,2W,Cout).                 */
 int dvg_convT4x4s2_bn_act_v2(const float* x, const float* skip, const float* w_k16,
                              const float* scale, const float* shift, float* y, float* stats,
                              int N, int H, int W, int C1, int C2, int Cout, int act, float slope,
@@ -775,6 +765,16 @@ int dvg_grad_sumsq(const float* g, long n, double* partials, void* stream);
 int dvg_grad_guard_finish(const double* partials, int nblocks, double max_norm, int skip, float* stat, int* counters, void* stream);
 int dvg_adam_step_guarded(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1, float beta2,
                           float eps, float weight_decay, int step, const int* step_dev, const float* stat, int* skips_dev, void* stream);
+/* Learning-rate schedule (train.py --lr_schedule here; docs/DESIGN_NOTES_lr_schedule.md).  No reference counterpart: its
+ * train.py:95-104 hard-codes the rate.  dvg_lr_schedule_tick, one thread: k = *iter_dev; *scale_dev = (float)s(k), s in fp64:
+ * (k + 1) / W while k < W, else by kind with u = min(1, (k - W) / (N - W)): 0 constant 1; 1 linear R + (1 - R)(1 - u); 2 cosine
+ * R + (1 - R)(1 + cos(pi u)) / 2; 3 step max(R, G^((k - W) / K)); then *iter_dev = min(k + 1, INT_MAX).  0 <= W < N, R in [0, 1];
+ * step: K >= 1, G in (0, 1].  dvg_adam_step_scheduled: dvg_adam_step (stat = skips_dev = NULL) or dvg_adam_step_guarded at the
+ * rate (double)lr * *lr_scale_dev, formed in fp64 before the division by the bias correction: same bits for 1.  Within ABI 9. */
+int dvg_lr_schedule_tick(int kind, int W, int N, int K, double R, double G, int* iter_dev, float* scale_dev, void* stream);
+int dvg_adam_step_scheduled(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1,
+                            float beta2, float eps, float weight_decay, int step, const int* step_dev, const float* stat,
+                            int* skips_dev, const float* lr_scale_dev, void* stream);
 
 /* Exponential moving average of a flat parameter range (train.py --ema_decay here; docs/DESIGN_NOTES_ema.md).  No reference
  * counterpart: it follows the optimiser steps of the reference's train.py:242-245.  ema = fmaf(w, param - ema, ema), w = (float)(1 -

@@ -4,7 +4,7 @@
 Same flags (train.py:17-46) and the same three step closures (`train_model` :200-248,
 `train_frame_predictor` :175-198, `train_GP_Frame_predictor` :146-172), loss weights (:239), optimisers
 (:95-106, lr hard-coded 0.002 like the reference; `--lr/--beta1/--optimizer/--z_dim/--name` stay accepted
-and unused), scheduler-before-epoch order (:347), log line (:368) and checkpoint dict (:380-388).
+and unused - `--lr` except under `--lr_schedule`), scheduler-before-epoch order (:347), log line (:368) and checkpoint dict (:380-388).
 
 Consciously fixed (each was unrunnable in the reference — SURVEY.md §5 quirks):
   * the model family follows `--model` / `--image_width` instead of a hard-coded dcgan_64 (:75);
@@ -35,6 +35,8 @@ graph, and writes `model_ema.pth` beside `model.pth` (dvg_amd/ema.py, docs/DESIG
 (dvg_clip_gather_aug_u8; dvg_amd/datasets.py ClipAugmenter, docs/DESIGN_NOTES_augment.md).
 `--val_every N` scores a fixed set of held-out clips every N epochs on rank 0 (eval-mode rollouts, Finn metrics, dvg_val_accumulate),
 logs them to `val_log.jsonl` and keeps `model_best.pth` (dvg_amd/validate.py, docs/DESIGN_NOTES_validation.md).
+`--lr_schedule KIND` makes `--lr` the base rate of all four optimisers and moves it every iteration by a device-side multiplier:
+warm-up, then constant | linear | cosine | step; one launch per iteration (dvg_amd/lr_schedule.py, docs/DESIGN_NOTES_lr_schedule.md).
 """
 import argparse
 import importlib
@@ -51,7 +53,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 import utils  # noqa: E402
-from dvg_amd import datasets, ema as weight_ema, fused, parallel, train_state, validate, viz  # noqa: E402
+from dvg_amd import datasets, ema as weight_ema, fused, lr_schedule, optim, parallel, train_state, validate, viz  # noqa: E402
 from dvg_amd.data import SyntheticMovingMNIST, make_batch_generator, synthetic_video  # noqa: E402,F401
 from dvg_amd.models.gp_models import GaussianLikelihood, GPRegressionLayer1, VariationalELBO  # noqa: E402
 from dvg_amd.optim import FlatArena, FusedAdam, guard_options, guarded_step, make_guard, zero_grads  # noqa: E402,F401
@@ -61,7 +63,7 @@ from dvg_amd.train_state import detached_copy as _detached_copy  # noqa: E402
 
 def build_parser():
     p = argparse.ArgumentParser()
-    p.add_argument('--lr', default=0.002, type=float, help='learning rate (unused, as in the reference)')
+    p.add_argument('--lr', default=0.002, type=float, help='unused, as in the reference; under --lr_schedule: the base rate of all four optimisers')
     p.add_argument('--beta1', default=0.9, type=float)
     p.add_argument('--batch_size', default=50, type=int, help='GLOBAL batch size')
     p.add_argument('--log_dir', default='logs')
@@ -111,12 +113,7 @@ def build_parser():
     p.add_argument('--synthetic_data', action='store_true',
                    help='kth | bair | ucf: train on synthetic clips of that shape instead of reading --data_root; smmnist: '
                         'the in-repo sprites even where --data_root holds MNIST')
-    p.add_argument('--clip_grad_norm', default=0.0, type=float, metavar='C',   # docs/DESIGN_NOTES_gradguard.md
-                   help='limit the L2 norm of ALL gradients that step together after one backward pass to C, by the factor '
-                        'min(1, C / (norm + 1e-6)) of torch\'s clip_grad_norm_; decided on the device, also in a hipGraph (0 = off)')
-    p.add_argument('--skip_nonfinite', action='store_true',
-                   help='skip such a step when a gradient is Inf or NaN: no parameter, Adam moment or step count changes')
-    for mod in (weight_ema, datasets, validate):   # --ema_decay, --augment, --val_every / --val_batches / --val_nsample
+    for mod in (optim, weight_ema, datasets, validate, lr_schedule):   # guard flags, --ema_decay, --augment, --val_*, --lr_*
         mod.add_arguments(p)
     return p
 
@@ -178,11 +175,12 @@ class Trainer:
         Adam = FusedAdam   # HIP only, like the models themselves: no CPU fallback on the product path
         allp = [p for m in self.modules for p in m.parameters()]
         self.arena = FlatArena(FlatArena.size_for(allp), device)
+        lr = lr_schedule.base_rate(opt)   # 0.002, as the reference; --lr under --lr_schedule
         self.optimizer = Adam([{'params': self.gp_layer.parameters()},
-                               {'params': self.likelihood.parameters()}], lr=0.002, arena=self.arena)
-        self.frame_predictor_optimizer = Adam(self.frame_predictor.parameters(), lr=0.002, arena=self.arena)
-        self.decoder_optimizer = Adam(self.decoder.parameters(), lr=0.002, arena=self.arena)
-        self.encoder_optimizer = Adam(self.encoder.parameters(), lr=0.002, arena=self.arena)
+                               {'params': self.likelihood.parameters()}], lr=lr, arena=self.arena)
+        self.frame_predictor_optimizer = Adam(self.frame_predictor.parameters(), lr=lr, arena=self.arena)
+        self.decoder_optimizer = Adam(self.decoder.parameters(), lr=lr, arena=self.arena)
+        self.encoder_optimizer = Adam(self.encoder.parameters(), lr=lr, arena=self.arena)
         self.scheduler = torch.optim.lr_scheduler.MultiStepLR(self.optimizer, milestones=[3, 5], gamma=0.1)
         # num_data = the GLOBAL batch (train.py:112 passes opt.batch_size): each rank's loss is ll_r/B_local - KL/num_data and
         # the ranks are averaged, which gives the reference's ll/B - KL/B at the same global batch for any number of ranks
@@ -209,6 +207,8 @@ class Trainer:
         self.guard = make_guard(opt, device, self.optimizers())
         # --ema_decay: an averaged copy of arena.p (after the broadcast above), moved once per iteration; None = nothing exists
         self.ema = weight_ema.make_average(opt, self.arena)
+        # --lr_schedule: the multiplier of the iteration in one device float that every Adam launch reads; None = nothing exists
+        self.lr_schedule = lr_schedule.make_schedule(opt, device, self.optimizers())
         self.validation = validate.make(opt, device)   # --val_every, rank 0: the held-out stream and the history; else None
 
     def _step(self, optimizers):
@@ -647,6 +647,7 @@ class Trainer:
     def iteration(self, x):
         """One iteration of the training loop (train.py:354-361): train_model, then the two fine-tuning closures when
         opt.ft.  Returns (mse_ctrl, indices, temp_loss) as Python floats."""
+        self.lr_schedule is None or self.lr_schedule.tick()   # first: all step sites of the iteration read one multiplier
         mse_ctrl, indices = self.train_model(x)
         temp_loss = self.finetune_temporal_encoders(x) if self.opt.ft else 0
         self.ema is None or self.ema.update()   # after the last step site of the iteration
@@ -767,10 +768,9 @@ def main(argv=None):
             print('[%02d] mse loss: %.5f (%d) %.5f' % (epoch, epoch_mse / opt.epoch_size,
                                                        epoch * opt.epoch_size * opt.batch_size, indices))
             print('     train frames/s: %.1f' % fps)
-        if tr.guard is not None:   # the one read of the guard's device counters: per epoch, outside the iterations
-            line = tr.guard.epoch_line()
-            rank == 0 and print(line)
-        weight_ema.print_epoch_line(tr.ema, rank)   # --ema_decay: every rank reads its own counters, rank 0 prints
+        for part in (tr.guard, tr.ema, tr.lr_schedule):   # one read of each one's device counters: per epoch, outside the iterations
+            line = part is not None and part.epoch_line()   # every rank reads its own (the same bits everywhere), rank 0 prints
+            line and rank == 0 and print(line)
         if epoch % opt.save_every == 0:
             tr.frame_predictor.eval()
             tr.gp_layer.eval()
