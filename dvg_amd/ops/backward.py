@@ -42,6 +42,48 @@ def frame_losses(pred, target, weights):
     return sums, dpred
 
 
+FRAME_LOSS_KINDS = ("mse", "l1", "charbonnier")     # dvg_frame_losses_ext's `kind` = the index
+
+
+def frame_losses_ext(pred, target, spec_or_kind, weights, eps=1e-3, gdl=0.0):
+    """pred (S, K, ..., H, W) - the K decoder calls of every step -, target (S, ..., H, W) contiguous, W % 4 == 0:
+    (sums (2, K), dpred like pred) with sums[0, k] = sum rho(pred[:, k] - target), sums[1, k] = the gradient-difference sum of call
+    k (an exact 0 for gdl = 0) and dpred = d(sum_k weights[k] (sums[0, k] + gdl sums[1, k])) / d pred, one pass
+    (dvg_frame_losses_ext; docs/DESIGN_NOTES_frame_loss.md).  `spec_or_kind`: a frame_loss.FrameLossSpec (its eps and gdl are
+    used), or a name of FRAME_LOSS_KINDS with `eps` and `gdl`.  `weights`: K Python floats (loss weight / elements per call)."""
+    if isinstance(spec_or_kind, str):
+        kind = spec_or_kind
+    else:
+        kind, eps, gdl = spec_or_kind.kind, spec_or_kind.eps, spec_or_kind.gdl
+    if kind not in FRAME_LOSS_KINDS:
+        raise RuntimeError(f"frame_losses_ext: kind must be one of {', '.join(FRAME_LOSS_KINDS)}")
+    _dev_f32(pred, "frame_losses_ext.pred")
+    _dev_f32(target, "frame_losses_ext.target")
+    if not pred.is_contiguous() or not target.is_contiguous():
+        raise RuntimeError("frame_losses_ext: contiguous operands expected")
+    if pred.dim() < 4 or target.dim() != pred.dim() - 1 or pred.shape[:1] + pred.shape[2:] != target.shape or \
+            len(weights) != pred.shape[1]:
+        raise RuntimeError(f"frame_losses_ext: pred {tuple(pred.shape)} / target {tuple(target.shape)} / {len(weights)} weights")
+    s_, k, h, w_ = pred.shape[0], pred.shape[1], pred.shape[-2], pred.shape[-1]
+    planes = target[0].numel() // (h * w_)
+    key = (pred.device, "ext", tuple(float(w) for w in weights), float(gdl))
+    w = _LOSS_W.get(key)
+    if w is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("frame_losses_ext: first call with these weights during a capture (run one eager iteration first)")
+        w = _LOSS_W[key] = torch.tensor([key[2], [x * key[3] for x in key[2]]], dtype=torch.float32, device=pred.device)
+    blocks = lib().dvg_frame_losses_ext_blocks(s_, planes, h, w_)
+    if blocks <= 0 or not 1 <= k <= 3:
+        raise RuntimeError(f"frame_losses_ext: unsupported shape S={s_} K={k} planes={planes} H={h} W={w_}")
+    sums = torch.empty((2, k), device=pred.device, dtype=torch.float32)
+    dpred = torch.empty_like(pred)
+    partial = torch.empty(blocks * 2 * k, device=pred.device, dtype=torch.float32)
+    _run("frame_losses_ext", 20.0 * pred.numel(), 4.0 * (2 * pred.numel() + target.numel()), lib().dvg_frame_losses_ext, _p(pred),
+         _p(target), _p(sums), _p(dpred), s_, k, planes, h, w_, FRAME_LOSS_KINDS.index(kind), float(eps), _p(w[0]), _p(w[1]),
+         _p(partial), _stream())
+    return sums, dpred
+
+
 def mse_sum_grad(a, b, scale, need_grad=True):
     """(sum (a - b)^2 as a 0-dim tensor, 2 scale (a - b) or None) for small tensors (dvg_mse_sum_grad): a closure's latent MSE
     and its gradient (train.py:188,223)."""

@@ -178,3 +178,30 @@ def broadcast_parameters(modules: Iterable[torch.nn.Module], src: int = 0, group
         if rest:
             n += broadcast_coalesced(rest, src=src, group=group)
     return n
+
+
+def allreduce_stats(tr, iters: int):
+    """train.Trainer.allreduce_stats: collectives and bytes per iteration, and their standalone duration (the same ranges
+    all-reduced back to back, timed with events on the launch stream; how much of it an iteration actually waits for is a separate
+    measurement).  `iters`: the iterations the reducer's counts cover; None without
+    an active reducer or before the first counted iteration."""
+    if not tr.reducer.active() or not iters:
+        return None
+    ranges = [(tr.rng_gp[0], tr.rng_dec[1]), tr.rng_enc, (tr.rng_gp[0], tr.rng_fp[1])] if tr.opt.ft else \
+        [(tr.rng_gp[0], tr.rng_dec[1]), tr.rng_enc]
+    scratch = torch.zeros_like(tr.arena.g)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    for _ in range(3):
+        for lo, hi in ranges:
+            dist.all_reduce(scratch[lo:hi])
+    torch.cuda.synchronize()
+    reps = 10
+    e0.record()
+    for _ in range(reps):
+        for lo, hi in ranges:
+            dist.all_reduce(scratch[lo:hi])
+    e1.record()
+    torch.cuda.synchronize()
+    return {"allreduce_ms_per_iter": round(e0.elapsed_time(e1) / reps, 3),
+            "allreduces_per_iter": round(tr.reducer.calls / iters, 2),
+            "allreduce_MB_per_iter": round(4e-6 * tr.reducer.floats / iters, 2)}

@@ -44,9 +44,7 @@ const char* dvg_last_error(void);
  * capture is only initialised when that graph replays, so such a cache must be keyed by the capture.                     */
 long dvg_stream_capture_id(void* stream);
 
-/* ------------------------------------------------------------------ *
- * Weight re-layout (one launch per parameter, cached by the caller).
- * ------------------------------------------------------------------ */
+/* ---- Weight re-layout (one launch per parameter, cached by the caller) ---- */
 /* Conv2d weight (Cout,Cin,KH,KW) [vgg_64.py:8, dcgan_64.py:8] -> packed [KH*KW][Cout][Cin] (Cin contiguous = implicit-GEMM K). */
 int dvg_pack_conv_weight(const float* w_oihw, float* w_packed, int cout, int cin, int kh, int kw, void* stream);
 
@@ -58,9 +56,7 @@ int dvg_pack_convT_weight(const float* w_iohw, float* w_packed, int cin, int cou
 int dvg_unpack_conv_weight(const float* w_packed, float* w_oihw, int cout, int cin, int kh, int kw, void* stream);
 int dvg_unpack_convT_weight(const float* w_packed, float* w_iohw, int cin, int cout, int kh, int kw, void* stream);
 
-/* ------------------------------------------------------------------ *
- * Encoder / decoder blocks
- * ------------------------------------------------------------------ */
+/* ---- Encoder / decoder blocks ---- */
 /* vgg_layer = Conv2d(nin,nout,3,1,1)+BatchNorm2d+LeakyReLU(0.2)  (vgg_64.py:5-15) as ONE fp32-MFMA implicit GEMM
  * (M = N*H*W pixels, N = Cout, K = 9*Cin):
  *
@@ -314,9 +310,7 @@ int dvg_bn_act_apply(const float* u, const float* scale, const float* shift, flo
                      float* y_pool, int N, int H, int W, int C, int act, float slope,
                      int group_images, void* stream);
 
-/* ------------------------------------------------------------------ *
- * Dense ends and the recurrent predictor
- * ------------------------------------------------------------------ */
+/* ---- Dense ends and the recurrent predictor ---- */
 /* out[m][n] = act( (sum_k a[m][k]*w[n][k]) * scale[n % period] + shift[n % period] )
  * Small-M GEMM used for: encoder head Conv2d(512,dim,4,1,0)+BN+Tanh on the 4x4
  * map (vgg_64.py:44-48; K = 8192), decoder stem ConvTranspose2d(dim,512,4,1,0)
@@ -371,8 +365,7 @@ int dvg_stem_gemm(const float* vec, int ldv, const float* w_kn, int KP, const fl
 /* ------------------------------------------------------------------ *
  * Sparse variational GP trigger (gp_models.py:10-24 + gpytorch 0.3.x
  * WhitenedVariationalStrategy / GaussianLikelihood / MultivariateNormal;
- * equations of record in DESIGN.md §GP).  One workgroup per latent dim.
- * ------------------------------------------------------------------ */
+ * equations of record in DESIGN.md §GP).  One workgroup per latent dim. */
 
 /* Predictive distribution q(f(x)) for D independent 1-D GPs, M inducing points.
  *   h            [B][D]   latent codes; GP d sees column d (the reference's
@@ -424,8 +417,7 @@ int dvg_gp_step_group(int B, int S, int P, int M);
  * forward implicit-GEMM kernels with re-packed weights:
  *   dgrad(Conv2d 3x3)        = dvg_conv3x3_bn_act_v2    with the transposed/flipped k16 pack of W
  *   dgrad(Conv2d 4x4 s2)     = dvg_convT4x4s2_bn_act_v2 with the transposed k16 pack of W
- *   dgrad(ConvTranspose 4x4) = dvg_conv4x4s2_bn_act_v2  with the plain k16 pack of W
- * ------------------------------------------------------------------ */
+ *   dgrad(ConvTranspose 4x4) = dvg_conv4x4s2_bn_act_v2  with the plain k16 pack of W */
 
 /* BatchNorm + activation (+ 2x2 max-pool) backward, pass 1:
  *   dp = (dy + scatter_maxpool(dyp)) * act'(y)          (written to `dp`, NHWC)
@@ -698,9 +690,7 @@ int dvg_gp_elbo_bwd(const float* mean, const float* var, const float* kl, const 
                     const float* raw_noise, const float* gelbo, float* gmean, float* gvar, float* gkl, float* gtarget,
                     float* graw_noise, int B, int D, int num_data, int noise_period, void* stream);
 
-/* ------------------------------------------------------------------ *
- * Small elementwise helpers on the path
- * ------------------------------------------------------------------ */
+/* ---- Small elementwise helpers on the path ---- */
 /* (N,C,H,W) contiguous -> NHWC and back (skip tensors handed to / taken from callers that insist on contiguous NCHW). */
 int dvg_nchw_to_nhwc(const float* x, float* y, int N, int C, int H, int W, void* stream);
 int dvg_nhwc_to_nchw(const float* x, float* y, int N, int C, int H, int W, void* stream);
@@ -708,8 +698,7 @@ int dvg_nhwc_to_nchw(const float* x, float* y, int N, int C, int H, int W, void*
 /* ------------------------------------------------------------------ *
  * Debug hooks (tools/diag_*.py).  Not part of the product path: they hand the next launches of one kernel family a device
  * buffer that every workgroup fills with clock64()/wall_clock64() phase stamps.  buf == NULL (the default) disables stamping;
- * the kernels then pay one uniform branch.  Not thread-safe: set, launch, synchronise, reset from ONE host thread.
- * ------------------------------------------------------------------ */
+ * the kernels then pay one uniform branch.  Not thread-safe: set, launch, synchronise, reset from ONE host thread. */
 void dvg_debug_set_clockbuf(void* buf, unsigned records);        /* conv_igemm2 kernels: 8 x u64 per workgroup */
 void dvg_debug_set_gp_clockbuf(void* buf, unsigned records);     /* gp_predict_kernel: 12 x u64 per workgroup  */
 void dvg_debug_set_wgrad_clockbuf(void* buf, unsigned records);  /* wgrad_igemm_kernel: 4 x u64 per workgroup  */
@@ -748,6 +737,17 @@ int dvg_frame_losses_blocks(long elems);
 int dvg_frame_losses(const float* pred, const float* target, float* sums, float* dpred, long n, int S, int K, const float* w,
                      float* partial, void* stream);
 int dvg_mse_sum_grad(const float* a, const float* b, float* sum, float* da, long n, float scale, void* stream);
+
+/* Frame terms with another pixel penalty and / or the gradient-difference loss (train.py --frame_loss / --gdl_weight here;
+ * docs/DESIGN_NOTES_frame_loss.md; the reference's train.py:227-239 is nn.MSELoss: dvg_frame_losses).  pred [S][K][planes][H][W],
+ * target [S][planes][H][W], d = pred - target: sums [2][K] = pix_k = sum rho(d), rho = d^2 | |d| | sqrt(d^2 + eps^2) for kind 0 | 1 | 2,
+ * and gdl_k = sum over the x- and y-neighbour pairs inside a plane of | |P - P'| - |T - T'| |; dpred = the gradient of sum_k w_pix[k]
+ * pix_k + w_gdl[k] gdl_k, sign(0) = 0 throughout.  w_pix, w_gdl: [K] on the device; w_gdl[k] == 0: no edge work, gdl_k = 0.  partial:
+ * dvg_frame_losses_ext_blocks(...) x 2 K floats (0 blocks: shape not served).  W % 4 == 0, 4 <= W <= 1332, H >= 1, K in 1..3; pred,
+ * target, dpred 16-byte aligned.  One pass, deterministic, a launch per call + the finish.  Within ABI 9. */
+int dvg_frame_losses_ext_blocks(int S, long planes, int H, int W);
+int dvg_frame_losses_ext(const float* pred, const float* target, float* sums, float* dpred, int S, int K, long planes, int H, int W,
+                         int kind, float eps, const float* w_pix, const float* w_gdl, float* partial, void* stream);
 
 /* optimizer.zero_grad() of adjacent parameter groups of the gradient arena as ONE fill (train.py:201-203 zeroes three modules),
  * and the device-side Adam step counts t0..t3 (NULL: none) advanced by one in the same launch (dvg_adam_step's step_dev): a

@@ -33,12 +33,15 @@ def main():
     ap.add_argument("--clip_grad_norm", type=float, default=0.0, help="train.py's flag: the gradient guard's clip threshold")
     ap.add_argument("--skip_nonfinite", action="store_true", help="train.py's flag: skip step sites with Inf / NaN gradients")
     ap.add_argument("--ema_decay", type=float, default=None, help="train.py's flag: the weight average, one update per iteration")
+    ap.add_argument("--frame_loss", default="mse", help="train.py's flag: the pixel penalty of the frame terms")
+    ap.add_argument("--gdl_weight", type=float, default=0.0, help="train.py's flag: the gradient-difference loss")
     a = ap.parse_args()
     o = train.build_parser().parse_args(["--model", a.model, "--batch_size", str(a.batch), "--n_past", str(a.n_past),
                                          "--n_future", str(a.n_future), "--no_save", "--channels", str(a.channels),
                                          "--image_width", str(a.image_width), "--clip_grad_norm", repr(a.clip_grad_norm)] +
                                         (["--skip_nonfinite"] if a.skip_nonfinite else []) +
-                                        ([] if a.ema_decay is None else ["--ema_decay", repr(a.ema_decay)]))
+                                        ([] if a.ema_decay is None else ["--ema_decay", repr(a.ema_decay)]) +
+                                        ["--frame_loss", a.frame_loss, "--gdl_weight", repr(a.gdl_weight)])
     o.ft, o.rank, o.world, o.local_batch = not a.no_ft, 0, 1, a.batch
     if os.environ.get("DVG_FORCE_ALLREDUCE") == "1":
         import torch.distributed as dist
@@ -86,7 +89,7 @@ def main():
     agg = timer.summary()
     tot = sum(v["ms"] for v in agg.values())
     out = {"launch": ("hipGraph segments (%d) + eager all-reduces" % g.n_segments) if a.segmented else
-           "hipGraph replay" if a.graph else "eager", "grad_guard": tr.guard is not None, "ema": tr.ema is not None, "model": f"{a.model}_{a.image_width}", "channels": a.channels, "batch": a.batch, "T": a.n_past + a.n_future, "ms_per_iter": round(dt * 1e3, 1),
+           "hipGraph replay" if a.graph else "eager", "grad_guard": tr.guard is not None, "ema": tr.ema is not None, "frame_loss": tr.frame_loss and tr.frame_loss.label(), "model": f"{a.model}_{a.image_width}", "channels": a.channels, "batch": a.batch, "T": a.n_past + a.n_future, "ms_per_iter": round(dt * 1e3, 1),
            "train_frames_per_s": round(a.batch * (a.n_past + a.n_future - 1) / dt, 1),
            "peak_mem_GB": round(torch.cuda.max_memory_allocated() / 2**30, 1), "timed_kernel_ms": round(tot, 1),
            "kernels": {k: {"n": v["launches"], "ms": round(v["ms"], 1),

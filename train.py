@@ -37,6 +37,7 @@ graph, and writes `model_ema.pth` beside `model.pth` (dvg_amd/ema.py, docs/DESIG
 logs them to `val_log.jsonl` and keeps `model_best.pth` (dvg_amd/validate.py, docs/DESIGN_NOTES_validation.md).
 `--lr_schedule KIND` makes `--lr` the base rate of all four optimisers and moves it every iteration by a device-side multiplier:
 warm-up, then constant | linear | cosine | step; one launch per iteration (dvg_amd/lr_schedule.py, docs/DESIGN_NOTES_lr_schedule.md).
+`--frame_loss l1|charbonnier`, `--gdl_weight G`: another pixel penalty / the gradient-difference loss in the frame terms (dvg_amd/frame_loss.py).
 """
 import argparse
 import importlib
@@ -53,7 +54,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 import utils  # noqa: E402
-from dvg_amd import datasets, ema as weight_ema, fused, lr_schedule, optim, parallel, train_state, validate, viz  # noqa: E402
+from dvg_amd import datasets, ema as weight_ema, frame_loss, fused, lr_schedule, optim, parallel, train_state, validate, viz  # noqa: E402
 from dvg_amd.data import SyntheticMovingMNIST, make_batch_generator, synthetic_video  # noqa: E402,F401
 from dvg_amd.models.gp_models import GaussianLikelihood, GPRegressionLayer1, VariationalELBO  # noqa: E402
 from dvg_amd.optim import FlatArena, FusedAdam, guard_options, guarded_step, make_guard, zero_grads  # noqa: E402,F401
@@ -113,7 +114,7 @@ def build_parser():
     p.add_argument('--synthetic_data', action='store_true',
                    help='kth | bair | ucf: train on synthetic clips of that shape instead of reading --data_root; smmnist: '
                         'the in-repo sprites even where --data_root holds MNIST')
-    for mod in (optim, weight_ema, datasets, validate, lr_schedule):   # guard flags, --ema_decay, --augment, --val_*, --lr_*
+    for mod in (optim, weight_ema, datasets, validate, lr_schedule, frame_loss):   # guard flags, --ema_decay, --augment, --val_*, --lr_*, --frame_loss
         mod.add_arguments(p)
     return p
 
@@ -210,6 +211,8 @@ class Trainer:
         # --lr_schedule: the multiplier of the iteration in one device float that every Adam launch reads; None = nothing exists
         self.lr_schedule = lr_schedule.make_schedule(opt, device, self.optimizers())
         self.validation = validate.make(opt, device)   # --val_every, rank 0: the held-out stream and the history; else None
+        self.frame_loss = frame_loss.make(opt)   # --frame_loss / --gdl_weight: the spec; None = the reference's MSE, nothing else exists
+        self.frame_terms = self.frame_loss and frame_loss.FrameTerms(self.frame_loss, device)   # the terms + the epoch line's device sums
 
     def _step(self, optimizers):
         """A step site: the optimisers that step together after one backward pass (with several ranks: after the all-reduce
@@ -246,29 +249,8 @@ class Trainer:
         self._iters = 0
 
     def allreduce_stats(self):
-        """Collectives and bytes per iteration, and their standalone duration (the same ranges all-reduced back to back,
-        timed with events on the launch stream; how much of it an iteration actually waits for is a separate measurement)."""
-        if not self.reducer.active() or not getattr(self, '_iters', 0):
-            return None
-        import torch.distributed as dist
-        ranges = [(self.rng_gp[0], self.rng_dec[1]), self.rng_enc, (self.rng_gp[0], self.rng_fp[1])] if self.opt.ft else \
-            [(self.rng_gp[0], self.rng_dec[1]), self.rng_enc]
-        scratch = torch.zeros_like(self.arena.g)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        for _ in range(3):
-            for lo, hi in ranges:
-                dist.all_reduce(scratch[lo:hi])
-        torch.cuda.synchronize()
-        reps = 10
-        e0.record()
-        for _ in range(reps):
-            for lo, hi in ranges:
-                dist.all_reduce(scratch[lo:hi])
-        e1.record()
-        torch.cuda.synchronize()
-        return {"allreduce_ms_per_iter": round(e0.elapsed_time(e1) / reps, 3),
-                "allreduces_per_iter": round(self.reducer.calls / self._iters, 2),
-                "allreduce_MB_per_iter": round(4e-6 * self.reducer.floats / self._iters, 2)}
+        """Collectives and bytes per iteration, and their standalone duration (parallel.allreduce_stats)."""
+        return parallel.allreduce_stats(self, getattr(self, '_iters', 0))
 
     # ---- mode switches (train.py:342-346,372-374) -------------------------------------------
     def train_mode(self):
@@ -527,17 +509,23 @@ class Trainer:
             # above, d loss / d elbo = -0.0001; backward starts from those seeds.  ~40 elementwise / reduction launches of torch
             # per iteration (two of them passes over all 3 S B frames) become 3.
             n_call = float(frames[0].numel() * B)
-            sq, d_x = ops.frame_losses(x_all.detach().view(S, 3, -1), frames[B:].view(S, -1),
-                                       (0.001 / n_call, 1000.0 / n_call, 0.001 / n_call))
+            if self.frame_loss is None:
+                sq, d_x = ops.frame_losses(x_all.detach().view(S, 3, -1), frames[B:].view(S, -1),
+                                           (0.001 / n_call, 1000.0 / n_call, 0.001 / n_call))
+            else:     # --frame_loss / --gdl_weight: the same pass with another penalty and the edge terms (dvg_frame_losses_ext)
+                sq, d_x = self.frame_terms.fused(x_all.detach(), frames[B:], S, B)
             wv = self._loss_weights(x_all.device, n_call, elbo.numel())       # elbo: one entry per (step, latent dim)
             loss = torch.dot(torch.cat([sq, mse_latent.view(1), elbo.detach()]), wv)
             torch.autograd.backward([x_all, pred, tgt_h, elbo], [d_x.view_as(x_all), d_pred, -d_pred, wv[4:]])
         else:
             tgt = frames[B:].view(S, 1, B, *frames.shape[1:])
-            per = x_all.view(S, 3, B, *frames.shape[1:]) - tgt
-            # nn.MSELoss per call, summed over the steps = sum of squares / elements per call
-            sq = (per * per).sum((0, 2, 3, 4, 5)) / float(per[0, 0].numel())
-            mse, ae_mse, mse_gp = sq[0], sq[1], sq[2]
+            if self.frame_loss is None:
+                per = x_all.view(S, 3, B, *frames.shape[1:]) - tgt
+                # nn.MSELoss per call, summed over the steps = sum of squares / elements per call
+                sq = (per * per).sum((0, 2, 3, 4, 5)) / float(per[0, 0].numel())
+                mse, ae_mse, mse_gp = sq[0], sq[1], sq[2]
+            else:     # --frame_loss / --gdl_weight as torch ops (frame_loss.torch_terms)
+                mse, ae_mse, mse_gp = self.frame_terms.torch_calls(x_all.view(S, 3, B, *frames.shape[1:]), tgt[:, 0])
             loss = 1000 * ae_mse + 0.001 * mse + 0.01 * mse_latent + 0.001 * mse_gp + 0.0001 * max_ll.sum()
             loss.backward()
         self._encoder_backward_and_step(
@@ -610,9 +598,12 @@ class Trainer:
                 x_pred = self.decoder([h_pred, skip])
                 x_target_pred = self.decoder([h_target, skip])
                 x_pred_gp = self.decoder([gp_mean, skip])
-            ae_mse = ae_mse + self.mse_latent_criterion(x_target_pred, x[i])
-            mse = mse + self.mse_criterion(x_pred, x[i])
-            mse_gp = mse_gp + self.mse_latent_criterion(x_pred_gp, x[i])
+            if self.frame_loss is None:
+                ae_mse = ae_mse + self.mse_latent_criterion(x_target_pred, x[i])
+                mse = mse + self.mse_criterion(x_pred, x[i])
+                mse_gp = mse_gp + self.mse_latent_criterion(x_pred_gp, x[i])
+            else:     # --frame_loss / --gdl_weight as torch ops, one step
+                mse, ae_mse, mse_gp = self.frame_terms.torch_step((mse, ae_mse, mse_gp), (x_pred, x_target_pred, x_pred_gp), x[i])
         if side is not None:
             cur.wait_stream(side)
         loss = 1000 * ae_mse + 0.001 * mse + 0.01 * mse_latent + 0.001 * mse_gp + 0.0001 * max_ll.sum()
@@ -768,8 +759,8 @@ def main(argv=None):
             print('[%02d] mse loss: %.5f (%d) %.5f' % (epoch, epoch_mse / opt.epoch_size,
                                                        epoch * opt.epoch_size * opt.batch_size, indices))
             print('     train frames/s: %.1f' % fps)
-        for part in (tr.guard, tr.ema, tr.lr_schedule):   # one read of each one's device counters: per epoch, outside the iterations
-            line = part is not None and part.epoch_line()   # every rank reads its own (the same bits everywhere), rank 0 prints
+        for part in (tr.guard, tr.ema, tr.lr_schedule, tr.frame_terms):   # one read of each one's device counters: per epoch, outside the iterations
+            line = part is not None and part.epoch_line()   # every rank reads its own (the same bits everywhere; frame loss: its shard's means), rank 0 prints
             line and rank == 0 and print(line)
         if epoch % opt.save_every == 0:
             tr.frame_predictor.eval()
