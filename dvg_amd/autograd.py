@@ -12,7 +12,7 @@ Gradient recipe per conv block  y = act(BN(conv(cat(up(x), skip)) + b)):
 
 Parameter gradients are written IN PLACE: the kernel that finishes a gradient (dvg_wgrad_finish, dvg_bn_bwd_finalize,
 dvg_gemm_nt_bias_act / dvg_colsum with `accumulate`) adds it straight into the parameter's `.grad` buffer - a view of the
-optimiser's flat gradient arena under train.Trainer - and the Function returns None for that input.  The reference's
+optimiser's flat gradient arena under trainer.Trainer - and the Function returns None for that input.  The reference's
 `loss.backward()` (train.py:240) accumulates one gradient tensor per USE of a parameter (a decoder weight is used 3 S times
 per iteration): that was 18 468 `at::native` add launches per 4 iterations here (5.5 % of the GPU time of a vgg_64 iteration).
 autograd.DIRECT_PARAM_GRADS = False returns the gradients to autograd instead (same values; tests run both).
@@ -113,7 +113,7 @@ def _dense_wgrad(w_sinks, b_sinks, dy, inputs):
         _wgrad_flush_queued = True
 
 
-# Streams other than the current one on which backward nodes may have queued weight-gradient operands (train.Trainer's
+# Streams other than the current one on which backward nodes may have queued weight-gradient operands (trainer.Trainer's
 # latent-path stream): the flush, which runs on the stream that called backward(), waits for them first.
 JOIN_STREAMS = []
 

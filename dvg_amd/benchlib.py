@@ -377,11 +377,10 @@ def measure_train(ctx: Ctx, args, graphed, allreduce: bool = True, shape=TRAIN_C
     model, width, nc, per_gpu, n_past, n_future = shape
     iters = iters or args.train_iters
     T = n_past + n_future
-    opt = train.build_parser().parse_args(["--model", model, "--channels", str(nc), "--image_width", str(width), "--dataset",
-                                           "smmnist" if (nc, width) == (1, 64) else "bair",
-                                           "--batch_size", str(per_gpu * ctx.world), "--n_past", str(n_past),
-                                           "--n_future", str(n_future), "--no_save", "--synthetic_data"])
-    opt.ft, opt.rank, opt.world, opt.local_batch = True, ctx.rank, ctx.world, per_gpu
+    opt = train.options(["--model", model, "--channels", str(nc), "--image_width", str(width), "--dataset",
+                         "smmnist" if (nc, width) == (1, 64) else "bair", "--batch_size", str(per_gpu * ctx.world),
+                         "--n_past", str(n_past), "--n_future", str(n_future), "--no_save", "--synthetic_data"],
+                        rank=ctx.rank, world=ctx.world)
     torch.manual_seed(args.seed)
     tr = train.Trainer(opt, ctx.dev)
     tr.train_mode()

@@ -84,7 +84,7 @@ class WeightAverage:
         return sd
 
     def save(self, tr, path) -> None:
-        """`model.pth`'s seven-key container with the averaged parameters (train.Trainer.save writes the live ones)."""
+        """`model.pth`'s seven-key container with the averaged parameters (trainer.Trainer.save writes the live ones)."""
         torch.save({'encoder': self.module_copy(tr.encoder), 'decoder': self.module_copy(tr.decoder),
                     'frame_predictor': self.module_copy(tr.frame_predictor),
                     'likelihood': self.state_dict_copy(tr.likelihood), 'gp_layer': self.state_dict_copy(tr.gp_layer),

@@ -172,7 +172,7 @@ def _skip_half(kind, skip, ps):
 # A train-mode forward pass that stands for k identical reference passes (train.py encodes every middle frame of a
 # sequence twice per closure: as step i's target and as step i+1's input - same weights, same batch, same outputs):
 # k momentum updates with the same batch statistics equal ONE update with momentum 1 - (1 - m)^k, and
-# num_batches_tracked advances by k.  Set by train.Trainer through `bn_passes(k)`.
+# num_batches_tracked advances by k.  Set by trainer.Trainer through `bn_passes(k)`.
 # (This and the scoped settings further down live in one holder: a `with` form sets its fields and puts the former values back
 # on exit.)
 _scope = types.SimpleNamespace(passes=1, groups=None, trace=None, share=None)
@@ -348,7 +348,7 @@ def declare_frozen_skips(skips) -> None:
 
 def share_skip_halves():
     """Training-side twin of the rollout hoisting: inside this scope the decoder calls that receive the SAME skip
-    tensors share one skip half per concat block, forward and backward (autograd._SkipHalf).  train.Trainer opens one
+    tensors share one skip half per concat block, forward and backward (autograd._SkipHalf).  trainer.Trainer opens one
     scope per time step around the three decoder calls of train.py:227-231."""
     return _scoped(share={})
 

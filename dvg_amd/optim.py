@@ -7,7 +7,7 @@ parameter group lives in ONE flat fp32 buffer: parameters are re-pointed at view
 two more, the GRADIENTS are views of a fourth (`p.grad` is set to its view, so backward accumulates straight into
 the flat buffer) and a step is ONE `dvg_adam_step` launch per group.
 
-`FlatArena`: several optimisers can carve their groups out of one shared arena (train.Trainer does: GP, likelihood,
+`FlatArena`: several optimisers can carve their groups out of one shared arena (trainer.Trainer does: GP, likelihood,
 LSTM, decoder, encoder in that order), so that the data-parallel gradient all-reduce (dvg_amd/parallel.py) runs on
 contiguous ranges of ONE buffer - no gather into a communication buffer, no scatter back, no copy into the
 optimiser's buffer.
@@ -55,6 +55,7 @@ class FusedAdam(torch.optim.Optimizer):
         self.arena = arena
         self._flat = {}   # group index -> dict(p, g, m, v, params, offsets, gviews, tdev, lo, hi)
         self._captured_groups = []   # groups stepped while a hipGraph was being captured (see after_graph_replay)
+        self._graph_stale = False    # an eager step() or a restored state since that capture (see begin_capture)
         # one device fp32 (an lr_schedule.LrSchedule's multiplier) every launch of step() multiplies its group's rate with, read on
         # the device (dvg_adam_step_scheduled); None: the rate is param_groups[...]['lr'] and the launches are the unscheduled ones
         self.lr_scale: Optional[torch.Tensor] = None
@@ -116,7 +117,7 @@ class FusedAdam(torch.optim.Optimizer):
 
     def state_dict(self):
         """torch.optim layout, but every per-parameter tensor is a COPY that owns its storage: `exp_avg` / `exp_avg_sq` are
-        views of the flat moment buffers (of the shared arena under train.Trainer), and torch.save writes the whole storage
+        views of the flat moment buffers (of the shared arena under trainer.Trainer), and torch.save writes the whole storage
         behind a view - the GP optimiser's entry of a checkpoint (train.py:385) would carry the Adam moments of every
         module (+2 x all parameter bytes)."""
         self.sync_step_counts()
@@ -223,7 +224,7 @@ class FusedAdam(torch.optim.Optimizer):
 
     def check_graph_fresh(self) -> None:
         """Call BEFORE replaying a captured graph: raises when an eager step() ran since the capture (nothing has executed yet)."""
-        if getattr(self, "_graph_stale", False) and self._captured_groups:
+        if self._graph_stale and self._captured_groups:
             raise RuntimeError("FusedAdam: an eager step() ran since the graph was captured: its device-side step counts are "
                                "stale (a replay would apply wrong Adam bias corrections).  Re-capture after eager steps.")
 
@@ -231,7 +232,7 @@ class FusedAdam(torch.optim.Optimizer):
         """The replayed kernels stepped the parameters through raw pointers: advance the host-side step counts (state_dict,
         torch.optim compatibility) and the version counters the packed-weight caches key on.  Raises when an eager step()
         ran since the capture (see begin_capture: the replay just applied stale bias corrections)."""
-        if getattr(self, "_graph_stale", False) and self._captured_groups:
+        if self._graph_stale and self._captured_groups:
             raise RuntimeError("FusedAdam: a captured graph was replayed after an eager step(): its device-side step counts "
                                "are stale (wrong Adam bias corrections were applied).  Re-capture after eager steps.")
         for gi in self._captured_groups:

@@ -9,7 +9,7 @@ of that buffer, in place: no gather into a communication buffer, no scatter back
 few large messages let RCCL use all links at once, whereas per-parameter all-reduces (170 tensors, many of them
 64-512 floats) would be latency-bound.  `ArenaReducer.start()` issues the collective asynchronously (RCCL runs it
 on its own stream, ordered after the work already queued on the caller's stream) and `finish()` makes the caller's
-stream wait for it: train.Trainer starts the decoder / LSTM / GP range as soon as the decoder phase of the backward
+stream wait for it: trainer.Trainer starts the decoder / LSTM / GP range as soon as the decoder phase of the backward
 pass is done and the encoder range after the encoder phase, so the first - larger - collective overlaps the encoder
 backward.  BatchNorm uses per-replica statistics (DDP semantics).
 """
@@ -100,7 +100,7 @@ class ArenaReducer:
 
 class FlatGradReducer:
     """Average the gradients of an arbitrary parameter list with one all-reduce of a gathered flat buffer (for
-    parameters that do not live in a FusedAdam arena; train.Trainer uses ArenaReducer)."""
+    parameters that do not live in a FusedAdam arena; trainer.Trainer uses ArenaReducer)."""
 
     def __init__(self, params: Iterable[torch.nn.Parameter], group=None):
         self.params: List[torch.nn.Parameter] = [p for p in params if p.requires_grad]
@@ -181,7 +181,7 @@ def broadcast_parameters(modules: Iterable[torch.nn.Module], src: int = 0, group
 
 
 def allreduce_stats(tr, iters: int):
-    """train.Trainer.allreduce_stats: collectives and bytes per iteration, and their standalone duration (the same ranges
+    """trainer.Trainer.allreduce_stats: collectives and bytes per iteration, and their standalone duration (the same ranges
     all-reduced back to back, timed with events on the launch stream; how much of it an iteration actually waits for is a separate
     measurement).  `iters`: the iterations the reducer's counts cover; None without
     an active reducer or before the first counted iteration."""

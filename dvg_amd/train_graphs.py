@@ -1,7 +1,7 @@
 """How train.py replays its iterations: one hipGraph per iteration (GraphedIteration), a chain of hipGraphs cut at the gradient
 all-reduces for several ranks (SegmentedIteration), and the background thread that draws the next batch while the GPU works
-(BatchPrefetcher).  Split from train.py in r06 (re-exported there: `train.GraphedIteration` etc. keep working); the closures
-and the Trainer state they drive stay in train.py."""
+(BatchPrefetcher).  Re-exported by train.py (`train.GraphedIteration` etc.); the closures, the iteration body that is captured
+here (Trainer._iteration_dev) and the Trainer state they drive are in dvg_amd/trainer.py."""
 import sys
 
 import torch
@@ -35,7 +35,7 @@ class GraphedIteration:
     def _signature(self, x):
         lrs = tuple(g['lr'] for o in self.tr.optimizers() for g in o.param_groups)
         return (lrs, tuple(tuple(t.shape) for t in x), self.tr.opt.ft, tuple(m.training for m in self.tr.modules),
-                getattr(self.tr, "state_loads", 0))     # Trainer.load_state_dict: another state behind the same pointers
+                self.tr.state_loads)     # Trainer.load_state_dict: another state behind the same pointers
 
     def _release(self):
         """Drop the captured graph(s) and everything they keep alive BEFORE a re-capture allocates a new private pool
@@ -64,14 +64,7 @@ class GraphedIteration:
             self._body()
 
     def _body(self):
-        tr = self.tr
-        tr.lr_schedule is None or tr.lr_schedule.tick()   # --lr_schedule: first, as Trainer.iteration (the first segment)
-        mse_latent, loss = tr._train_model_dev(self.static_x)
-        fp = gp = None
-        if tr.opt.ft:
-            fp, gp = tr._finetune_dev(self.static_x)
-        tr.ema is None or tr.ema.update()      # --ema_decay: once per iteration, after the last step site (the last segment)
-        self.outs = (mse_latent, loss, fp, gp)
+        self.outs = self.tr._iteration_dev(self.static_x)   # the eager iteration's launches: schedule tick first, EMA update last
 
     def __call__(self, x):
         tr = self.tr
@@ -103,19 +96,13 @@ class GraphedIteration:
         for dst, src in zip(self.static_x, x):
             dst.copy_(src)
         self._replay()
-        tr._iters = getattr(tr, '_iters', 0) + 1
         for o in tr.optimizers():
             o.after_graph_replay()
         with torch.no_grad():
             for m in tr.modules:
                 for b in m.buffers():
                     torch.autograd.graph.increment_version(b)   # BatchNorm running statistics
-        mse_latent, loss, fp, gp = self.outs
-        T = tr.opt.n_past + tr.opt.n_future
-        v = float(mse_latent) / T
-        tr.last_loss = float(loss)
-        temp = (float(fp) + float(gp)) / T if tr.opt.ft else 0
-        return v, v, temp
+        return tr._iteration_result(self.outs)
 
 
 class SegmentedIteration(GraphedIteration):

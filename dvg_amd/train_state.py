@@ -1,6 +1,6 @@
 """The file side of `train.py --resume`: where a training state lives, how it is written so that a kill cannot damage the last
 good one, how it is read so that every failure is one line, and the fingerprint that refuses a state from another configuration.
-What the state IS - which tensors and counters of a train.Trainer - is `capture` / `restore` below, which
+What the state IS - which tensors and counters of a Trainer (dvg_amd/trainer.py) - is `capture` / `restore` below, which
 `Trainer.state_dict` / `Trainer.load_state_dict` call (docs/DESIGN_NOTES_resume.md lists every entry and why it is state).
 
 One process: `<output_path>/train_state.pth` holds everything.  Several ranks: rank 0 writes the shared part (parameters, Adam
@@ -142,8 +142,7 @@ def set_random_streams(rng: dict, device) -> None:
 def detached_copy(module):
     """A deep copy of `module` whose parameters and buffers are fresh tensors with their OWN storage and no gradient
     (copy.deepcopy alone clones the whole storage behind every arena view, and would copy `.grad` as well).  Trainer.save's
-    helper; it lives here, beside the other code that writes training state, because train.py is held to 800 lines
-    (tests/test_host_logic.py) and the gradient-guard flags needed the room."""
+    helper (checkpoint below), beside the other code that writes training state."""
     import copy
     memo = {}
     for p in module.parameters():
@@ -172,7 +171,7 @@ def checkpoint(tr) -> dict:
             'gp_layer': owned_state_dict(tr.gp_layer.state_dict()), 'gp_layer_optimizer': tr.optimizer.state_dict(), 'opt': tr.opt}
 
 
-# ---- what the state of a train.Trainer is -----------------------------------------------------------------------------------
+# ---- what the state of a trainer.Trainer is ---------------------------------------------------------------------------------
 def named_optimizers(tr):
     return (("gp", tr.optimizer), ("frame_predictor", tr.frame_predictor_optimizer), ("decoder", tr.decoder_optimizer),
             ("encoder", tr.encoder_optimizer))
@@ -202,7 +201,7 @@ def capture(tr, epoch=0, train_gen=None, test_gen=None, shared=True) -> dict:
     stopped.  epoch: the number of the NEXT epoch; train_gen / test_gen: the batch generators whose positions to record;
     shared=False leaves out what rank 0 writes for all ranks.  Every tensor owns its storage (a view of the arena would make
     torch.save write the whole arena behind it)."""
-    writer = getattr(tr, "_plot_writer", None)
+    writer = tr._plot_writer
     mine = {"rank": tr.rank,
             "buffers": {k: b.detach().clone() for k, b in named_buffers(tr)},
             "rng": random_streams(tr.dev),
@@ -222,16 +221,13 @@ def capture(tr, epoch=0, train_gen=None, test_gen=None, shared=True) -> dict:
                          "g_gp": a.g[lo:hi].detach().clone(), "g_gp_range": (lo, hi)},
                   optimizers={name: o.host_state() for name, o in named_optimizers(tr)},
                   scheduler=tr.scheduler.state_dict())
-        ema = getattr(tr, "ema", None)
-        if ema is not None:      # --ema_decay: the average and its count of updates (dvg_amd/ema.py); no key without the flag
-            st = ema.state()
+        if tr.ema is not None:   # --ema_decay: the average and its count of updates (dvg_amd/ema.py); no key without the flag
+            st = tr.ema.state()
             sd["arena"]["e"], sd["ema"] = st["e"], st["ema"]
-        sched = getattr(tr, "lr_schedule", None)
-        if sched is not None:    # --lr_schedule: the spec and the count of iterations (dvg_amd/lr_schedule.py); no key without the flag
-            sd["lr_schedule"] = sched.state()
-        val = getattr(tr, "validation", None)
-        if val is not None:      # --val_every: the history and the best scores (dvg_amd/validate.py); no key without the flag
-            sd["validation"] = val.state()
+        if tr.lr_schedule is not None:   # --lr_schedule: the spec and the count of iterations (dvg_amd/lr_schedule.py); no key without the flag
+            sd["lr_schedule"] = tr.lr_schedule.state()
+        if tr.validation is not None:    # --val_every: the history and the best scores (dvg_amd/validate.py); no key without the flag
+            sd["validation"] = tr.validation.state()
     return sd
 
 
@@ -247,23 +243,21 @@ def restore(tr, sd, train_gen=None, test_gen=None, path="<state>") -> int:
         getattr(a, name).copy_(saved[name])
     lo, hi = saved["g_gp_range"]
     a.g[lo:hi].copy_(saved["g_gp"])
-    ema = getattr(tr, "ema", None)
-    if ema is not None:          # the decay of THIS run applies; a state without an average restarts it from the restored weights
-        ema.load_state(saved.get("e"), sd.get("ema"))
+    if tr.ema is not None:       # the decay of THIS run applies; a state without an average restarts it from the restored weights
+        tr.ema.load_state(saved.get("e"), sd.get("ema"))
         if "e" not in saved and tr.rank == 0:
             print(f"{path}: no weight average in the file: --ema_decay restarts it from the restored weights", flush=True)
     elif "e" in saved and tr.rank == 0:
         print(f"{path}: the weight average in the file is ignored: this run has no --ema_decay", flush=True)
-    val = getattr(tr, "validation", None)
-    if val is not None:          # a state without validations starts an empty history
-        val.load_state(sd.get("validation"))
+    if tr.validation is not None:   # a state without validations starts an empty history
+        tr.validation.load_state(sd.get("validation"))
     elif "validation" in sd and tr.rank == 0 and not getattr(tr.opt, "val_every", 0):
         print(f"{path}: the validation history in the file is ignored: this run has no --val_every", flush=True)
     for name, o in named_optimizers(tr):
         o.load_host_state(sd["optimizers"][name])      # step counts (begin_capture seeds the device counts from them), lr
     tr.scheduler.load_state_dict(sd["scheduler"])
     from . import lr_schedule    # --lr_schedule: the count of iterations, a state from before the flag counts from its global step
-    lr_schedule.restore(getattr(tr, "lr_schedule", None), sd, path, sd.get("global_step", global_step(tr)), tr.rank,
+    lr_schedule.restore(tr.lr_schedule, sd, path, sd.get("global_step", global_step(tr)), tr.rank,
                         tr.encoder_optimizer.param_groups[0]["lr"])
     mine = sd[RANK_KEY]
     buffers = dict(named_buffers(tr))
@@ -281,11 +275,11 @@ def restore(tr, sd, train_gen=None, test_gen=None, path="<state>") -> int:
     # the host-side memo of the `variational_params_initialized` buffer just restored (read here, not during a capture)
     tr.gp_layer._init_checked = bool(int(tr.gp_layer.variational_strategy.variational_params_initialized.item()))
     # a captured iteration holds device step counts and packs of the old state: GraphedIteration re-captures when this moves
-    tr.state_loads = getattr(tr, "state_loads", 0) + 1
+    tr.state_loads += 1
     set_random_streams(mine["rng"], tr.dev)
     if mine.get("plot_writer") is not None:
         from . import viz
-        tr._plot_writer = getattr(tr, "_plot_writer", None) or viz.PlotWriter(getattr(tr.opt, "seed", 1))
+        tr._plot_writer = tr._plot_writer or viz.PlotWriter(getattr(tr.opt, "seed", 1))
         tr._plot_writer.rng.set_state(mine["plot_writer"])
     for gen, pos in ((train_gen, mine["data"]["train"]), (test_gen, mine["data"]["test"])):
         if gen is not None and pos is not None:

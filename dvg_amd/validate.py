@@ -191,7 +191,7 @@ class Validator:
 
     @torch.no_grad()
     def run(self, modules, trainer=None) -> dict:
-        """One validation of (encoder, decoder, frame_predictor, gp_layer, likelihood).  trainer: the train.Trainer that owns
+        """One validation of (encoder, decoder, frame_predictor, gp_layer, likelihood).  trainer: the trainer.Trainer that owns
         them, if one does (its fine-tuning cache is put back as well)."""
         live = _Live(modules, trainer)
         try:
@@ -244,7 +244,7 @@ class _Live:
         self.flags = [(sm, sm.training) for m in modules for sm in m.modules()]
         self.fp, self.trainer = modules[2], trainer
         self.hidden, self.batch_size = getattr(self.fp, "hidden", None), getattr(self.fp, "batch_size", None)
-        self.ft_cache = getattr(trainer, "_ft_cache", None)
+        self.ft_cache = trainer._ft_cache if trainer is not None else None
         self.skips, self.derived = _derived.skip_mark(), _derived.derived_mark()
 
     def put_back(self):
@@ -320,7 +320,7 @@ def make(opt, device):
 
 def after_epoch(tr, epoch: int) -> None:
     """train.py's call, once per epoch after its log lines and checkpoint: validates when the epoch is one of every N."""
-    v = getattr(tr, "validation", None)
+    v = tr.validation
     if v is not None and epoch % v.every == 0:
         v.validate(tr, epoch)
 

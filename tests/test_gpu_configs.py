@@ -96,10 +96,8 @@ def test_train_step_at_config_shapes(model, width, nc, batch):
     import utils
     from dvg_amd.data import synthetic_video
     torch.manual_seed(11)
-    o = train.build_parser().parse_args(["--model", model, "--image_width", str(width), "--channels", str(nc),
-                                         "--batch_size", str(batch), "--n_past", "2", "--n_future", "2", "--dataset",
-                                         "bair", "--no_save", "--synthetic_data"])
-    o.ft, o.rank, o.world, o.local_batch = True, 0, 1, batch
+    o = train.options(["--model", model, "--image_width", str(width), "--channels", str(nc), "--batch_size", str(batch),
+                       "--n_past", "2", "--n_future", "2", "--dataset", "bair", "--no_save", "--synthetic_data"])
     tr = train.Trainer(o, torch.device(DEV))
     tr.train_mode()
     x, _ = utils.normalize_data(o, torch.cuda.FloatTensor, synthetic_video(batch, 4, nc, width, seed=5))

@@ -11,22 +11,18 @@ Shapes: n around the 8 192-float chunk (a one-vector launch, two vectors, the la
 chunks and a last workgroup with a single float4, 2^20 + 12); dcgan_64 at batch 4, n_past 2, n_future 2 for the Trainer."""
 import io
 import os
-import subprocess
-import sys
 import types
 
 import numpy as np
 import pytest
 import torch
 
-from tests import ema_ref as ref
+from tests import ema_ref as ref, train_harness
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
 CHUNK = ref.CHUNK
 SIZES = [4, 8, CHUNK - 4, CHUNK, CHUNK + 4, 3 * CHUNK + 8, 2 ** 20 + 12]
-ARGS = ["--model", "dcgan", "--batch_size", "4", "--n_past", "2", "--n_future", "2", "--n_eval", "4", "--dataset", "smmnist"]
 KEYS = {"encoder", "decoder", "frame_predictor", "likelihood", "gp_layer", "gp_layer_optimizer", "opt"}
 
 
@@ -223,29 +219,9 @@ def test_wrapper_checks():
 
 
 # ---- the Trainer ------------------------------------------------------------------------------------------------------------------
-def _opt(extra=()):
-    import train
-    o = train.build_parser().parse_args(ARGS + ["--niter", "1", "--epoch_size", "1", "--no_save"] + list(extra))
-    o.ft = not o.no_ft
-    o.rank, o.world, o.local_batch = 0, 1, o.batch_size
-    return o
-
-
-def _trainer(extra=(), seed=3):
-    import train
-    torch.manual_seed(seed)
-    torch.cuda.manual_seed_all(seed)
-    tr = train.Trainer(_opt(extra), torch.device(DEV))
-    tr.train_mode()
-    return tr
-
-
 @pytest.fixture(scope="module")
 def batches():
-    import utils
-    from dvg_amd.data import SyntheticMovingMNIST
-    gen = SyntheticMovingMNIST(seq_len=4, seed=9)
-    return [utils.normalize_data(_opt(), torch.cuda.FloatTensor, gen.batch(4))[0] for _ in range(4)]
+    return train_harness.make_batches(4)
 
 
 def _iterate(tr, xs, graphed, warmup=1, resume_after=None, flags=()):
@@ -261,7 +237,7 @@ def _iterate(tr, xs, graphed, warmup=1, resume_after=None, flags=()):
             torch.save(tr.state_dict(epoch=0), f)
             f.seek(0)
             del tr, step
-            tr = _trainer(flags, seed=99)
+            tr = train_harness.trainer(flags, seed=99)
             tr.load_state_dict(torch.load(f, weights_only=False))
             step = train.GraphedIteration(tr, warmup=max(warmup - resume_after, 0)) if graphed else tr.iteration
         step(x)
@@ -287,7 +263,7 @@ def _walk(o):
 
 
 def test_without_the_flag_nothing_exists(batches, tmp_path):
-    tr = _trainer()
+    tr = train_harness.trainer()
     assert tr.ema is None
     tr.iteration(batches[0])
     sd = tr.state_dict()
@@ -301,10 +277,10 @@ def runs(batches):
     """Four iterations without the flag and with --ema_decay 0.9, eager and as GraphedIteration (capture at the second)."""
     out = {}
     for graphed in (False, True):
-        plain, _ = _iterate(_trainer(), batches, graphed)
+        plain, _ = _iterate(train_harness.trainer(), batches, graphed)
         kept = {n: getattr(plain.arena, n).clone() for n in ("p", "m", "v")}
         del plain
-        avg = _trainer(["--ema_decay", "0.9"])
+        avg = train_harness.trainer(["--ema_decay", "0.9"])
         p0 = avg.arena.p.clone()
         assert torch.equal(avg.ema.e, p0) and avg.ema.e.data_ptr() != avg.arena.p.data_ptr() and int(avg.ema.updates) == 0
         avg, ps = _iterate(avg, batches, graphed)
@@ -379,10 +355,10 @@ def test_resume_continues_the_average(runs, batches, graphed):
     capture at the fourth iteration.  The rule of test_gpu_resume.test_continuation: A-versus-A is measured first, bit-identical
     runs demand a bit-identical continuation - parameters, average and count."""
     flags = ["--ema_decay", "0.9"]
-    a1, _ = _iterate(_trainer(flags), batches, graphed, warmup=3)
-    a2, _ = _iterate(_trainer(flags), batches, graphed, warmup=3)
+    a1, _ = _iterate(train_harness.trainer(flags), batches, graphed, warmup=3)
+    a2, _ = _iterate(train_harness.trainer(flags), batches, graphed, warmup=3)
     noise = float((a2.arena.p - a1.arena.p).abs().max())
-    b, _ = _iterate(_trainer(flags), batches, graphed, warmup=3, resume_after=2, flags=flags)
+    b, _ = _iterate(train_harness.trainer(flags), batches, graphed, warmup=3, resume_after=2, flags=flags)
     print(f"\nresume with an average ({'graph' if graphed else 'eager'}): A vs A {noise:.3e}")
     assert int(b.ema.updates) == int(a1.ema.updates) == 4
     if noise == 0.0:
@@ -393,7 +369,7 @@ def test_resume_continues_the_average(runs, batches, graphed):
 
 def test_states_with_and_without_an_average(batches, capsys):
     flags = ["--ema_decay", "0.9"]
-    with_avg, _ = _iterate(_trainer(flags), batches[:2], False)
+    with_avg, _ = _iterate(train_harness.trainer(flags), batches[:2], False)
     sd = with_avg.state_dict(epoch=1)
     assert sd["ema"] == {"decay": 0.9, "updates": 2} and torch.equal(sd["arena"]["e"], with_avg.ema.e)
     assert sd["format"] == 1 and "ema_decay" not in sd["fingerprint"]
@@ -401,9 +377,9 @@ def test_states_with_and_without_an_average(batches, capsys):
     assert len(tensors) > 20
     for t in tensors:                                                  # every tensor of the state owns its storage
         assert t.untyped_storage().nbytes() == t.numel() * t.element_size()
-    plain, _ = _iterate(_trainer(), batches[:1], False)
+    plain, _ = _iterate(train_harness.trainer(), batches[:1], False)
     # a state without an average into a run with the flag: the average restarts from the restored parameters
-    fresh = _trainer(flags, seed=99)
+    fresh = train_harness.trainer(flags, seed=99)
     fresh.ema.updates.fill_(7)
     capsys.readouterr()
     fresh.load_state_dict(plain.state_dict(epoch=1))
@@ -411,12 +387,12 @@ def test_states_with_and_without_an_average(batches, capsys):
     assert torch.equal(fresh.arena.p, plain.arena.p) and torch.equal(fresh.ema.e, plain.arena.p) and int(fresh.ema.updates) == 0
     assert out.count("\n") == 1 and "restarts" in out
     # a state with an average into a run without the flag: loads, says so, builds nothing
-    bare = _trainer(seed=98)
+    bare = train_harness.trainer(seed=98)
     bare.load_state_dict(sd)
     out = capsys.readouterr().out
     assert bare.ema is None and torch.equal(bare.arena.p, with_avg.arena.p) and out.count("\n") == 1 and "ignored" in out
     # with the flag: through the existing buffers, this run's decay
-    other = _trainer(["--ema_decay", "0.5"], seed=97)
+    other = train_harness.trainer(["--ema_decay", "0.5"], seed=97)
     e_ptr = other.ema.e.data_ptr()
     other.load_state_dict(sd)
     assert capsys.readouterr().out == ""
@@ -429,7 +405,7 @@ def test_command_line_writes_and_reads_the_averaged_checkpoint(tmp_path, capsys)
     import generate_frames
     import train
     out = str(tmp_path / "run")
-    tr = train.main(ARGS + ["--ema_decay", "0.5", "--niter", "1", "--epoch_size", "2", "--no_images", "--output_path", out])
+    tr = train.main(train_harness.ARGS + ["--ema_decay", "0.5", "--niter", "1", "--epoch_size", "2", "--no_images", "--output_path", out])
     text = capsys.readouterr().out
     lines = text.splitlines()
     at = [i for i, ln in enumerate(lines) if ln.startswith("     train frames/s:")]
@@ -482,15 +458,6 @@ def test_command_line_writes_and_reads_the_averaged_checkpoint(tmp_path, capsys)
     assert "smmnist_ema.pth" in msg and "model_ema.pth" in msg and "\n" not in msg
 
 
-def _free_port() -> int:
-    import socket
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def test_two_ranks_average_alike_and_resume(tmp_path):
     """Two ranks on one GPU over gloo (the rehearsal switches and fresh child processes of test_two_ranks_clip_alike): every rank
     computes the same average from the same parameters without a collective - as a chain of hipGraphs (SegmentedIteration,
@@ -498,15 +465,11 @@ def test_two_ranks_average_alike_and_resume(tmp_path):
     + one end with the same bits in the parameters and in the average.  The resume legs run with --no_hip_graph: a fresh process
     starts with eager warm-up iterations where the uninterrupted run replays, and those agree to a tolerance only
     (test_graphed_iteration_matches_eager) - the single-process test above lines the capture points up instead."""
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    env.update(DVG_DP_SHARE_GPU="1", DVG_DP_BACKEND="gloo", OMP_NUM_THREADS="2")
     args = ["--model", "dcgan", "--dataset", "smmnist", "--n_past", "2", "--n_future", "2", "--n_eval", "4", "--batch_size", "8",
             "--save_every", "1", "--no_images", "--print_param_checksum", "--ema_decay", "0.9"]
 
     def run(extra):
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-               "--master-port", str(_free_port()), os.path.join(ROOT, "train.py")] + args + extra
-        r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        r = train_harness.run_train_py(args + extra, ranks=2, env=train_harness.REHEARSAL)
         assert r.returncode == 0, r.stderr[-2000:]
         assert "capture failed" not in r.stderr
         sums = {ln.split()[1]: ln.split()[4:] for ln in r.stdout.splitlines() if " ema checksum " in ln}

@@ -9,7 +9,7 @@ import ctypes
 import pytest
 import torch
 
-from tests import frame_loss_ref as ref
+from tests import frame_loss_ref as ref, train_harness
 from tests.common import rel_err, rel_err_elem
 
 pytestmark = pytest.mark.gpu
@@ -164,33 +164,12 @@ def test_bad_arguments_return_their_code_and_launch_nothing():
 
 
 # ---- the Trainer ---------------------------------------------------------------------------------------------------------------------
-ARGS = ["--batch_size", "4", "--n_past", "2", "--n_future", "2", "--n_eval", "4", "--dataset", "smmnist"]
 L1_GDL = ["--frame_loss", "l1", "--gdl_weight", "1"]
-
-
-def _opt(extra=(), model="dcgan"):
-    import train
-    o = train.build_parser().parse_args(["--model", model] + ARGS + ["--niter", "1", "--epoch_size", "1", "--no_save"] + list(extra))
-    o.ft = not o.no_ft
-    o.rank, o.world, o.local_batch = 0, 1, o.batch_size
-    return o
-
-
-def _trainer(extra=(), seed=3, model="dcgan"):
-    import train
-    torch.manual_seed(seed)
-    torch.cuda.manual_seed_all(seed)
-    tr = train.Trainer(_opt(extra, model), torch.device(DEV))
-    tr.train_mode()
-    return tr
 
 
 @pytest.fixture(scope="module")
 def batches():
-    import utils
-    from dvg_amd.data import SyntheticMovingMNIST
-    gen = SyntheticMovingMNIST(seq_len=4, seed=9)
-    return [utils.normalize_data(_opt(), torch.cuda.FloatTensor, gen.batch(4))[0] for _ in range(5)]
+    return train_harness.make_batches(5)
 
 
 def _one_train_model(tr, x):
@@ -210,9 +189,9 @@ def _compare_ranges(tr, ga, gb, bar):
 
 
 def test_trainer_builds_a_spec_only_when_asked():
-    plain = _trainer()
+    plain = train_harness.trainer()
     assert plain.frame_loss is None and plain.frame_terms is None
-    tr = _trainer(L1_GDL)
+    tr = train_harness.trainer(L1_GDL)
     assert tr.frame_loss.label() == "l1 + 1 gdl" and float(tr.frame_terms.acc.abs().max()) == 0.0
     assert tr.frame_terms.epoch_line() == "     frame loss: l1 + 1 gdl   pixel 0  gdl 0"
     from dvg_amd import graphs
@@ -226,7 +205,7 @@ def test_the_default_flags_change_no_bit(batches):
     """--frame_loss mse --gdl_weight 0 is the run without the flags: the same code path, loss and parameters bit-equal."""
     res = []
     for extra in ([], ["--frame_loss", "mse", "--gdl_weight", "0"]):
-        tr = _trainer(extra)
+        tr = train_harness.trainer(extra)
         assert tr.frame_loss is None
         loss, _ = _one_train_model(tr, batches[0])
         res.append((loss, tr.arena.p.clone()))
@@ -241,7 +220,7 @@ def test_fused_losses_match_the_torch_composition(batches):
     range of the gradient arena `d <= 2e-3 * na` for dcgan (lines 526-527)."""
     res, stats = [], []
     for fused in (True, False):
-        tr = _trainer(L1_GDL)
+        tr = train_harness.trainer(L1_GDL)
         tr.fused_losses = fused
         res.append(_one_train_model(tr, batches[0]))
         stats.append(tr.frame_terms.read_and_reset())
@@ -261,7 +240,7 @@ def test_step_by_step_path_matches_the_batched_one(batches):
     last-bit difference of the two forward passes may flip a sign: the value only."""
     res = []
     for tb in (False, True):
-        tr = _trainer(["--frame_loss", "charbonnier"])
+        tr = train_harness.trainer(["--frame_loss", "charbonnier"])
         tr.time_batched = tb
         res.append(_one_train_model(tr, batches[0]))
     (la, ga), (lb, gb) = res
@@ -270,7 +249,7 @@ def test_step_by_step_path_matches_the_batched_one(batches):
     _compare_ranges(tr, ga, gb, 2e-3)
     vals = []
     for tb in (False, True):
-        tr = _trainer(L1_GDL)
+        tr = train_harness.trainer(L1_GDL)
         tr.time_batched = tb
         vals.append(_one_train_model(tr, batches[0])[0])
     print(f"l1 + gdl: step by step {vals[0]!r} batched {vals[1]!r}")
@@ -282,16 +261,12 @@ def test_graph_replay_matches_eager_with_the_flags_on(batches):
     hipGraph, against five eager iterations - within the bars of test_one_capture_serves_a_multiplier_that_moves_every_iteration
     (tests/test_gpu_lr_schedule.py) and of the EMA graph test: values 2e-4, parameters / buffers / moments rtol 2e-3 atol 2e-5.
     The epoch line's device sums advance inside the replayed graph: the counts are equal and the means agree like the values."""
-    import train
     res = []
     for graphed in (False, True):
-        tr = _trainer(L1_GDL, seed=11)
-        step = train.GraphedIteration(tr, warmup=2) if graphed else tr.iteration
-        torch.manual_seed(77)
-        out = []
-        for x in batches[:5]:
-            out.append((step(x) + (tr.last_loss,), step.graph if graphed else None))
-        torch.cuda.synchronize()
+        tr = train_harness.trainer(L1_GDL, seed=11)
+        step, out = train_harness.iterate(tr, batches[:5], graphed, warmup=2,
+                                          each=lambda tr, step, i: (tr.last_loss, step.graph if graphed else None))
+        out = [(r + (loss,), graph) for r, (loss, graph) in out]
         if graphed:
             assert not step.failed and out[2][1] is not None and all(g is out[2][1] for _, g in out[2:])
             assert out[0][1] is None and out[1][1] is None and step.calls == 5

@@ -11,23 +11,18 @@ Shapes: n around the 16 384-float chunk of the reduction (one block, the last fl
 blocks and a ragged last one), dcgan_64 at batch 4, n_past 2, n_future 2 for the Trainer (the shapes of
 test_graphed_iteration_matches_eager and test_gpu_resume)."""
 import io
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from tests import gradguard_ref as ref
+from tests import gradguard_ref as ref, train_harness
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
 CHUNK = ref.CHUNK
 BAR = 1.2e-7
 SIZES = [4, 1024, CHUNK - 4, CHUNK, CHUNK + 4, 3 * CHUNK + 8, 2 ** 20 + 12]
-ARGS = ["--model", "dcgan", "--batch_size", "4", "--n_past", "2", "--n_future", "2", "--n_eval", "4", "--dataset", "smmnist"]
 
 
 # ---- the kernels ---------------------------------------------------------------------------------------------------------------
@@ -307,50 +302,14 @@ def test_load_state_dict_forgets_pending_skips():
 
 
 # ---- the Trainer ---------------------------------------------------------------------------------------------------------------
-def _opt(extra=()):
-    import train
-    o = train.build_parser().parse_args(ARGS + ["--niter", "1", "--epoch_size", "1", "--no_save"] + list(extra))
-    o.ft = not o.no_ft
-    o.rank, o.world, o.local_batch = 0, 1, o.batch_size
-    return o
-
-
-def _trainer(extra=(), seed=3):
-    import train
-    torch.manual_seed(seed)
-    torch.cuda.manual_seed_all(seed)
-    tr = train.Trainer(_opt(extra), torch.device(DEV))
-    tr.train_mode()
-    return tr
-
-
 @pytest.fixture(scope="module")
 def batches():
-    import utils
-    from dvg_amd.data import SyntheticMovingMNIST
-    gen = SyntheticMovingMNIST(seq_len=4, seed=9)
-    return [utils.normalize_data(_opt(), torch.cuda.FloatTensor, gen.batch(4))[0] for _ in range(4)]
-
-
-def _iterate(tr, xs, graphed, warmup=1):
-    import train
-    step = train.GraphedIteration(tr, warmup=warmup) if graphed else tr.iteration
-    torch.manual_seed(77)                    # the GP samples of the iterations
-    for x in xs:
-        step(x)
-    torch.cuda.synchronize()
-    if graphed:
-        assert not step.failed and step.graph is not None
-    return step
-
-
-def _arena(tr):
-    return {n: getattr(tr.arena, n).clone() for n in ("p", "m", "v")}
+    return train_harness.make_batches(4)
 
 
 def test_trainer_builds_a_guard_only_when_asked(batches):
-    assert _trainer().guard is None
-    tr = _trainer(["--skip_nonfinite"])
+    assert train_harness.trainer().guard is None
+    tr = train_harness.trainer(["--skip_nonfinite"])
     assert tr.guard is not None and tr.guard.max_norm == 0.0 and tr.guard.skip_nonfinite
     assert tr.guard.partials.numel() >= sum(ref.blocks(f["g"].numel()) for o in tr.optimizers() for f in o._flat.values())
 
@@ -359,10 +318,10 @@ def test_trainer_builds_a_guard_only_when_asked(batches):
 def test_a_guard_that_never_bites_changes_nothing(batches, graphed):
     """--clip_grad_norm 1e30: factor exactly 1 at every site - parameters and both moments bit-equal to the unguarded Trainer
     from the same seed and batches after 3 iterations, eager and as a hipGraph (capture at the second iteration)."""
-    plain, guarded = _trainer(), _trainer(["--clip_grad_norm", "1e30"])
-    _iterate(plain, batches[:3], graphed)
-    _iterate(guarded, batches[:3], graphed)
-    a, b = _arena(plain), _arena(guarded)
+    plain, guarded = train_harness.trainer(), train_harness.trainer(["--clip_grad_norm", "1e30"])
+    train_harness.iterate(plain, batches[:3], graphed)
+    train_harness.iterate(guarded, batches[:3], graphed)
+    a, b = train_harness.arena(plain), train_harness.arena(guarded)
     for n in a:
         assert torch.equal(a[n], b[n]), n
     d = guarded.guard.read_and_reset()
@@ -373,21 +332,21 @@ def test_trainer_norm_is_the_norm_of_the_whole_site(batches):
     """--no_ft: the only site is train_model's, over [GP | likelihood | LSTM | decoder | encoder].  stat[0] is the fp64 norm of
     that range of arena.g (the guard does not write g) to 1.2e-7; with C = half of it the site is clipped, and the graphed
     run agrees with the eager one within test_graphed_iteration_matches_eager's bars."""
-    tr = _trainer(["--no_ft", "--clip_grad_norm", "1e30"])
-    _iterate(tr, batches[:1], False)
+    tr = train_harness.trainer(["--no_ft", "--clip_grad_norm", "1e30"])
+    train_harness.iterate(tr, batches[:1], False)
     lo, hi = tr.rng_gp[0], tr.rng_enc[1]
     want, got = float(tr.arena.g[lo:hi].double().norm()), float(tr.guard.stat[0])
     print(f"\nTrainer site norm {got!r} against fp64 {want!r}: relative {abs(got - want) / want:.3e} / bar {BAR:.1e}")
     assert want > 0 and abs(got - want) <= BAR * want and float(tr.guard.stat[1]) == 1.0
     flags = ["--no_ft", "--clip_grad_norm", repr(want / 2)]
-    eager = _trainer(flags)
-    _iterate(eager, batches[:1], False)
+    eager = train_harness.trainer(flags)
+    train_harness.iterate(eager, batches[:1], False)
     d = eager.guard.read_and_reset()
     assert (d["sites"], d["clipped"], d["skipped"]) == (1, 1, 0) and abs(d["last"] - want) <= 1e-3 * want
     assert abs(float(eager.guard.stat[1]) - 0.5) < 1e-2
-    _iterate(eager, batches[1:3], False)
-    graph = _trainer(flags)
-    _iterate(graph, batches[:3], True)
+    train_harness.iterate(eager, batches[1:3], False)
+    graph = train_harness.trainer(flags)
+    train_harness.iterate(graph, batches[:3], True)
     assert graph.guard.read_and_reset()["clipped"] >= 1
     assert torch.allclose(graph.arena.p, eager.arena.p, rtol=2e-3, atol=2e-5)
 
@@ -403,10 +362,10 @@ def _poisoned(tr, at):
         orig(*actions)
         last = actions[-1]
         if "before" in seen and "after" not in seen:
-            seen["after"] = _arena(tr)
+            seen["after"] = train_harness.arena(tr)
         if last == ("finish", "b") or (last[0] == "reduce" and tuple(last[1]) == whole):
             if seen["site"] == at:
-                seen["before"] = _arena(tr)
+                seen["before"] = train_harness.arena(tr)
                 tr.arena.g[tr.rng_enc[0] + 5] = float("nan")
             seen["site"] += 1
     tr._ar = ar
@@ -417,7 +376,7 @@ def _skip_run(xs, flags, resume_after=None, graphed=False, poison_at=1):
     """len(xs) iterations with the poison of _poisoned in iteration `poison_at` (None: none); resume_after = k: after k
     iterations the state goes through a file image into a fresh Trainer with another seed, which does the rest."""
     import train
-    tr = _trainer(flags)
+    tr = train_harness.trainer(flags)
     seen = _poisoned(tr, poison_at) if poison_at is not None else {}
     step = train.GraphedIteration(tr, warmup=3) if graphed else tr.iteration
     torch.manual_seed(77)
@@ -427,7 +386,7 @@ def _skip_run(xs, flags, resume_after=None, graphed=False, poison_at=1):
             torch.save(tr.state_dict(epoch=0), f)
             f.seek(0)
             del tr, step
-            tr = _trainer(flags, seed=99)
+            tr = train_harness.trainer(flags, seed=99)
             tr.load_state_dict(torch.load(f, weights_only=False))
             step = train.GraphedIteration(tr, warmup=3 - resume_after) if graphed else tr.iteration
         step(x)
@@ -501,7 +460,7 @@ def test_graphed_continuation_with_a_clip_that_bites(batches):
 # ---- the command line ----------------------------------------------------------------------------------------------------------
 def test_command_line_prints_the_epoch_line(capsys):
     import train
-    tr = train.main(ARGS + ["--clip_grad_norm", "0.5", "--skip_nonfinite", "--niter", "1", "--epoch_size", "2", "--no_save"])
+    tr = train.main(train_harness.ARGS + ["--clip_grad_norm", "0.5", "--skip_nonfinite", "--niter", "1", "--epoch_size", "2", "--no_save"])
     out = capsys.readouterr().out
     lines = out.splitlines()
     at = [i for i, ln in enumerate(lines) if ln.startswith("     train frames/s:")]
@@ -510,25 +469,12 @@ def test_command_line_prints_the_epoch_line(capsys):
     assert tr.guard.counters.tolist() == [0, 0, 0]
 
 
-def _free_port() -> int:
-    import socket
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def test_two_ranks_clip_alike():
     """Two ranks on one GPU over gloo (the rehearsal switches of tests/test_gpu_multirank.py): the norm is taken after the
     all-reduce, so both ranks compute the same factor without another collective and end with identical parameters."""
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    env.update(DVG_DP_SHARE_GPU="1", DVG_DP_BACKEND="gloo", OMP_NUM_THREADS="2")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "train.py"), "--model", "dcgan", "--dataset", "smmnist",
-           "--batch_size", "8", "--n_past", "2", "--n_future", "2", "--n_eval", "4", "--niter", "1", "--epoch_size", "4",
-           "--no_save", "--save_every", "1000", "--print_param_checksum", "--clip_grad_norm", "0.5"]
-    r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    args = ["--model", "dcgan", "--dataset", "smmnist", "--batch_size", "8", "--n_past", "2", "--n_future", "2", "--n_eval", "4",
+            "--niter", "1", "--epoch_size", "4", "--no_save", "--save_every", "1000", "--print_param_checksum", "--clip_grad_norm", "0.5"]
+    r = train_harness.run_train_py(args, ranks=2, env=train_harness.REHEARSAL)
     assert r.returncode == 0, r.stderr[-2000:]
     sums = {ln.split()[1]: ln.split()[-2:] for ln in r.stdout.splitlines() if "param checksum" in ln}
     assert set(sums) == {"0", "1"} and sums["0"] == sums["1"], sums

@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests import lr_schedule_ref as ref
+from tests import lr_schedule_ref as ref, train_harness
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -159,44 +159,17 @@ def test_fused_adam_with_a_schedule_matches_torch_adam_with_lambda_lr():
 
 
 # ---- the Trainer ---------------------------------------------------------------------------------------------------------------------
-ARGS = ["--batch_size", "4", "--n_past", "2", "--n_future", "2", "--n_eval", "4", "--dataset", "smmnist"]
-
-
-def _opt(extra=(), model="dcgan"):
-    import train
-    o = train.build_parser().parse_args(["--model", model] + ARGS + ["--niter", "1", "--epoch_size", "1", "--no_save"] + list(extra))
-    o.ft = not o.no_ft
-    o.rank, o.world, o.local_batch = 0, 1, o.batch_size
-    return o
-
-
-def _trainer(extra=(), seed=3, model="dcgan"):
-    import train
-    torch.manual_seed(seed)
-    torch.cuda.manual_seed_all(seed)
-    tr = train.Trainer(_opt(extra, model), torch.device(DEV))
-    tr.train_mode()
-    return tr
-
-
 @pytest.fixture(scope="module")
 def batches():
-    import utils
-    from dvg_amd.data import SyntheticMovingMNIST
-    gen = SyntheticMovingMNIST(seq_len=4, seed=9)
-    return [utils.normalize_data(_opt(), torch.cuda.FloatTensor, gen.batch(4))[0] for _ in range(5)]
-
-
-def _arena(tr):
-    return {n: getattr(tr.arena, n).clone() for n in ("p", "m", "v")}
+    return train_harness.make_batches(5)
 
 
 def test_trainer_builds_a_schedule_only_when_asked():
-    plain = _trainer()
+    plain = train_harness.trainer()
     assert plain.lr_schedule is None and all(o.lr_scale is None for o in plain.optimizers())
     assert {g["lr"] for o in plain.optimizers() for g in o.param_groups} == {0.002}
     assert "lr_schedule" not in plain.state_dict()
-    tr = _trainer(["--lr_schedule", "cosine", "--lr_warmup", "4", "--lr_total", "9", "--lr", "0.01"])
+    tr = train_harness.trainer(["--lr_schedule", "cosine", "--lr_warmup", "4", "--lr_total", "9", "--lr", "0.01"])
     assert {g["lr"] for o in tr.optimizers() for g in o.param_groups} == {0.01}     # --lr is the base rate of all four
     assert all(o.lr_scale is tr.lr_schedule.scale for o in tr.optimizers())
     assert float(tr.lr_schedule.scale) == 0.25 and int(tr.lr_schedule.iters) == 0   # s(0) = 1 / W before the first tick
@@ -213,10 +186,10 @@ def test_trainer_builds_a_schedule_only_when_asked():
 def test_a_zero_rate_moves_no_parameter(batches):
     """linear, R = 0, the count set to N: the multiplier of the iteration is exactly 0.  All six Adam launches run - the moments
     move - and no parameter changes a bit."""
-    tr = _trainer(["--lr_schedule", "linear", "--lr_total", "8"])
+    tr = train_harness.trainer(["--lr_schedule", "linear", "--lr_total", "8"])
     tr.gp_layer(torch.zeros(4, 90, device=DEV))          # the one-off prior initialisation of the variational parameters
     tr.lr_schedule.load_state(8)
-    before = _arena(tr)
+    before = train_harness.arena(tr)
     tr.iteration(batches[0])
     torch.cuda.synchronize()
     assert tr.lr_schedule.read() == {"iters": 9, "scale": 0.0}
@@ -226,24 +199,18 @@ def test_a_zero_rate_moves_no_parameter(batches):
 
 # ---- 5. the flag alone changes nothing ----------------------------------------------------------------------------------------------
 def _iterate(tr, xs, graphed=False, warmup=2):
-    import train
-    step = train.GraphedIteration(tr, warmup=warmup) if graphed else tr.iteration
-    torch.manual_seed(77)                                # the GP samples of the iterations
-    out = []
-    for x in xs:
-        out.append((step(x) + (tr.last_loss,), step.graph if graphed else None,
-                    tr.lr_schedule.read() if tr.lr_schedule is not None else None))
-    torch.cuda.synchronize()
-    return step, out
+    step, out = train_harness.iterate(tr, xs, graphed, warmup, each=lambda tr, step, i: (
+        tr.last_loss, step.graph if graphed else None, tr.lr_schedule.read() if tr.lr_schedule is not None else None))
+    return step, [(res + (loss,), graph, sched) for res, (loss, graph, sched) in out]
 
 
 def test_constant_at_the_reference_rate_is_the_run_without_the_flag(batches):
     """--lr_schedule constant --lr 0.002, no warm-up: the multiplier is 1 at every iteration, so every Adam launch has the operands
     of the unscheduled one - parameters and both moments bit-equal after three eager iterations from one seed."""
-    plain, sched = _trainer(), _trainer(["--lr_schedule", "constant", "--lr", "0.002"])
+    plain, sched = train_harness.trainer(), train_harness.trainer(["--lr_schedule", "constant", "--lr", "0.002"])
     _iterate(plain, batches[:3])
     _iterate(sched, batches[:3])
-    a, b = _arena(plain), _arena(sched)
+    a, b = train_harness.arena(plain), train_harness.arena(sched)
     for n in a:
         assert torch.equal(a[n], b[n]), n
     assert sched.lr_schedule.read() == {"iters": 3, "scale": 1.0}
@@ -258,14 +225,14 @@ def test_one_capture_serves_a_multiplier_that_moves_every_iteration(batches, mod
     flags = ["--lr_schedule", "cosine", "--lr_warmup", "2", "--lr_total", "5"]
     res = []
     for graphed in (False, True):
-        tr = _trainer(flags, seed=11, model=model)
+        tr = train_harness.trainer(flags, seed=11, model=model)
         step, out = _iterate(tr, batches[:5], graphed, warmup=2)
         for i, (_, _, d) in enumerate(out, start=1):
             assert d["iters"] == i and np.float32(d["scale"]) == ref.s32("cosine", i - 1, 2, 5), (graphed, i, d)
         if graphed:
             assert not step.failed and out[2][1] is not None and all(g is out[2][1] for _, g, _ in out[2:])
             assert out[0][1] is None and out[1][1] is None and step.calls == 5
-        res.append(([o[0] for o in out], [{k: t.detach().clone() for k, t in m.state_dict().items()} for m in tr.modules], _arena(tr),
+        res.append(([o[0] for o in out], [{k: t.detach().clone() for k, t in m.state_dict().items()} for m in tr.modules], train_harness.arena(tr),
                     float(tr.encoder_optimizer.state_dict()["state"][0]["step"])))
     (la, sa, aa, stepa), (lb, sb, ab, stepb) = res
     assert stepa == stepb == 5.0
@@ -285,7 +252,7 @@ def test_a_skipped_step_still_counts_as_an_iteration(batches):
     site.  The site is skipped - parameters and moments bit-equal across it - and the count of iterations has advanced all the
     same: it counts iterations, not optimiser steps."""
     from dvg_amd import train_state
-    tr = _trainer(["--skip_nonfinite", "--lr_schedule", "linear", "--lr_warmup", "2", "--lr_total", "10"])
+    tr = train_harness.trainer(["--skip_nonfinite", "--lr_schedule", "linear", "--lr_warmup", "2", "--lr_total", "10"])
     seen = {"site": 0}
     orig, whole = tr._ar, (tr.rng_gp[0], tr.rng_enc[1])
 
@@ -293,10 +260,10 @@ def test_a_skipped_step_still_counts_as_an_iteration(batches):
         orig(*actions)
         last = actions[-1]
         if "before" in seen and "after" not in seen:     # the next all-reduce point: the fine-tuning site's
-            seen["after"], seen["iters_after"] = _arena(tr), int(tr.lr_schedule.iters)
+            seen["after"], seen["iters_after"] = train_harness.arena(tr), int(tr.lr_schedule.iters)
         if last == ("finish", "b") or (last[0] == "reduce" and tuple(last[1]) == whole):
             if seen["site"] == 1:
-                seen["before"] = _arena(tr)
+                seen["before"] = train_harness.arena(tr)
                 tr.arena.g[tr.rng_enc[0] + 5] = float("inf")
             seen["site"] += 1
     tr._ar = ar
@@ -322,8 +289,8 @@ def _run(n, resume_after=None, flags=RESUME_FLAGS, load_flags=None):
     from dvg_amd.data import make_batch_generator
 
     def stream():
-        return train.BatchPrefetcher(make_batch_generator(_opt(), 4, 5, torch.device(DEV)))
-    tr, gen = _trainer(flags, seed=3), stream()
+        return train.BatchPrefetcher(make_batch_generator(train_harness.opt(), 4, 5, torch.device(DEV)))
+    tr, gen = train_harness.trainer(flags, seed=3), stream()
     tr.scheduler.step()
     for i in range(n):
         if resume_after is not None and i == resume_after:
@@ -331,7 +298,7 @@ def _run(n, resume_after=None, flags=RESUME_FLAGS, load_flags=None):
             torch.save(tr.state_dict(epoch=0, train_gen=gen), f)
             f.seek(0)
             del tr
-            tr, gen = _trainer(flags if load_flags is None else load_flags, seed=99), stream()
+            tr, gen = train_harness.trainer(flags if load_flags is None else load_flags, seed=99), stream()
             tr.load_state_dict(torch.load(f, weights_only=False), train_gen=gen)
         tr.iteration(next(gen)())
     torch.cuda.synchronize()
@@ -354,22 +321,22 @@ def test_a_resumed_run_takes_the_same_third_iteration():
 
 
 def test_restore_refuses_another_spec_and_says_what_it_does_with_old_and_unwanted_states(batches, capsys):
-    saver = _trainer(RESUME_FLAGS)
+    saver = train_harness.trainer(RESUME_FLAGS)
     saver.iteration(batches[0])
     sd = saver.state_dict(epoch=0)
     assert sd["lr_schedule"] == {"spec": dict(saver.lr_schedule.spec), "iters": 1}
     with pytest.raises(SystemExit, match="lr_schedule.total "):          # another spec than the saved one: the field is named
-        _trainer(RESUME_FLAGS[:5] + ["7"] + RESUME_FLAGS[6:]).load_state_dict(sd)
+        train_harness.trainer(RESUME_FLAGS[:5] + ["7"] + RESUME_FLAGS[6:]).load_state_dict(sd)
     capsys.readouterr()
-    dropped = _trainer()                                                 # a state with the key, restored without the flag
+    dropped = train_harness.trainer()                                                 # a state with the key, restored without the flag
     dropped.load_state_dict(sd)
     out = capsys.readouterr().out
     assert out.count("\n") == 1 and "ignored" in out and dropped.lr_schedule is None
     old_sd = dropped.state_dict(epoch=0)                                 # ... and what it writes is a state from before the flag
     assert "lr_schedule" not in old_sd and old_sd["global_step"] == 1
-    late = _trainer(["--lr_schedule", "constant"])
+    late = train_harness.trainer(["--lr_schedule", "constant"])
     late.load_state_dict(old_sd)
     out = capsys.readouterr().out
     assert out.count("\n") == 1 and "counts from global step 1" in out and late.lr_schedule.read()["iters"] == 1
     with pytest.raises(SystemExit, match="lr_schedule.lr "):             # the restored rate of the optimisers is not this --lr
-        _trainer(["--lr_schedule", "constant", "--lr", "0.01"]).load_state_dict(old_sd)
+        train_harness.trainer(["--lr_schedule", "constant", "--lr", "0.01"]).load_state_dict(old_sd)

@@ -11,23 +11,15 @@ import sys
 
 import pytest
 
+from tests import train_harness
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _free_port() -> int:
-    import socket
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 @pytest.mark.parametrize("ranks", [2, 4])
 def test_bench_ranks_rehearsal(ranks):
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    env.update(DVG_DP_SHARE_GPU="1", DVG_DP_BACKEND="gloo", OMP_NUM_THREADS="2")
+    env = train_harness.clean_env(**train_harness.REHEARSAL)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(ranks), "--steps", "3", "--warmup", "1",
                         "--full", "--model", "dcgan", "--no-families", "--no-cpu-baseline", "--train-iters", "1",
                         "--train-graph-timeout", "120"],
@@ -50,7 +42,7 @@ def test_bench_ranks_rehearsal(ranks):
 
 def test_bench_refuses_a_group_that_does_not_span_gpus_ranks():
     """`--gpus 2` under a launcher that only started ONE rank: WORLD_SIZE disagrees -> exit code 2 before any GPU work."""
-    env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
+    env = dict(os.environ, RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(train_harness.free_port()))
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode == 2 and "WORLD_SIZE=1" in r.stderr and not r.stdout.strip()
@@ -63,22 +55,18 @@ def test_train_py_ranks_end_with_identical_parameters(ranks):
     replayed as a chain of hipGraphs with the all-reduces eager between them (train.SegmentedIteration) - after four
     iterations (train_model + both fine-tuning closures each) every rank must hold bit-identical parameters, and they must
     differ from a single-rank run on rank 0's data alone (i.e. the other rank's gradients did arrive)."""
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    env.update(DVG_DP_SHARE_GPU="1", DVG_DP_BACKEND="gloo", OMP_NUM_THREADS="2")
     args = ["--model", "dcgan", "--dataset", "smmnist", "--n_past", "2", "--n_future", "3", "--n_eval", "5", "--niter", "1",
             "--epoch_size", "4", "--no_save", "--save_every", "1000", "--print_param_checksum"]
 
-    def run(cmd):
-        r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
+    def run(n, batch):
+        r = train_harness.run_train_py(["--batch_size", str(batch)] + args, ranks=n, env=train_harness.REHEARSAL, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
         return {ln.split()[1]: ln.split()[-2:] for ln in r.stdout.splitlines() if "param checksum" in ln}
 
-    two = run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}", "--master-addr",
-               "127.0.0.1", "--master-port", str(_free_port()), os.path.join(ROOT, "train.py"), "--batch_size",
-               str(4 * ranks)] + args)
+    two = run(ranks, 4 * ranks)
     assert set(two) == {str(r) for r in range(ranks)}, two
     assert all(two[str(r)] == two["0"] for r in range(ranks)), two
-    one = run([sys.executable, os.path.join(ROOT, "train.py"), "--batch_size", "4"] + args)
+    one = run(1, 4)
     assert one["0"] != two["0"]
 
 
@@ -122,8 +110,7 @@ def test_two_ranks_with_sync_bn_train_like_one_process(model, linear, tmp_path):
         more than 1e-5 of the tensor's largest magnitude is bounded (dcgan_64: < 5e-3, measured 3e-4; the control: 0.25);
       * after three iterations: relative L2 distance per module < 3e-2 and far below the control's."""
     import torch
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    env.update(DVG_DP_SHARE_GPU="1", DVG_DP_BACKEND="gloo", OMP_NUM_THREADS="2")
+    env = train_harness.clean_env(**train_harness.REHEARSAL)
     # (Until the last day of r06 the vgg_64 case ran with DVG_WINOGRAD=0: with a second process on the device the F(4x4) weight
     # transform wrote zero rows into U in 1-30 % of its launches - winograd.hip, wrow_owner_note; test_packed_weights_with_a_second_process
     # below guards the fix.)
@@ -132,10 +119,8 @@ def test_two_ranks_with_sync_bn_train_like_one_process(model, linear, tmp_path):
 
     def run(world, extra, name):
         out = str(tmp_path / name)
-        cmd = [sys.executable] + ([] if world == 1 else ["-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
-                                                        "--master-addr", "127.0.0.1", "--master-port", str(_free_port())])
-        r = subprocess.run(cmd + [script] + common + extra + ["--out", out], cwd=ROOT, env=env, stdout=subprocess.PIPE,
-                           stderr=subprocess.PIPE, text=True, timeout=900)
+        r = subprocess.run([sys.executable] + train_harness.launcher(world) + [script] + common + extra + ["--out", out], cwd=ROOT,
+                           env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
         assert r.returncode == 0, r.stderr[-2000:]
         return torch.load(out)
     one = run(1, [], "one.pt")
@@ -206,7 +191,7 @@ def test_packed_weights_with_a_second_process_on_the_device():
     every time (tools/diag_pack_repeat.py).  r06: in its earlier form the F(4x4) weight transform wrote whole rows of U as zeros in
     1-30 % of its launches under exactly this contention (193 of 5 700 recomputations; 0 alone on the device; a wrong packed-FMA result) - the cause of the one-GPU
     rehearsal's run-to-run different vgg_64 gradients (profiles/r06_dp_race_bisect.txt)."""
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    env = train_harness.clean_env()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "diag_pack_repeat.py"), "--noise", "train", "--iters", "40"],
                        cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]

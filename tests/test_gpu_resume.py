@@ -9,42 +9,22 @@ n_past 2, n_future 2, g_dim 90, rnn_size 256, the in-repo synthetic smmnist.
 Run-to-run stability is MEASURED here, not assumed (`_rel`, `test_continuation`): where two identical runs end bit-identical a
 resumed run must be bit-identical to the uninterrupted one; where they do not, it may differ by at most twice what they do."""
 import os
-import subprocess
-import sys
 
 import pytest
 import torch
 
 from dvg_amd import train_state
+from tests import train_harness
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
-ARGS = ["--model", "dcgan", "--batch_size", "4", "--n_past", "2", "--n_future", "2", "--n_eval", "4", "--dataset", "smmnist"]
 DATA_SEED = 5
-
-
-def _opt(extra=()):
-    import train
-    o = train.build_parser().parse_args(ARGS + ["--niter", "1", "--epoch_size", "1", "--no_save"] + list(extra))
-    o.ft = True
-    o.rank, o.world, o.local_batch = 0, 1, o.batch_size
-    return o
-
-
-def _trainer(seed):
-    import train
-    torch.manual_seed(seed)
-    torch.cuda.manual_seed_all(seed)
-    tr = train.Trainer(_opt(), torch.device(DEV))
-    tr.train_mode()
-    return tr
 
 
 def _stream():
     import train
     from dvg_amd.data import make_batch_generator
-    return train.BatchPrefetcher(make_batch_generator(_opt(), 4, DATA_SEED, torch.device(DEV)))
+    return train.BatchPrefetcher(make_batch_generator(train_harness.opt(), 4, DATA_SEED, torch.device(DEV)))
 
 
 def _rel(a, b):
@@ -73,7 +53,7 @@ def _live(tr):
 def source():
     """Trainer A after 3 eager iterations (the second scheduler step has moved the learning rate of the GP groups): its state
     dict, clones of its live state, the batches, and the arena after the 4th iteration of the UNINTERRUPTED run."""
-    tr = _trainer(3)
+    tr = train_harness.trainer(seed=3)
     gen = _stream()
     xs = [next(gen)() for _ in range(3)]
     tr.scheduler.step()
@@ -116,7 +96,7 @@ def test_state_dict_owns_its_storage_and_names_what_it_holds(source):
 
 def test_round_trip_is_bit_exact_through_the_existing_views(source):
     sd, live = source["sd"], source["live"]
-    tr = _trainer(41)
+    tr = train_harness.trainer(seed=41)
     ptrs = [tr.arena.p.data_ptr(), tr.arena.g.data_ptr(), tr.arena.m.data_ptr(), tr.arena.v.data_ptr()]
     params = [p for m in tr.modules for p in m.parameters()]
     pp = [(p.data_ptr(), p.grad.data_ptr(), p._version) for p in params]
@@ -148,7 +128,7 @@ def test_round_trip_through_a_file_and_refusal_of_another_layout(source, tmp_pat
     f = train_state.write(source["sd"], str(tmp_path), 0, 1)
     assert f.endswith("train_state.pth") and os.listdir(str(tmp_path)) == ["train_state.pth"]
     sd = train_state.read(f)
-    tr = _trainer(43)
+    tr = train_harness.trainer(seed=43)
     tr.load_state_dict(sd, path=f)
     assert torch.equal(tr.arena.p, source["live"]["p"]) and torch.equal(tr.arena.v, source["live"]["v"])
     other = dict(sd, fingerprint=dict(sd["fingerprint"], layout=sd["fingerprint"]["layout"][:-1]))
@@ -161,7 +141,7 @@ def test_warm_caches_do_not_serve_the_old_weights(source):
     exist, keyed by parameter version - before A's state is loaded into it.  Its encoder and decoder must then compute
     exactly what a fresh Trainer computes after the same load, in training mode and in eval mode (the folds)."""
     sd, x = source["sd"], source["xs"][0]
-    b = _trainer(7)
+    b = train_harness.trainer(seed=7)
 
     def forward(tr):
         out = []
@@ -176,7 +156,7 @@ def test_warm_caches_do_not_serve_the_old_weights(source):
     b.iteration(x)
     stale = forward(b)
     b.load_state_dict(sd)
-    fresh = _trainer(8)
+    fresh = train_harness.trainer(seed=8)
     fresh.load_state_dict(sd)
     got, want = forward(b), forward(fresh)
     assert len(got) == len(want) > 4
@@ -193,7 +173,7 @@ def test_the_leaked_gp_gradients_are_state(source):
     sd, x4 = source["sd"], source["x4"]
 
     def gp_after(seed, zero, leak=True):
-        tr = _trainer(seed)
+        tr = train_harness.trainer(seed=seed)
         tr.reference_gp_grad_leak = leak
         tr.load_state_dict(sd)
         lo, hi = tr.rng_gp
@@ -203,7 +183,7 @@ def test_the_leaked_gp_gradients_are_state(source):
         torch.cuda.synchronize()
         return tr.arena.p[lo:hi].clone()
     # the uninterrupted run: A's three iterations again, then the same train_model
-    u = _trainer(3)
+    u = train_harness.trainer(seed=3)
     u.scheduler.step()
     for i, x in enumerate(source["xs"]):
         u.iteration(x)
@@ -234,7 +214,7 @@ def _run(mode, n, seed=3, resume_after=None, load_seed=99):
     capture at the 4th iteration."""
     import io
     import train
-    tr, gen = _trainer(seed), _stream()
+    tr, gen = train_harness.trainer(seed=seed), _stream()
     step = tr.iteration if mode == "eager" else train.GraphedIteration(tr, warmup=3)
     tr.scheduler.step()
     for i in range(n):
@@ -243,7 +223,7 @@ def _run(mode, n, seed=3, resume_after=None, load_seed=99):
             torch.save(tr.state_dict(epoch=0, train_gen=gen), f)
             f.seek(0)
             del tr, step
-            tr, gen = _trainer(load_seed), _stream()
+            tr, gen = train_harness.trainer(seed=load_seed), _stream()
             tr.load_state_dict(torch.load(f, weights_only=False), train_gen=gen)
             step = tr.iteration if mode == "eager" else train.GraphedIteration(tr, warmup=3 - resume_after)
         step(next(gen)())
@@ -288,7 +268,7 @@ def test_a_load_makes_a_captured_iteration_capture_again(source):
     packs of the old state) - it captures again, seeded from the restored host counts - and does what the uninterrupted run's
     4th iteration did."""
     import train
-    tr = _trainer(21)
+    tr = train_harness.trainer(seed=21)
     step = train.GraphedIteration(tr, warmup=1)
     tr.scheduler.step()
     step(source["xs"][0])
@@ -310,7 +290,7 @@ def test_a_load_makes_a_captured_iteration_capture_again(source):
 def test_end_to_end_resume_runs_exactly_the_missing_epoch(tmp_path, capsys):
     import train
     out = str(tmp_path)
-    common = ARGS + ["--epoch_size", "2", "--save_every", "1", "--output_path", out]
+    common = train_harness.ARGS + ["--epoch_size", "2", "--save_every", "1", "--output_path", out]
     train.main(common + ["--niter", "2"])
     first = capsys.readouterr().out
     assert "[00] mse loss" in first and "[01] mse loss" in first and "resumed from" not in first
@@ -336,30 +316,16 @@ def test_end_to_end_resume_runs_exactly_the_missing_epoch(tmp_path, capsys):
     assert "resumed from" in third and "mse loss" not in third
 
 
-def _free_port() -> int:
-    import socket
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def test_two_ranks_save_and_resume_and_one_rank_is_refused(tmp_path):
     """Two ranks on one GPU over gloo (the rehearsal switches of tests/test_gpu_multirank.py; fresh child processes): the shared
     part is written once, what differs per rank beside it; the resumed run ends with identical parameters on both ranks; the
     same state is refused by a single process."""
     out = str(tmp_path)
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    env.update(DVG_DP_SHARE_GPU="1", DVG_DP_BACKEND="gloo", OMP_NUM_THREADS="2")
     args = ["--model", "dcgan", "--dataset", "smmnist", "--n_past", "2", "--n_future", "2", "--n_eval", "4", "--batch_size", "8",
             "--epoch_size", "2", "--save_every", "1", "--no_images", "--output_path", out, "--print_param_checksum"]
 
     def run(ranks, extra):
-        launcher = [] if ranks == 1 else ["-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={ranks}",
-                                          "--master-addr", "127.0.0.1", "--master-port", str(_free_port())]
-        return subprocess.run([sys.executable] + launcher + [os.path.join(ROOT, "train.py")] + args + extra, cwd=ROOT, env=env,
-                              stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        return train_harness.run_train_py(args + extra, ranks=ranks, env=train_harness.REHEARSAL)
 
     def checksums(r):
         return {ln.split()[1]: ln.split()[-2:] for ln in r.stdout.splitlines() if "param checksum" in ln}

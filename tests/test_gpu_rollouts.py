@@ -28,10 +28,8 @@ def _cpu_state(m):
 def _trainer(model, batch, n_past, n_future, n_eval, nc=1, width=64, seed=3):
     import train
     torch.manual_seed(seed)
-    o = train.build_parser().parse_args(["--model", model, "--batch_size", str(batch), "--n_past", str(n_past),
-                                         "--n_future", str(n_future), "--n_eval", str(n_eval), "--channels", str(nc),
-                                         "--image_width", str(width), "--dataset", "smmnist", "--no_save"])
-    o.ft, o.rank, o.world, o.local_batch = True, 0, 1, batch
+    o = train.options(["--model", model, "--batch_size", str(batch), "--n_past", str(n_past), "--n_future", str(n_future),
+                       "--n_eval", str(n_eval), "--channels", str(nc), "--image_width", str(width), "--dataset", "smmnist", "--no_save"])
     tr = train.Trainer(o, torch.device(DEV))
     tr.train_mode()
     tr.gp_layer(torch.zeros(batch, 90, device=DEV))   # prior initialisation of the variational distribution

@@ -10,20 +10,11 @@ import torch
 import torch.nn.functional as F
 
 from oracle import dvg_oracle as orc
+from tests import train_harness
 from tests.common import to64, yardstick
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def _opt(model, extra=()):
-    import train
-    argv = ["--model", model, "--batch_size", "4", "--n_past", "2", "--n_future", "2", "--n_eval", "4", "--niter", "1",
-            "--epoch_size", "1", "--dataset", "smmnist", "--no_save"] + list(extra)
-    o = train.build_parser().parse_args(argv)
-    o.ft = True
-    o.rank, o.world, o.local_batch = 0, 1, o.batch_size
-    return o
 
 
 LOSS_BAR = 2e-6        # closure VALUES against the oracle: measured r05 <= 1.3e-7 (HIP) / 1.3e-7 (fp32 oracle) against fp64
@@ -45,7 +36,7 @@ def test_train_model_loss_matches_oracle(model):
     import utils
     from dvg_amd.data import SyntheticMovingMNIST
     torch.manual_seed(3)
-    opt = _opt(model)
+    opt = train_harness.opt(model=model)
     tr = train.Trainer(opt, torch.device("cuda:0"))
     tr.train_mode()
     seq = SyntheticMovingMNIST(seq_len=4, seed=5).batch(4)
@@ -88,7 +79,7 @@ def test_finetune_closures_without_encoder_autograd_match_reference_structure():
     res = []
     for with_grad in (False, True):
         torch.manual_seed(3)
-        opt = _opt("dcgan")
+        opt = train_harness.opt(model="dcgan")
         tr = train.Trainer(opt, torch.device("cuda:0"))
         tr.train_mode()
         tr.finetune_encoder_grad = with_grad
@@ -117,7 +108,7 @@ def test_elbo_num_data_is_the_global_batch_under_data_parallelism():
 
     def gp_grads(local, world, rows):
         torch.manual_seed(3)
-        opt = _opt("dcgan", ["--batch_size", "8"])
+        opt = train_harness.opt(["--batch_size", "8"], "dcgan")
         opt.world, opt.local_batch = world, local
         tr = train.Trainer(opt, torch.device("cuda:0"))
         assert tr.mll.num_data == 8
@@ -145,7 +136,7 @@ def test_reference_gp_grad_leak_switch():
     out = {}
     for leak in (True, False):
         torch.manual_seed(3)
-        opt = _opt("dcgan")
+        opt = train_harness.opt(model="dcgan")
         tr = train.Trainer(opt, torch.device("cuda:0"))
         assert tr.reference_gp_grad_leak is True
         tr.reference_gp_grad_leak = leak
@@ -278,7 +269,7 @@ def test_graphed_iteration_matches_eager(model):
     res = []
     for graphed in (False, True):
         torch.manual_seed(11)
-        opt = _opt(model)
+        opt = train_harness.opt(model=model)
         tr = train.Trainer(opt, torch.device("cuda:0"))
         tr.train_mode()
         gen = SyntheticMovingMNIST(seq_len=4, seed=9)
@@ -307,6 +298,29 @@ def test_graphed_iteration_matches_eager(model):
     assert torch.allclose(ha, hb, rtol=2e-3, atol=2e-5)
 
 
+def test_every_per_iteration_part_runs_once_in_every_form():
+    """The iteration body is written once (Trainer._iteration_dev) and read back once (Trainer._iteration_result): with a
+    schedule, a weight average and a gradient guard, four iterations - eager, and one eager warm-up + the capture + two replays
+    of a GraphedIteration from the same seed - tick the schedule four times, update the average four times, pass 2 x 4 step
+    sites (train_model's and the fine-tuning closures') and count four iterations; the returned triples and last_loss agree
+    within test_graphed_iteration_matches_eager's bar on the losses."""
+    flags = ["--lr_schedule", "cosine", "--lr_warmup", "2", "--lr_total", "6", "--ema_decay", "0.9", "--clip_grad_norm", "1.0"]
+    xs = train_harness.make_batches(4)
+    res = []
+    for graphed in (False, True):
+        tr = train_harness.trainer(flags)
+        _, out = train_harness.iterate(tr, xs, graphed, warmup=1, each=lambda tr, step, i: tr.last_loss)
+        assert tr.lr_schedule.read()["iters"] == 4
+        assert int(tr.ema.updates) == 4
+        assert tr.guard.read_and_reset()["sites"] == 2 * 4
+        assert tr._iters == 4
+        res.append([triple + (loss,) for triple, loss in out])
+    for a, b in zip(*res):
+        assert len(a) == len(b) == 4
+        for u, v in zip(a, b):
+            assert abs(u - v) <= 2e-4 * max(1.0, abs(u)), res
+
+
 def test_graph_replay_after_an_eager_step_is_refused():
     """the captured Adam launches read their step count from the device (FusedAdam.begin_capture); an eager
     step() between two replays advances only the host count, so the next replay would apply stale bias corrections without
@@ -317,7 +331,7 @@ def test_graph_replay_after_an_eager_step_is_refused():
     from dvg_amd.data import SyntheticMovingMNIST
     from dvg_amd.optim import zero_grads
     torch.manual_seed(12)
-    opt = _opt("dcgan")
+    opt = train_harness.opt(model="dcgan")
     tr = train.Trainer(opt, torch.device("cuda:0"))
     tr.train_mode()
     gen = SyntheticMovingMNIST(seq_len=4, seed=9)
@@ -368,7 +382,7 @@ def test_segmented_iteration_cuts_at_the_allreduces_and_matches_eager():
         res = []
         for seg in (False, True):
             torch.manual_seed(11)
-            opt = _opt("dcgan")
+            opt = train_harness.opt(model="dcgan")
             tr = train.Trainer(opt, torch.device("cuda:0"))
             tr.train_mode()
             assert tr.reducer.active()
@@ -412,7 +426,7 @@ def test_shared_encoder_passes_match_reference_structure(model):
     res = []
     for share in (False, True):
         torch.manual_seed(5)
-        opt = _opt(model, ["--n_past", "2", "--n_future", "3"])
+        opt = train_harness.opt(["--n_past", "2", "--n_future", "3"], model)
         tr = train.Trainer(opt, torch.device("cuda:0"))
         tr.train_mode()
         tr.share_encoder_passes = share
@@ -466,9 +480,8 @@ def test_time_batched_encoder_matches_the_per_frame_path(model, width, batch):
     res = {}
     for tb in (False, True):
         torch.manual_seed(21)
-        opt = _opt(model, ["--n_past", "2", "--n_future", "3", "--batch_size", str(batch), "--image_width", str(width),
-                           "--channels", "3" if width == 128 else "1"] + (["--dataset", "ucf", "--synthetic_data"] if width == 128 else []))
-        opt.local_batch = batch
+        opt = train_harness.opt(["--n_past", "2", "--n_future", "3", "--batch_size", str(batch), "--image_width", str(width), "--channels",
+                                 "3" if width == 128 else "1"] + (["--dataset", "ucf", "--synthetic_data"] if width == 128 else []), model)
         tr = train.Trainer(opt, torch.device("cuda:0"))
         tr.train_mode()
         tr.time_batched = tb
@@ -558,7 +571,7 @@ def test_shared_skip_halves_match_reference_structure(model):
     res = []
     for share in (False, True):
         torch.manual_seed(5)
-        opt = _opt(model, ["--n_past", "2", "--n_future", "3"])
+        opt = train_harness.opt(["--n_past", "2", "--n_future", "3"], model)
         tr = train.Trainer(opt, torch.device("cuda:0"))
         tr.train_mode()
         tr.share_skip_halves = share
@@ -602,7 +615,7 @@ def test_gp_closure_reuses_lstm_closure_encodings_exactly(model):
     res = []
     for share in (False, True):
         torch.manual_seed(6)
-        opt = _opt(model, ["--n_past", "2", "--n_future", "3"])
+        opt = train_harness.opt(["--n_past", "2", "--n_future", "3"], model)
         tr = train.Trainer(opt, torch.device("cuda:0"))
         tr.train_mode()
         tr.share_closure_encodings = share
@@ -636,7 +649,7 @@ def test_capture_failure_falls_back_to_eager_without_stale_caches(model, where):
     res = []
     for broken in (False, True):
         torch.manual_seed(11)
-        opt = _opt(model)
+        opt = train_harness.opt(model=model)
         tr = train.Trainer(opt, torch.device("cuda:0"))
         tr.train_mode()
         gen = SyntheticMovingMNIST(seq_len=4, seed=9)

@@ -13,19 +13,15 @@ Shapes: (B, S, T) of val_ref.SHAPES for the kernel - one row, one sample, one st
 import json
 import os
 import shutil
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 import torch
 
-from tests import val_ref as ref
+from tests import val_ref as ref, train_harness
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DEV = "cuda:0"
-ARGS = ["--model", "dcgan", "--batch_size", "4", "--n_past", "2", "--n_future", "2", "--n_eval", "4", "--dataset", "smmnist"]
 VAL = ["--val_every", "1", "--val_batches", "2", "--val_nsample", "2"]
 RUN = ["--epoch_size", "2", "--save_every", "1", "--no_images", "--print_param_checksum"]
 
@@ -132,28 +128,8 @@ def test_wrapper_refuses_what_the_kernel_cannot_take():
 
 
 # ---- the Validator ----------------------------------------------------------------------------------------------------------------
-def _opt(extra=()):
-    import train
-    o = train.build_parser().parse_args(ARGS + ["--niter", "1", "--epoch_size", "1", "--no_save"] + list(extra))
-    o.ft = not o.no_ft
-    o.rank, o.world, o.local_batch = 0, 1, o.batch_size
-    return o
-
-
-def _trainer(extra=(), seed=3):
-    import train
-    torch.manual_seed(seed)
-    torch.cuda.manual_seed_all(seed)
-    tr = train.Trainer(_opt(extra), torch.device(DEV))
-    tr.train_mode()
-    return tr
-
-
 def _train_batch(seed=9):
-    import utils
-    from dvg_amd.data import SyntheticMovingMNIST
-    gen = SyntheticMovingMNIST(seq_len=4, seed=seed)
-    return utils.normalize_data(_opt(), torch.cuda.FloatTensor, gen.batch(4))[0]
+    return train_harness.make_batches(1, seed=seed)[0]
 
 
 def test_validator_reports_the_rollouts_numbers_and_leaves_no_trace():
@@ -162,7 +138,7 @@ def test_validator_reports_the_rollouts_numbers_and_leaves_no_trace():
     samples; two runs give the same bits; modes, recurrent state, batch size, the fine-tuning cache and the caches are put back."""
     from dvg_amd import _derived, rollout, validate
     from dvg_amd import utils as dutils
-    tr = _trainer(["--n_eval", "17"] + VAL)
+    tr = train_harness.trainer(["--n_eval", "17"] + VAL)
     assert tr.validation is not None and tr.validation.every == 1
     x = _train_batch()
     tr.iteration(x)                                   # the GP's first call initialises its variational parameters
@@ -235,12 +211,12 @@ def test_validator_reports_the_rollouts_numbers_and_leaves_no_trace():
 
 
 def test_without_the_flag_nothing_exists():
-    tr = _trainer()
+    tr = train_harness.trainer()
     assert tr.validation is None and "validation" not in tr.state_dict(epoch=0)
-    with_val = _trainer(VAL)
+    with_val = train_harness.trainer(VAL)
     sd = with_val.state_dict(epoch=0)
     assert sd["validation"] == {"history": [], "best": {"score": None, "epoch": None}, "ema_best": {"score": None, "epoch": None}}
-    o = _opt(VAL)
+    o = train_harness.opt(VAL)
     o.rank = 1
     from dvg_amd import validate
     assert validate.make(o, torch.device(DEV)) is None            # rank 0 alone validates
@@ -251,12 +227,12 @@ _RUNS = {}
 
 
 def _main(tmp_path_factory, capsys, name, extra):
-    """train.main(ARGS + RUN + extra) into a directory of its own, once per `name`: {"out", "text", "tr"}."""
+    """train.main(train_harness.ARGS + RUN + extra) into a directory of its own, once per `name`: {"out", "text", "tr"}."""
     import train
     if name not in _RUNS:
         out = str(tmp_path_factory.mktemp("val") / name)
         capsys.readouterr()
-        tr = train.main(ARGS + RUN + ["--output_path", out] + list(extra))
+        tr = train.main(train_harness.ARGS + RUN + ["--output_path", out] + list(extra))
         _RUNS[name] = {"out": out, "text": capsys.readouterr().out, "tr": tr}
     return _RUNS[name]
 
@@ -355,7 +331,7 @@ def test_resume_continues_the_history_and_the_best_checkpoint(tmp_path_factory, 
     shutil.copytree(two["out"], out)
     import train
     capsys.readouterr()
-    tr = train.main(ARGS + RUN + eager + ["--niter", "4", "--output_path", out, "--resume", out] + VAL)
+    tr = train.main(train_harness.ARGS + RUN + eager + ["--niter", "4", "--output_path", out, "--resume", out] + VAL)
     text = capsys.readouterr().out
     assert "resumed from" in text and text.count("     val: ssim ") == 2
     a, b = (open(os.path.join(d, "val_log.jsonl"), "rb").read() for d in (whole["out"], out))
@@ -369,14 +345,14 @@ def test_resume_continues_the_history_and_the_best_checkpoint(tmp_path_factory, 
     out2 = str(tmp_path_factory.mktemp("val") / "late")
     shutil.copytree(plain["out"], out2)
     capsys.readouterr()
-    tr2 = train.main(ARGS + RUN + eager + ["--niter", "3", "--output_path", out2, "--resume", out2] + VAL)
+    tr2 = train.main(train_harness.ARGS + RUN + eager + ["--niter", "3", "--output_path", out2, "--resume", out2] + VAL)
     assert [r["epoch"] for r in tr2.validation.history] == [2]
     assert open(os.path.join(out2, "val_log.jsonl")).read().count("\n") == 1
     # a state with validations, resumed without the flag: one line, no object, no new key
     out3 = str(tmp_path_factory.mktemp("val") / "dropped")
     shutil.copytree(two["out"], out3)
     capsys.readouterr()
-    tr3 = train.main(ARGS + RUN + eager + ["--niter", "3", "--output_path", out3, "--resume", out3])
+    tr3 = train.main(train_harness.ARGS + RUN + eager + ["--niter", "3", "--output_path", out3, "--resume", out3])
     text3 = capsys.readouterr().out
     assert text3.count("the validation history in the file is ignored: this run has no --val_every") == 1
     assert tr3.validation is None and "     val: " not in text3
@@ -415,28 +391,15 @@ def test_best_checkpoint_is_the_checkpoint_of_the_best_epoch(tmp_path_factory, c
     del _RUNS["eager-whole"]            # its directory is no longer what the run left
 
 
-def _free_port() -> int:
-    import socket
-    s = socket.socket()
-    s.bind(("127.0.0.1", 0))
-    port = s.getsockname()[1]
-    s.close()
-    return port
-
-
 def test_two_ranks_rank_zero_validates_and_nobody_notices(tmp_path):
     """Two ranks on one GPU over gloo (the rehearsal switches and fresh child processes of tests/test_gpu_ema.py's two-rank
     test): with and without --val_every both ranks end with the same parameters as each other and as the other run, and every
     validation prints exactly one line."""
-    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    env.update(DVG_DP_SHARE_GPU="1", DVG_DP_BACKEND="gloo", DVG_FORCE_ALLREDUCE="1", OMP_NUM_THREADS="2")
     args = ["--model", "dcgan", "--dataset", "smmnist", "--n_past", "2", "--n_future", "2", "--n_eval", "4", "--batch_size", "8",
             "--save_every", "1", "--no_images", "--print_param_checksum", "--niter", "2", "--epoch_size", "2"]
 
     def run(extra):
-        cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1",
-               "--master-port", str(_free_port()), os.path.join(ROOT, "train.py")] + args + extra
-        r = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        r = train_harness.run_train_py(args + extra, ranks=2, env=dict(train_harness.REHEARSAL, DVG_FORCE_ALLREDUCE="1"))
         assert r.returncode == 0, r.stderr[-2000:]
         assert "capture failed" not in r.stderr
         pars = {ln.split()[1]: ln.split()[-2:] for ln in r.stdout.splitlines() if " param checksum " in ln}

@@ -646,6 +646,36 @@ def test_the_capture_protocol_is_written_in_graphs_only():
     assert all(v == {"graphs.py"} for v in found.values()), found
 
 
+def test_the_iteration_is_written_in_the_trainer_only():
+    """The body of a training iteration and its read-back are Trainer._iteration_dev / _iteration_result: the graph holders and
+    the training benchmark name none of their parts, `_iteration_dev(` appears as its definition and its two callers, and no
+    code asks a Trainer (or a FusedAdam) with a default for state that their __init__ declares (options objects may: old
+    pickled ones lack newer flags)."""
+    import glob
+    import re
+    for name in (os.path.join("dvg_amd", "train_graphs.py"), os.path.join("tools", "bench_train.py")):
+        src = _code_only(os.path.join(ROOT, name))
+        assert "def " in src and "import" in src
+        for part in ("_train_model_dev", "_finetune_dev", ".tick(", "ema.update(", "last_loss =", "_iters"):
+            assert part not in src, (name, part)
+    files = sorted(glob.glob(os.path.join(ROOT, "dvg_amd", "*.py"))) + [os.path.join(ROOT, "train.py")]
+    assert len(files) > 20
+    declared = "_iters|_ft_cache|_segmenter|_ar_pending|_plot_writer|state_loads|last_loss|_graph_stale|ema|lr_schedule|validation"
+    calls, asked = [], []
+    for f in files:
+        src = _code_only(f)
+        rel = os.path.relpath(f, ROOT)
+        calls += [(rel, ln.strip()) for ln in src.splitlines() if "_iteration_dev(" in ln]
+        asked += [(rel, m.group(0)) for m in re.finditer(r"getattr\(\s*([\w.]+)\s*,\s*[\"'](%s)[\"']" % declared, src)
+                  if not m.group(1).endswith("opt")]
+        asked += [(rel, m.group(0)) for m in re.finditer(r"setdefault\(\s*[\"'](%s)[\"']" % declared, src)]
+    assert not asked, asked
+    assert sorted(rel for rel, _ in calls) == [os.path.join("dvg_amd", "train_graphs.py")] + [os.path.join("dvg_amd", "trainer.py")] * 2, calls
+    assert sorted(re.sub(r"\s+", "", ln) for _, ln in calls) == [
+        "def_iteration_dev(self,x):", "returnself._iteration_result(self._iteration_dev(x))",
+        "self.outs=self.tr._iteration_dev(self.static_x)"], calls
+
+
 class _FakeGraph:
     made = []
 

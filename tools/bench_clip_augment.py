@@ -98,8 +98,7 @@ def load_leg(dev, tmp, rounds, iters):
                 str(channels), "--dataset", dataset, "--no_save", "--data_root", clip_tree.data_root(tmp, dataset)]
         gens = {}
         for name, extra in (("plain", []), ("augment", ["--augment", FULL])):
-            o = train.build_parser().parse_args(argv + extra)
-            o.ft, o.rank, o.world, o.local_batch = True, 0, 1, batch
+            o = train.options(argv + extra)
             gens[name] = make_batch_generator(o, seq, 1, dev)
         for g in gens.values():
             wall_ms(lambda: next(g)(), 10)

@@ -77,10 +77,7 @@ def main():
         # the C4 shape: dcgan_64, nc = 3, 16 clips per GPU, 2 frames in / 10 out, on the BAIR tree
         argv = ["--model", "dcgan", "--batch_size", "16", "--n_past", "2", "--n_future", "10", "--channels", "3",
                 "--dataset", "bair", "--no_save", "--data_root", clip_tree.data_root(tmp, "bair")]
-        real = train.build_parser().parse_args(argv)
-        synth = train.build_parser().parse_args(argv + ["--synthetic_data"])
-        for o in (real, synth):
-            o.ft, o.rank, o.world, o.local_batch = True, 0, 1, 16
+        real, synth = train.options(argv), train.options(argv + ["--synthetic_data"])
         index = datasets.open_index("bair", real.data_root, True)
         t0 = time.perf_counter()
         pool = datasets.build_pool(index, 64, dev, real.data_threads)

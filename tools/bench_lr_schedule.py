@@ -32,9 +32,8 @@ MODELS = ("dcgan", "vgg")
 
 
 def make_leg(model, batch, frames, extra):
-    o = train.build_parser().parse_args(["--model", model, "--batch_size", str(batch), "--n_past", str(frames // 2),
-                                         "--n_future", str(frames - frames // 2), "--no_save"] + extra)
-    o.ft, o.rank, o.world, o.local_batch = True, 0, 1, batch
+    o = train.options(["--model", model, "--batch_size", str(batch), "--n_past", str(frames // 2),
+                       "--n_future", str(frames - frames // 2), "--no_save"] + extra)
     torch.manual_seed(1)
     tr = train.Trainer(o, torch.device("cuda:0"))
     tr.train_mode()

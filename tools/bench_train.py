@@ -36,13 +36,12 @@ def main():
     ap.add_argument("--frame_loss", default="mse", help="train.py's flag: the pixel penalty of the frame terms")
     ap.add_argument("--gdl_weight", type=float, default=0.0, help="train.py's flag: the gradient-difference loss")
     a = ap.parse_args()
-    o = train.build_parser().parse_args(["--model", a.model, "--batch_size", str(a.batch), "--n_past", str(a.n_past),
-                                         "--n_future", str(a.n_future), "--no_save", "--channels", str(a.channels),
-                                         "--image_width", str(a.image_width), "--clip_grad_norm", repr(a.clip_grad_norm)] +
-                                        (["--skip_nonfinite"] if a.skip_nonfinite else []) +
-                                        ([] if a.ema_decay is None else ["--ema_decay", repr(a.ema_decay)]) +
-                                        ["--frame_loss", a.frame_loss, "--gdl_weight", repr(a.gdl_weight)])
-    o.ft, o.rank, o.world, o.local_batch = not a.no_ft, 0, 1, a.batch
+    o = train.options(["--model", a.model, "--batch_size", str(a.batch), "--n_past", str(a.n_past),
+                       "--n_future", str(a.n_future), "--no_save", "--channels", str(a.channels),
+                       "--image_width", str(a.image_width), "--clip_grad_norm", repr(a.clip_grad_norm)] +
+                      (["--no_ft"] if a.no_ft else []) + (["--skip_nonfinite"] if a.skip_nonfinite else []) +
+                      ([] if a.ema_decay is None else ["--ema_decay", repr(a.ema_decay)]) +
+                      ["--frame_loss", a.frame_loss, "--gdl_weight", repr(a.gdl_weight)])
     if os.environ.get("DVG_FORCE_ALLREDUCE") == "1":
         import torch.distributed as dist
         import socket
@@ -64,10 +63,7 @@ def main():
     x, _ = utils.normalize_data(o, torch.cuda.FloatTensor, seq)
 
     def it():
-        tr.train_model(x)
-        if o.ft:
-            tr.finetune_temporal_encoders(x)
-        tr.ema is None or tr.ema.update()
+        tr.iteration(x)
     if a.graph or a.segmented:
         g = (train.SegmentedIteration if a.segmented else train.GraphedIteration)(tr, warmup=2)
         run = lambda: g(x)   # noqa: E731

@@ -33,11 +33,8 @@ def main(argv=None):
     a = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     for model in a.models.split(","):
-        opt = train.build_parser().parse_args(["--model", model, "--batch_size", str(a.batch_size), "--n_past", "10", "--n_future",
-                                               "10", "--n_eval", "20", "--dataset", "smmnist", "--synthetic_data", "--val_every",
-                                               "1", "--no_save"])
-        opt.ft = True
-        opt.rank, opt.world, opt.local_batch = 0, 1, opt.batch_size
+        opt = train.options(["--model", model, "--batch_size", str(a.batch_size), "--n_past", "10", "--n_future", "10", "--n_eval",
+                             "20", "--dataset", "smmnist", "--synthetic_data", "--val_every", "1", "--no_save"])
         torch.manual_seed(1)
         torch.cuda.manual_seed_all(1)
         tr = train.Trainer(opt, dev)

@@ -37,8 +37,7 @@ def main():
     import utils
     from dvg_amd.data import SyntheticMovingMNIST
     model = sys.argv[1] if len(sys.argv) > 1 else "dcgan"
-    o = train.build_parser().parse_args(["--model", model, "--batch_size", "64", "--n_past", "10", "--n_future", "10", "--no_save"])
-    o.ft, o.rank, o.world, o.local_batch = True, 0, 1, 64
+    o = train.options(["--model", model, "--batch_size", "64", "--n_past", "10", "--n_future", "10", "--no_save"])
     torch.manual_seed(1)
     tr = train.Trainer(o, torch.device("cuda:0"))
     tr.train_mode()

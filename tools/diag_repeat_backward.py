@@ -79,9 +79,7 @@ def main():
         assert line.strip() == "ready", line
     argv = ["--model", a.model, "--dataset", "smmnist", "--batch_size", str(a.batch), "--n_past", str(a.n_past),
             "--n_future", str(a.n_future), "--no_save"]
-    opt = train.build_parser().parse_args(argv)
-    opt.ft, opt.rank, opt.world = True, rank, world
-    opt.local_batch = a.batch          # --batch is the PER-RANK batch here
+    opt = train.options(argv, rank=rank, world=world, local_batch=a.batch)   # --batch is the PER-RANK batch here
     torch.manual_seed(5)
     tr = train.Trainer(opt, dev)
     tr.train_mode()

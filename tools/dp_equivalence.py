@@ -54,9 +54,7 @@ def main():
     dev = torch.device("cuda", local)
     argv = ["--model", a.model, "--dataset", "smmnist", "--batch_size", str(a.batch), "--n_past", str(a.n_past),
             "--n_future", str(a.n_future), "--no_save"] + (["--sync_bn"] if a.sync_bn else [])
-    opt = train.build_parser().parse_args(argv)
-    opt.ft, opt.rank, opt.world = True, rank, world
-    opt.local_batch = parallel.shard_batch(a.batch, world)
+    opt = train.options(argv, rank=rank, world=world)
     torch.manual_seed(5)
     tr = train.Trainer(opt, dev)
     tr.train_mode()

@@ -63,10 +63,9 @@ def main():
     import utils
     from dvg_amd.data import synthetic_video
     T = a.n_past + a.n_future
-    opt = train.build_parser().parse_args(["--model", a.model, "--channels", str(a.channels), "--image_width", str(a.image_width),
-                                           "--dataset", "bair", "--batch_size", str(a.batch), "--n_past", str(a.n_past),
-                                           "--n_future", str(a.n_future), "--no_save", "--synthetic_data"])
-    opt.ft, opt.rank, opt.world, opt.local_batch = True, 0, 1, a.batch
+    opt = train.options(["--model", a.model, "--channels", str(a.channels), "--image_width", str(a.image_width),
+                         "--dataset", "bair", "--batch_size", str(a.batch), "--n_past", str(a.n_past),
+                         "--n_future", str(a.n_future), "--no_save", "--synthetic_data"])
     torch.manual_seed(1)
     tr = train.Trainer(opt, torch.device("cuda:0"))
     tr.train_mode()
