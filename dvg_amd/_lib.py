@@ -79,6 +79,10 @@ SIGNATURES = {
     "dvg_lstm_cell_pre": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
     "dvg_lstm_cell_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
     "dvg_lstm_cell_x": (_i, [_p, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _i, _i, _p]),
+    "dvg_gru_cell": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
+    "dvg_gru_cell_pre": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p]),
+    "dvg_rnn_cell": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
+    "dvg_gru_gates_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
     "dvg_stem_gemm": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
     "dvg_gp_precision": (_i, [_i, _i, _i]),
     "dvg_gp_bwd_precision": (_i, [_i, _i]),

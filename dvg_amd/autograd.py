@@ -593,8 +593,9 @@ def gp_train_autograd(layer, h, noise):
     return gp_train(layer, h, noise)
 
 
-# nn.Linear / nn.LSTMCell / the LSTM sequence: dvg_amd/autograd_recurrent.py (r06).  Imported LAST: that module reads this one's
+# nn.Linear / nn.LSTMCell / nn.GRUCell / nn.RNNCell / the LSTM and GRU sequences: dvg_amd/autograd_recurrent.py (r06).  Imported LAST: that module reads this one's
 # helpers and switches through the module object at call time.
 from .autograd_recurrent import (  # noqa: E402,F401
     _Linear, _LSTMCell, _LSTMSequence, linear_autograd, lstm_cell_autograd, lstm_sequence_autograd,
+    _GRUCell, _RNNCell, _GRUSequence, gru_cell_autograd, rnn_cell_autograd, gru_sequence_autograd,
 )

@@ -1,6 +1,6 @@
-"""torch.autograd glue of the dense / recurrent part of the training path: nn.Linear (+ activation), nn.LSTMCell, and the
-teacher-forced LSTM sequence (lstm.py:42-72 driven by train.py:175-198,213-226) - forward and backward are kernels of
-libdvg_hip.so (dense.hip).  Split from autograd.py in r06; that module re-exports these names and owns the shared machinery
+"""torch.autograd glue of the dense / recurrent part of the training path: nn.Linear (+ activation), nn.LSTMCell, nn.GRUCell,
+nn.RNNCell, and the teacher-forced LSTM / GRU sequence (lstm.py:42-136 driven by train.py:175-198,213-226) - forward and backward
+are kernels of libdvg_hip.so (dense.hip).  Split from autograd.py in r06; that module re-exports these names and owns the shared machinery
 (`_sink`, the deferred dense weight-gradient queues, the switches tests toggle), reached here through `_ag.` at call time."""
 from __future__ import annotations
 
@@ -188,3 +188,187 @@ class _LSTMSequence(torch.autograd.Function):
 
 def lstm_sequence_autograd(x, S, params):
     return _LSTMSequence.apply(x, S, *params)
+
+
+def _cell_param_grads(ctx_params, ng, dys, inputs):
+    """The parameter gradients (dW_ih, dW_hh, db_ih, db_hh) of one use of a GRUCell / RNNCell: dW_ih = dys[0]^T inputs[0],
+    dW_hh = dys[1]^T inputs[1], the bias gradients their column sums - queued for the batched GEMM of the BPTT pass when all
+    four accumulate in place (autograd._dense_wgrad), computed here otherwise.  Returns what autograd is handed (None for
+    a gradient that went into its sink)."""
+    sinks = [_ag._sink(p, n) for p, n in zip(ctx_params, ng)]
+    if _ag.DENSE_BATCH > 1 and all(t is not None for t in sinks):
+        if dys[0] is dys[1]:
+            _ag._dense_wgrad((sinks[0], sinks[1]), (sinks[2], sinks[3]), dys[0], inputs)
+        else:
+            _ag._dense_wgrad((sinks[0],), (sinks[2],), dys[0], (inputs[0],))
+            _ag._dense_wgrad((sinks[1],), (sinks[3],), dys[1], (inputs[1],))
+        return None, None, None, None
+    out = []
+    for k in range(2):
+        g = ops.gemm_tn(dys[k], inputs[k], out=sinks[k], accumulate=sinks[k] is not None, colsums=(sinks[2 + k],))
+        out.append(None if sinks[k] is not None else g)
+    for k in range(2):
+        out.append(ops.colsum(dys[k]) if sinks[2 + k] is None and ng[2 + k] else None)
+    return tuple(out)
+
+
+class _GRUCell(torch.autograd.Function):
+    """nn.GRUCell (lstm.py:84,101): forward dvg_gru_cell, backward dvg_gru_gates_bwd + the GEMMs of its two halves."""
+
+    @staticmethod
+    def forward(ctx, x, h, w_ih, w_hh, b_ih, b_hh):
+        x, h = _ag._c(x), _ag._c(h)
+        h2, acts = ops.gru_cell(x, h, w_ih, w_hh, b_ih, b_hh, want_acts=True)
+        ctx.save_for_backward(x, h, w_ih, w_hh, acts)
+        ctx.params = (w_ih, w_hh, b_ih, b_hh)
+        return h2
+
+    @staticmethod
+    def backward(ctx, dh2):
+        x, h, w_ih, w_hh, acts = ctx.saved_tensors
+        ng = ctx.needs_input_grad
+        dGi, dGh, dh = ops.gru_gates_bwd(_ag._c(dh2), None, acts, h, want_dh_prev=ng[1])
+        dx = ops.gemm_nt(dGi, weights.transposed(ctx.params[0]), None, None) if ng[0] else None
+        if ng[1]:       # dh = d z (written above) + dGh W_hh
+            ops.gemm_nt(dGh, weights.transposed(ctx.params[1]), None, None, out=dh, accumulate=True)
+        return (dx, dh) + _cell_param_grads(ctx.params, ng[2:6], (dGi, dGh), (x, h))
+
+
+def gru_cell_autograd(x, h, w_ih, w_hh, b_ih, b_hh):
+    return _GRUCell.apply(x, h, w_ih, w_hh, b_ih, b_hh)
+
+
+class _RNNCell(torch.autograd.Function):
+    """nn.RNNCell (lstm.py:116,133): forward dvg_rnn_cell; the backward needs no kernel of its own (tanh', two NT GEMMs, the
+    weight-gradient GEMM)."""
+
+    @staticmethod
+    def forward(ctx, x, h, w_ih, w_hh, b_ih, b_hh):
+        x, h = _ag._c(x), _ag._c(h)
+        h2 = ops.rnn_cell(x, h, w_ih, w_hh, b_ih, b_hh)
+        ctx.save_for_backward(x, h, w_ih, w_hh, h2)
+        ctx.params = (w_ih, w_hh, b_ih, b_hh)
+        return h2
+
+    @staticmethod
+    def backward(ctx, dh2):
+        x, h, w_ih, w_hh, h2 = ctx.saved_tensors
+        ng = ctx.needs_input_grad
+        dpre = ops.act_bwd(_ag._c(dh2), h2, ops.ACT_TANH)
+        dx = ops.gemm_nt(dpre, weights.transposed(ctx.params[0]), None, None) if ng[0] else None
+        dh = ops.gemm_nt(dpre, weights.transposed(ctx.params[1]), None, None) if ng[1] else None
+        return (dx, dh) + _cell_param_grads(ctx.params, ng[2:6], (dpre, dpre), (x, h))
+
+
+def rnn_cell_autograd(x, h, w_ih, w_hh, b_ih, b_hh):
+    return _RNNCell.apply(x, h, w_ih, w_hh, b_ih, b_hh)
+
+
+class _GRUSequence(torch.autograd.Function):
+    """lstm.gru (lstm.py:75-104) over a whole TEACHER-FORCED sequence from the zero state of `init_hidden()`, parallel to
+    _LSTMSequence: the embedding, every cell's input half W_ih (.) + b_ih (+ b_hr, b_hz: b_hn stays with the recurrent half,
+    inside the r * product) and the output head run as ONE GEMM each over the S x B rows; per time step and layer one
+    dvg_gru_cell_pre launch forward, and backward one dvg_gru_gates_bwd launch plus the accumulating GEMM dh_{t-1} += dGh_t
+    W_hh (two launches where the LSTM's fused dvg_lstm_cell_bwd has one).  Any H % 64 == 0.
+    x (S*B, in).  params = (W_e, b_e, [W_ih, W_hh, b_ih, b_hh] x L, W_o, b_o).  Returns y (S*B, out)."""
+
+    @staticmethod
+    def forward(ctx, x, S, *params):
+        L = (len(params) - 4) // 4
+        we, be, wo, bo = params[0], params[1], params[-2], params[-1]
+        x = _ag._c(x)
+        rows, B = x.shape[0], x.shape[0] // S
+        H = we.shape[0]
+        dev = x.device
+        e = ops.gemm_nt(x, we.detach(), None, be.detach())
+        zero = zero_state(B, H, dev)
+        if zero is None:       # first call inside a hipGraph capture: from the graph's pool, not cached
+            zero = torch.zeros((B, H), device=dev)
+        inp, saved = e, []
+        for l in range(L):
+            wih, whh, bih, bhh = params[2 + 4 * l: 6 + 4 * l]
+            bias = bih.detach().clone()
+            bias[:2 * H] += bhh.detach()[:2 * H]
+            pre = ops.gemm_nt(inp, wih.detach(), None, bias)                                # (S*B, 3H)
+            b_hn = bhh.detach()[2 * H:]
+            hs = torch.empty((rows, H), device=dev)
+            acts = torch.empty((rows, 4 * H), device=dev)
+            hp = zero
+            for t in range(S):
+                sl = slice(t * B, (t + 1) * B)
+                ops.gru_cell_pre(pre[sl], hp, whh.detach(), b_hn, hs[sl], acts[sl])
+                hp = hs[sl]
+            saved += [inp, hs, acts]
+            inp = hs
+        y = ops.gemm_nt(inp, wo.detach(), None, bo.detach(), act=ops.ACT_TANH)
+        ctx.save_for_backward(x, y, *saved)
+        ctx.params, ctx.meta = params, (S, B, H, L)
+        ctx.param_versions = tuple(p._version for p in params)   # backward re-reads the weights: see the check there
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, y, *saved = ctx.saved_tensors
+        params = ctx.params
+        # as _LSTMSequence.backward: the parameters are kept as objects, outside autograd's own version check
+        if tuple(p._version for p in params) != ctx.param_versions:
+            raise RuntimeError("_GRUSequence.backward: a GRU parameter was modified in place after the forward pass")
+        S, B, H, L = ctx.meta
+        ng = ctx.needs_input_grad            # (x, S, *params)
+        pg = list(ng[2:])
+        grads = [None] * len(params)
+
+        def acc_wb(i, d, inp, bias=()):      # dW_i = d^T inp (i None: no weight) and db_j = column sums of d (j in bias)
+            sinks = []
+            plain = None
+            for j in bias:
+                if not pg[j]:
+                    continue
+                s_ = _ag._sink(params[j], True)
+                if s_ is not None:
+                    sinks.append(s_)
+                else:
+                    plain = ops.colsum(d) if plain is None else plain
+                    grads[j] = plain
+            if i is not None and pg[i]:
+                s_ = _ag._sink(params[i], True)
+                g = ops.gemm_tn(d, inp, out=s_, accumulate=s_ is not None, colsums=sinks)
+                grads[i] = None if s_ is not None else g
+            else:
+                for s_ in sinks:
+                    ops.colsum(d, out=s_, accumulate=True)
+        dpre = ops.act_bwd(_ag._c(dy), y, ops.ACT_TANH)
+        top = saved[3 * (L - 1) + 1]
+        acc_wb(len(params) - 2, dpre, top, [len(params) - 1])
+        dh_all = ops.gemm_nt(dpre, weights.transposed(params[-2]), None, None)          # d h^L_t for every t, (S*B, H)
+        dev = x.device
+        for l in reversed(range(L)):
+            inp, hs, acts = saved[3 * l: 3 * l + 3]
+            wih, whh = params[2 + 4 * l], params[3 + 4 * l]
+            whh_t = weights.transposed(whh)                                              # [H][3H]
+            dGi = torch.empty((S * B, 3 * H), device=dev)
+            dGh = torch.empty((S * B, 3 * H), device=dev)
+            dhb = [torch.empty((B, H), device=dev), torch.empty((B, H), device=dev)]
+            dh_rec = None
+            for t in reversed(range(S)):
+                sl = slice(t * B, (t + 1) * B)
+                h_prev = hs[(t - 1) * B: t * B] if t > 0 else None                       # None: the zero initial state
+                dhp = dhb[t & 1] if t > 0 else None
+                ops.gru_gates_bwd(dh_all[sl], dh_rec, acts[sl], h_prev, dGi[sl], dGh[sl], dhp, want_dh_prev=False)
+                if t > 0:
+                    ops.gemm_nt(dGh[sl], whh_t, None, None, out=dhp, accumulate=True)    # dh_{t-1} = d z + dGh W_hh
+                dh_rec = dhp
+            acc_wb(2 + 4 * l, dGi, inp, [4 + 4 * l])
+            if S > 1:                           # h_{-1} = 0: the first step contributes nothing to dW_hh ...
+                acc_wb(3 + 4 * l, dGh[B:], hs[:(S - 1) * B])
+            acc_wb(None, dGh, None, [5 + 4 * l])        # ... but it does to db_hh
+            if l > 0 or pg[0] or pg[1] or ng[0]:
+                dh_all = ops.gemm_nt(dGi, weights.transposed(wih), None, None)         # gradient w.r.t. this layer's input sequence
+        de = dh_all
+        acc_wb(0, de, x, [1])
+        dx = ops.gemm_nt(de, weights.transposed(params[0]), None, None) if ng[0] else None
+        return (dx, None) + tuple(grads)
+
+
+def gru_sequence_autograd(x, S, params):
+    return _GRUSequence.apply(x, S, *params)

@@ -57,18 +57,18 @@ def rollout_traffic(model: str, args, ms_per_step: float):
 
 
 # ------------------------------------------------------------------------------------------------------------
-def build_models(model: str, batch: int, nc: int, dev, seed: int):
+def build_models(model: str, batch: int, nc: int, dev, seed: int, predictor: str = "lstm"):
     import importlib
     import torch
     from dvg_amd import utils
     from dvg_amd.models.gp_models import GaussianLikelihood, GPRegressionLayer1
-    from dvg_amd.models.lstm import lstm
+    from dvg_amd.models.lstm import PREDICTORS
     torch.manual_seed(seed)
     m = importlib.import_module(f"dvg_amd.models.{model}_64")
     enc, dec = m.encoder(90, nc), m.decoder(90, nc)
     enc.apply(utils.init_weights)
     dec.apply(utils.init_weights)
-    fp = lstm(90, 90, 256, 2, batch)
+    fp = PREDICTORS[predictor](90, 90, 256, 2, batch)      # --predictor of train.py / generate_frames.py; the headline is the lstm
     fp.apply(utils.init_weights)
     gp, lik = GPRegressionLayer1(90), GaussianLikelihood(batch_size=90)
     mods = [enc, dec, fp, gp, lik]
@@ -366,7 +366,7 @@ TRAIN_EXTRA = {                                # measured at N = 1 only (one hip
 }
 
 
-def measure_train(ctx: Ctx, args, graphed, allreduce: bool = True, shape=TRAIN_C4, iters=None) -> dict:
+def measure_train(ctx: Ctx, args, graphed, allreduce: bool = True, shape=TRAIN_C4, iters=None, predictor: str = "lstm") -> dict:
     """Data-parallel training at `shape` (default BASELINE.json configs[3]'s: BAIR-like dcgan_64, nc=3, 16 clips per GPU,
     2-in/10-out): train_model + both fine-tuning closures per iteration (train.py:354-361), gradients averaged over
     RCCL (dvg_amd/parallel.py).  Weak scaling: the global batch is clips per GPU x ranks."""
@@ -379,7 +379,8 @@ def measure_train(ctx: Ctx, args, graphed, allreduce: bool = True, shape=TRAIN_C
     T = n_past + n_future
     opt = train.options(["--model", model, "--channels", str(nc), "--image_width", str(width), "--dataset",
                          "smmnist" if (nc, width) == (1, 64) else "bair", "--batch_size", str(per_gpu * ctx.world),
-                         "--n_past", str(n_past), "--n_future", str(n_future), "--no_save", "--synthetic_data"],
+                         "--n_past", str(n_past), "--n_future", str(n_future), "--no_save", "--synthetic_data",
+                         "--predictor", predictor],      # train.py's flag; the headline legs keep the lstm
                         rank=ctx.rank, world=ctx.world)
     torch.manual_seed(args.seed)
     tr = train.Trainer(opt, ctx.dev)

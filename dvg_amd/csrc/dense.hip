@@ -11,6 +11,8 @@
 //    K split across its 64 lanes; a 63-shuffle butterfly transpose-reduce leaves
 //    exactly one finished pre-activation per lane, and three more shuffles bring
 //    the i,f,g,o of one (batch, unit) together for the state update.
+//  * gru_cell / rnn_cell: the nn.GRUCell and nn.RNNCell steps of lstm.py:75-136 on the same wave scheme, and the
+//    elementwise half of the GRU's backward.
 #include "dvg_common.h"
 
 namespace dvg {
@@ -323,6 +325,190 @@ __global__ __launch_bounds__(256) void lstm_cell_x_kernel(const float* __restric
         const float cn = gf * e_c + gi * gg;
         c_out[(size_t)(b0 + b) * H + j] = cn;
         h_out[(size_t)(b0 + b) * H + j] = go * tanhf(cn);
+    }
+}
+
+// ------------------------------------------------------------------------------------
+// gru_cell / rnn_cell: one nn.GRUCell step (lstm.py:84,101; gate order r,z,n) and one nn.RNNCell step (lstm.py:116,133).
+// lstm_cell_kernel's wave scheme as it stands: a wave owns 8 batch rows x 2 hidden units with 4 accumulators per
+// (row, unit).  For the GRU the four slots are  r: W_ir x + W_hr h,  z: W_iz x + W_hz h,  W_in x  and  W_hn h  - the two
+// halves of the candidate stay apart because b_hn and W_hn h sit INSIDE the r * (.) product:
+//     n = tanh(W_in x + b_in + r * (W_hn h + b_hn)),   h' = (1 - z) n + z h.
+// Six rows of each weight matrix per wave instead of the LSTM's eight (3/4 of its weight traffic), no cell state.
+// PRE (teacher-forced training): `x` is [B][3H] = W_ih x + b_ih with b_hr, b_hz already added, `b_hh` points at b_hn [H]
+// and only the recurrent half runs (the W_in x slot stays zero and its lane adds the given pre-activation).
+// acts_out (optional) [B][4H] = r, z, n, hn = W_hn h + b_hn: what dvg_gru_gates_bwd needs.
+// ------------------------------------------------------------------------------------
+template <bool PRE>
+__global__ __launch_bounds__(256) void gru_cell_kernel(const float* __restrict__ x, const float* __restrict__ h,
+                                                       const float* __restrict__ w_ih, const float* __restrict__ w_hh,
+                                                       const float* __restrict__ b_ih, const float* __restrict__ b_hh,
+                                                       float* __restrict__ h_out, float* __restrict__ acts_out,
+                                                       int B, int H) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j0 = blockIdx.x * 2;
+    const int b0 = blockIdx.y * 32 + wave * 8;
+    if (b0 >= B) return;  // whole wave out of range (wave-uniform; no barriers below)
+
+    float v[64];  // v[b*8 + jj*4 + s], s = r, z, W_in x, W_hn h
+#pragma unroll
+    for (int i = 0; i < 64; ++i) v[i] = 0.f;
+
+    // epilogue operands of this lane's (batch, unit, slot), fetched with the first K slice
+    const int eb = min(b0 + (lane >> 3), B - 1), ej = j0 + ((lane >> 2) & 1), es = lane & 3;
+    float e_bias;
+    if (PRE) e_bias = es < 3 ? x[(size_t)eb * 3 * H + es * H + ej] : b_hh[ej];
+    else e_bias = es < 2 ? b_ih[es * H + ej] + b_hh[es * H + ej] : (es == 2 ? b_ih[2 * H + ej] : b_hh[2 * H + ej]);
+    const float e_h = h[(size_t)eb * H + ej];
+
+    // all loads of a 256-deep K slice before the first FMA, none behind a branch (rows past B clamped, dropped at the end)
+    for (int k0 = lane * 4; k0 < H; k0 += 256) {
+        f32x4 xv[PRE ? 1 : 8], hv[8], wi[PRE ? 1 : 6], wh[6];   // w?[jj*3 + g]
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const int bb = min(b0 + b, B - 1);
+            if constexpr (!PRE) xv[b] = *reinterpret_cast<const f32x4*>(x + (size_t)bb * H + k0);
+            hv[b] = *reinterpret_cast<const f32x4*>(h + (size_t)bb * H + k0);
+        }
+#pragma unroll
+        for (int r = 0; r < 6; ++r) {
+            const int row = (r % 3) * H + j0 + r / 3;
+            if constexpr (!PRE) wi[r] = *reinterpret_cast<const f32x4*>(w_ih + (size_t)row * H + k0);
+            wh[r] = *reinterpret_cast<const f32x4*>(w_hh + (size_t)row * H + k0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            const int jj = r >> 2, s = r & 3;
+            const int g = jj * 3 + (s == 3 ? 2 : s);   // weight row of this slot
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                float a = v[b * 8 + r];
+                if constexpr (!PRE) {
+                    if (s != 3) {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) a = fmaf(xv[b][e], wi[g][e], a);
+                    }
+                }
+                if (s != 2) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) a = fmaf(hv[b][e], wh[g][e], a);
+                }
+                v[b * 8 + r] = a;
+            }
+        }
+    }
+    butterfly_step<32>(v, lane);
+    butterfly_step<16>(v, lane);
+    butterfly_step<8>(v, lane);
+    butterfly_step<4>(v, lane);
+    butterfly_step<2>(v, lane);
+    butterfly_step<1>(v, lane);
+
+    const int b = lane >> 3, jj = (lane >> 2) & 1, s = lane & 3;
+    const int j = j0 + jj;
+    const float pre = v[0] + e_bias;
+    const float a = s < 2 ? sigmoidf_(pre) : pre;
+    const int q = lane & ~3;
+    const float gr = __shfl(a, q), gz = __shfl(a, q + 1), gin = __shfl(a, q + 2), ghn = __shfl(a, q + 3);
+    const float gn = tanhf(gin + gr * ghn);
+    if (b0 + b < B) {
+        if (acts_out) acts_out[(size_t)(b0 + b) * 4 * H + s * H + j] = s == 2 ? gn : a;
+        if (s == 0) h_out[(size_t)(b0 + b) * H + j] = (1.f - gz) * gn + gz * e_h;
+    }
+}
+
+// One gate: the wave's 64 accumulators are 8 batch rows x 8 hidden units, h' = tanh(W_ih x + b_ih + W_hh h + b_hh).
+__global__ __launch_bounds__(256) void rnn_cell_kernel(const float* __restrict__ x, const float* __restrict__ h,
+                                                       const float* __restrict__ w_ih, const float* __restrict__ w_hh,
+                                                       const float* __restrict__ b_ih, const float* __restrict__ b_hh,
+                                                       float* __restrict__ h_out, int B, int H) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int j0 = blockIdx.x * 8;
+    const int b0 = blockIdx.y * 32 + wave * 8;
+    if (b0 >= B) return;  // wave-uniform; no barriers below
+
+    float v[64];  // v[b*8 + jj]
+#pragma unroll
+    for (int i = 0; i < 64; ++i) v[i] = 0.f;
+    const int ej = j0 + (lane & 7);
+    const float e_bias = b_ih[ej] + b_hh[ej];
+
+    for (int k0 = lane * 4; k0 < H; k0 += 256) {
+        f32x4 xv[8], hv[8], wi[8], wh[8];
+#pragma unroll
+        for (int b = 0; b < 8; ++b) {
+            const int bb = min(b0 + b, B - 1);
+            xv[b] = *reinterpret_cast<const f32x4*>(x + (size_t)bb * H + k0);
+            hv[b] = *reinterpret_cast<const f32x4*>(h + (size_t)bb * H + k0);
+        }
+#pragma unroll
+        for (int r = 0; r < 8; ++r) {
+            wi[r] = *reinterpret_cast<const f32x4*>(w_ih + (size_t)(j0 + r) * H + k0);
+            wh[r] = *reinterpret_cast<const f32x4*>(w_hh + (size_t)(j0 + r) * H + k0);
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int r = 0; r < 8; ++r)
+#pragma unroll
+            for (int b = 0; b < 8; ++b) {
+                float a = v[b * 8 + r];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) a = fmaf(xv[b][e], wi[r][e], a);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) a = fmaf(hv[b][e], wh[r][e], a);
+                v[b * 8 + r] = a;
+            }
+    }
+    butterfly_step<32>(v, lane);
+    butterfly_step<16>(v, lane);
+    butterfly_step<8>(v, lane);
+    butterfly_step<4>(v, lane);
+    butterfly_step<2>(v, lane);
+    butterfly_step<1>(v, lane);
+    const int b = lane >> 3;
+    if (b0 + b < B) h_out[(size_t)(b0 + b) * H + ej] = tanhf(v[0] + e_bias);
+}
+
+// nn.GRUCell backward, elementwise part (one pass over [B][H], float4 per thread): from d = dh_a + dh_b, the saved
+// r, z, n, hn and h_prev (NULL: the zero initial state)
+//   da_n = d (1 - z)(1 - n^2),  da_r = da_n hn r (1 - r),  da_z = d (h - n) z (1 - z)
+//   dGi = [da_r, da_z, da_n] (input side),  dGh = [da_r, da_z, da_n r] (hidden side),  dh_prev = d z (optional).
+__global__ __launch_bounds__(256) void gru_gates_bwd_kernel(const float* __restrict__ dh_a, const float* __restrict__ dh_b,
+                                                            const float* __restrict__ acts, const float* __restrict__ h_prev,
+                                                            float* __restrict__ dGi, float* __restrict__ dGh,
+                                                            float* __restrict__ dh_prev, int B, int H) {
+    const int H4 = H / 4;
+    const long total = (long)B * H4;
+    const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int b = (int)(i / H4), j = (int)(i % H4) * 4;
+        const size_t o = (size_t)b * H + j;
+        const float* ap = acts + (size_t)b * 4 * H + j;
+        const f32x4 r = *reinterpret_cast<const f32x4*>(ap), z = *reinterpret_cast<const f32x4*>(ap + H);
+        const f32x4 n = *reinterpret_cast<const f32x4*>(ap + 2 * H), hn = *reinterpret_cast<const f32x4*>(ap + 3 * H);
+        const f32x4 da = dh_a ? *reinterpret_cast<const f32x4*>(dh_a + o) : zero4;
+        const f32x4 db = dh_b ? *reinterpret_cast<const f32x4*>(dh_b + o) : zero4;
+        const f32x4 hp = h_prev ? *reinterpret_cast<const f32x4*>(h_prev + o) : zero4;
+        f32x4 gr, gz, gn, gnr, dp;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float d = da[e] + db[e];
+            gn[e] = d * (1.f - z[e]) * (1.f - n[e] * n[e]);
+            gr[e] = gn[e] * hn[e] * r[e] * (1.f - r[e]);
+            gz[e] = d * (hp[e] - n[e]) * z[e] * (1.f - z[e]);
+            gnr[e] = gn[e] * r[e];
+            dp[e] = d * z[e];
+        }
+        float* gi = dGi + (size_t)b * 3 * H + j;
+        float* gh = dGh + (size_t)b * 3 * H + j;
+        *reinterpret_cast<f32x4*>(gi) = gr;
+        *reinterpret_cast<f32x4*>(gi + H) = gz;
+        *reinterpret_cast<f32x4*>(gi + 2 * H) = gn;
+        *reinterpret_cast<f32x4*>(gh) = gr;
+        *reinterpret_cast<f32x4*>(gh + H) = gz;
+        *reinterpret_cast<f32x4*>(gh + 2 * H) = gnr;
+        if (dh_prev) *reinterpret_cast<f32x4*>(dh_prev + o) = dp;
     }
 }
 
@@ -785,6 +971,54 @@ extern "C" int dvg_lstm_cell_x(const float* x, int ldx, int Kx, const float* h, 
     hipLaunchKernelGGL(lstm_cell_x_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, ldx, Kx, h, c, w_x, Kxp, w_hh, bias,
                        h_out, c_out, B, H);
     return check_launch("dvg_lstm_cell_x");
+}
+
+extern "C" int dvg_gru_cell(const float* x, const float* h, const float* w_ih, const float* w_hh, const float* b_ih,
+                            const float* b_hh, float* h_out, float* acts_out, int B, int H, void* stream) {
+    DVG_REQUIRE(x && h && w_ih && w_hh && b_ih && b_hh && h_out, DVG_ERR_NULL, "dvg_gru_cell: NULL pointer");
+    DVG_REQUIRE(B > 0 && H > 0 && H % 64 == 0, DVG_ERR_SHAPE, "dvg_gru_cell: H=%d must be a multiple of 64", H);
+    DVG_REQUIRE(h_out != h && h_out != x, DVG_ERR_SHAPE, "dvg_gru_cell: in-place state update");
+    DVG_REQUIRE(aligned16(x) && aligned16(h) && aligned16(w_ih) && aligned16(w_hh), DVG_ERR_ALIGN, "dvg_gru_cell: alignment");
+    dim3 grid(H / 2, (B + 31) / 32);
+    hipLaunchKernelGGL(gru_cell_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream, x, h, w_ih, w_hh, b_ih, b_hh, h_out,
+                       acts_out, B, H);
+    return check_launch("dvg_gru_cell");
+}
+
+extern "C" int dvg_gru_cell_pre(const float* pre, const float* h, const float* w_hh, const float* b_hn, float* h_out,
+                                float* acts_out, int B, int H, void* stream) {
+    DVG_REQUIRE(pre && h && w_hh && b_hn && h_out, DVG_ERR_NULL, "dvg_gru_cell_pre: NULL pointer");
+    DVG_REQUIRE(B > 0 && H > 0 && H % 64 == 0, DVG_ERR_SHAPE, "dvg_gru_cell_pre: H=%d must be a multiple of 64", H);
+    DVG_REQUIRE(h_out != h && h_out != pre, DVG_ERR_SHAPE, "dvg_gru_cell_pre: in-place state update");
+    DVG_REQUIRE(aligned16(h) && aligned16(w_hh), DVG_ERR_ALIGN, "dvg_gru_cell_pre: alignment");
+    dim3 grid(H / 2, (B + 31) / 32);
+    hipLaunchKernelGGL(gru_cell_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream, pre, h, nullptr, w_hh, nullptr, b_hn,
+                       h_out, acts_out, B, H);
+    return check_launch("dvg_gru_cell_pre");
+}
+
+extern "C" int dvg_rnn_cell(const float* x, const float* h, const float* w_ih, const float* w_hh, const float* b_ih,
+                            const float* b_hh, float* h_out, int B, int H, void* stream) {
+    DVG_REQUIRE(x && h && w_ih && w_hh && b_ih && b_hh && h_out, DVG_ERR_NULL, "dvg_rnn_cell: NULL pointer");
+    DVG_REQUIRE(B > 0 && H > 0 && H % 64 == 0, DVG_ERR_SHAPE, "dvg_rnn_cell: H=%d must be a multiple of 64", H);
+    DVG_REQUIRE(h_out != h && h_out != x, DVG_ERR_SHAPE, "dvg_rnn_cell: in-place state update");
+    DVG_REQUIRE(aligned16(x) && aligned16(h) && aligned16(w_ih) && aligned16(w_hh), DVG_ERR_ALIGN, "dvg_rnn_cell: alignment");
+    dim3 grid(H / 8, (B + 31) / 32);
+    hipLaunchKernelGGL(rnn_cell_kernel, grid, dim3(256), 0, (hipStream_t)stream, x, h, w_ih, w_hh, b_ih, b_hh, h_out, B, H);
+    return check_launch("dvg_rnn_cell");
+}
+
+extern "C" int dvg_gru_gates_bwd(const float* dh_a, const float* dh_b, const float* acts, const float* h_prev, float* dGi,
+                                 float* dGh, float* dh_prev, int B, int H, void* stream) {
+    DVG_REQUIRE(acts && dGi && dGh, DVG_ERR_NULL, "dvg_gru_gates_bwd: NULL pointer");
+    DVG_REQUIRE(dh_a || dh_b, DVG_ERR_NULL, "dvg_gru_gates_bwd: no incoming gradient");
+    DVG_REQUIRE(B > 0 && H > 0 && H % 4 == 0, DVG_ERR_SHAPE, "dvg_gru_gates_bwd: H=%d must be a multiple of 4", H);
+    DVG_REQUIRE(dGi != dGh, DVG_ERR_SHAPE, "dvg_gru_gates_bwd: dGi and dGh must be two buffers");
+    DVG_REQUIRE(aligned16(dh_a) && aligned16(dh_b) && aligned16(acts) && aligned16(h_prev) && aligned16(dGi) &&
+                aligned16(dGh) && aligned16(dh_prev), DVG_ERR_ALIGN, "dvg_gru_gates_bwd: alignment");
+    hipLaunchKernelGGL(gru_gates_bwd_kernel, dim3(grid_for((long)B * (H / 4), 256, 4096)), dim3(256), 0, (hipStream_t)stream,
+                       dh_a, dh_b, acts, h_prev, dGi, dGh, dh_prev, B, H);
+    return check_launch("dvg_gru_gates_bwd");
 }
 
 extern "C" int dvg_stem_gemm(const float* vec, int ldv, const float* w_kn, int KP, const float* scale, const float* shift,

@@ -29,7 +29,7 @@ from .edge import (  # noqa: F401
 )
 from .dense import (  # noqa: F401
     gemm_nt, lstm_cell, lstm_cell_pre, lstm_cell_bwd, lstm_cell_x, stem_gemm, transpose2d, colsum, GEMM_TN_MAX_ROWS,
-    gemm_tn, lstm_gates_bwd,
+    gemm_tn, lstm_gates_bwd, gru_cell, gru_cell_pre, rnn_cell, gru_gates_bwd,
 )
 from .norm import (  # noqa: F401
     channel_stats, set_sync_bn_state, sync_bn_state, sync_partial_rows, bn_finalize, bn_act_apply, bn_act_bwd,

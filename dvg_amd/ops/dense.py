@@ -1,4 +1,4 @@
-"""Dense / recurrent wrappers (dense.hip): NT / TN GEMMs with fused bias + activation, the LSTM cell kernels, the decoder
+"""Dense / recurrent wrappers (dense.hip): NT / TN GEMMs with fused bias + activation, the LSTM / GRU / RNN cell kernels, the decoder
 stem, transposes and column sums."""
 from __future__ import annotations
 
@@ -85,6 +85,88 @@ def lstm_cell_x(x, h, c, w_x, w_hh, bias):
          _p(x), x.stride(0), kx, _p(h), _p(c), _p(w_x), w_x.shape[1], _p(w_hh.detach()), _p(bias), _p(h_out), _p(c_out),
          b, hid, _stream())
     return h_out, c_out
+
+
+def _cell_operands(name, x, h, w_ih, w_hh, gates):
+    """(x, h, B, H) of a GRUCell / RNNCell step: device fp32, contiguous, input size == hidden size, weights [gates*H][H]."""
+    _dev_f32(x, name + ".x")
+    _dev_f32(h, name + ".h")
+    if h.dim() != 2:
+        raise RuntimeError(f"{name}: h must be (B, H)")
+    b, hid = h.shape
+    x = x if x.is_contiguous() else x.contiguous()
+    h = h if h.is_contiguous() else h.contiguous()
+    if tuple(x.shape) != (b, hid) or tuple(w_ih.shape) != (gates * hid, hid) or tuple(w_hh.shape) != (gates * hid, hid):
+        raise RuntimeError(f"{name}: shape mismatch (input size must equal hidden size)")
+    return x, h, b, hid
+
+
+def gru_cell(x, h, w_ih, w_hh, b_ih, b_hh, want_acts=False):
+    """One nn.GRUCell step (dvg_gru_cell): h' (B,H); want_acts: also r, z, n, hn (B,4H) for gru_gates_bwd."""
+    x, h, b, hid = _cell_operands("gru_cell", x, h, w_ih, w_hh, 3)
+    if b_ih.numel() != 3 * hid or b_hh.numel() != 3 * hid:
+        raise RuntimeError("gru_cell: bias shape mismatch")
+    h_out = torch.empty_like(h)
+    acts = torch.empty((b, 4 * hid), device=h.device, dtype=torch.float32) if want_acts else None
+    _run("gru_cell", 2.0 * b * 3 * hid * 2 * hid, 4.0 * (6 * hid * hid + 3 * b * hid), lib().dvg_gru_cell, _p(x), _p(h),
+         _p(w_ih.detach()), _p(w_hh.detach()), _p(b_ih.detach()), _p(b_hh.detach()), _p(h_out), _p(acts), b, hid, _stream())
+    return (h_out, acts) if want_acts else h_out
+
+
+def gru_cell_pre(pre, h, w_hh, b_hn, h_out, acts_out):
+    """One GRUCell step whose input half `pre` = W_ih x + b_ih (+ b_hr, b_hz) (B,3H) is given (dvg_gru_cell_pre); writes into
+    the caller's h_out / acts_out (slices of the per-sequence buffers of autograd._GRUSequence)."""
+    for t, nm in ((pre, "pre"), (h, "h"), (h_out, "h_out")):
+        _dev_f32(t, "gru_cell_pre." + nm)
+    b, hid = h.shape
+    if tuple(pre.shape) != (b, 3 * hid) or tuple(w_hh.shape) != (3 * hid, hid) or b_hn.numel() != hid or \
+            tuple(h_out.shape) != (b, hid) or not (pre.is_contiguous() and h.is_contiguous() and h_out.is_contiguous()) or \
+            (acts_out is not None and (tuple(acts_out.shape) != (b, 4 * hid) or not acts_out.is_contiguous())):
+        raise RuntimeError("gru_cell_pre: shape mismatch")
+    _run("gru_cell", 2.0 * b * 3 * hid * hid, 4.0 * (3 * hid * hid + 9 * b * hid), lib().dvg_gru_cell_pre, _p(pre), _p(h),
+         _p(w_hh), _p(b_hn), _p(h_out), _p(acts_out), b, hid, _stream())
+
+
+def rnn_cell(x, h, w_ih, w_hh, b_ih, b_hh):
+    """One nn.RNNCell step (dvg_rnn_cell): tanh(W_ih x + b_ih + W_hh h + b_hh), (B,H)."""
+    x, h, b, hid = _cell_operands("rnn_cell", x, h, w_ih, w_hh, 1)
+    if b_ih.numel() != hid or b_hh.numel() != hid:
+        raise RuntimeError("rnn_cell: bias shape mismatch")
+    h_out = torch.empty_like(h)
+    _run("rnn_cell", 2.0 * b * hid * 2 * hid, 4.0 * (2 * hid * hid + 3 * b * hid), lib().dvg_rnn_cell, _p(x), _p(h),
+         _p(w_ih.detach()), _p(w_hh.detach()), _p(b_ih.detach()), _p(b_hh.detach()), _p(h_out), b, hid, _stream())
+    return h_out
+
+
+def gru_gates_bwd(dh_a, dh_b, acts, h_prev, dGi=None, dGh=None, dh_prev=None, want_dh_prev=True):
+    """The elementwise half of a GRUCell's backward (dvg_gru_gates_bwd): d = dh_a + dh_b (either may be None), acts (B,4H)
+    = r, z, n, hn, h_prev (B,H) or None for the zero state -> dGi, dGh (B,3H) and dh_prev = d z (B,H; None unless
+    want_dh_prev or a buffer is given).  The caller adds dGh W_hh to dh_prev."""
+    if dh_a is None and dh_b is None:
+        raise RuntimeError("gru_gates_bwd: no incoming gradient")
+    _dev_f32(acts, "gru_gates_bwd.acts")
+    if acts.dim() != 2 or acts.shape[1] % 4 or not acts.is_contiguous():
+        raise RuntimeError("gru_gates_bwd: acts must be a contiguous (B, 4H)")
+    b, hid = acts.shape[0], acts.shape[1] // 4
+    ins = []
+    for t, nm in ((dh_a, "dh_a"), (dh_b, "dh_b"), (h_prev, "h_prev")):
+        if t is not None:
+            _dev_f32(t, "gru_gates_bwd." + nm)
+            if tuple(t.shape) != (b, hid):
+                raise RuntimeError(f"gru_gates_bwd: {nm} must be ({b},{hid})")
+            t = t if t.is_contiguous() else t.contiguous()
+        ins.append(t)
+    dev = acts.device
+    dGi = torch.empty((b, 3 * hid), device=dev, dtype=torch.float32) if dGi is None else dGi
+    dGh = torch.empty((b, 3 * hid), device=dev, dtype=torch.float32) if dGh is None else dGh
+    if dh_prev is None and want_dh_prev:
+        dh_prev = torch.empty((b, hid), device=dev, dtype=torch.float32)
+    for t, shape, nm in ((dGi, (b, 3 * hid), "dGi"), (dGh, (b, 3 * hid), "dGh"), (dh_prev, (b, hid), "dh_prev")):
+        if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda):
+            raise RuntimeError(f"gru_gates_bwd: {nm} must be a contiguous device tensor of shape {shape}")
+    check(lib().dvg_gru_gates_bwd(_p(ins[0]), _p(ins[1]), _p(acts), _p(ins[2]), _p(dGi), _p(dGh), _p(dh_prev), b, hid,
+                                  _stream()), "gru_gates_bwd")
+    return dGi, dGh, dh_prev
 
 
 def stem_gemm(vec, w_kn, k, scale, shift, out, *, period, act=ACT_LRELU, slope=0.2):

@@ -52,14 +52,16 @@ def gp_input(gp_layer, h):
 
 def _zero_hidden(frame_predictor):
     """init_hidden() (lstm.py:58-63) without its 2 x n_layers fill launches per rollout: one cached all-zero tensor per
-    (device, batch, hidden size).  Safe to share: no kernel of the recurrent path writes its state in place (dvg_lstm_cell
-    rejects in-place updates), and the tensors are only ever replaced in the `hidden` list."""
+    (device, batch, hidden size).  Safe to share: no kernel of the recurrent path writes its state in place (dvg_lstm_cell,
+    dvg_gru_cell and dvg_rnn_cell reject in-place updates), and the tensors are only ever replaced in the `hidden` list.
+    The predictor shapes the list (pairs for an LSTM, single tensors for a GRU / RNN: set_state_tensors)."""
     if not hasattr(frame_predictor, "step_state_only"):
         return frame_predictor.init_hidden()
     z = _derived.zero_state(frame_predictor.batch_size, frame_predictor.hidden_size, frame_predictor.embed.weight.device)
     if z is None:
         return frame_predictor.init_hidden()    # never cache a tensor that lives in a graph's private pool
-    return [(z, z) for _ in range(frame_predictor.n_layers)]
+    frame_predictor.set_state_tensors([z] * (frame_predictor.n_layers * frame_predictor.state_per_layer))
+    return frame_predictor.hidden
 
 
 # Skip tensors the rollout never reads are not stored (encoder.encode(x, skips_from), VggEncoder.features): of the conditioning
@@ -261,11 +263,11 @@ def trigger_body(state: dict, encoder, decoder, frame_predictor, gp_layer, likel
         pred = likelihood(gp_layer(gp_input(gp_layer, h)))
         z = pred.rsample(eps_all[i - warmup])                       # (D,B); the same launch leaves the variance
         ops.gp_trigger_step(pred.variance, probe, ctx, coef, log["flag"], log["values"], log["thresholds"], log["flags"], i)
-        old = [t for hc in frame_predictor.hidden for t in hc]
+        old = frame_predictor.state_tensors()
         h_pred = frame_predictor(h)
-        new = [t for hc in frame_predictor.hidden for t in hc]
+        new = frame_predictor.state_tensors()
         vec, st = ops.gp_trigger_select(log["flag"], z, h_pred, old, new)
-        frame_predictor.hidden = [(st[2 * l], st[2 * l + 1]) for l in range(len(st) // 2)]
+        frame_predictor.set_state_tensors(st)
         x_in = decoder([vec, skip])
         frames.append(x_in)
     return frames
@@ -278,8 +280,8 @@ def trigger_log(total: int, device) -> dict:
 
 class GraphedTrigger:
     """GPtrigger_gen for one batch as two hipGraphs: the warm-up (once per batch) and the main loop (once per batch index; it
-    reads the warm-up graph's state - frames, LSTM state, skip tensors and the decoder's hoisted skip halves - and its own
-    static window / base samples / logs).  `warm(x0)` then `run(index)`; one device-to-host copy of the logs per index."""
+    reads the warm-up graph's state - frames, the predictor's recurrent state, skip tensors and the decoder's hoisted skip halves -
+    and its own static window / base samples / logs).  `warm(x0)` then `run(index)`; one device-to-host copy of the logs per index."""
 
     def __init__(self, encoder, decoder, frame_predictor, gp_layer, likelihood, x0, warmup=12, total=105, depth=1,
                  skip_steps=5, probe=3):

@@ -39,16 +39,31 @@ def rank_path(path: str, rank: int) -> str:
     return f"{root}.rank{rank}{ext}"
 
 
+# fields a fingerprint carries only when they differ from the value given here: a state without the field was written by a run
+# with that value (every state from before --predictor is an `lstm` state), and such a run writes the fingerprint it always did
+ABSENT_MEANS = {"predictor": "lstm"}
+
+
 def option_fingerprint(opt) -> dict:
     fp = {k: getattr(opt, k) for k in OPTION_FIELDS}
     fp["world"] = int(opt.world)
+    for k, default in ABSENT_MEANS.items():
+        if getattr(opt, k, default) != default:
+            fp[k] = getattr(opt, k)
     return fp
 
 
 def check_fingerprint(saved: dict, now: dict, path: str) -> None:
     """Ends the program naming the first field that disagrees.  `now` may be a part of the fingerprint (train.py checks the
     options before it builds anything, the arena layout once the Trainer exists)."""
+    if "model" in now:            # an options fingerprint: the fields of ABSENT_MEANS are compared whichever side lacks them
+        for k, default in ABSENT_MEANS.items():
+            a, b = saved.get(k, default), now.get(k, default)
+            if a != b:
+                refuse(path, f"{k} is {a!r} in the file and {b!r} in this run")
     for k, v in now.items():
+        if k in ABSENT_MEANS:
+            continue
         if k not in saved:
             refuse(path, f"the fingerprint has no field {k!r}")
         a, b = saved[k], v
@@ -150,8 +165,10 @@ def detached_copy(module):
     for b in module.buffers():
         memo[id(b)] = b.detach().clone()
     hidden = getattr(module, "hidden", None)
-    if hidden is not None:         # lstm.hidden: the recurrent state of the last sequence, may carry an autograd graph
-        memo[id(hidden)] = [(h.detach().clone(), c.detach().clone()) for h, c in hidden]
+    if hidden is not None:         # the recurrent state of the last sequence, may carry an autograd graph: (h, c) pairs for
+        # an lstm, single tensors for a gru / rnn
+        memo[id(hidden)] = [s.detach().clone() if torch.is_tensor(s) else tuple(t.detach().clone() for t in s)
+                            for s in hidden]
     return copy.deepcopy(module, memo)
 
 

@@ -27,8 +27,9 @@ class Trainer:
         self.decoder = model.decoder(opt.g_dim, opt.channels)
         self.encoder.apply(init_weights)
         self.decoder.apply(init_weights)
-        self.frame_predictor = lstm_models.lstm(opt.g_dim, opt.g_dim, opt.rnn_size, opt.predictor_rnn_layers,
-                                                opt.local_batch)
+        # --predictor: the reference's lstm (the default), gru or rnn (lstm.py:42-136)
+        predictor = lstm_models.PREDICTORS[getattr(opt, "predictor", "lstm")]
+        self.frame_predictor = predictor(opt.g_dim, opt.g_dim, opt.rnn_size, opt.predictor_rnn_layers, opt.local_batch)
         self.frame_predictor.apply(init_weights)
         self.gp_layer = GPRegressionLayer1(num_dims=opt.g_dim)
         self.likelihood = GaussianLikelihood(batch_size=opt.g_dim)

@@ -56,6 +56,8 @@ def build_parser():
     p.add_argument('--n_future', type=int, default=100)
     p.add_argument('--n_eval', type=int, default=105)
     p.add_argument('--rnn_size', type=int, default=256)
+    p.add_argument('--predictor', default='lstm', choices=('lstm', 'gru', 'rnn'),
+                   help='--synthetic_ckpt: the frame predictor class to build (a loaded checkpoint runs the class it carries)')
     p.add_argument('--predictor_rnn_layers', type=int, default=2)
     p.add_argument('--z_dim', type=int, default=10)
     p.add_argument('--g_dim', type=int, default=90)
@@ -350,7 +352,8 @@ def synthetic_checkpoint(opt):
     model = importlib.import_module(f"models.{opt.model}_{opt.image_width}")
     enc, dec = model.encoder(opt.g_dim, opt.channels), model.decoder(opt.g_dim, opt.channels)
     enc.apply(utils.init_weights), dec.apply(utils.init_weights)
-    fp = lstm_models.lstm(opt.g_dim, opt.g_dim, opt.rnn_size, opt.predictor_rnn_layers, opt.batch_size)
+    predictor = lstm_models.PREDICTORS[getattr(opt, 'predictor', 'lstm')]
+    fp = predictor(opt.g_dim, opt.g_dim, opt.rnn_size, opt.predictor_rnn_layers, opt.batch_size)
     fp.apply(utils.init_weights)
     gp, lik = GPRegressionLayer1(opt.g_dim), GaussianLikelihood(batch_size=opt.g_dim)
     return {'encoder': enc, 'decoder': dec, 'frame_predictor': fp, 'likelihood': lik.state_dict(),

@@ -208,34 +208,26 @@ int dvg_winograd_output_up_input(const float* mm, const float* scale, const floa
 int dvg_winograd_output_pool_input(const float* m, const float* scale, const float* shift, float* y, float* v_next, int N,
                                    int H, int W, int C, int act, float slope, int y_from, void* stream);
 
-/* First encoder layer: Conv2d(nc,Cout,3,1,1)+BN+LReLU with nc in {1..4}
- * (vgg_64.py:23 `vgg_layer(nc, 64)`).  HBM-bound direct convolution.
- * x is NCHW (N,nc,H,W) exactly as the caller's frame tensor (utils.py:90-91);
- * w is the ORIGINAL (Cout,nc,3,3) weight; y is NHWC (N,H,W,Cout).
- * Cout % 64 == 0.  stats as above (optional).                                */
-int dvg_conv3x3_first(const float* x_nchw, const float* w_oihw, const float* scale,
-                      const float* shift, float* y, float* stats, int N, int H,
-                      int W, int nc, int Cout, int act, float slope, void* stream);
+/* First encoder layer: Conv2d(nc,Cout,3,1,1)+BN+LReLU with nc in {1..4} (vgg_64.py:23 `vgg_layer(nc, 64)`).  HBM-bound direct
+ * convolution.  x is NCHW (N,nc,H,W) exactly as the caller's frame tensor (utils.py:90-91); w is the ORIGINAL (Cout,nc,3,3) weight;
+ * y is NHWC (N,H,W,Cout).  Cout % 64 == 0.  stats as above (optional).                                                         */
+int dvg_conv3x3_first(const float* x_nchw, const float* w_oihw, const float* scale, const float* shift, float* y, float* stats,
+                      int N, int H, int W, int nc, int Cout, int act, float slope, void* stream);
 
-/* Last decoder layer: ConvTranspose2d(Cin,nc,3,1,1)+Sigmoid (vgg_64.py:88-92),
- * nc in {1..4}.  x NHWC (N,H,W,Cin), w the ORIGINAL (Cin,nc,3,3) weight,
- * bias [nc], y NCHW (N,nc,H,W).  Cin % 4 == 0, Cin <= 128.                    */
-int dvg_convT3x3_last(const float* x, const float* w_iohw, const float* bias,
-                      float* y_nchw, int N, int H, int W, int Cin, int nc, int act,
-                      void* stream);
+/* Last decoder layer: ConvTranspose2d(Cin,nc,3,1,1)+Sigmoid (vgg_64.py:88-92), nc in {1..4}.  x NHWC (N,H,W,Cin), w the ORIGINAL
+ * (Cin,nc,3,3) weight, bias [nc], y NCHW (N,nc,H,W).  Cin % 4 == 0, Cin <= 128.                                               */
+int dvg_convT3x3_last(const float* x, const float* w_iohw, const float* bias, float* y_nchw, int N, int H, int W, int Cin,
+                      int nc, int act, void* stream);
 
 /* First dcgan layer Conv2d(nc,Cout,4,2,1)+BN+LReLU, nc in {1..4}
  * (dcgan_64.py:34).  x NCHW, w ORIGINAL (Cout,nc,4,4), y NHWC (N,H/2,W/2,Cout). */
-int dvg_conv4x4s2_first(const float* x_nchw, const float* w_oihw, const float* scale,
-                        const float* shift, float* y, float* stats, int N, int H,
-                        int W, int nc, int Cout, int act, float slope, void* stream);
+int dvg_conv4x4s2_first(const float* x_nchw, const float* w_oihw, const float* scale, const float* shift, float* y, float* stats,
+                        int N, int H, int W, int nc, int Cout, int act, float slope, void* stream);
 
-/* Last dcgan layer ConvTranspose2d(C1+C2,nc,4,2,1)+Tanh|Sigmoid on cat([x,skip])
- * (dcgan_64.py:75-79; dcgan_128.py:80-84).  w ORIGINAL (C1+C2,nc,4,4),
- * y NCHW (N,nc,2H,2W).                                                        */
-int dvg_convT4x4s2_last(const float* x, const float* skip, const float* w_iohw,
-                        const float* bias, float* y_nchw, int N, int H, int W,
-                        int C1, int C2, int nc, int act, void* stream);
+/* Last dcgan layer ConvTranspose2d(C1+C2,nc,4,2,1)+Tanh|Sigmoid on cat([x,skip]) (dcgan_64.py:75-79; dcgan_128.py:80-84).
+ * w ORIGINAL (C1+C2,nc,4,4), y NCHW (N,nc,2H,2W).                                                                              */
+int dvg_convT4x4s2_last(const float* x, const float* skip, const float* w_iohw, const float* bias, float* y_nchw, int N, int H,
+                        int W, int C1, int C2, int nc, int act, void* stream);
 
 /* First step of the two-step last layer: d[px][t] = sum_c in[px][c] * w[t][c] for the P = N*H*W pixels of an
  * NHWC activation (C = 64 or 128 channels) and the T = ks*ks*nc <= 48 tap outputs of the decoder's final
@@ -311,24 +303,19 @@ int dvg_bn_act_apply(const float* u, const float* scale, const float* shift, flo
                      int group_images, void* stream);
 
 /* ---- Dense ends and the recurrent predictor ---- */
-/* out[m][n] = act( (sum_k a[m][k]*w[n][k]) * scale[n % period] + shift[n % period] )
- * Small-M GEMM used for: encoder head Conv2d(512,dim,4,1,0)+BN+Tanh on the 4x4
- * map (vgg_64.py:44-48; K = 8192), decoder stem ConvTranspose2d(dim,512,4,1,0)
- * +BN+LReLU (vgg_64.py:65-69; N = 8192, period = 512), nn.Linear of lstm.py:50,
- * 53-55.  a [M][K] (row stride lda), w [N][K], out [M][N] (row stride ldo).
- * scale/shift may be NULL.  `workspace` must hold M*N*splitk floats when
- * splitk > 1 (NULL allowed when splitk == 1).                                  */
+/* out[m][n] = act( (sum_k a[m][k]*w[n][k]) * scale[n % period] + shift[n % period] ).  Small-M GEMM used for: encoder head
+ * Conv2d(512,dim,4,1,0)+BN+Tanh on the 4x4 map (vgg_64.py:44-48; K = 8192), decoder stem ConvTranspose2d(dim,512,4,1,0)+BN+LReLU
+ * (vgg_64.py:65-69; N = 8192, period = 512), nn.Linear of lstm.py:50,53-55.  a [M][K] (row stride lda), w [N][K], out [M][N] (row
+ * stride ldo).  scale/shift may be NULL.  `workspace` must hold M*N*splitk floats when splitk > 1 (NULL allowed when splitk == 1). */
 int dvg_gemm_nt_bias_act(const float* a, const float* w, const float* scale, const float* shift, float* out, float* workspace,
                          int M, int N, int K, int lda, int ldo, int period, int splitk, int act, float slope,
                          int accumulate /* out += result */, void* stream);
 
 /* One nn.LSTMCell step (lstm.py:51,68-70; gate order i,f,g,o):
- *   g = W_ih x + b_ih + W_hh h + b_hh ; c' = sig(f)*c + sig(i)*tanh(g~) ;
- *   h' = sig(o)*tanh(c')
- * x,h,c,h_out,c_out: [B][H] contiguous; w_ih,w_hh: [4H][H]; b_ih,b_hh: [4H].
- * In-place state update (h_out == h, c_out == c) is NOT allowed (every
- * workgroup reads all of h).  gates_out (optional, [B][4H]) receives the
- * post-activation gates (i,f,g~,o) for the backward pass.  H % 64 == 0.       */
+ *   g = W_ih x + b_ih + W_hh h + b_hh ; c' = sig(f)*c + sig(i)*tanh(g~) ; h' = sig(o)*tanh(c')
+ * x,h,c,h_out,c_out: [B][H] contiguous; w_ih,w_hh: [4H][H]; b_ih,b_hh: [4H].  In-place state update (h_out == h, c_out == c) is NOT
+ * allowed (every workgroup reads all of h).  gates_out (optional, [B][4H]) receives the post-activation gates (i,f,g~,o) for the
+ * backward pass.  H % 64 == 0.                                                                                                  */
 int dvg_lstm_cell(const float* x, const float* h, const float* c, const float* w_ih, const float* w_hh, const float* b_ih,
                   const float* b_hh, float* h_out, float* c_out, float* gates_out, int B, int H, void* stream);
 
@@ -356,6 +343,26 @@ int dvg_lstm_cell_bwd(const float* dh_a, const float* dh_b, const float* dc, con
 int dvg_lstm_cell_x(const float* x, int ldx, int Kx, const float* h, const float* c, const float* w_x, int Kxp,
                     const float* w_hh, const float* bias, float* h_out, float* c_out, int B, int H, void* stream);
 
+/* lstm.gru / lstm.rnn (lstm.py:75-136; additions within ABI 9).  dvg_gru_cell: one nn.GRUCell step (lstm.py:84,101; weights [3H][H],
+ * biases [3H], gate order r,z,n): r = sig(W_ir x + b_ir + W_hr h + b_hr); z = sig(W_iz x + b_iz + W_hz h + b_hz); hn = W_hn h + b_hn;
+ * n = tanh(W_in x + b_in + r*hn); h' = (1 - z)*n + z*h.  x, h, h_out [B][H] contiguous and 16-byte aligned, no in-place update
+ * (h_out != h, != x), H % 64 == 0; acts_out (optional, [B][4H]) = r, z, n, hn for the backward.  dvg_gru_cell_pre: the same step of a
+ * teacher-forced sequence (train.py:213-222): `pre` [B][3H] = W_ih x + b_ih with b_hr, b_hz added by the caller; b_hn [H] stays inside
+ * the r * product.  dvg_rnn_cell: one nn.RNNCell step (lstm.py:116,133), h' = tanh(W_ih x + b_ih + W_hh h + b_hh), weights [H][H]; its
+ * backward is dvg_act_bwd + dvg_gemm_nt_bias_act + dvg_gemm_tn.  dvg_gru_gates_bwd: the elementwise part of the GRU cell's backward
+ * (`loss.backward()` of train.py:194,240 through lstm.py:101): d = dh_a + dh_b (either NULL, not both), acts as saved above, h_prev
+ * [B][H] (NULL = the zero state of lstm.py:91-95) -> da_n = d*(1-z)*(1-n^2); da_r = da_n*hn*r*(1-r); da_z = d*(h-n)*z*(1-z);
+ * dGi [B][3H] = [da_r, da_z, da_n] (input side), dGh [B][3H] = [da_r, da_z, da_n*r] (hidden side), dh_prev [B][H] (optional) = d*z, which
+ * the caller completes with dvg_gemm_nt_bias_act(accumulate = 1): dh_prev += dGh W_hh.  H % 4 == 0, all pointers 16-byte aligned. */
+int dvg_gru_cell(const float* x, const float* h, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                 float* h_out, float* acts_out, int B, int H, void* stream);
+int dvg_gru_cell_pre(const float* pre, const float* h, const float* w_hh, const float* b_hn, float* h_out, float* acts_out,
+                     int B, int H, void* stream);
+int dvg_rnn_cell(const float* x, const float* h, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                 float* h_out, int B, int H, void* stream);
+int dvg_gru_gates_bwd(const float* dh_a, const float* dh_b, const float* acts, const float* h_prev, float* dGi, float* dGh,
+                      float* dh_prev, int B, int H, void* stream);
+
 /* Decoder stem ConvTranspose2d(dim,512,4,1,0)+BN+LReLU on a 1x1 map (vgg_64.py:65-69, dcgan_64.py:62-67), eval mode:
  * out[m][n] = act((sum_k vec[m][k] * w_kn[k][n]) * scale[n % period] + shift[n % period]); w_kn is the GEMM weight
  * TRANSPOSED to [KP][N] (N = 16*512 in NHWC flatten order, N % 32 == 0; KP = 96 or 128 rows, rows K.. zero), K = dim. */
@@ -363,25 +370,20 @@ int dvg_stem_gemm(const float* vec, int ldv, const float* w_kn, int KP, const fl
                   float* out, int ldo, int M, int N, int K, int period, int act, float slope, void* stream);
 
 /* ------------------------------------------------------------------ *
- * Sparse variational GP trigger (gp_models.py:10-24 + gpytorch 0.3.x
- * WhitenedVariationalStrategy / GaussianLikelihood / MultivariateNormal;
- * equations of record in DESIGN.md §GP).  One workgroup per latent dim. */
+ * Sparse variational GP trigger (gp_models.py:10-24 + gpytorch 0.3.x WhitenedVariationalStrategy / GaussianLikelihood /
+ * MultivariateNormal; equations of record in DESIGN.md §GP).  One workgroup per latent dim. */
 
 /* Predictive distribution q(f(x)) for D independent 1-D GPs, M inducing points.
- *   h            [B][D]   latent codes; GP d sees column d (the reference's
- *                         h.transpose(0,1).view(D,B,1), train.py:225)
+ *   h            [B][D]   latent codes; GP d sees column d (the reference's h.transpose(0,1).view(D,B,1), train.py:225)
  *   z            [D][M]   inducing inputs
  *   var_mean     [D][M]   variational mean m
  *   chol_var     [D][M][M] variational Cholesky factor (lower part is used)
  *   mean_const   [D], outputscale [D], lengthscale [D]  (already soft-plus'ed)
- *   noise        [D] or NULL: likelihood noise added to the variance/covariance
- *                (GaussianLikelihood.__call__, generate_frames.py:131,170)
+ *   noise        [D] or NULL: likelihood noise added to the variance/covariance (GaussianLikelihood.__call__, generate_frames.py:131,170)
  * Outputs (any may be NULL):
- *   mean [D][B]; var [D][B] (marginal variance; train-mode clamp at 0 when
- *   `train_mode` != 0); sample [D][B] = mean + chol(Sigma)*eps with
- *   eps [D][B] supplied by the caller (MultivariateNormal.rsample);
- *   cov [D][B][B] full predictive covariance (eval mode only).
- *   kl [D] (train mode: KL(q(u)||p(u))).
+ *   mean [D][B]; var [D][B] (marginal variance; train-mode clamp at 0 when `train_mode` != 0); sample [D][B] = mean +
+ *   chol(Sigma)*eps with eps [D][B] supplied by the caller (MultivariateNormal.rsample); cov [D][B][B] full predictive covariance
+ *   (eval mode only).  kl [D] (train mode: KL(q(u)||p(u))).
  * train_mode is a flag word: bit 0 = train-mode prediction (diagonal variance with the clamp, KL); bit 1 = outputscale /
  * lengthscale / noise point at the RAW parameters (covar_module.raw_outputscale, base_kernel.raw_lengthscale,
  * noise_covar.raw_noise) and the kernel applies soft-plus itself (noise: + the 1e-4 floor of GaussianLikelihood).
@@ -394,12 +396,9 @@ int dvg_stem_gemm(const float* vec, int ldv, const float* w_kn, int KP, const fl
  * Limits: M <= 64, B <= 128 and dvg_gp_lds_bytes(B, M, cov||sample) <= 160 KiB. */
 int dvg_gp_precision(int B, int M, int need_cov);
 size_t dvg_gp_lds_bytes(int B, int M, int need_cov);
-int dvg_gp_predict(const float* h, const float* z, const float* var_mean,
-                   const float* chol_var, const float* mean_const,
-                   const float* outputscale, const float* lengthscale,
-                   const float* noise, const float* eps, float* mean, float* var,
-                   float* sample, float* cov, float* kl, int B, int D, int M,
-                   int train_mode, float jitter,
+int dvg_gp_predict(const float* h, const float* z, const float* var_mean, const float* chol_var, const float* mean_const,
+                   const float* outputscale, const float* lengthscale, const float* noise, const float* eps, float* mean,
+                   float* var, float* sample, float* cov, float* kl, int B, int D, int M, int train_mode, float jitter,
                    int param_period /* ABI 8; 0 = D.  Workgroup d reads the parameters (z, var_mean, chol_var, mean_const,
                                        outputscale, lengthscale, noise) of latent dim d % param_period: the S time steps of a
                                        training closure side by side as D = S * g_dim dims on ONE parameter set */,

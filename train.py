@@ -89,6 +89,9 @@ def build_parser():
     p.add_argument('--n_future', type=int, default=10)
     p.add_argument('--n_eval', type=int, default=15)
     p.add_argument('--rnn_size', type=int, default=256)
+    p.add_argument('--predictor', default='lstm', choices=('lstm', 'gru', 'rnn'),
+                   help='the frame predictor\'s cell: the reference\'s models.lstm.lstm (default), .gru or .rnn; gru trains in the '
+                        'sequence form like lstm, rnn step by step.  Part of the --resume fingerprint when it is not lstm')
     p.add_argument('--predictor_rnn_layers', type=int, default=2)
     p.add_argument('--z_dim', type=int, default=10)
     p.add_argument('--g_dim', type=int, default=90)
