@@ -94,6 +94,11 @@ struct Igemm2Params {
     // tensors once the skip is frozen (generate_frames.py:154-157), and of the conditioning batch only the last frame's are
     // kept.  y is biased by -y_from images on the host, so image y_from lands at the start of the caller's buffer.
     int y_from;
+    // PROJ (dvg_convT4x4s2_bn_act_proj): the 64-channel activation of the decoder's last block is not stored; the workgroup
+    // projects its pixels onto the last ConvTranspose2d's T = ks * ks * nc tap outputs (what dvg_pixel_proj would make of y)
+    const float* proj_w;   // [T][64], as dvg_pixel_proj takes it
+    float* proj_out;       // [N * Ho * Wo][T]: the d1 of dvg_convT_gather
+    int proj_T;
 };
 
 // image of `addend` that output image n adds (see Igemm2Params::add_map)
@@ -113,10 +118,11 @@ __device__ __attribute__((aligned(16))) float dvg_zero_slot[4] = {0.f, 0.f, 0.f,
 // NT: 32-column tiles per wave (workgroup tile BM x 64 NT).  NT = 2 exists for the bf16-triple GEMM mode only: with the
 // matrix pipe 2.7x faster the LDS, not the MFMA, bounds a 128 x 64 tile (per MFMA 384 B of tile stores at ~80 B/clk and
 // 768 B of fragment reads at 256 B/clk: 97 % of the LDS cycles); 128 x 128 with 64 x 64 per wave needs 256 + 512 B (65 %).
-template <int MODE, int TI, int TH, int TW, int NT_ = 1, bool FIRST_ = false>
+template <int MODE, int TI, int TH, int TW, int NT_ = 1, bool FIRST_ = false, bool PROJ_ = false>
 struct Cfg2 {
     static constexpr int NT = NT_;
     static constexpr bool FIRST = FIRST_;
+    static constexpr bool PROJ = PROJ_;
     static constexpr bool GEMM = MODE == M2_GEMM;
     static constexpr int S = (MODE == M2_CONV4S2) ? 2 : 1;                  // stride in the IMAGE
     // PAR4 (r05, the stride-2 conv): the 16 taps of a chunk run as FOUR stages, one per input parity (alpha, beta) = (tap row & 1,
@@ -201,13 +207,16 @@ struct Cfg2 {
     // K is split only where a launch would leave CUs idle (< 384 workgroups): never on the 16-wide tiles (chosen from 512
     // workgroups on), the first layer or the batched GEMM - their kernels do not carry the split-K epilogue (its scalars cost
     // the 8x16 kernels 18 ... 35 SGPR spills)
-    static constexpr bool CAN_SPLIT = !FIRST && !GEMM && TW != 16;
+    static constexpr bool CAN_SPLIT = !FIRST && !GEMM && TW != 16 && !PROJ;
     static_assert(BM == 64 || BM == 128 || BM == 256, "BM");
+    // PROJ: the epilogue stages the workgroup's BM x 64 activated values over the (then dead) A / B regions
+    static_assert(!PROJ || (MODE == M2_CONVT4S2 && TI == 1 && NT == 1 && !FIRST && BM * 64 <= A_FLOATS + B_FLOATS),
+                  "PROJ: transposed-conv mode, one image per tile, the staged tile fits the stage buffers");
 };
 
-template <int MODE, int TI, int TH, int TW, int NT = 1, bool FIRST = false>
+template <int MODE, int TI, int TH, int TW, int NT = 1, bool FIRST = false, bool PROJ = false>
 __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PER_CU : ((MODE == M2_GEMM && NT == 1) ? DVG_GEMM128_WGS : 2)) void conv_igemm2_kernel(const Igemm2Params p) {
-    using C = Cfg2<MODE, TI, TH, TW, NT, FIRST>;
+    using C = Cfg2<MODE, TI, TH, TW, NT, FIRST, PROJ>;
     constexpr int S = C::S, HH = C::HH, HW = C::HW, HP = C::HP, LD = C::LD, MT = C::MT, GT = C::GT, NG = C::NG,
                   BN = C::BN, NLA = C::NLA, NLA1 = C::NLA1, LDB = C::LDB, NP = C::NP, PSTEP = C::PSTEP, NLB = C::NLB;
     constexpr bool GEMM = C::GEMM, X3 = C::X3;
@@ -780,6 +789,35 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
         return v;
     };
     const int hrow = hh * 4 * C::PK;     // C-layout row of (reg, lane half): C::row_c(reg) ^ hrow  (Cfg2: LAYOUT)
+    // PROJ: y is not stored.  The activated BM x 64 tile goes to LDS, over the A / B regions, and is projected from there with
+    // the instruction sequence of pixel_proj_kernel<4, .> (edge_layers.hip): v_mfma_f32_16x16x4_f32, lane l holds pixel l % 16 and
+    // the channels 16 j + 4 (l / 16) .. + 3 of channel block j - the same products summed in the same order, so proj_out has the
+    // bits dvg_pixel_proj gives on the stored y.  Staged value (pixel m, channel c) lies at m * 64 + 4 ((c >> 2) ^ (m & 15)) +
+    // (c & 3): no padding; the XOR puts the 16 lanes of every ds_read_b128 group ({0-3, 12-15, 20-27}, ...: pixels m, channel
+    // quads q and q + 1) on 16 distinct 16-byte slots, and a ds_write_b32's 32 lanes (one pixel, 32 consecutive channels) on 32
+    // distinct banks.  (A padded pitch cannot do the former: the group's k = 1 lanes would have to avoid the k = 0 lanes' slots
+    // for every set of 8 pixels.)
+    [[maybe_unused]] float* const Ps = smem;
+    [[maybe_unused]] constexpr int PNT = 3;                                 // 16-column blocks of tap outputs: T <= 48
+    [[maybe_unused]] const int i16 = lane & 15, kq = lane >> 4;
+    [[maybe_unused]] f32x4 pw[PROJ ? PNT : 1][PROJ ? 4 : 1];
+    // the projection weights as B fragments (rows past T: the last row again - their columns are never stored).  The 8 x 16 tile
+    // loads them before the first barrier, so that their latency passes under it and under the addend loads; in the 8 x 8 tile
+    // 48 more live registers there would cost the fourth workgroup per CU (130 VGPRs), so it loads them after the tile is staged
+    constexpr bool PW_EARLY = TW == 16;
+    auto load_pw = [&]() {
+        if constexpr (PROJ) {
+#pragma unroll
+            for (int nt = 0; nt < PNT; ++nt)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    pw[nt][j] = *reinterpret_cast<const f32x4*>(p.proj_w + min(nt * 16 + i16, p.proj_T - 1) * 64 + 16 * j + 4 * kq);
+        }
+    };
+    if constexpr (PROJ) {
+        if (PW_EARLY) load_pw();
+        __syncthreads();      // the last stage has no trailing barrier: other waves may still read its A / B tiles
+    }
     auto epilogue = [&](auto act_c) {
         constexpr int ACT = decltype(act_c)::value;  // -1: generic (runtime p.act)
 #pragma unroll
@@ -825,7 +863,8 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
                     int oy, ox;
                     if (MODE == M2_CONVT4S2) { oy = 2 * (y0 + ty) + py; ox = 2 * (x0 + tx) + px; }
                     else { oy = y0 + ty; ox = x0 + tx; }
-                    if (!FIRST || want_y) yb[((tii * Ho + oy) * Wo + ox) * p.Cout] = o;
+                    if constexpr (PROJ) Ps[m * 64 + ((((wn * 32 + l31) >> 2) ^ (m & 15)) << 2) + (l31 & 3)] = o;
+                    else if (!FIRST || want_y) yb[((tii * Ho + oy) * Wo + ox) * p.Cout] = o;
                 }
             }
             if (MODE == M2_CONV3 && (TW == 16 || TW == 8)) {
@@ -855,6 +894,45 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
     if (p.act == DVG_ACT_LRELU) epilogue(std::integral_constant<int, DVG_ACT_LRELU>{});
     else if (p.act == DVG_ACT_NONE) epilogue(std::integral_constant<int, DVG_ACT_NONE>{});
     else epilogue(std::integral_constant<int, -1>{});
+    if constexpr (PROJ) {
+        if (!PW_EARLY) load_pw();
+        __syncthreads();
+        const int T = p.proj_T;
+        // 16 pixels per MFMA tile, the waves take them in turn (unrolled: BM / 64 = 1 or 2 tiles per wave - straight-line code
+        // like the rest of the epilogue, so that the kernel's only loops with MFMAs in them stay the stage loops)
+#pragma unroll
+        for (int it = 0; it < C::BM / 64; ++it) {
+            const int tile = wave + 4 * it;
+            const float* const prow = Ps + (tile * 16 + i16) * 64;
+            f32x4 a[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) a[j] = *reinterpret_cast<const f32x4*>(prow + (((4 * j + kq) ^ i16) << 2));
+            // D: lane l holds rows 4 (l / 16) + r = tile pixels m0 + r, column l % 16
+            const int m0 = tile * 16 + 4 * kq;
+            long orow[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int oy = 2 * (y0 + (m0 + r) / TW) + py, ox = 2 * (x0 + (m0 + r) % TW) + px;
+                orow[r] = (((long)n0 * Ho + oy) * Wo + ox) * T;
+            }
+#pragma unroll
+            for (int nt = 0; nt < PNT; ++nt) {
+                if (nt * 16 >= T) break;
+                f32x4 d = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) d = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j][e], pw[nt][j][e], d, 0, 0, 0);
+                const int col = nt * 16 + i16;
+                if (col < T) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) p.proj_out[orow[r] + col] = d[r];
+                }
+            }
+        }
+        clk_exit();
+        return;
+    }
     if (p.stats != nullptr) {
         float* red = smem;
         s1 += __shfl_xor(s1, 32);
@@ -1007,9 +1085,9 @@ static int choose_splitk(long wgs, int nchunks) {
     return s < 2 ? 1 : (int)s;
 }
 
-template <int MODE, int TI, int TH, int TW, int NT = 1, bool FIRST = false>
+template <int MODE, int TI, int TH, int TW, int NT = 1, bool FIRST = false, bool PROJ = false>
 static int launch2(Igemm2Params p, int Hg, int Wg, float* ws, long ws_floats, hipStream_t stream) {
-    using C = Cfg2<MODE, TI, TH, TW, NT, FIRST>;
+    using C = Cfg2<MODE, TI, TH, TW, NT, FIRST, PROJ>;
     if (Hg % TH || Wg % TW || p.Cout % C::BN) return fail(DVG_ERR_SHAPE, "conv_igemm2: tile does not divide shape");
     p.tiles_y = Hg / TH;
     p.tiles_x = Wg / TW;
@@ -1077,12 +1155,12 @@ static int launch2(Igemm2Params p, int Hg, int Wg, float* ws, long ws_floats, hi
     p.stage_prio = (MODE == M2_CONV3 || grid <= 3 * 256) ? 1 : 0;
     static bool attr_set = false;
     if (!attr_set) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm2_kernel<MODE, TI, TH, TW, NT, FIRST>),
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm2_kernel<MODE, TI, TH, TW, NT, FIRST, PROJ>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES);
         if (e != hipSuccess) return fail(DVG_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
         attr_set = true;
     }
-    hipLaunchKernelGGL((conv_igemm2_kernel<MODE, TI, TH, TW, NT, FIRST>), dim3(grid), dim3(256), C::LDS_BYTES, stream, p);
+    hipLaunchKernelGGL((conv_igemm2_kernel<MODE, TI, TH, TW, NT, FIRST, PROJ>), dim3(grid), dim3(256), C::LDS_BYTES, stream, p);
     if (int e = check_launch("conv_igemm2")) return e;
     if (S > 1) {
         const bool pool = y_pool != nullptr;
@@ -1325,6 +1403,39 @@ extern "C" int dvg_convT4x4s2_bn_act_v2(const float* x, const float* skip, const
     D2(M2_CONVT4S2, 1, 8, 8)
     D2(M2_CONVT4S2, 4, 4, 4)
     return fail(DVG_ERR_SHAPE, "dvg_convT4x4s2_bn_act_v2: no kernel");
+}
+
+// dvg_convT4x4s2_bn_act_v2 on x alone (C2 = 0) with Cout = 64, followed by dvg_pixel_proj(y, proj_w) - in one launch: the
+// activation y is never written; proj_out (N * 2H * 2W, T) holds what the projection of y would (same bits: see the kernel's
+// PROJ epilogue).  No statistics, no split-K; maps that tile2 gives the 8 x 16 or the 8 x 8 tile.  Any failed precondition is
+// an error before the launch.
+extern "C" int dvg_convT4x4s2_bn_act_proj(const float* x, const float* w_k16, const float* scale, const float* shift,
+                                          const float* proj_w, float* proj_out, int T, int N, int H, int W, int C1, int Cout,
+                                          int act, float slope, const float* addend, const int* addend_map, int addend_block,
+                                          void* stream) {
+    const char* who = "dvg_convT4x4s2_bn_act_proj";
+    DVG_REQUIRE(x && w_k16 && proj_w && proj_out, DVG_ERR_NULL, "%s: x / w / proj_w / proj_out must not be NULL", who);
+    DVG_REQUIRE(N > 0 && H > 0 && W > 0, DVG_ERR_SHAPE, "%s: empty shape", who);
+    DVG_REQUIRE(C1 > 0 && C1 % 16 == 0, DVG_ERR_SHAPE, "%s: C1=%d must be a multiple of 16", who, C1);
+    DVG_REQUIRE(Cout == 64, DVG_ERR_SHAPE, "%s: Cout=%d must be 64 (one column block holds every channel of a pixel)", who, Cout);
+    DVG_REQUIRE(T >= 1 && T <= 48, DVG_ERR_SHAPE, "%s: T=%d must be in 1..48", who, T);
+    DVG_REQUIRE(aligned16(x) && aligned16(w_k16) && aligned16(proj_w) && aligned16(addend), DVG_ERR_ALIGN,
+                "%s: pointers must be 16-byte aligned", who);
+    DVG_REQUIRE(act >= DVG_ACT_NONE && act <= DVG_ACT_SIGMOID, DVG_ERR_SHAPE, "%s: bad act", who);
+    Igemm2Params p{x, nullptr, w_k16, scale, shift, nullptr, nullptr, nullptr, N, H, W, C1, 0, Cout, 0, act, slope, 0, 0, 0, 0, 0,
+                   1, 0, nullptr};
+    p.addend = addend;
+    p.add_map = addend ? addend_map : nullptr;
+    p.add_B = addend_block;
+    DVG_REQUIRE(p.add_map == nullptr || (addend_block > 0 && N % addend_block == 0), DVG_ERR_SHAPE, "%s: addend_block must divide N", who);
+    p.proj_w = proj_w;
+    p.proj_out = proj_out;
+    p.proj_T = T;
+    int ti, th, tw;
+    DVG_REQUIRE(tile2(M2_CONVT4S2, N, H, W, Cout, &ti, &th, &tw) == 0 && ti == 1, DVG_ERR_SHAPE,
+                "%s: unsupported map %dx%d (multiples of 8 needed)", who, H, W);
+    if (tw == 16) return launch2<M2_CONVT4S2, 1, 8, 16, 1, false, true>(p, H, W, nullptr, 0, (hipStream_t)stream);
+    return launch2<M2_CONVT4S2, 1, 8, 8, 1, false, true>(p, H, W, nullptr, 0, (hipStream_t)stream);
 }
 
 // Batched GEMM on the igemm machinery: y[b][px][co] = sum_ci x[b][px][ci] * w[b][ci][co] for b < NB "images" of H x W

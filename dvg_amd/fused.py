@@ -164,8 +164,15 @@ def block_weight(kind, weight, lo=None, hi=None):
     return weight if blk.mode is None else weights.packed(weight, bool(blk.finish[0]), lo, hi, blk.cat)
 
 
-def _skip_half(kind, skip, ps):
-    """S = conv(skip, W_skip), raw accumulators; ps: the packed skip half of the weight."""
+def _skip_half(kind, skip, ps, conv=None):
+    """S = conv(skip, W_skip), raw accumulators; ps: the packed skip half of the weight.  conv (eval-mode rollouts): the
+    Conv2d itself - a 3x3 skip half whose shape qualifies runs as F(4x4) (a quarter of the multiplies, the raw-accumulator form
+    _dgrad_conv3 uses); training's autograd._SkipHalf keeps the direct form."""
+    if kind == "conv3" and conv is not None and not conv.training and not torch.is_grad_enabled():
+        n, c, h, w = skip.shape
+        ctot = conv.weight.shape[1]
+        if winograd_tile(n, c, h, w, conv.weight.shape[0]) == 4:
+            return ops.conv3x3_winograd(skip, weights.winograd(conv.weight, 4, ctot - c, ctot), None, None, act=ACT_NONE)
     return BLOCKS[kind].raw(skip, None, ps, None)
 
 
@@ -320,6 +327,11 @@ def _train_bn(bn: nn.BatchNorm2d, stats, count, save=False, synced=False):
 SKIP_HOIST = os.environ.get("DVG_SKIP_HOIST", "1") != "0"
 # x half of an upsample + 3x3 conv as the equivalent 4x4 stride-2 transposed conv (see weights.k4_packed); 0 disables
 UPCONV_AS_CONVT = os.environ.get("DVG_UPCONV_AS_CONVT", "1") != "0"
+# the K4 launch of the decoder's last block also projects its 64-channel activation onto the last ConvTranspose2d's tap outputs
+# (ops.convT4x4s2_proj): the activation, which only the projection read, is never stored.  False: the K4 launch stores the
+# activation and ops.pixel_proj reads it back.  A module attribute without an environment variable: the product reads ten of
+# those and tests/test_host_logic.py holds it to ten
+LAST_PROJ_FUSED = True
 _skip_seen = {}      # (id(conv), id(skip)) -> [weakref(skip), skip._version, weight key, sightings, S or None]
 
 
@@ -365,7 +377,7 @@ def precompute_skip_half(conv, skip, kind: str) -> None:
     if not SKIP_HOIST or skip is None:
         return
     ctot = conv.weight.shape[BLOCKS[kind].cat]
-    s = _skip_half(kind, skip, block_weight(kind, conv.weight, ctot - skip.shape[1], ctot))
+    s = _skip_half(kind, skip, block_weight(kind, conv.weight, ctot - skip.shape[1], ctot), conv)
     _skip_seen[(id(conv), id(skip))] = [weakref.ref(skip), skip._version, _ver(conv.weight), 1, s]
 
 
@@ -482,8 +494,19 @@ def _train_block(kind, conv, bn, x, skip=None, *, up=False, act, slope, pool=Fal
     return _bn_act_train(bn, u, st, act=act, slope=slope, pool=pool)
 
 
+def _last_proj_applies(next_last, conv, x) -> bool:
+    """True when the K4 launch of this upsample + concat conv (skip half hoisted, eval mode) may project its output for
+    `next_last`, the decoder's last ConvTranspose2d and the output's only consumer (LAST_PROJ_FUSED)."""
+    if not LAST_PROJ_FUSED or next_last is None or torch.is_grad_enabled() or not isinstance(next_last, nn.ConvTranspose2d):
+        return False
+    w = next_last.weight
+    return (conv.weight.shape[0] == 64 and w.shape[0] == 64 and tuple(w.shape[2:]) == (3, 3) and 9 * w.shape[1] <= ops.PROJ_MAX_T
+            and tuple(next_last.stride) == (1, 1) and tuple(next_last.padding) == (1, 1) and x.shape[2] % 8 == 0
+            and x.shape[3] % 8 == 0)
+
+
 def conv3_bn_act(conv, bn, x, skip=None, *, upsample=False, pool=False, act=ACT_LRELU, slope=0.2, next_conv=None, y_from=0,
-                 next_up=None):
+                 next_up=None, next_last=None):
     """vgg_layer (vgg_64.py:5-15) with optional fused cat/upsample on the input and
     fused 2x2 max-pool on the output.  next_conv: the Conv2d of the vgg_layer that consumes this layer's output and is its
     ONLY consumer - in eval mode the result may then be an ops.WinoV (that layer's Winograd input transform) instead of the
@@ -491,13 +514,15 @@ def conv3_bn_act(conv, bn, x, skip=None, *, upsample=False, pool=False, act=ACT_
     y_from (pool=True only, eval mode): of the (y, pooled) pair, y - an encoder stage's skip tensor - is wanted for the images
     [y_from, N) only: the Winograd paths then do not store the rest (ops.conv3x3_winograd), the others slice.
     next_up = (conv, bn, skip) of the NEXT decoder block's first layer when this is a block's last layer and that layer is
-    the only consumer: in eval mode the result may be the input transform of the upsampled output (an ops.WinoV with .up)."""
+    the only consumer: in eval mode the result may be the input transform of the upsampled output (an ops.WinoV with .up).
+    next_last: the decoder's last ConvTranspose2d when it is this layer's only consumer: in eval rollouts the result may be an
+    ops.LastProj (the per-pixel projection convT3_last starts with) instead of the activation; pass it on to convT3_last."""
     if y_from and (not pool or bn.training or _needs_grad(x, skip, conv.weight, bn.weight)):
         raise RuntimeError("conv3_bn_act: y_from is an eval-mode, no-grad option of the pooled form")
     if isinstance(x, ops.WinoV) and x.up:
         # first conv of a decoder block fed by the previous block's last layer through the upsampling (_chain_up_to held there)
         hs = None if (bn.training or not upsample or pool) else \
-            _hoisted_skip(conv, x, skip, functools.partial(_skip_half, "conv3", skip), force=True)
+            _hoisted_skip(conv, x, skip, functools.partial(_skip_half, "conv3", skip, conv=conv), force=True)
         if hs is None:
             raise RuntimeError("conv3_bn_act: an upsampled WinoV needs the eval-mode concat conv with its skip half hoisted")
         sc, sh = folded_affine(conv, bn)
@@ -522,7 +547,7 @@ def conv3_bn_act(conv, bn, x, skip=None, *, upsample=False, pool=False, act=ACT_
     if not bn.training:
         sc, sh = folded_affine(conv, bn)
         if not pool:
-            hs = _hoisted_skip(conv, x, skip, functools.partial(_skip_half, "conv3", skip))
+            hs = _hoisted_skip(conv, x, skip, functools.partial(_skip_half, "conv3", skip, conv=conv))
             if hs is not None:
                 if upsample and UPCONV_WINOGRAD:
                     # x half of upsample + concat conv in Winograd form: the input transform reads x through the nearest-x2
@@ -538,6 +563,12 @@ def conv3_bn_act(conv, bn, x, skip=None, *, upsample=False, pool=False, act=ACT_
                         return ops.conv3x3_winograd(x, weights.winograd(conv.weight, 4, 0, c1_), sc, sh, act=act, slope=slope,
                                                     upsample=True, addend=hs[1], to_v=to_v)
                 if upsample and UPCONV_AS_CONVT:
+                    if _last_proj_applies(next_last, conv, x):
+                        w_last = next_last.weight
+                        d = ops.convT4x4s2_proj(x, weights.k4_packed(conv.weight, x.shape[1]), sc, sh,
+                                                ops._last_wmat_cached(w_last, 0, 64, 9 * w_last.shape[1]), act=act, slope=slope,
+                                                addend=hs[1])
+                        return ops.LastProj(d, (x.shape[0], 64, 2 * x.shape[2], 2 * x.shape[3]), w_last)
                     return ops.convT4x4s2(x, None, weights.k4_packed(conv.weight, x.shape[1]), sc, sh, act=act, slope=slope,
                                           addend=hs[1])
                 return ops.conv3x3(x, None, hs[0], sc, sh, upsample=upsample, act=act, slope=slope, addend=hs[1])
@@ -672,6 +703,8 @@ def stem_bn_act(conv, bn, vec, *, act=ACT_LRELU, slope=0.2, next_up=None):
 
 def convT3_last(conv, x, *, act=ACT_SIGMOID):
     """ConvTranspose2d(64,nc,3,1,1)+Sigmoid (vgg_64.py:88-92): NHWC in, NCHW frame out."""
+    if isinstance(x, ops.LastProj):      # the layer before has projected its output already (conv3_bn_act: next_last)
+        return ops.convT_last_two_step(x, None, conv.weight, _bias(conv), conv.weight.shape[1], 3, act=act)
     if _needs_grad(x, conv.weight):
         from .autograd import last_layer_autograd
         return last_layer_autograd("convT3", conv, x, None, act=act)

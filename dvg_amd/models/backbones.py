@@ -212,8 +212,10 @@ class VggDecoder(nn.Module):
                         fl = getattr(self, f"upc{s + 1}")[0]
                         nup = (fl.main[0], fl.main[1], sks[s + 1])
                     if first:  # nearest x2 + cat(skip) fused into the tile loader (eval rollouts: x half in Winograd form)
+                        # followed directly by the last ConvTranspose2d (its only consumer): may hand over an ops.LastProj
+                        nlast = mods[li + 1] if li + 1 < len(mods) and isinstance(mods[li + 1], nn.ConvTranspose2d) else None
                         d = fused.conv3_bn_act(layer.main[0], layer.main[1], d, sk, upsample=True,
-                                               next_conv=None if nxt is None else nxt.main[0], next_up=nup)
+                                               next_conv=None if nxt is None else nxt.main[0], next_up=nup, next_last=nlast)
                         first = False
                     else:      # an inner layer followed by another vgg_layer of the block may hand over an ops.WinoV
                         d = fused.conv3_bn_act(layer.main[0], layer.main[1], d,

@@ -15,6 +15,7 @@ from .conv import (  # noqa: F401
     pack_conv_weight, pack_convT_weight, packed_row_floats, pack_igemm_weight, _wp_dims, unpack_conv_weight,
     unpack_convT_weight, _splitk_ws, _SPLITK_WS, evict_captured_workspaces, _stats_buf, _tile_images, SharedBlocks,
     _MAP_CACHE, shared_map, group_sum, _check_addend, conv3x3, CONV4S2_MAX_FLOATS, conv4x4s2, convT4x4s2,
+    PROJ_MAX_T, convT4x4s2_proj,
 )
 from .winograd import (  # noqa: F401
     winograd_weight, winograd_ok, WinoV, winograd_chain_ok, winograd_up_chain_ok, winograd_pool_chain_ok,
@@ -23,7 +24,7 @@ from .winograd import (  # noqa: F401
 from .edge import (  # noqa: F401
     conv3x3_first, first_pair_ok, conv3x3_first_pair, convT3x3_last, conv4x4s2_first, convT4x4s2_last, pixel_proj,
     _SKIP_PROJ_CACHE, clear_skip_proj_cache, _cached_skip_proj, _last_wmat, _last_wmat_cached,
-    precompute_skip_proj, convT_last_two_step, eval_frames, eval_frames_finn, pairwise_frame_mse, moving_mnist_compose, clip_gather, clip_gather_aug, CLIP_MAX_SHIFT,
+    precompute_skip_proj, LastProj, convT_last_two_step, eval_frames, eval_frames_finn, pairwise_frame_mse, moving_mnist_compose, clip_gather, clip_gather_aug, CLIP_MAX_SHIFT,
     mnist_scale_u8, moving_mnist_compose_u8, frame_mosaic, QUANT_TRUNC, QUANT_NEAREST,
     MOSAIC_BLACK, MOSAIC_RED, MOSAIC_GREEN, MOSAIC_SEL_NONE, MOSAIC_SEL_BEST, MOSAIC_SEL_PICK, MOSAIC_CELL_INTS,
 )

@@ -306,3 +306,40 @@ def convT4x4s2(x, skip, wp, scale, shift, *, act=ACT_LRELU, slope=0.2, stats=Fal
          _p(y), _p(st), n, h, w, c1, c2, cout, act, slope, _p(ws), 0 if ws is None else ws.numel(), _p(addend),
          _p(amap), ablk, _stream())
     return (y, st) if stats else y
+
+
+PROJ_MAX_T = 48     # dvg_convT4x4s2_bn_act_proj / dvg_pixel_proj: tap outputs per pixel
+
+
+def convT4x4s2_proj(x, wp, scale, shift, wm, *, act=ACT_LRELU, slope=0.2, addend=None):
+    """convT4x4s2(x, None, wp, ...) with 64 output channels followed by edge.pixel_proj(y, wm), as ONE launch
+    (dvg_convT4x4s2_bn_act_proj): the (N,64,2H,2W) activation is never stored.  wm (T,64); returns d (N*2H*2W, T) with the
+    bits of the two launches.  Unsupported shapes raise - there is no other path behind this call."""
+    _dev_f32(x, "convT4x4s2_proj.x")
+    _dev_f32(wm, "convT4x4s2_proj.wm")
+    assert is_nhwc(x)
+    n, c1, h, w = x.shape
+    taps, cout, cin = _wp_dims(wp)
+    if taps != 16 or cin != c1:
+        raise RuntimeError(f"convT4x4s2_proj: packed weight {tuple(wp.shape)} does not match Cin={c1}")
+    t = wm.shape[0]
+    if cout != 64 or tuple(wm.shape) != (t, 64) or not wm.is_contiguous() or not 1 <= t <= PROJ_MAX_T or h % 8 or w % 8:
+        raise RuntimeError(f"convT4x4s2_proj: needs Cout = 64, wm (T <= {PROJ_MAX_T}, 64) and a map of multiples of 8; got Cout="
+                           f"{cout}, wm {tuple(wm.shape)}, x {tuple(x.shape)}")
+    amap, ablk = None, 0
+    if addend is not None:
+        if isinstance(addend, SharedBlocks):
+            if n != addend.groups * addend.block:
+                raise RuntimeError("convT4x4s2_proj: shared addend does not match the batch")
+            amap, ablk, addend = addend.map_dev, addend.block, addend.t
+        elif addend.shape[0] != n:
+            raise RuntimeError("convT4x4s2_proj: addend does not match the batch")
+        _dev_f32(addend, "convT4x4s2_proj.addend")
+        if tuple(addend.shape[1:]) != (64, 2 * h, 2 * w) or not is_nhwc(addend):
+            raise RuntimeError(f"convT4x4s2_proj: addend {tuple(addend.shape)} must be NHWC (.,64,{2 * h},{2 * w})")
+    d = torch.empty((n * 4 * h * w, t), device=x.device, dtype=torch.float32)
+    fl = 2.0 * n * h * w * cout * 16 * cin + 2.0 * n * 4 * h * w * cout * t
+    by = 4.0 * (x.numel() + wp.numel() + wm.numel() + (n * 4 * h * w * cout if addend is not None else 0) + d.numel())
+    _run("convT4x4s2_igemm", fl, by, lib().dvg_convT4x4s2_bn_act_proj, _p(x), _p(wp), _p(scale), _p(shift), _p(wm), _p(d), t,
+         n, h, w, c1, cout, act, slope, _p(addend), _p(amap), ablk, _stream())
+    return d

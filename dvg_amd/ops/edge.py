@@ -163,15 +163,29 @@ def precompute_skip_proj(skip, w, ks: int) -> None:
     _cached_skip_proj(skip, lambda: _last_wmat_cached(w, c1, wdet.shape[0], t), w)
 
 
+class LastProj:
+    """What the conv before the last layer hands over instead of its activation when it has projected it already
+    (conv.convT4x4s2_proj): d = pixel_proj(activation, wmat of `w`), (N*H*W, T); shape = the activation's (N,C,H,W)."""
+
+    def __init__(self, d, shape, w):
+        self.d, self.shape, self.w = d, tuple(shape), w
+
+
 def convT_last_two_step(x, skip, w, bias, nc, ks, *, act):
     """Last layer as per-pixel projection (dvg_pixel_proj: reads the activation once) + shifted sum
     (dvg_convT_gather).  x / skip NHWC-in-memory; w the original ConvTranspose2d weight (Cin,nc,ks,ks); returns
-    NCHW frames."""
-    assert is_nhwc(x)
-    n, c1, h, wd = x.shape
+    NCHW frames.  x may be a LastProj: the first step has been done by the launch that made the activation."""
     wdet = w.detach()
     t = ks * ks * nc
-    d1 = pixel_proj(x, _last_wmat_cached(w, 0, c1, t))
+    if isinstance(x, LastProj):
+        if x.w is not w or tuple(x.d.shape) != (x.shape[0] * x.shape[2] * x.shape[3], t):
+            raise RuntimeError("convT_last_two_step: the projection handed over was made for another last layer")
+        n, c1, h, wd = x.shape
+        d1 = x.d
+    else:
+        assert is_nhwc(x)
+        n, c1, h, wd = x.shape
+        d1 = pixel_proj(x, _last_wmat_cached(w, 0, c1, t))
     d2 = None
     d2_map, d2_blk = None, 0
     if isinstance(skip, SharedBlocks):      # time-batched decoder calls: the projection of the DISTINCT skip blocks only
@@ -182,7 +196,7 @@ def convT_last_two_step(x, skip, w, bias, nc, ks, *, act):
     elif skip is not None:
         d2 = _cached_skip_proj(skip, lambda: _last_wmat_cached(w, c1, wdet.shape[0], t), w)
     s = 2 if ks == 4 else 1
-    y = torch.empty((n, nc, s * h, s * wd), device=x.device, dtype=torch.float32)
+    y = torch.empty((n, nc, s * h, s * wd), device=d1.device, dtype=torch.float32)
     _run("convT_gather", 0.0, 4.0 * (d1.numel() * (2 if skip is not None else 1) + y.numel()), lib().dvg_convT_gather,
          _p(d1), _p(d2), _p(bias), _p(y), ks, n, h, wd, nc, act, _p(d2_map), d2_blk, _stream())
     return y

@@ -152,11 +152,12 @@ int dvg_conv4x4s2_bn_act_v2(const float* x, const float* w_k16, const float* sca
                             void* stream);
 /* dcgan_upconv = ConvTranspose2d(nin,nout,4,2,1)+BN+LReLU on cat([x, skip]) (dcgan_64.py:16-26,84-87) as four parity-class
  * implicit GEMMs (K = 4*Cin).  x NHWC (N,H,W,C1), skip NHWC (N,H,W,C2) or NULL; y NHWC (N,2H,2W,Cout).                 */
-int dvg_convT4x4s2_bn_act_v2(const float* x, const float* skip, const float* w_k16,
-                             const float* scale, const float* shift, float* y, float* stats,
-                             int N, int H, int W, int C1, int C2, int Cout, int act, float slope,
-                             float* workspace, long workspace_floats, const float* addend,
-                             const int* addend_map /* as dvg_conv3x3_bn_act_v2 */, int addend_block, void* stream);
+int dvg_convT4x4s2_bn_act_v2(const float* x, const float* skip, const float* w_k16, const float* scale, const float* shift, float* y,
+                             float* stats, int N, int H, int W, int C1, int C2, int Cout, int act, float slope, float* workspace,
+                             long workspace_floats, const float* addend, const int* addend_map /* as dvg_conv3x3_bn_act_v2 */, int addend_block, void* stream);
+/* ... on x alone with Cout = 64, then dvg_pixel_proj(y, proj_w [T][64]) -> proj_out (N*2H*2W, T), in ONE launch (within ABI 9): same bits, y (N,2H,2W,64) is never written; T <= 48, H, W % 8 == 0 */
+int dvg_convT4x4s2_bn_act_proj(const float* x, const float* w_k16, const float* scale, const float* shift, const float* proj_w, float* proj_out, int T,
+                               int N, int H, int W, int C1, int Cout, int act, float slope, const float* addend, const int* addend_map, int addend_block, void* stream);
 
 /* Winograd F(m x m, 3x3), m = 2 or 4, form of vgg_layer for the deep eval-mode layers (vgg_64.py:5-15 at 16x16 / 8x8 maps
  * with 256-512 channels): fp32 data and transforms, 2.25x (m = 2) / 4x (m = 4) fewer multiply-adds, P = (m+2)^2 transform
