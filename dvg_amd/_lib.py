@@ -139,6 +139,8 @@ SIGNATURES = {
     "dvg_mse_sum_grad": (_i, [_p, _p, _p, _p, _l, _f, _p]),
     "dvg_frame_losses_ext_blocks": (_i, [_i, _l, _i, _i]),
     "dvg_frame_losses_ext": (_i, [_p, _p, _p, _p, _i, _i, _l, _i, _i, _i, _f, _p, _p, _p, _p]),
+    "dvg_frame_ssim_loss_blocks": (_i, [_i, _l, _i, _i]),
+    "dvg_frame_ssim_loss": (_i, [_p, _p, _p, _p, _i, _i, _l, _i, _i, _p, _i, _p, _p]),
     "dvg_gp_var_norms": (_i, [_p, _p, _i, _i, _p]),
     "dvg_gp_trigger_step": (_i, [_p, _i, _i, _i, _p, _i, _f, _p, _p, _p, _p, _i, _p]),
     "dvg_gp_trigger_replay": (_i, [_p, _i, _p, _i, _f, _p, _p, _p]),

@@ -127,7 +127,7 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
 // determinism tests compare bits: neither the tree inside a wave nor the order in which the wave sums are combined may change
 // silently.  The two orders are historical, not chosen; each call site keeps the one it was written with.
 //   SUM_WAVE_ORDER  ((0 + r0) + r1) + r2 ... left to right over the NT / 64 waves: gp.hip (gp_predict, gp_train_bwd, gp_elbo),
-//                   grad_guard.hip (grad_sumsq, grad_guard_finish), ema.hip (ema_update).  The leading + 0 is gp.hip's loop; the
+//                   grad_guard.hip (grad_sumsq, grad_guard_finish), ema.hip (ema_update), ssim_loss.hip (16 waves).  The leading + 0 is gp.hip's loop; the
 //                   wave sums of grad_guard.hip and ema.hip are sums of squares from + 0, never - 0, so it changes none of their bits.
 //   SUM_PAIRWISE    (r0 + r1) + (r2 + r3), four waves: finn_metrics.hip (eval_frames_finn) and eval_frames_kernel,
 //                   frame_losses_kernel in misc_kernels.hip.

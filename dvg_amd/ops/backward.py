@@ -84,6 +84,44 @@ def frame_losses_ext(pred, target, spec_or_kind, weights, eps=1e-3, gdl=0.0):
     return sums, dpred
 
 
+def frame_ssim_loss(pred, target, weights, dpred=None):
+    """pred (S, K, ..., H, W), target (S, ..., H, W) contiguous, H, W >= 11, W % 4 == 0: (sums (K,), dpred like pred) with sums[k] =
+    sum (1 - SSIM) of call k over steps, planes and the (H-10) x (W-10) window positions - SSIM the Finn SSIM of eval_frames_finn -
+    and dpred = d(sum_k weights[k] sums[k]) / d pred, ADDED to `dpred` when one is given (what frame_losses_ext returned), one launch
+    (dvg_frame_ssim_loss; docs/DESIGN_NOTES_frame_loss.md).  `weights`: K Python floats (W_s x loss weight / window positions)."""
+    _dev_f32(pred, "frame_ssim_loss.pred")
+    _dev_f32(target, "frame_ssim_loss.target")
+    if not pred.is_contiguous() or not target.is_contiguous():
+        raise RuntimeError("frame_ssim_loss: contiguous operands expected")
+    if pred.dim() < 4 or target.dim() != pred.dim() - 1 or pred.shape[:1] + pred.shape[2:] != target.shape or \
+            len(weights) != pred.shape[1]:
+        raise RuntimeError(f"frame_ssim_loss: pred {tuple(pred.shape)} / target {tuple(target.shape)} / {len(weights)} weights")
+    s_, k, h, w_ = pred.shape[0], pred.shape[1], pred.shape[-2], pred.shape[-1]
+    planes = target[0].numel() // (h * w_)
+    blocks = lib().dvg_frame_ssim_loss_blocks(s_, planes, h, w_)
+    if blocks <= 0 or not 1 <= k <= 3:
+        raise RuntimeError(f"frame_ssim_loss: unsupported shape S={s_} K={k} planes={planes} H={h} W={w_}")
+    accumulate = dpred is not None
+    if accumulate:
+        _dev_f32(dpred, "frame_ssim_loss.dpred")
+        if dpred.shape != pred.shape or not dpred.is_contiguous():
+            raise RuntimeError(f"frame_ssim_loss: dpred {tuple(dpred.shape)} must be contiguous and shaped like pred {tuple(pred.shape)}")
+    key = (pred.device, "ssim", tuple(float(w) for w in weights))
+    w = _LOSS_W.get(key)
+    if w is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("frame_ssim_loss: first call with these weights during a capture (run one eager iteration first)")
+        w = _LOSS_W[key] = torch.tensor(key[2], dtype=torch.float32, device=pred.device)
+    sums = torch.empty(k, device=pred.device, dtype=torch.float32)
+    if not accumulate:
+        dpred = torch.empty_like(pred)
+    partial = torch.empty(blocks * k, device=pred.device, dtype=torch.float64)
+    # per map position and call: 22 row taps x 3 moments / 11 column taps x 3, the same transposed: ~150 fp64 FMAs per pixel
+    _run("frame_ssim_loss", 300.0 * pred.numel(), 4.0 * ((2 + accumulate) * pred.numel() + target.numel()), lib().dvg_frame_ssim_loss,
+         _p(pred), _p(target), _p(sums), _p(dpred), s_, k, planes, h, w_, _p(w), int(accumulate), _p(partial), _stream())
+    return sums, dpred
+
+
 def mse_sum_grad(a, b, scale, need_grad=True):
     """(sum (a - b)^2 as a 0-dim tensor, 2 scale (a - b) or None) for small tensors (dvg_mse_sum_grad): a closure's latent MSE
     and its gradient (train.py:188,223)."""

@@ -59,22 +59,18 @@ int dvg_unpack_convT_weight(const float* w_packed, float* w_iohw, int cin, int c
 /* ---- Encoder / decoder blocks ---- */
 /* vgg_layer = Conv2d(nin,nout,3,1,1)+BatchNorm2d+LeakyReLU(0.2)  (vgg_64.py:5-15) as ONE fp32-MFMA implicit GEMM
  * (M = N*H*W pixels, N = Cout, K = 9*Cin):
- *
  *   u        = conv3x3(in) + 0            (bias is folded into `shift`)
  *   y        = act(u * scale[c] + shift[c])
  *   y_pool   = maxpool2x2(y)              (optional; nn.MaxPool2d(2,2) vgg_64.py:49)
- *
  * `in` is either `x` (N,H,W,C1) or, when `upsample_x` != 0, the channel concat cat([nearest_up2(x), skip], C)
  * (vgg_64.py:93,98-105) with x given at (N,H/2,W/2,C1) and skip at (N,H,W,C2); the concat and the up-sampling are done by
  * the tile loader and never materialised.  With skip == NULL, C2 must be 0.  When upsample_x == 0 and skip != NULL the
  * input is cat([x, skip]) at full resolution.
  * scale/shift: [Cout] (eval-mode BN folded with the conv bias); either may be NULL (=1 / =0).
- *
  * stats (optional, train-mode BN): float[rows][2][Cout] with rows = dvg_conv_stats_rows_v2(...); every workgroup writes the
  * per-channel sum(u') and sum(u'^2) of its own pixel tile, where u' = u*scale+shift BEFORE the activation (callers pass
  * scale=NULL, shift=bias, act=NONE to obtain the raw conv output and its statistics).  Deterministic (no atomics);
  * dvg_bn_finalize reduces the rows.
- *
  * Requirements: C1 % 32 == 0, C2 % 32 == 0, Cout % 64 == 0, H % 8 == 0, W % 8 == 0, all pointers 16-byte aligned.       */
 #define DVG_MODE_CONV3 0
 #define DVG_MODE_CONV4S2 1
@@ -90,7 +86,6 @@ int dvg_conv_first_stats_rows(int ks, int N, int H, int W);
  * a 4x4 plain pack orders them by INPUT parity (r05): it feeds dvg_conv4x4s2_bn_act_v2, which runs one stage per parity and needs
  * N * H * W * Cin < 2^31; a 3x3 pack feeds dvg_conv3x3_bn_act_v2), and `stats` has dvg_conv_stats_rows_v2(...) rows.
  * C1, C2 multiples of 16; Cout multiple of 64.
- *
  * ABI 7 - arithmetic of the implicit-GEMM kernels.  dvg_mfma_mode() == 1 (the default build): every fp32 operand is split EXACTLY
  * into three bf16 terms (8 + 8 + 8 significant bits; activations when a tile is staged in LDS, weights when they are packed: a
  * packed row is 3 x 16 bf16 = 24 floats) and a K = 16 slab of the product is six v_mfma_f32_32x32x16_bf16 with fp32 accumulation;
@@ -603,20 +598,17 @@ int dvg_pairwise_frame_mse(const float* samples, float* out, int S, long sample_
  * train.py:291-335 (plot -> save_tensors_image + utils.save_gif), the chain utils.image_tensor (utils.py:104-150),
  * add_border (generate_frames.py:306-319), draw_text_tensor (utils.py:167-173) and make_image (utils.py:160-165), which
  * work on .cpu() tensors in Python loops.  Only the bytes leave the device.  An addition within ABI 9.
- *
  * out: uint8 [F][GH][GW][3], GH = R*cell_h + (R-1)*pad_y, GW = Cc*cell_w + (Cc-1)*pad_x: F frames, each an R x Cc grid of
  * cell_h x cell_w cells separated by pad_y / pad_x pixels of 1.0 (image_tensor's canvas of ones).  A cell is filled with its
  * colour (DVG_MOSAIC_BLACK, _RED = 0.7 in channel 0, _GREEN = 0.7 in channel 1: add_border) and holds one H x W image at
  * (oy, ox); nc = 1 is replicated to three channels, nc = 3 copied.  Where the cell's label mask is set the pixel is black
  * (draw_text_tensor's fill (0,0,0)); labels: uint8 [n_labels][lh][lw] anchored at the cell's corner, NULL = none.
- *
  * cells: DEVICE int32 [F][R][Cc][DVG_MOSAIC_CELL_INTS] = {src, base, stride, sel, b, k, colour, label}: the image is number
  * base + s * stride of source `src` (0..2; images are nc*H*W contiguous floats, so an NCHW batch (.., B, C, H, W) is a run of
  * them) with s = 0 (DVG_MOSAIC_SEL_NONE), best[b] (_SEL_BEST; int64 [n_best]) or picks[b][k] (_SEL_PICK; int32
  * [n_pick_rows][pick_k]), read ON THE DEVICE: no index is read back before the launch.  label = -1: none.  The kernel
  * checks every table entry and index against n0 / n1 / n2 (the sources' image counts), n_best, n_pick_rows, pick_k and
  * n_labels; an entry that fails (src = -1 included) draws its background only.
- *
  * quant: DVG_QUANT_TRUNC = uint8(clamp(v,0,1) * 255) (draw_text_tensor's np.uint8(np_x*255): the GIFs), DVG_QUANT_NEAREST =
  * uint8(clamp(v,0,1) * 255 + 0.5) (scipy.misc.toimage's bytescale with cmin = 0, cmax = 1: the PNGs); product and add are
  * separately rounded fp32.  The one deviation: toimage stretches by the image's minimum, (v - min) * 255 * max / (max - min);
@@ -748,6 +740,14 @@ int dvg_mse_sum_grad(const float* a, const float* b, float* sum, float* da, long
 int dvg_frame_losses_ext_blocks(int S, long planes, int H, int W);
 int dvg_frame_losses_ext(const float* pred, const float* target, float* sums, float* dpred, int S, int K, long planes, int H, int W,
                          int kind, float eps, const float* w_pix, const float* w_gdl, float* partial, void* stream);
+/* The DSSIM frame term (train.py --ssim_weight here; docs/DESIGN_NOTES_frame_loss.md), same layouts: sums [K] = sum (1 - SSIM) of call k
+ * over steps, planes and the (H-10) x (W-10) valid positions, SSIM = dvg_eval_frames_finn's, fp64 inside; dpred = (accumulate ? dpred : 0)
+ * - w_ssim[k] d(sum SSIM)/d pred, the owner's read-modify-write after dvg_frame_losses_ext.  w_ssim [K] on the device.  partial:
+ * dvg_frame_ssim_loss_blocks(...) x K doubles (<= 0: shape not served).  H, W >= 11, W % 4 == 0, K in 1..3, S K planes H W < 2^31; pred,
+ * target, dpred 16-byte aligned.  Deterministic, one launch + the finish.  Within ABI 9. */
+int dvg_frame_ssim_loss_blocks(int S, long planes, int H, int W);
+int dvg_frame_ssim_loss(const float* pred, const float* target, float* sums, float* dpred, int S, int K, long planes, int H, int W,
+                        const float* w_ssim, int accumulate, double* partial, void* stream);
 
 /* optimizer.zero_grad() of adjacent parameter groups of the gradient arena as ONE fill (train.py:201-203 zeroes three modules),
  * and the device-side Adam step counts t0..t3 (NULL: none) advanced by one in the same launch (dvg_adam_step's step_dev): a

@@ -35,13 +35,14 @@ def main():
     ap.add_argument("--ema_decay", type=float, default=None, help="train.py's flag: the weight average, one update per iteration")
     ap.add_argument("--frame_loss", default="mse", help="train.py's flag: the pixel penalty of the frame terms")
     ap.add_argument("--gdl_weight", type=float, default=0.0, help="train.py's flag: the gradient-difference loss")
+    ap.add_argument("--ssim_weight", type=float, default=0.0, help="train.py's flag: the DSSIM term of the frame losses")
     a = ap.parse_args()
     o = train.options(["--model", a.model, "--batch_size", str(a.batch), "--n_past", str(a.n_past),
                        "--n_future", str(a.n_future), "--no_save", "--channels", str(a.channels),
                        "--image_width", str(a.image_width), "--clip_grad_norm", repr(a.clip_grad_norm)] +
                       (["--no_ft"] if a.no_ft else []) + (["--skip_nonfinite"] if a.skip_nonfinite else []) +
                       ([] if a.ema_decay is None else ["--ema_decay", repr(a.ema_decay)]) +
-                      ["--frame_loss", a.frame_loss, "--gdl_weight", repr(a.gdl_weight)])
+                      ["--frame_loss", a.frame_loss, "--gdl_weight", repr(a.gdl_weight), "--ssim_weight", repr(a.ssim_weight)])
     if os.environ.get("DVG_FORCE_ALLREDUCE") == "1":
         import torch.distributed as dist
         import socket

@@ -38,7 +38,8 @@ graph, and writes `model_ema.pth` beside `model.pth` (dvg_amd/ema.py, docs/DESIG
 logs them to `val_log.jsonl` and keeps `model_best.pth` (dvg_amd/validate.py, docs/DESIGN_NOTES_validation.md).
 `--lr_schedule KIND` makes `--lr` the base rate of all four optimisers and moves it every iteration by a device-side multiplier:
 warm-up, then constant | linear | cosine | step; one launch per iteration (dvg_amd/lr_schedule.py, docs/DESIGN_NOTES_lr_schedule.md).
-`--frame_loss l1|charbonnier`, `--gdl_weight G`: another pixel penalty / the gradient-difference loss in the frame terms (dvg_amd/frame_loss.py).
+`--frame_loss l1|charbonnier`, `--gdl_weight G`, `--ssim_weight W`: another pixel penalty / the gradient-difference loss / 1 - SSIM in the frame terms
+(dvg_amd/frame_loss.py).
 """
 import argparse
 import os
