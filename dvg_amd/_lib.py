@@ -133,6 +133,7 @@ SIGNATURES = {
     "dvg_ema_update": (_i, [_p, _p, _l, _d, _p, _p, _p]),
     "dvg_lr_schedule_tick": (_i, [_i, _i, _i, _i, _d, _d, _p, _p, _p]),
     "dvg_adam_step_scheduled": (_i, [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p, _p, _p, _p, _p]),
+    "dvg_optim_step": (_i, [_i, _p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p, _i, _p, _p, _p, _p, _p]),
     "dvg_val_accumulate": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "dvg_frame_losses_blocks": (_i, [_l]),
     "dvg_frame_losses": (_i, [_p, _p, _p, _p, _l, _i, _i, _p, _p, _p]),

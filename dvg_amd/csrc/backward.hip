@@ -674,6 +674,131 @@ __global__ void adam_step_scheduled_kernel(float* __restrict__ p, const float* _
         adam_sweep<false>(p, g, m, v, n, c, 1.f);
 }
 
+// ------------------------------------------------------------------------------------
+// dvg_optim_step: the update rule train.py's --optimizer picks, with weight decay chosen per 16-byte piece (--weight_decay).
+//   ADAM     torch.optim.Adam      adam_element with the piece's decay as its L2 term
+//   ADAMW    torch.optim.AdamW     p *= 1 - lr wd, then adam_element on the bare gradient
+//   SGD      torch.optim.SGD       g' = g + wd p;  buf = a buf + g';  p -= lr (nesterov ? g' + a buf : buf)     (a = momentum)
+//   RMSPROP  torch.optim.RMSprop   g' = g + wd p;  sq = a sq + (1-a) g'^2;  d = g' / (sqrt(sq) + eps);
+//                                  b > 0: buf = b buf + d, p -= lr buf;  else p -= lr d        (a = alpha, b = momentum)
+// The decay of a piece is a SELECT between the launch's value and 0 into a register, never a product with a literal 0
+// (winograd.hip's note on packed FMAs with an inline-constant 0 multiplier); for ADAMW the L2 term of adam_element is
+// the kernel argument `wd_l2`, which the host passes as 0 - a run-time value as well.
+// ------------------------------------------------------------------------------------
+enum { OPTIM_ADAM = 0, OPTIM_ADAMW = 1, OPTIM_SGD = 2, OPTIM_RMSPROP = 3, OPTIM_RULES = 4 };
+
+struct OptimCoef {
+    AdamCoef adam;        // ADAM, ADAMW
+    float lr, a, b, eps;  // SGD, RMSPROP: the rate of the launch rounded to fp32 once, and the rule's constants
+    float wd_l2, keep;    // the L2 decay of a piece that decays; ADAMW: 1 - lr wd
+    int nesterov;
+};
+
+// One element under rule RULE; wd / keep: what the element's piece decays by (0 / 1: not at all).
+template <int RULE, typename V, typename I>
+__device__ __forceinline__ void optim_element(V& p, float g, V& m, V& v, const OptimCoef& c, const AdamCoef& ca, float wd,
+                                              float keep, I e) {
+    if (RULE == OPTIM_ADAM) {
+        adam_element(p, g, m, v, ca, e);
+    } else if (RULE == OPTIM_ADAMW) {
+        p[e] *= keep;
+        adam_element(p, g, m, v, ca, e);
+    } else if (RULE == OPTIM_SGD) {
+        // every multiply-add of the two rules written here is an fmaf and nothing else may be contracted: the bits do not depend
+        // on what the optimiser makes of a form of the kernel (the SCALED sweep once had wd * p packed with g * scale, unfused)
+#pragma clang fp contract(off)
+        float gg = fmaf(wd, p[e], g);
+        if (c.a != 0.f) {
+            const float buf = fmaf(c.a, m[e], gg);
+            m[e] = buf;
+            gg = c.nesterov ? fmaf(c.a, buf, gg) : buf;
+        }
+        p[e] = fmaf(-c.lr, gg, p[e]);
+    } else {
+#pragma clang fp contract(off)
+        const float gg = fmaf(wd, p[e], g);
+        const float sq = fmaf(c.a, v[e], (1.f - c.a) * gg * gg);
+        v[e] = sq;
+        const float d = gg / (sqrtf(sq) + c.eps);
+        if (c.b > 0.f) {
+            const float buf = fmaf(c.b, m[e], d);
+            m[e] = buf;
+            p[e] = fmaf(-c.lr, buf, p[e]);
+        } else {
+            p[e] = fmaf(-c.lr, d, p[e]);
+        }
+    }
+}
+
+// adam_sweep's loop and tail with the rule's element and one mask byte per piece (NULL: every piece decays).  A buffer the
+// rule does not use is neither read nor written: v under SGD, m under SGD / RMSPROP without momentum.
+template <int RULE, bool SCALED>
+__device__ __forceinline__ void optim_sweep(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                            float* __restrict__ v, long n, const OptimCoef& c,
+                                            const unsigned char* __restrict__ mask, float scale) {
+    const bool adam = RULE == OPTIM_ADAM || RULE == OPTIM_ADAMW;
+    const bool use_m = adam || (RULE == OPTIM_SGD ? c.a != 0.f : c.b > 0.f), use_v = RULE != OPTIM_SGD;
+    const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    const long n4 = n >> 2;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const bool decays = mask == nullptr || mask[i] != 0;
+        const float wd = decays ? c.wd_l2 : 0.f, keep = decays ? c.keep : 1.f;
+        AdamCoef ca = c.adam;
+        ca.wd = wd;
+        f32x4 pv = reinterpret_cast<f32x4*>(p)[i];
+        f32x4 mv = use_m ? reinterpret_cast<f32x4*>(m)[i] : z, vv = use_v ? reinterpret_cast<f32x4*>(v)[i] : z;
+        const f32x4 gv = reinterpret_cast<const f32x4*>(g)[i];
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            optim_element<RULE>(pv, SCALED ? gg_mul_rn(gv[e], scale) : gv[e], mv, vv, c, ca, wd, keep, e);
+        reinterpret_cast<f32x4*>(p)[i] = pv;
+        if (use_m) reinterpret_cast<f32x4*>(m)[i] = mv;
+        if (use_v) reinterpret_cast<f32x4*>(v)[i] = vv;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {   // tail: piece n4
+        const long i = (n4 << 2) + threadIdx.x;
+        const bool decays = mask == nullptr || mask[n4] != 0;
+        const float wd = decays ? c.wd_l2 : 0.f, keep = decays ? c.keep : 1.f;
+        AdamCoef ca = c.adam;
+        ca.wd = wd;
+        // a buffer the rule does not use may be NULL: its element is then never named (optim_element's branches are uniform)
+        optim_element<RULE>(p, SCALED ? gg_mul_rn(g[i], scale) : g[i], m, v, c, ca, wd, keep, i);
+    }
+}
+
+// Guard, skip counter and schedule as adam_step_scheduled_kernel has them, each optional here: stat != NULL (with skips_dev) is the
+// guarded form, lr_scale_dev != NULL the scheduled one.  Without either every operand is the one adam_step_kernel has.
+template <int RULE>
+__global__ void optim_step_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
+                                  long n, float lr, float a, float b, float eps, float wd_l2, float wd_decoupled, int nesterov,
+                                  const unsigned char* __restrict__ mask, const int* __restrict__ step_dev, int step_host,
+                                  const float* __restrict__ stat, int* __restrict__ skips_dev,
+                                  const float* __restrict__ lr_scale_dev) {
+    if (stat != nullptr && stat[2] != 0.f) {   // uniform over the grid; this launch does not read *skips_dev
+        if (blockIdx.x == 0 && threadIdx.x == 0) *skips_dev += 1;
+        return;
+    }
+    const double rate = lr_scale_dev != nullptr ? (double)lr * (double)*lr_scale_dev : (double)lr;
+    OptimCoef c;
+    if (RULE == OPTIM_ADAM || RULE == OPTIM_ADAMW) {
+        const int t = (step_dev ? *step_dev : step_host) - (stat != nullptr ? *skips_dev : 0);
+        c.adam = adam_coef(rate, a, b, eps, wd_l2, t);
+    } else {
+        c.adam = AdamCoef{a, b, eps, wd_l2, 0.f, 0.f};
+    }
+    c.lr = (float)rate;
+    c.a = a;
+    c.b = b;
+    c.eps = eps;
+    c.wd_l2 = wd_l2;
+    c.keep = (float)(1.0 - rate * (double)wd_decoupled);
+    c.nesterov = nesterov;
+    if (stat != nullptr)
+        optim_sweep<RULE, true>(p, g, m, v, n, c, mask, stat[1]);
+    else
+        optim_sweep<RULE, false>(p, g, m, v, n, c, mask, 1.f);
+}
+
 // zero_grad of one or several ADJACENT parameter groups of the gradient arena as one fill, and the device-side step counts
 // of up to four of them advanced by one in the same launch (a captured iteration replays with fresh bias corrections; the
 // increment used to be a one-element torch add_ per optimiser step).
@@ -959,6 +1084,36 @@ extern "C" int dvg_adam_step_scheduled(float* param, const float* grad, float* e
                        param, grad, exp_avg, exp_avg_sq, n, lr, beta1, beta2, eps, weight_decay, step_dev, step, stat, skips_dev,
                        lr_scale_dev);
     return check_launch("dvg_adam_step_scheduled");
+}
+
+// One step of rule 0 ADAM | 1 ADAMW | 2 SGD | 3 RMSPROP (optim_step_kernel) with the decay masked per 16-byte piece; guard,
+// skip counter and schedule as dvg_adam_step_scheduled has them, each optional.
+extern "C" int dvg_optim_step(int rule, float* param, const float* grad, float* m, float* v, long n, float lr, float a, float b,
+                              float eps, float weight_decay, int flags, const uint8_t* decay_mask, int step, const int* step_dev,
+                              const float* stat, int* skips_dev, const float* lr_scale_dev, void* stream) {
+    DVG_REQUIRE(rule >= 0 && rule < OPTIM_RULES, DVG_ERR_SHAPE, "dvg_optim_step: rule=%d (0 adam, 1 adamw, 2 sgd, 3 rmsprop)", rule);
+    DVG_REQUIRE(param && grad && m && (v || rule == OPTIM_SGD), DVG_ERR_NULL, "dvg_optim_step: NULL pointer");
+    DVG_REQUIRE((stat == nullptr) == (skips_dev == nullptr), DVG_ERR_NULL,
+                "dvg_optim_step: stat and skips_dev go together (both NULL: unguarded)");
+    DVG_REQUIRE(n > 0 && (step >= 1 || step_dev != nullptr), DVG_ERR_SHAPE, "dvg_optim_step: n=%ld step=%d", n, step);
+    DVG_REQUIRE(aligned16(param) && aligned16(grad) && aligned16(m) && aligned16(v), DVG_ERR_ALIGN,
+                "dvg_optim_step: buffers must be 16-byte aligned");
+    DVG_REQUIRE(aligned_to<4>(stat) && aligned_to<4>(skips_dev) && aligned_to<4>(step_dev) && aligned_to<4>(lr_scale_dev),
+                DVG_ERR_ALIGN, "dvg_optim_step: stat, skips_dev, step_dev and lr_scale_dev must be 4-byte aligned");
+    // the L2 term of adam_element and the decoupled decay are two kernel arguments: ADAMW runs adam_element with a run-time 0
+    const float wd_l2 = rule == OPTIM_ADAMW ? 0.f : weight_decay, wd_decoupled = rule == OPTIM_ADAMW ? weight_decay : 0.f;
+    const dim3 grid(grid_for((n + 3) / 4, 256, 4096)), block(256);
+#define DVG_OPTIM_LAUNCH(RULE)                                                                                                 \
+    hipLaunchKernelGGL(optim_step_kernel<RULE>, grid, block, 0, (hipStream_t)stream, param, grad, m, v, n, lr, a, b, eps, wd_l2, \
+                       wd_decoupled, flags & 1, decay_mask, step_dev, step, stat, skips_dev, lr_scale_dev)
+    switch (rule) {
+        case OPTIM_ADAM: DVG_OPTIM_LAUNCH(OPTIM_ADAM); break;
+        case OPTIM_ADAMW: DVG_OPTIM_LAUNCH(OPTIM_ADAMW); break;
+        case OPTIM_SGD: DVG_OPTIM_LAUNCH(OPTIM_SGD); break;
+        default: DVG_OPTIM_LAUNCH(OPTIM_RMSPROP); break;
+    }
+#undef DVG_OPTIM_LAUNCH
+    return check_launch("dvg_optim_step");
 }
 
 // g[0:n] = 0 and *t_k += 1 for the non-NULL step counters (see zero_tick_kernel): optimizer.zero_grad() of adjacent groups of

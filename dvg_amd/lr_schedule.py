@@ -199,9 +199,10 @@ def schedule_options(opt):
 
 
 def base_rate(opt) -> float:
-    """The `lr` train.py builds its four optimisers with: --lr under a schedule, else the reference's literal 0.002 (--lr stays
-    unused, so no existing command line changes its result)."""
-    return REFERENCE_LR if getattr(opt, "lr_schedule", None) is None else float(opt.lr)
+    """The `lr` train.py builds its four optimisers with: --lr under a schedule or with an --optimizer other than adam, else the
+    reference's literal 0.002 (--lr stays unused, so no existing command line changes its result)."""
+    plain = getattr(opt, "lr_schedule", None) is None and getattr(opt, "optimizer", "adam") == "adam"
+    return REFERENCE_LR if plain else float(opt.lr)
 
 
 def make_schedule(opt, device, optimizers=()):

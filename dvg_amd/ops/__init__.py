@@ -42,6 +42,7 @@ from .gp import (  # noqa: F401
 from .backward import (  # noqa: F401
     _LOSS_W, frame_losses, FRAME_LOSS_KINDS, frame_losses_ext, frame_ssim_loss, mse_sum_grad, conv_wgrad_partial, conv_wgrad_partial_multi, winograd_wgrad_ok,
     winograd_wgrad_partial_multi, wgrad_finish, k4_to_w3, conv_wgrad, wgrad_thin, act_bwd, upsample2x_bwd, adam_step, adam_step_guarded,
+    optim_step, ADAM, ADAMW, SGD, RMSPROP, NESTEROV,
 )
 from .guard import grad_sumsq_blocks, grad_sumsq, grad_guard_finish  # noqa: F401
 from .ema import ema_update_blocks, ema_update  # noqa: F401

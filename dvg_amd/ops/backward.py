@@ -358,3 +358,37 @@ def adam_step(p, g, m, v, lr, beta1, beta2, eps, weight_decay, step, step_dev, s
 
 
 adam_step_guarded = adam_step    # the name tools and tests call the guarded form by
+
+ADAM, ADAMW, SGD, RMSPROP = 0, 1, 2, 3      # dvg_optim_step's rules (include/dvg_hip.h)
+NESTEROV = 1                                # its flags
+
+
+def optim_step(rule, p, g, m, v, lr, a, b, eps, weight_decay, flags, decay_mask, step, step_dev, stat=None, skips_dev=None,
+               lr_scale=None) -> None:
+    """One step of `rule` (ADAM | ADAMW | SGD | RMSPROP: torch.optim's class of that name) over the buffers p, g, m, v -
+    dvg_optim_step; a, b: betas | (momentum, -) | (alpha, momentum); v may be None for SGD.  `decay_mask`: None, or one uint8 per
+    16-byte piece of p, 0 = this piece does not decay.  step / step_dev / stat / skips_dev / lr_scale as adam_step, each optional
+    in the one entry point."""
+    name = "optim_step"
+    if rule not in (ADAM, ADAMW, SGD, RMSPROP):
+        raise RuntimeError(f"{name}: rule {rule!r}")
+    for which, t in (("p", p), ("g", g), ("m", m), ("v", v)):
+        if t is None and which == "v" and rule == SGD:
+            continue
+        _dev_f32(t, f"{name}.{which}")
+        if not t.is_contiguous() or t.numel() != p.numel() or t.device != p.device:
+            raise RuntimeError(f"{name}: {which} must be contiguous, on p's device and of p's size")
+    guarded = stat is not None or skips_dev is not None
+    stat_ok = not guarded or (stat is not None and skips_dev is not None and stat.dtype == torch.float32 and stat.numel() == 4
+                              and stat.device == p.device and stat.is_contiguous())
+    ints = [t for t in (step_dev, skips_dev) if t is not None]
+    if not stat_ok or any(t.dtype != torch.int32 or t.numel() != 1 or t.device != p.device for t in ints):
+        raise RuntimeError(f"{name}: 4 fp32 stat values and one-element int32 counters on p's device expected")
+    if lr_scale is not None and (lr_scale.dtype != torch.float32 or lr_scale.numel() != 1 or lr_scale.device != p.device):
+        raise RuntimeError(f"{name}: lr_scale must be one fp32 value on p's device")
+    if decay_mask is not None and (decay_mask.dtype != torch.uint8 or decay_mask.numel() != (p.numel() + 3) // 4
+                                   or decay_mask.device != p.device or not decay_mask.is_contiguous()):
+        raise RuntimeError(f"{name}: decay_mask must be {(p.numel() + 3) // 4} contiguous uint8 values on p's device")
+    check(lib().dvg_optim_step(int(rule), _p(p), _p(g), _p(m), _p(v), p.numel(), float(lr), float(a), float(b), float(eps),
+                               float(weight_decay), int(flags), _p(decay_mask), int(step), _p(step_dev), _p(stat), _p(skips_dev),
+                               _p(lr_scale), _stream()), name)

@@ -40,8 +40,9 @@ def rank_path(path: str, rank: int) -> str:
 
 
 # fields a fingerprint carries only when they differ from the value given here: a state without the field was written by a run
-# with that value (every state from before --predictor is an `lstm` state), and such a run writes the fingerprint it always did
-ABSENT_MEANS = {"predictor": "lstm"}
+# with that value (every state from before --predictor is an `lstm` state, every one from before --optimizer was honoured an
+# `adam` state), and such a run writes the fingerprint it always did
+ABSENT_MEANS = {"predictor": "lstm", "optimizer": "adam"}
 
 
 def option_fingerprint(opt) -> dict:
@@ -253,6 +254,14 @@ def restore(tr, sd, train_gen=None, test_gen=None, path="<state>") -> int:
     """Write a capture() into `tr` THROUGH the existing arena views: no parameter, gradient or moment changes its address.
     Returns the number of the next epoch.  A mismatch of the fingerprint ends the program (SystemExit naming the field)."""
     check_fingerprint(sd["fingerprint"], fingerprint(tr), path)
+    for name, o in named_optimizers(tr):    # the hyper-parameters are state, as the rates are: a command line cannot change them
+        bad = o.hyper_mismatch(sd["optimizers"][name])
+        if bad is None and name != "gp" and getattr(tr.opt, "optimizer", "adam") != "adam":
+            # under another rule --lr is the base rate; only the GP optimiser's is moved by its milestones
+            a, b = sd["optimizers"][name]["param_groups"][0]["lr"], o.param_groups[0]["lr"]
+            bad = ("lr", a, b) if float(a) != float(b) else None
+        if bad is not None:
+            refuse(path, f"optimizers.{name}.{bad[0]} is {bad[1]!r} in the file and {bad[2]!r} in this run")
     a, saved = tr.arena, sd["arena"]
     for name in ("p", "m", "v"):
         if saved[name].numel() != getattr(a, name).numel():

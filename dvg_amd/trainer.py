@@ -11,7 +11,7 @@ import torch.nn as nn
 from . import _derived, ema as weight_ema, frame_loss, fused, lr_schedule, parallel, train_state, validate, viz
 from .models import lstm as lstm_models
 from .models.gp_models import GaussianLikelihood, GPRegressionLayer1, VariationalELBO
-from .optim import FlatArena, FusedAdam, guarded_step, make_guard, zero_grads
+from .optim import FlatArena, OptimizerReport, guarded_step, make_guard, make_optimizer, optimizer_options, zero_grads
 from .rollout import frames_as_batch, gp_input
 from .utils import init_weights
 
@@ -77,15 +77,19 @@ class Trainer:
         # optim.Adam(lr=0.002) x4 (train.py:95-104) as one fused HIP launch per parameter group.  All groups live in ONE
         # flat arena in the order [GP | likelihood | LSTM | decoder | encoder]: parameters, gradients (p.grad are views)
         # and both moments; the data-parallel all-reduce works on ranges of arena.g in place.
-        Adam = FusedAdam   # HIP only, like the models themselves: no CPU fallback on the product path
+        # --optimizer / --weight_decay: another rule (dvg_optim_step) and the decay masks; None = FusedAdam as ever.  HIP only,
+        # like the models themselves: no CPU fallback on the product path
+        spec = optimizer_options(opt)
         allp = [p for m in self.modules for p in m.parameters()]
         self.arena = FlatArena(FlatArena.size_for(allp), device)
-        lr = lr_schedule.base_rate(opt)   # 0.002, as the reference; --lr under --lr_schedule
-        self.optimizer = Adam([{'params': self.gp_layer.parameters()},
-                               {'params': self.likelihood.parameters()}], lr=lr, arena=self.arena)
-        self.frame_predictor_optimizer = Adam(self.frame_predictor.parameters(), lr=lr, arena=self.arena)
-        self.decoder_optimizer = Adam(self.decoder.parameters(), lr=lr, arena=self.arena)
-        self.encoder_optimizer = Adam(self.encoder.parameters(), lr=lr, arena=self.arena)
+        lr = lr_schedule.base_rate(opt)   # 0.002, as the reference; --lr under --lr_schedule or a rule other than adam
+        self.optimizer = make_optimizer(spec, "gp", [{'params': self.gp_layer.parameters()},
+                                                     {'params': self.likelihood.parameters()}], lr, self.arena)
+        self.frame_predictor_optimizer = make_optimizer(spec, "frame_predictor", self.frame_predictor.parameters(), lr, self.arena)
+        self.decoder_optimizer = make_optimizer(spec, "decoder", self.decoder.parameters(), lr, self.arena)
+        self.encoder_optimizer = make_optimizer(spec, "encoder", self.encoder.parameters(), lr, self.arena)
+        # the epoch line of the new flags; None = nothing exists
+        self.optim_report = spec and OptimizerReport(spec, self.optimizers(), self.arena.p.numel())
         self.scheduler = torch.optim.lr_scheduler.MultiStepLR(self.optimizer, milestones=[3, 5], gamma=0.1)
         # num_data = the GLOBAL batch (train.py:112 passes opt.batch_size): each rank's loss is ll_r/B_local - KL/num_data and
         # the ranks are averaged, which gives the reference's ll/B - KL/B at the same global batch for any number of ranks

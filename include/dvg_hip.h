@@ -686,7 +686,6 @@ int dvg_gp_elbo_bwd(const float* mean, const float* var, const float* kl, const 
 /* (N,C,H,W) contiguous -> NHWC and back (skip tensors handed to / taken from callers that insist on contiguous NCHW). */
 int dvg_nchw_to_nhwc(const float* x, float* y, int N, int C, int H, int W, void* stream);
 int dvg_nhwc_to_nchw(const float* x, float* y, int N, int C, int H, int W, void* stream);
-
 /* ------------------------------------------------------------------ *
  * Debug hooks (tools/diag_*.py).  Not part of the product path: they hand the next launches of one kernel family a device
  * buffer that every workgroup fills with clock64()/wall_clock64() phase stamps.  buf == NULL (the default) disables stamping;
@@ -717,7 +716,6 @@ int dvg_gp_trigger_replay(const float* values, int n, const float* ctx0, int win
 int dvg_gp_trigger_select(const int* flag, const float* sample_db, const float* h_pred, float* vec, int D, int B, int n_state,
                           long state_elems, const float* const* state_old, const float* const* state_new,
                           float* const* state_out, void* stream);
-
 /* ---- losses of the step closures and their gradients in one pass (train.py:188,223,227-239; ABI 8) ---------------------------
  * dvg_frame_losses: pred [S][K][n] - per time step the K decoder calls in the reference's call order (x_pred, x_target_pred,
  * x_pred_gp, :227-232) -, target [S][n] (the step's ground-truth frame): sums[k] = sum over steps and elements of
@@ -729,7 +727,6 @@ int dvg_frame_losses_blocks(long elems);
 int dvg_frame_losses(const float* pred, const float* target, float* sums, float* dpred, long n, int S, int K, const float* w,
                      float* partial, void* stream);
 int dvg_mse_sum_grad(const float* a, const float* b, float* sum, float* da, long n, float scale, void* stream);
-
 /* Frame terms with another pixel penalty and / or the gradient-difference loss (train.py --frame_loss / --gdl_weight here;
  * docs/DESIGN_NOTES_frame_loss.md; the reference's train.py:227-239 is nn.MSELoss: dvg_frame_losses).  pred [S][K][planes][H][W],
  * target [S][planes][H][W], d = pred - target: sums [2][K] = pix_k = sum rho(d), rho = d^2 | |d| | sqrt(d^2 + eps^2) for kind 0 | 1 | 2,
@@ -748,12 +745,10 @@ int dvg_frame_losses_ext(const float* pred, const float* target, float* sums, fl
 int dvg_frame_ssim_loss_blocks(int S, long planes, int H, int W);
 int dvg_frame_ssim_loss(const float* pred, const float* target, float* sums, float* dpred, int S, int K, long planes, int H, int W,
                         const float* w_ssim, int accumulate, double* partial, void* stream);
-
 /* optimizer.zero_grad() of adjacent parameter groups of the gradient arena as ONE fill (train.py:201-203 zeroes three modules),
  * and the device-side Adam step counts t0..t3 (NULL: none) advanced by one in the same launch (dvg_adam_step's step_dev): a
  * captured iteration needs no one-element increment launch per optimiser step.  ABI 8.                                   */
 int dvg_zero_tick(float* g, long n, int* t0, int* t1, int* t2, int* t3, void* stream);
-
 /* Gradient guard (train.py --clip_grad_norm / --skip_nonfinite here; the reference's optimizer.step() calls train.py:171,196,245
  * apply whatever backward() left); semantics in docs/DESIGN_NOTES_gradguard.md.  dvg_grad_sumsq: partials[b] = fp64 sum of exact
  * squares of floats [16384 b, 16384 (b + 1)) of g[0:n], fixed order, no atomics; n % 4 == 0, g 16-byte aligned;
@@ -775,7 +770,13 @@ int dvg_lr_schedule_tick(int kind, int W, int N, int K, double R, double G, int*
 int dvg_adam_step_scheduled(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1,
                             float beta2, float eps, float weight_decay, int step, const int* step_dev, const float* stat,
                             int* skips_dev, const float* lr_scale_dev, void* stream);
-
+/* train.py --optimizer / --weight_decay (docs/DESIGN_NOTES_optimizers.md; the reference's train.py:95-104 builds optim.Adam whatever --optimizer says).  One launch over a flat range,
+ * torch's default non-foreach, non-amsgrad, non-centered arithmetic: rule 0 torch.optim.Adam(lr, (a, b), eps, weight_decay).step(), dvg_adam_step's bits without a mask; 1 torch.optim.AdamW(same).step():
+ * p *= 1 - lr wd, then Adam on the bare gradient; 2 torch.optim.SGD(lr, momentum=a, weight_decay, nesterov=flags & 1).step(): m the momentum buffer, v untouched, may be NULL; 3 torch.optim.RMSprop(lr,
+ * alpha=a, eps, weight_decay, momentum=b).step(): v square_avg, m the momentum buffer (b > 0).  decay_mask: NULL, or (n + 3) / 4 bytes, one per 16-byte piece of param: 0 = weight decay 0 there.  step,
+ * step_dev as dvg_adam_step; stat + skips_dev (both or neither) and lr_scale_dev (or NULL) as dvg_adam_step_scheduled.  param, grad, m, v 16-byte aligned.  Within ABI 9. */
+int dvg_optim_step(int rule, float* param, const float* grad, float* m, float* v, long n, float lr, float a, float b, float eps, float weight_decay, int flags,
+                   const uint8_t* decay_mask, int step, const int* step_dev, const float* stat, int* skips_dev, const float* lr_scale_dev, void* stream);
 /* Exponential moving average of a flat parameter range (train.py --ema_decay here; docs/DESIGN_NOTES_ema.md).  No reference
  * counterpart: it follows the optimiser steps of the reference's train.py:242-245.  ema = fmaf(w, param - ema, ema), w = (float)(1 -
  * min(decay, (1 + k) / (10 + k))) formed in fp64 in the kernel from k = *updates_dev, the updates already applied (read, never
@@ -783,7 +784,6 @@ int dvg_adam_step_scheduled(float* param, const float* grad, float* exp_avg, flo
  * fp64, fixed order; dvg_ema_update_blocks(n) pairs.  n % 4 == 0, 16-byte aligned, ema != param, decay in [0, 1).  Within ABI 9. */
 int dvg_ema_update_blocks(long n);
 int dvg_ema_update(float* ema, const float* param, long n, double decay, const int* updates_dev, double* partials, void* stream);
-
 /* The reduction of a validation pass (train.py --val_every here; docs/DESIGN_NOTES_validation.md).  No reference counterpart: its
  * train.py scores nothing.  ssim / psnr / mse: (B, S, T) fp32, the layout make_gifs fills (batch row, sample, predicted step).
  * best[b] (int[B], may be NULL) = the sample with the largest fp64 sum over t, from 0.0 with t ascending, of ssim[b, s, t]: a NaN sum

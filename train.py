@@ -3,8 +3,8 @@
 
 Same flags (train.py:17-46) and the same three step closures (`train_model` :200-248,
 `train_frame_predictor` :175-198, `train_GP_Frame_predictor` :146-172), loss weights (:239), optimisers
-(:95-106, lr hard-coded 0.002 like the reference; `--lr/--beta1/--optimizer/--z_dim/--name` stay accepted
-and unused - `--lr` except under `--lr_schedule`), scheduler-before-epoch order (:347), log line (:368) and checkpoint dict (:380-388).
+(:95-106, lr hard-coded 0.002 like the reference; `--lr/--beta1/--z_dim/--name` stay accepted
+and unused - `--lr` except under `--lr_schedule` or an `--optimizer` other than adam), scheduler-before-epoch order (:347), log line (:368) and checkpoint dict (:380-388).
 This file is the command line: flags, `options`, the epoch loop.  The closures and the iteration are `Trainer`, dvg_amd/trainer.py.
 
 Consciously fixed (each was unrunnable in the reference — SURVEY.md §5 quirks):
@@ -40,6 +40,9 @@ logs them to `val_log.jsonl` and keeps `model_best.pth` (dvg_amd/validate.py, do
 warm-up, then constant | linear | cosine | step; one launch per iteration (dvg_amd/lr_schedule.py, docs/DESIGN_NOTES_lr_schedule.md).
 `--frame_loss l1|charbonnier`, `--gdl_weight G`, `--ssim_weight W`: another pixel penalty / the gradient-difference loss / 1 - SSIM in the frame terms
 (dvg_amd/frame_loss.py).
+`--optimizer adam|adamw|sgd|rmsprop`, `--weight_decay W`, `--momentum M`, `--nesterov`, `--rmsprop_alpha A`: the update rule of all four
+optimisers (the reference accepts --optimizer and builds Adam whatever it says, :95-104) and a decay of the weight matrices of the
+encoder, decoder and frame predictor, one dvg_optim_step launch per group (dvg_amd/optim.py, docs/DESIGN_NOTES_optimizers.md).
 """
 import argparse
 import os
@@ -64,7 +67,7 @@ from dvg_amd.trainer import Trainer  # noqa: E402,F401
 
 def build_parser():
     p = argparse.ArgumentParser()
-    p.add_argument('--lr', default=0.002, type=float, help='unused, as in the reference; under --lr_schedule: the base rate of all four optimisers')
+    p.add_argument('--lr', default=0.002, type=float, help='unused, as in the reference; under --lr_schedule or an --optimizer other than adam: the base rate of all four optimisers')
     p.add_argument('--beta1', default=0.9, type=float)
     p.add_argument('--batch_size', default=50, type=int, help='GLOBAL batch size')
     p.add_argument('--log_dir', default='logs')
@@ -77,7 +80,6 @@ def build_parser():
     p.add_argument('--data_root', default='path/to/data/',
                    help='kth | bair | ucf: the root of the processed dataset tree; smmnist: a directory holding the MNIST IDX '
                         'image files (<root>/MNIST/raw, <root>/raw or <root>, raw or .gz)')
-    p.add_argument('--optimizer', default='adam')
     p.add_argument('--niter', type=int, default=601)
     p.add_argument('--seed', default=1, type=int)
     p.add_argument('--epoch_size', type=int, default=300)
@@ -129,6 +131,7 @@ def options(argv=None, *, rank=0, world=1, local_batch=None):
     opt.ft = not opt.no_ft
     opt.rank, opt.world = rank, world
     opt.local_batch = parallel.shard_batch(opt.batch_size, world) if local_batch is None else local_batch
+    optim.optimizer_options(opt)   # --optimizer and its companions: refused here, before anything is built
     return opt
 
 
@@ -182,7 +185,7 @@ def main(argv=None):
             print('[%02d] mse loss: %.5f (%d) %.5f' % (epoch, epoch_mse / opt.epoch_size,
                                                        epoch * opt.epoch_size * opt.batch_size, indices))
             print('     train frames/s: %.1f' % fps)
-        for part in (tr.guard, tr.ema, tr.lr_schedule, tr.frame_terms):   # one read of each one's device counters: per epoch, outside the iterations
+        for part in (tr.guard, tr.ema, tr.lr_schedule, tr.frame_terms, tr.optim_report):   # one read of each one's device counters: per epoch, outside the iterations
             line = part is not None and part.epoch_line()   # every rank reads its own (the same bits everywhere; frame loss: its shard's means), rank 0 prints
             line and rank == 0 and print(line)
         if epoch % opt.save_every == 0:
