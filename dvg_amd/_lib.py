@@ -61,6 +61,8 @@ SIGNATURES = {
     "dvg_clip_gather_aug_u8": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _p]),
     "dvg_mnist_scale_u8": (_i, [_p, _p, _i, _i, _i, _p, _p, _p]),
     "dvg_moving_mnist_compose_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
+    "dvg_resample_u8_band": (_i, [_p, _i, _i, _i, _i, _i, _i, _p]),
+    "dvg_resample_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p]),
     "dvg_eval_frames": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
     "dvg_eval_frames_finn": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
     "dvg_pairwise_frame_mse": (_i, [_p, _p, _i, _l, _i, _l, _i, _p]),

@@ -229,11 +229,12 @@ def make_batch_generator(opt, seq_len, seed, device=None, train=True):
     the wanted split is read, uploaded and scaled to 32x32 ONCE, before this returns (dvg_mnist_scale_u8); a batch is then the
     reference's draws (mnist.MovingMnistSampler) and one dvg_moving_mnist_compose_u8 launch.  Without them, or with
     --synthetic_data, it is the reference's trajectory generator over seeded in-repo sprites, and says so.
-    kth | bair | ucf: the `train` / test split under `--data_root` is indexed and decoded once into a device frame pool
+    kth | bair | ucf | frames (a folder of clips: datasets.frames_index): the `train` / test split under `--data_root` is indexed and decoded once into a device frame pool
     (dvg_amd/datasets.py) BEFORE this returns - a missing tree is a SystemExit here, on the caller's thread; the host half
     then draws `local_batch` clips like the reference's loaders, the callable uploads the B pool indices and gathers the
     clips on the current stream (dvg_clip_gather_u8).  With --synthetic_data those names train on random textured clips of
-    their shape instead.  `opt.augment` (train.py --augment; docs/DESIGN_NOTES_augment.md) applies to the TRAIN split of these
+    their shape instead.  `opt.resize` / `opt.resize_fit` (--resize; docs/DESIGN_NOTES_frames.md): decoded frames that are not
+    image_width x image_width are scaled into the pool by dvg_resample_u8, bit-equal to Pillow's Image.resize.  `opt.augment` (train.py --augment; docs/DESIGN_NOTES_augment.md) applies to the TRAIN split of these
     three only: the host also draws per-clip flip / reverse / shift / jitter parameters (datasets.ClipAugmenter) and the gather
     is dvg_clip_gather_aug_u8; `train=False` ignores it.
     The result is a BatchStream: `position()` / `restore()` report and set where the stream stands (train.py --resume)."""
@@ -253,7 +254,8 @@ def make_batch_generator(opt, seq_len, seed, device=None, train=True):
 def _clip_batches(opt, seq_len, seed, device, train):
     index = datasets.open_index(opt.dataset, opt.data_root, train, opt.image_width)
     sampler = datasets.make_sampler(index, seq_len, seed)
-    pool = datasets.shared_pool(index, opt.data_root, opt.image_width, device, getattr(opt, 'data_threads', 5))
+    pool = datasets.shared_pool(index, opt.data_root, opt.image_width, device, getattr(opt, 'data_threads', 5),
+                                datasets.resize_spec(opt))       # --resize: frames of another size are scaled into the pool
     if opt.channels != pool.shape[3] and not (opt.channels == 1 and pool.shape[3] == 3):
         raise SystemExit(f"dataset: --channels {opt.channels} from {opt.dataset} frames of {pool.shape[3]} channel(s) under "
                          f"{opt.data_root!r}")
@@ -293,7 +295,7 @@ def _mnist_batches(opt, seq_len, seed, device, path):
 def _synthetic_batches(opt, seq_len, seed, device, mnist_tried=None):
     def first():
         if opt.dataset != 'smmnist' and not getattr(opt, 'synthetic_data', False):
-            raise SystemExit(f"train.py: no loader for --dataset {opt.dataset} (kth | bair | ucf read --data_root). "
+            raise SystemExit(f"train.py: no loader for --dataset {opt.dataset} (kth | bair | ucf | frames read --data_root). "
                              "Pass --synthetic_data to train on synthetic clips of that dataset's shape.")
         if opt.rank == 0:
             what = ("Moving-MNIST trajectories over synthetic sprites (not MNIST digits)" if opt.dataset == 'smmnist'

@@ -9,25 +9,39 @@ into normalize_data's list of T x (B,C,H,W) float32 frames on the device.  Host 
           whatever it is given, so the UCF test split IS the train split - kept
     BAIR  <root>/processed_data/{train,test}/<d1>/<d2>/<i>.png, i = 0, 1, ... (bair.py:17-26,53)
 
+    frames  <root>/{train,test}/.../<clip>/<frame>.{png,jpg,jpeg}: every directory below a split that directly holds at least one
+          such file is one clip (nested freely); clips sorted by path, frames in natural order (frame2 before frame10).  Not a
+          format of the reference: a folder of clips as a camera or a frame dump leaves it, frames of ANY size - see `--resize`
+
+`--resize FILTER` (docs/DESIGN_NOTES_frames.md): a decoded frame that is not image_width x image_width is scaled as Pillow's
+`Image.resize` scales it - on the device while the pool is built (`ops.resample_u8`, dvg_resample_u8: bit-equal to Pillow), by
+Pillow itself for a host pool.  It applies to every dataset read here; without it a frame of another size is refused, as ever.
+
 Deviation: the reference lists the BAIR directories with os.listdir, whose order depends on the file system; here they are
 listed SORTED, so the ordered test walk and the train draws name the same directories on every machine.
 
-Out of scope: the converters and download scripts that make these trees, a cache of the decoded pool on disk, and datasets
+Out of scope: the download scripts and the Lua / ffmpeg / TFRecord converters that make the reference's trees (what they do
+for the model - scaling the frames - is `--resize`), video containers, a cache of the decoded pool on disk, and datasets
 larger than the device memory (the pool holds every indexed frame: BAIR at 64x64 is about 16 GB)."""
 from __future__ import annotations
 
+import argparse
 import json
 import os
 import random
+import re
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
 
+from . import resample
+
 KTH_CLASSES = ['boxing', 'handclapping', 'handwaving', 'jogging', 'running', 'walking']                      # kth.py:16-17
 UCF_CLASSES = ['BenchPress', 'BodyWeightSquats', 'CleanAndJerk', 'PullUps', 'PushUps', 'Shotput', 'TennisSwing', 'Lunges',
                'Fencing']                                                                                    # ucf.py:17-18
-REAL_DATASETS = ('kth', 'bair', 'ucf')
+REAL_DATASETS = ('kth', 'bair', 'ucf', 'frames')
+FRAME_EXTENSIONS = ('.png', '.jpg', '.jpeg')
 STAGING_BYTES = 256 << 20       # the pinned staging buffer of build_pool, at most
 MAX_DECODE_THREADS = 16
 
@@ -113,10 +127,33 @@ def bair_index(root, train, image_width=64):
     return idx
 
 
+def _natural(name):
+    """The sort key of a natural order: digit runs compare as numbers (frame2 before frame10)."""
+    return [(0, int(t), '') if t.isdigit() else (1, 0, t) for t in re.split(r'(\d+)', name) if t]
+
+
+def frames_index(root, train, image_width=64):
+    """A folder of clips: every directory below <root>/train (or /test) that directly holds at least one .png / .jpg / .jpeg file
+    is one clip, its frames in natural order; clips sorted by path.  Frames may have any size (`--resize`); no labels."""
+    split = 'train' if train else 'test'
+    base = _need(os.path.join(_need(root, "--data_root"), split), "directory")
+    idx = ClipIndex('frames', split)
+    for d, subdirs, names in os.walk(base):
+        subdirs.sort()                                      # clips sorted by path, on every file system
+        frames = sorted((f for f in names if f.lower().endswith(FRAME_EXTENSIONS)), key=lambda f: (_natural(f), f))
+        if frames:
+            idx._add([os.path.join(d, f) for f in frames], -1)
+    if not idx.sequences:
+        raise SystemExit(f"dataset: no directory with .png / .jpg / .jpeg frames under {base!r}")
+    order = sorted(range(len(idx.sequences)), key=lambda i: os.path.dirname(idx.sequences[i][0]))
+    idx.sequences = [idx.sequences[i] for i in order]
+    return idx
+
+
 def open_index(dataset, root, train, image_width=64):
     if dataset not in REAL_DATASETS:
-        raise SystemExit(f"dataset: no loader for {dataset!r} (kth | bair | ucf)")
-    return {'kth': kth_index, 'ucf': ucf_index, 'bair': bair_index}[dataset](root, train, image_width)
+        raise SystemExit(f"dataset: no loader for {dataset!r} (kth | bair | ucf | frames)")
+    return {'kth': kth_index, 'ucf': ucf_index, 'bair': bair_index, 'frames': frames_index}[dataset](root, train, image_width)
 
 
 class MetaSampler:
@@ -188,6 +225,45 @@ class BairSampler:
         self.np_rng.set_state(pos["np"])
 
 
+class FramesSampler:
+    """Clips of a `frames` tree.  Train: the clip is np.random.RandomState(seed).randint(n_clips), drawn again while the clip is
+    shorter than seq_len; the start frame randint(0, len - T + 1) from the same generator.  Test: an ordered walk over the clips
+    that are long enough, from frame 0, wrapping at the end (like BairSampler).  No label: -1."""
+
+    def __init__(self, index, seq_len, seed):
+        self.index, self.seq_len = index, seq_len
+        self.ordered = index.split == 'test'
+        self.np_rng = np.random.RandomState(seed)
+        self.bases, self.lengths = index.bases, index.lengths
+        self.long = np.nonzero(self.lengths >= seq_len)[0]      # the clips the ordered walk visits
+        self.d = 0
+        if not self.long.size:
+            raise SystemExit(f"dataset: no frames {index.split} clip has {seq_len} frames")
+
+    def draw(self):
+        if self.ordered:
+            s = int(self.long[self.d])
+            self.d = 0 if self.d == len(self.long) - 1 else self.d + 1
+            return int(self.bases[s]), -1
+        while True:                                             # skip clips that are too short
+            s = self.np_rng.randint(len(self.bases))
+            if self.lengths[s] >= self.seq_len:
+                break
+        st = self.np_rng.randint(0, int(self.lengths[s]) - self.seq_len + 1)
+        return int(self.bases[s]) + st, -1
+
+    def position(self):
+        """The next clip of the ordered walk and the state of the random one (data.BatchStream; train.py --resume)."""
+        return {"sampler": "FramesSampler", "ordered": self.ordered, "d": self.d, "np": self.np_rng.get_state()}
+
+    def restore(self, pos):
+        check_position(pos, "FramesSampler")
+        if bool(pos["ordered"]) != self.ordered or not 0 <= int(pos["d"]) < len(self.long):
+            raise SystemExit("data position: saved for another frames split or tree")
+        self.d = int(pos["d"])
+        self.np_rng.set_state(pos["np"])
+
+
 def check_position(pos, sampler):
     if not isinstance(pos, dict) or pos.get("sampler") != sampler:
         got = pos.get("sampler") if isinstance(pos, dict) else type(pos).__name__
@@ -195,7 +271,7 @@ def check_position(pos, sampler):
 
 
 def make_sampler(index, seq_len, seed):
-    return (BairSampler if index.dataset == 'bair' else MetaSampler)(index, seq_len, seed)
+    return {'bair': BairSampler, 'frames': FramesSampler}.get(index.dataset, MetaSampler)(index, seq_len, seed)
 
 
 # ---- --augment: per-clip augmentation parameters, drawn on the host, applied by ops.clip_gather_aug -----------------------------
@@ -244,9 +320,39 @@ def augment_spec(cfg):
 def add_arguments(p) -> None:
     """train.py's `--augment` option (as ema.add_arguments: the option lives with what it configures)."""
     p.add_argument('--augment', default='', metavar='LIST',   # docs/DESIGN_NOTES_augment.md
-                   help='kth | bair | ucf from --data_root, train split only: a comma list of hflip, reverse, shift=N (1..16 pixels, '
+                   help='kth | bair | ucf | frames from --data_root, train split only: a comma list of hflip, reverse, shift=N (1..16 pixels, '
                         'edge-replicated) and jitter=G (0 < G <= 0.5: contrast and brightness); parameters are drawn per clip and '
                         'applied on the device inside the gather (default: none)')
+    add_resize_arguments(p)
+
+
+def add_resize_arguments(p) -> None:
+    """`--resize` / `--resize_fit` of train.py and generate_frames.py (docs/DESIGN_NOTES_frames.md)."""
+    # default=SUPPRESS: a run without the flags has the options object it always had (resize_spec supplies none / crop)
+    p.add_argument('--resize', default=argparse.SUPPRESS, choices=('none',) + resample.FILTERS,
+                   help='kth | bair | ucf | frames from --data_root: scale every decoded frame that is not image_width x image_width '
+                        'with this filter of Pillow\'s Image.resize, on the device while the frame pool is built, bit-equal to '
+                        'Pillow (default none: such a frame is refused)')
+    p.add_argument('--resize_fit', default=argparse.SUPPRESS, choices=resample.FITS,
+                   help='--resize: crop = the largest centred box of the target\'s aspect ratio, stretch = the whole frame (default crop)')
+
+
+def resize_spec(opt):
+    """(filter, fit) of an options object, None without `--resize` (objects made before the option existed have none)."""
+    f = getattr(opt, 'resize', None) or 'none'
+    fit = getattr(opt, 'resize_fit', None) or 'crop'
+    if f != 'none' and f not in resample.FILTERS or fit not in resample.FITS:
+        raise SystemExit(f"--resize {f} --resize_fit {fit}: none | {' | '.join(resample.FILTERS)} and {' | '.join(resample.FITS)}")
+    return None if f == 'none' else (f, fit)
+
+
+def check_resize(opt, who='train.py'):
+    """`--resize` scales frames that are READ: refused, before anything is built, where no frame is (the choices are argparse's)."""
+    spec = resize_spec(opt)
+    if spec and (opt.dataset not in REAL_DATASETS or getattr(opt, 'synthetic_data', False)):
+        raise SystemExit(f"{who} --resize: applies to kth | bair | ucf | frames clips read from --data_root, not to "
+                         f"{'--synthetic_data' if getattr(opt, 'synthetic_data', False) else '--dataset ' + opt.dataset}")
+    return spec
 
 
 def check_augment(opt) -> str:
@@ -254,7 +360,7 @@ def check_augment(opt) -> str:
     Moving-MNIST and synthetic streams draw a new clip for every batch, there is nothing to augment."""
     spec = augment_spec(parse_augment(opt.augment))
     if spec and (opt.dataset not in REAL_DATASETS or opt.synthetic_data):
-        raise SystemExit(f"train.py --augment: applies to kth | bair | ucf clips read from --data_root, not to "
+        raise SystemExit(f"train.py --augment: applies to kth | bair | ucf | frames clips read from --data_root, not to "
                          f"{'--synthetic_data' if opt.synthetic_data else '--dataset ' + opt.dataset}")
     return spec
 
@@ -302,15 +408,44 @@ class ClipAugmenter:
         self.rng.set_state(pos["np"])
 
 
-def _decode(path, dst, image_width):
-    """One PNG into dst (H,W,pool_c) uint8: mode L as one channel, RGB interleaved; no resizing (nor does the reference)."""
+def _decode(path, dst, image_width, resize=None):
+    """One PNG into dst (H,W,pool_c) uint8: mode L as one channel, RGB interleaved; no resizing (nor does the reference) unless
+    `resize` = (filter, fit) is given: a frame of another size is then scaled by Pillow itself, here on the decoding thread (the
+    host pool; what the device path must equal byte for byte)."""
     from PIL import Image
     try:
         with Image.open(path) as im:
-            if im.size != (image_width, image_width):
-                raise SystemExit(f"dataset: {path!r} is {im.size[0]}x{im.size[1]}, not {image_width}x{image_width}")
+            if im.size != (image_width, image_width) and resize is None:
+                raise SystemExit(f"dataset: {path!r} is {im.size[0]}x{im.size[1]}, not {image_width}x{image_width}"
+                                 f" (--resize FILTER scales such frames)")
             if im.mode != ('L' if dst.shape[2] == 1 else 'RGB'):
                 raise SystemExit(f"dataset: {path!r} has mode {im.mode}, the pool holds {dst.shape[2]}-channel frames")
+            if im.size != (image_width, image_width):
+                im = resample.pil_resize(im, image_width, *resize)
+            dst[...] = np.asarray(im).reshape(dst.shape)
+    except OSError as e:
+        raise SystemExit(f"dataset: cannot read {path!r}: {e}")
+
+
+def _frame_size(path):
+    """(W, H) from the file's header."""
+    from PIL import Image
+    try:
+        with Image.open(path) as im:
+            return im.size
+    except OSError as e:
+        raise SystemExit(f"dataset: cannot read {path!r}: {e}")
+
+
+def _decode_native(path, dst):
+    """One frame at its own size into dst (H,W,pool_c) uint8 (a view of the staging buffer)."""
+    from PIL import Image
+    try:
+        with Image.open(path) as im:
+            if im.mode != ('L' if dst.shape[2] == 1 else 'RGB'):
+                raise SystemExit(f"dataset: {path!r} has mode {im.mode}, the pool holds {dst.shape[2]}-channel frames")
+            if im.size != (dst.shape[1], dst.shape[0]):
+                raise SystemExit(f"dataset: {path!r} changed its size while it was read")
             dst[...] = np.asarray(im).reshape(dst.shape)
     except OSError as e:
         raise SystemExit(f"dataset: cannot read {path!r}: {e}")
@@ -327,25 +462,28 @@ def _pool_channels(path):
         raise SystemExit(f"dataset: cannot read {path!r}: {e}")
 
 
-_pools = {}     # (dataset, root, split, width, device) -> the pool build_pool made: the streams of one split share it
+_pools = {}     # (dataset, root, split, width, device, resize) -> the pool build_pool made: the streams of one split share it
 
 
-def shared_pool(index, root, image_width, device=None, threads=5):
-    """build_pool(index, ...), once per (dataset, root, split, width, device) and process: train.py's test stream and its
-    validation stream (--val_every) read the test split from ONE frame pool.  The pool is read only."""
+def shared_pool(index, root, image_width, device=None, threads=5, resize=None):
+    """build_pool(index, ...), once per (dataset, root, split, width, device, resize) and process: train.py's test stream and
+    its validation stream (--val_every) read the test split from ONE frame pool.  The pool is read only."""
     dev = torch.device(device) if device is not None else torch.device('cpu')
     if dev.type == 'cuda' and dev.index is None:
         dev = torch.device('cuda', torch.cuda.current_device())
-    key = (index.dataset, os.path.abspath(root), index.split, int(image_width), str(dev))
+    key = (index.dataset, os.path.abspath(root), index.split, int(image_width), str(dev), None if resize is None else tuple(resize))
     if key not in _pools:
-        _pools[key] = build_pool(index, image_width, dev, threads)
+        _pools[key] = build_pool(index, image_width, dev, threads, resize)
     return _pools[key]
 
 
-def build_pool(index, image_width, device=None, threads=5):
+def build_pool(index, image_width, device=None, threads=5, resize=None):
     """(n_frames, S, S, pool_c) uint8: every frame of `index`, sequence after sequence (sequence i starts at index.bases[i]).
     Decoded with Pillow on min(threads, 16) threads.  For a GPU `device` the frames are decoded into a pinned staging
-    buffer of at most STAGING_BYTES and uploaded chunk by chunk into ONE device tensor; device None / cpu: a host tensor."""
+    buffer of at most STAGING_BYTES and uploaded chunk by chunk into ONE device tensor; device None / cpu: a host tensor.
+    resize = (filter, fit) (`--resize`, `--resize_fit`): frames of another size are scaled to S x S as Pillow's Image.resize
+    scales them - for a GPU device by dvg_resample_u8 (_build_pool_resized), for a host pool by Pillow on the decoding thread;
+    the two pools are equal byte for byte.  None: such a frame ends the program, and nothing here differs from before."""
     files = [f for seq in index.sequences for f in seq]
     if not files:
         raise SystemExit(f"dataset: the {index.dataset} {index.split} split lists no frame")
@@ -357,8 +495,10 @@ def build_pool(index, image_width, device=None, threads=5):
     with ThreadPoolExecutor(workers) as ex:
         if dev.type == 'cpu':
             host = pool.numpy()
-            list(ex.map(lambda i: _decode(files[i], host[i], image_width), range(len(files))))
+            list(ex.map(lambda i: _decode(files[i], host[i], image_width, resize), range(len(files))))
             return pool
+        if resize is not None:
+            return _build_pool_resized(ex, files, pool, resize)
         chunk = max(1, min(len(files), STAGING_BYTES // frame_bytes))
         staging = torch.empty((chunk, image_width, image_width, pc), dtype=torch.uint8).pin_memory()
         host = staging.numpy()
@@ -367,4 +507,52 @@ def build_pool(index, image_width, device=None, threads=5):
             list(ex.map(lambda i: _decode(files[a + i], host[i], image_width), range(n)))
             pool[a:a + n].copy_(staging[:n], non_blocking=True)
             torch.cuda.current_stream(dev).synchronize()      # the staging buffer is written again by the next chunk
+    return pool
+
+
+def _build_pool_resized(ex, files, pool, resize):
+    """build_pool's GPU path under `--resize`: the worker threads decode every frame at its OWN size into the pinned staging
+    buffer, packed by bytes (at most STAGING_BYTES a chunk; a run of equal-sized frames starts 16-byte aligned and is contiguous);
+    each run of consecutive frames with the same (H, W) is then one upload and one ops.resample_u8 straight into its slice of
+    the pool (a run that already is S x S: one copy).  The sizes come from the files' headers first, so the packing is known
+    before a pixel is decoded."""
+    from . import ops
+    dev, S, pc = pool.device, pool.shape[1], pool.shape[3]
+    flt, fit = resize
+    sizes = list(ex.map(_frame_size, files))                      # (W, H)
+    nbytes = [w * h * pc for w, h in sizes]
+    cap = max(min(STAGING_BYTES, sum(nbytes) + 16 * len(files)), max(nbytes))
+    staging = torch.empty(cap, dtype=torch.uint8).pin_memory()
+    landing = torch.empty(cap, dtype=torch.uint8, device=dev)
+    host = staging.numpy()
+    a = 0
+    while a < len(files):
+        offs, used, b = [], 0, a
+        while b < len(files):
+            at = used if b > a and sizes[b] == sizes[b - 1] else (used + 15) & ~15
+            if b > a and at + nbytes[b] > cap:
+                break
+            offs.append(at)
+            used = at + nbytes[b]
+            b += 1
+
+        def decode(i):
+            w, h = sizes[a + i]
+            _decode_native(files[a + i], host[offs[i]:offs[i] + nbytes[a + i]].reshape(h, w, pc))
+        list(ex.map(decode, range(b - a)))
+        i = a
+        while i < b:
+            j = i + 1
+            while j < b and sizes[j] == sizes[i]:
+                j += 1
+            (w, h), o0, o1 = sizes[i], offs[i - a], offs[i - a] + (j - i) * nbytes[i]
+            landing[o0:o1].copy_(staging[o0:o1], non_blocking=True)
+            src = landing[o0:o1].view(j - i, h, w, pc)
+            if (w, h) == (S, S):
+                pool[i:j].copy_(src)
+            else:
+                ops.resample_u8(src, (S, S), flt, box=resample.fit_box(w, h, S, S, fit), out=pool[i:j])
+            i = j
+        torch.cuda.current_stream(dev).synchronize()              # the staging buffer is written again by the next chunk
+        a = b
     return pool

@@ -48,4 +48,5 @@ from .guard import grad_sumsq_blocks, grad_sumsq, grad_guard_finish  # noqa: F40
 from .ema import ema_update_blocks, ema_update  # noqa: F401
 from .lr_schedule import LR_KINDS, lr_schedule_tick  # noqa: F401
 from .validate import val_accumulators, val_accumulate  # noqa: F401
+from .resample import resample_u8, resample_band  # noqa: F401
 from .._lib import check, lib  # noqa: F401

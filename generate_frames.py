@@ -32,7 +32,7 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 import utils  # noqa: E402
-from dvg_amd import mnist, ops, viz  # noqa: E402
+from dvg_amd import datasets, mnist, ops, viz  # noqa: E402
 from dvg_amd.data import SyntheticMovingMNIST, make_batch_generator, synthetic_video  # noqa: E402
 from dvg_amd.rollout import (GraphedSampler, GraphedTrigger, condition, gp_input, posterior_from, sample_from, sample_rollout,  # noqa: E402
                              trigger_body, trigger_log, trigger_warmup)
@@ -46,7 +46,7 @@ def build_parser():
     p.add_argument('--model_dir', default='')
     p.add_argument('--name', default='')
     p.add_argument('--data_root', default='./data/kth',
-                   help='kth | bair | ucf: the processed dataset tree; smmnist: a directory with the MNIST IDX image files')
+                   help='kth | bair | ucf: the processed dataset tree; frames: train/ and test/ with one directory of frames per clip; smmnist: a directory with the MNIST IDX image files')
     p.add_argument('--seed', default=1, type=int)
     p.add_argument('--image_width', type=int, default=64)
     p.add_argument('--channels', default=1, type=int)
@@ -91,6 +91,7 @@ def build_parser():
     p.add_argument('--synthetic_data', action='store_true',
                    help='kth | bair | ucf: synthetic clips of that shape instead of the test split under --data_root; smmnist: '
                         'the in-repo sprites even where --data_root holds MNIST')
+    datasets.add_resize_arguments(p)      # --resize, --resize_fit: as train.py
     return p
 
 
@@ -367,6 +368,8 @@ def data_seed(seed):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    if args.synthetic_ckpt:     # (a loaded checkpoint names its own dataset: checked below, once it is read)
+        datasets.check_resize(args, 'generate_frames.py')
     assert torch.cuda.is_available(), "generate_frames.py needs a GPU: the DVG hot path has no CPU fallback"
     device = torch.device('cuda', 0)
     if args.synthetic_ckpt:
@@ -395,11 +398,14 @@ def main(argv=None):
     torch.cuda.manual_seed_all(opt.seed)
     gen = Generator(opt, ckpt, device)
     dataset = getattr(opt, 'dataset', 'smmnist')
+    datasets.check_resize(argparse.Namespace(resize=getattr(args, 'resize', 'none'), resize_fit=getattr(args, 'resize_fit', 'crop'),
+                                             dataset=dataset, synthetic_data=args.synthetic_data), 'generate_frames.py')
     real_digits = dataset == 'smmnist' and not args.synthetic_data and mnist.find_tree(args.data_root, False) is not None
     if (dataset != 'smmnist' and not args.synthetic_data) or real_digits:
         # the test split under --data_root (the command line's, not the checkpoint's), as generate_frames.py:89-104; smmnist
         # takes this branch when the MNIST image files are there (dvg_amd/mnist.py)
         opt.data_root, opt.data_threads, opt.synthetic_data = args.data_root, args.data_threads, False
+        opt.resize, opt.resize_fit = datasets.resize_spec(args) or ('none', 'crop')      # the command line's, like --data_root
         opt.num_digits = getattr(opt, 'num_digits', 2)
         opt.local_batch, opt.rank = opt.batch_size, 0
         test_gen = make_batch_generator(opt, opt.n_eval, data_seed(opt.seed), device, train=False)

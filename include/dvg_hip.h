@@ -524,15 +524,13 @@ int dvg_k4_to_w3(const float* dk4_packed, float* dw, int cout, int c1, int ctot,
  * rows = dvg_wgrad_thin_rows(ks,N,Hi,Wi).  First layers: inp = frame, dout = du.
  * Last (transposed) layers: inp = dpre (frame side), dout = the layer INPUT x.     */
 int dvg_wgrad_thin_rows(int ks, int N, int Hi, int Wi);
-int dvg_wgrad_thin(const float* inp_nchw, const float* dout_nhwc, float* partial, int ks, int N,
-                   int Hi, int Wi, int nc, int C, void* stream);
+int dvg_wgrad_thin(const float* inp_nchw, const float* dout_nhwc, float* partial, int ks, int N, int Hi, int Wi, int nc, int C, void* stream);
 
 /* Compositing step of the Moving-MNIST generator (data/moving_mnist.py:86-90) fused with the layout change of
  * utils.normalize_data (utils.py:86-95): out (T,B,1,S,S) = min(1, sum_d sprite[ids[b,d]] placed at pos[b,d,t] =
  * (sy,sx)), digits added in index order.  sprites (n_sprites,D,D) fp32; ids (B,num_digits) int32; pos
  * (B,num_digits,T,2) int32 with 0 <= sy,sx <= S-D (the host computes the trajectories, moving_mnist.py:49-85). */
-int dvg_moving_mnist_compose(const float* sprites, const int* ids, const int* pos, float* out, int n_sprites, int T,
-                             int B, int num_digits, int image_size, int digit_size, void* stream);
+int dvg_moving_mnist_compose(const float* sprites, const int* ids, const int* pos, float* out, int n_sprites, int T, int B, int num_digits, int image_size, int digit_size, void* stream);
 
 /* A batch of clips gathered from a device-resident pool of decoded frames: replaces the per-frame `imread(f)/255.` loops of
  * data/kth.py:52-56, data/bair.py:52-57, data/ucf.py:56-61 and the layout change of utils.normalize_data (utils.py:86-95).
@@ -545,10 +543,8 @@ int dvg_moving_mnist_compose(const float* sprites, const int* ids, const int* po
  * first[b] + (reverse ? T-1-t : t) at row clamp(y + dy, 0, H-1), column clamp((hflip ? W-1-x : x) + dx, 0, W-1) (edge replicate)
  * and writes min(max(gain * v + bias, 0), 1), the multiply and the add rounded separately (no FMA): identity parameters give
  * dvg_clip_gather_u8's bits.  dy / dx are clamped to +-16, hflip / reverse read as != 0.  Additions within ABI 9. */
-int dvg_clip_gather_u8(const uint8_t* pool, const int64_t* first, float* out, int64_t n_frames, int T, int B, int C, int H,
-                       int W, int pool_c, void* stream);
-int dvg_clip_gather_aug_u8(const uint8_t* pool, const int64_t* first, const int32_t* geom, const float* photo, float* out,
-                           int64_t n_frames, int T, int B, int C, int H, int W, int pool_c, void* stream);
+int dvg_clip_gather_u8(const uint8_t* pool, const int64_t* first, float* out, int64_t n_frames, int T, int B, int C, int H, int W, int pool_c, void* stream);
+int dvg_clip_gather_aug_u8(const uint8_t* pool, const int64_t* first, const int32_t* geom, const float* photo, float* out, int64_t n_frames, int T, int B, int C, int H, int W, int pool_c, void* stream);
 
 /* `transforms.Scale(out_size)` on the MNIST digits (data/moving_mnist.py:24-26): Pillow's 8-bit bilinear resize, bit for bit.
  * raw (n,in_size,in_size) uint8 -> out (n,out_size,out_size) uint8, a horizontal pass into a uint8 intermediate, then a
@@ -556,15 +552,19 @@ int dvg_clip_gather_aug_u8(const uint8_t* pool, const int64_t* first, const int3
  * (out_size,3) are DEVICE int32 tables shared by both passes: Pillow's filter bounds and its weights, normalised in double and
  * rounded to 22-bit fixed point on the host (dvg_amd/mnist.py); the kernel clamps xmin and skips taps past the line.
  * in_size <= out_size <= 64: only the up-scaling filter is restated.  An addition within ABI 9. */
-int dvg_mnist_scale_u8(const uint8_t* raw, uint8_t* out, int n, int in_size, int out_size, const int* xmin, const int* coef,
-                       void* stream);
+int dvg_mnist_scale_u8(const uint8_t* raw, uint8_t* out, int n, int in_size, int out_size, const int* xmin, const int* coef, void* stream);
+/* Pillow's 8-bit `Image.resize` (box | bilinear | hamming | bicubic | lanczos), bit for bit, for frames of any size (`--resize`): src (n,Hin,Win,C) uint8 -> dst (n,Hout,Wout,C) uint8, C = 1 or 3
+ * interleaved; mnist_scale's arithmetic.  DEVICE int32 tables xmin (Wout), xcoef (Wout,xk), ymin (Hout), ycoef (Hout,yk) from dvg_amd/resample.py; xmin / ymin are absolute input positions (a crop box
+ * lives in them), clamped in the kernel.  xk / yk == 0: that pass is not needed, the axis is copied, its tables may be NULL.  dvg_resample_u8_band: the output rows per workgroup (64 KB of LDS: four source
+ * rows + *span intermediate rows) from ymin_host, the HOST copy of ymin; 0 = not even one row fits: DVG_ERR_SHAPE before any launch.  Contract: dvg_amd/csrc/resample.hip.  Additions within ABI 9. */
+int dvg_resample_u8_band(const int* ymin_host, int Hin, int Win, int Hout, int Wout, int C, int yk, int* span);
+int dvg_resample_u8(const uint8_t* src, uint8_t* dst, int n, int Hin, int Win, int Hout, int Wout, int C, const int* xmin, const int* xcoef, int xk, const int* ymin, const int* ycoef, int yk, const int* ymin_host, void* stream);
 
 /* dvg_moving_mnist_compose from a uint8 digit pool (data/moving_mnist.py:86-90 + utils.normalize_data's layout, utils.py:86-95):
  * sprites (n_sprites,D,D) uint8, a byte becomes float32 as `ToTensor` makes it, (float)v / 255.0f by a true division; digits are
  * added in index order, the sum is clipped at 1, out (T,B,1,S,S) float32.  ids (B,num_digits) int32, clamped in the kernel; pos
  * (B,num_digits,T,2) int32 = (sy,sx), every sprite access bounds-checked against it.  S % 4 == 0, out 16-byte aligned.  ABI 9. */
-int dvg_moving_mnist_compose_u8(const uint8_t* sprites, const int* ids, const int* pos, float* out, int n_sprites, int T,
-                                int B, int num_digits, int image_size, int digit_size, void* stream);
+int dvg_moving_mnist_compose_u8(const uint8_t* sprites, const int* ids, const int* pos, float* out, int n_sprites, int T, int B, int num_digits, int image_size, int digit_size, void* stream);
 
 /* Evaluation metrics of utils.eval_seq (utils.py:220-234): per (sample, channel) image, SSIM as
  * skimage.measure.compare_ssim computes it with its defaults (7x7 uniform window, sample covariance, data range 2

@@ -34,6 +34,9 @@ model" section, :86, is empty and `--model_dir` is never read: both kept); dvg_a
 graph, and writes `model_ema.pth` beside `model.pth` (dvg_amd/ema.py, docs/DESIGN_NOTES_ema.md).
 `--augment LIST` (kth | bair | ucf, train split): flip / reverse / shift / jitter per clip, applied inside the gather
 (dvg_clip_gather_aug_u8; dvg_amd/datasets.py ClipAugmenter, docs/DESIGN_NOTES_augment.md).
+`--dataset frames --resize FILTER [--resize_fit crop|stretch]`: a folder of clips, <root>/{train,test}/.../<clip>/<frame>.png|jpg, frames
+of any size; `--resize` scales every frame that is not image_width x image_width on the device while the frame pool is built, bit-equal
+to Pillow's Image.resize (dvg_resample_u8; dvg_amd/resample.py, docs/DESIGN_NOTES_frames.md).  It applies to kth | bair | ucf trees too.
 `--val_every N` scores a fixed set of held-out clips every N epochs on rank 0 (eval-mode rollouts, Finn metrics, dvg_val_accumulate),
 logs them to `val_log.jsonl` and keeps `model_best.pth` (dvg_amd/validate.py, docs/DESIGN_NOTES_validation.md).
 `--lr_schedule KIND` makes `--lr` the base rate of all four optimisers and moves it every iteration by a device-side multiplier:
@@ -78,7 +81,8 @@ def build_parser():
     p.add_argument('--name', default='')
     p.add_argument('--output_path', default='.')
     p.add_argument('--data_root', default='path/to/data/',
-                   help='kth | bair | ucf: the root of the processed dataset tree; smmnist: a directory holding the MNIST IDX '
+                   help='kth | bair | ucf: the root of the processed dataset tree; frames: a directory with train/ and test/, '
+                        'below them one directory of .png / .jpg frames per clip; smmnist: a directory holding the MNIST IDX '
                         'image files (<root>/MNIST/raw, <root>/raw or <root>, raw or .gz)')
     p.add_argument('--niter', type=int, default=601)
     p.add_argument('--seed', default=1, type=int)
@@ -139,6 +143,7 @@ def main(argv=None):
     rank, world, local = parallel.init_distributed()
     opt = options(argv, rank=rank, world=world)
     opt.augment = datasets.check_augment(opt)   # --augment: parsed and refused before anything is built
+    datasets.check_resize(opt)                  # --resize: likewise
     if hasattr(torch.autograd.graph, "set_warn_on_accumulate_grad_stream_mismatch"):
         # the latent path of an eager iteration runs on a second stream on purpose (autograd.JOIN_STREAMS joins them)
         torch.autograd.graph.set_warn_on_accumulate_grad_stream_mismatch(False)
