@@ -19,6 +19,7 @@ _i = C.c_int
 _f = C.c_float
 _d = C.c_double
 _l = C.c_long
+_ip = C.POINTER(C.c_int)
 
 # name -> (restype, argtypes); must list EVERY symbol of include/dvg_hip.h
 # (tests/test_abi.py parses the header and cross-checks this table).
@@ -47,6 +48,8 @@ SIGNATURES = {
     "dvg_winograd_weight": (_i, [_p, _p, _i, _i, _i, _p]),
     "dvg_winograd_input": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
     "dvg_gemm_batched_k16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "dvg_gemm_batched_plan": (_i, [_i, _i, _i, _i, _i, _ip, _ip, _ip]),
+    "dvg_winograd_transform_width": (_i, [_l, _i]),
     "dvg_winograd_output": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _i, _p]),
     "dvg_winograd_output_input": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p]),
     "dvg_stem_up_winograd_input": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _i, _i, _i, _f, _p]),

@@ -1085,6 +1085,21 @@ static int choose_splitk(long wgs, int nchunks) {
     return s < 2 ? 1 : (int)s;
 }
 
+// GEMM mode: consecutive images one workgroup runs back to back in one software pipeline (launch2, dvg_gemm_batched_plan).
+// bf16 triples: the 64-row tile runs three workgroups per CU (768 resident), and with the matrix work 2.7 x shorter a
+// workgroup's prologue weighs more.  When the launch is a whole number r <= 6 of residency rounds, ONE round of
+// workgroups that run r images back to back in one pipeline is faster (16x16 256->256: 39.6 -> 36.1 us,
+// 32x32 128->128: 43.2 -> 40.4 us); otherwise the finer grain balances better (8x8 512->512, 1.5 rounds: 38.6 vs 39.5).
+static int gemm_images_per_wg(int tw, int nt, int NB, int Hg, int Wg, int Cout) {
+#if DVG_BF16X3
+    if (tw == 8 && nt == 1) {
+        const long w1 = (long)(Hg / 8) * (Wg / 8) * NB * (Cout / 64), slots = 256L * DVG_GEMM_WGS_PER_CU;
+        if (w1 % slots == 0 && w1 / slots >= 2 && w1 / slots <= 6 && NB % (w1 / slots) == 0) return (int)(w1 / slots);
+    }
+#endif
+    return 1;
+}
+
 template <int MODE, int TI, int TH, int TW, int NT = 1, bool FIRST = false, bool PROJ = false>
 static int launch2(Igemm2Params p, int Hg, int Wg, float* ws, long ws_floats, hipStream_t stream) {
     using C = Cfg2<MODE, TI, TH, TW, NT, FIRST, PROJ>;
@@ -1098,17 +1113,7 @@ static int launch2(Igemm2Params p, int Hg, int Wg, float* ws, long ws_floats, hi
         // a few % faster on the K <= 256 shapes; at 4 per CU (127 VGPRs, __launch_bounds__ above) the extra wave hides the
         // prologues and the finer-grained workgroups balance the CUs better: 1 image is fastest or tied on every vgg_64
         // shape (tools/ab_gemm_ni.sh: e.g. 16x16 256->256 48.4 us vs 52.0 (2) / 59.0 (4); 8x8 512->256 31.7 vs 41.7 / 57.6).
-        int ni = 1;
-#if DVG_BF16X3
-        // bf16 triples: the 64-row tile runs three workgroups per CU (768 resident), and with the matrix work 2.7 x shorter a
-        // workgroup's prologue weighs more.  When the launch is a whole number r <= 6 of residency rounds, ONE round of
-        // workgroups that run r images back to back in one pipeline is faster (16x16 256->256: 39.6 -> 36.1 us,
-        // 32x32 128->128: 43.2 -> 40.4 us); otherwise the finer grain balances better (8x8 512->512, 1.5 rounds: 38.6 vs 39.5).
-        if (TW == 8 && NT == 1) {
-            const long w1 = (long)p.tiles_y * p.tiles_x * p.N * (p.Cout / C::BN), slots = 256L * DVG_GEMM_WGS_PER_CU;
-            if (w1 % slots == 0 && w1 / slots >= 2 && w1 / slots <= 6 && p.N % (w1 / slots) == 0) ni = (int)(w1 / slots);
-        }
-#endif
+        const int ni = gemm_images_per_wg(TW, NT, p.N, Hg, Wg, p.Cout);
         p.gemm_ni = ni;
         p.tiles_n = p.N / ni;
     }
@@ -1195,6 +1200,21 @@ static int tile2(int mode, int N, int Hg, int Wg, int Cout, int* ti, int* th, in
             // (f32 MFMA build: the 64-row tile at 4 per CU throughout, as measured in r03)
             if (!DVG_BF16X3 || wgs < DVG_GEMM128_MIN_WGS) *tw = 8;
         }
+    }
+    return 0;
+}
+
+// The batched GEMM's tile (dvg_gemm_batched_k16, dvg_gemm_batched_plan): *tw = 8 the 64-row tile, 16 the 128-row tile; *nt = 2
+// the 128 x 128 workgroup tile (64 x 64 per wave: half the fragment reads and half the L2 -> LDS bytes per MFMA of the 128 x 64
+// tile) from DVG_GEMM_NT2 workgroups on: the energy-lean tile (see the constant above; bf16-triple build only).
+static int gemm_tile(int NB, int Hg, int Wg, int Cout, int* tw, int* nt) {
+    int ti, th;
+    if (tile2(M2_GEMM, NB, Hg, Wg, Cout, &ti, &th, tw) != 0 || ti != 1) return -1;
+    *nt = 1;
+    if (DVG_BF16X3 && g_tile_policy && Cout % 128 == 0 && Wg % 16 == 0 &&
+        (long)NB * (Hg / 8) * (Wg / 16) * (Cout / 128) >= DVG_GEMM_NT2) {
+        *tw = 16;
+        *nt = 2;
     }
     return 0;
 }
@@ -1439,8 +1459,9 @@ extern "C" int dvg_convT4x4s2_bn_act_proj(const float* x, const float* w_k16, co
 }
 
 // Batched GEMM on the igemm machinery: y[b][px][co] = sum_ci x[b][px][ci] * w[b][ci][co] for b < NB "images" of H x W
-// pixels each (x NHWC (NB,H,W,Cin), y NHWC (NB,H,W,Cout), w = NB packed slabs [Cin/16][1][Cout][16] as
-// dvg_pack_conv_weight_k16 writes them for a 1x1 kernel).  The 16 Winograd-domain products of dvg_winograd_* below.
+// pixels each (x NHWC (NB,H,W,Cin), y NHWC (NB,H,W,Cout), w = NB packed slabs [Cout/64][Cin/16][64][DVG_WROW] - Cout block
+// outermost, as dvg_winograd_weight writes them (gload_b); dvg_pack_conv_weight_k16's 1x1 layout [Cin/16][Cout/64][64][row]
+// is the same only at Cout == 64).  The 16 / 36 Winograd-domain products of dvg_winograd_*.
 // Cin % 64 == 0, Cout % 64 == 0, H % 8 == 0, W % 8 == 0.
 extern "C" int dvg_gemm_batched_k16(const float* x, const float* w_k16, float* y, int NB, int H, int W, int Cin, int Cout,
                                     void* stream) {
@@ -1453,16 +1474,24 @@ extern "C" int dvg_gemm_batched_k16(const float* x, const float* w_k16, float* y
     p.w_image_stride = (long)Cin / 16 * Cout * DVG_WROW;
     float* workspace = nullptr;
     const long workspace_floats = 0;
-    int Hg = H, Wg = W, ti, th, tw;
-    DVG_REQUIRE(tile2(M2_GEMM, NB, Hg, Wg, Cout, &ti, &th, &tw) == 0 && ti == 1, DVG_ERR_SHAPE,
-                "dvg_gemm_batched_k16: no tile for %dx%d", H, W);
+    const int Hg = H, Wg = W, ti = 1, th = 8;
+    int tw, nt;
+    DVG_REQUIRE(gemm_tile(NB, Hg, Wg, Cout, &tw, &nt) == 0, DVG_ERR_SHAPE, "dvg_gemm_batched_k16: no tile for %dx%d", H, W);
 #if DVG_BF16X3
-    // 128 x 128 workgroup tile (64 x 64 per wave: half the fragment reads and half the L2 -> LDS bytes per MFMA of the 128 x 64
-    // tile) from DVG_GEMM_NT2 workgroups on: the energy-lean tile (see the constant above)
-    if (g_tile_policy && Cout % 128 == 0 && Wg % 16 == 0 && (long)NB * (Hg / 8) * (Wg / 16) * (Cout / 128) >= DVG_GEMM_NT2)
-        return launch2<M2_GEMM, 1, 8, 16, 2>(p, Hg, Wg, workspace, workspace_floats, (hipStream_t)stream);
+    if (nt == 2) return launch2<M2_GEMM, 1, 8, 16, 2>(p, Hg, Wg, workspace, workspace_floats, (hipStream_t)stream);
 #endif
     D2(M2_GEMM, 1, 8, 16)
     D2(M2_GEMM, 1, 8, 8)
     return fail(DVG_ERR_SHAPE, "dvg_gemm_batched_k16: no kernel");
+}
+
+// What dvg_gemm_batched_k16 launches for this shape under the tile policy in force, without launching (host only): *tile_w the
+// pixel tile's width (8: the 64-row tile, 16: the 128-row tile), *nt the 64-wide Cout blocks per workgroup (2: the 128 x 128
+// tile), *ni the images a workgroup runs back to back in one pipeline.  0, or -1 for a shape the launcher rejects.
+extern "C" int dvg_gemm_batched_plan(int NB, int H, int W, int Cin, int Cout, int* tile_w, int* nt, int* ni) {
+    if (!tile_w || !nt || !ni || NB <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return -1;
+    if (Cin % (16 * DVG_GEMM_GT) || Cout % 64 || H % 8 || W % 8) return -1;
+    if (gemm_tile(NB, H, W, Cout, tile_w, nt)) return -1;
+    *ni = gemm_images_per_wg(*tile_w, *nt, NB, H, W, Cout);
+    return 0;
 }

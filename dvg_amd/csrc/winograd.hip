@@ -668,6 +668,14 @@ __global__ __launch_bounds__(256) void stem_up_input_kernel(const float* __restr
     }
 }
 
+// Channels per thread of the F(4x4) input, output and d(out) transforms: the widest form that still gives >= 1024 workgroups
+// of 256 threads (see winograd4_input_kernel)
+static int wino4_width(long tiles, int C) {
+    if (tiles * (C / 4) >= 1024L * 256) return 4;
+    if (tiles * (C / 2) >= 1024L * 256) return 2;
+    return 1;
+}
+
 static int chain_variant() { return 0; }      // (the variants below were A/B'd per shape: numbers in the comments)
 
 static inline unsigned wgrid(long n) {
@@ -705,15 +713,22 @@ extern "C" int dvg_winograd_input(const float* x, float* v, int N, int H, int W,
     if (m == 2) {
         hipLaunchKernelGGL(winograd_input_kernel, dim3(wgrid(tiles * (C / 4))), dim3(256), 0, st, x, v, N, H, W, C / 4);
     } else {
-        // channels per thread: the widest form that still gives >= 1024 workgroups (see the kernel)
-        if (tiles * (C / 4) >= 1024L * 256)
+        const int cw = wino4_width(tiles, C);
+        if (cw == 4)
             hipLaunchKernelGGL(winograd4_input_kernel<f32x4>, dim3(wgrid(tiles * (C / 4))), dim3(256), 0, st, x, v, N, H, W, C / 4, tiles, 0L, up);
-        else if (tiles * (C / 2) >= 1024L * 256)
+        else if (cw == 2)
             hipLaunchKernelGGL(winograd4_input_kernel<f32x2>, dim3(wgrid(tiles * (C / 2))), dim3(256), 0, st, x, v, N, H, W, C / 2, tiles, 0L, up);
         else
             hipLaunchKernelGGL(winograd4_input_kernel<float>, dim3(wgrid(tiles * C)), dim3(256), 0, st, x, v, N, H, W, C, tiles, 0L, up);
     }
     return check_launch("dvg_winograd_input");
+}
+
+// Channels per thread (4, 2 or 1) of the F(4x4) transform kernels dvg_winograd_input, dvg_winograd_output and
+// dvg_winograd_wgrad_operands launch for `tiles` 4x4 tiles of C channels (host only); 0 for an empty or unaligned shape.
+extern "C" int dvg_winograd_transform_width(long tiles, int C) {
+    if (tiles <= 0 || C <= 0 || C % 4) return 0;
+    return wino4_width(tiles, C);
 }
 
 // Operands of the Winograd-form weight gradient (wino_wgrad.hip) for ONE use of a layer: V = B^T x B of the layer input
@@ -733,9 +748,10 @@ extern "C" int dvg_winograd_wgrad_operands(const float* x, const float* dy, floa
     const hipStream_t st = (hipStream_t)stream;
 #define WOPS(KERNEL_, SRC_, DST_, C_, ...)                                                                                        \
     do {                                                                                                                       \
-        if (tiles * ((C_) / 4) >= 1024L * 256)                                                                                 \
+        const int cw_ = wino4_width(tiles, (C_));                                                                              \
+        if (cw_ == 4)                                                                                                          \
             hipLaunchKernelGGL(KERNEL_<f32x4>, dim3(wgrid(tiles * ((C_) / 4))), dim3(256), 0, st, SRC_, DST_, N, H, W, (C_) / 4, t_total, t_off __VA_ARGS__); \
-        else if (tiles * ((C_) / 2) >= 1024L * 256)                                                                            \
+        else if (cw_ == 2)                                                                                                     \
             hipLaunchKernelGGL(KERNEL_<f32x2>, dim3(wgrid(tiles * ((C_) / 2))), dim3(256), 0, st, SRC_, DST_, N, H, W, (C_) / 2, t_total, t_off __VA_ARGS__); \
         else                                                                                                                   \
             hipLaunchKernelGGL(KERNEL_<float>, dim3(wgrid(tiles * (C_))), dim3(256), 0, st, SRC_, DST_, N, H, W, (C_), t_total, t_off __VA_ARGS__);           \
@@ -870,8 +886,9 @@ extern "C" int dvg_winograd_output(const float* m, const float* scale, const flo
 #define W4OUT(POOL_, V_, CW_)                                                                                             \
     hipLaunchKernelGGL((winograd4_output_kernel<POOL_, V_>), dim3(wgrid(tiles * (C / CW_))), dim3(256), 0, st, m, scale, shift, \
                        y, y_pool, N, H, W, C / CW_, act, slope, addend, y_from)
-        if (tiles * (C / 4) >= 1024L * 256) { if (y_pool) W4OUT(true, f32x4, 4); else W4OUT(false, f32x4, 4); }
-        else if (tiles * (C / 2) >= 1024L * 256) { if (y_pool) W4OUT(true, f32x2, 2); else W4OUT(false, f32x2, 2); }
+        const int cw = wino4_width(tiles, C);
+        if (cw == 4) { if (y_pool) W4OUT(true, f32x4, 4); else W4OUT(false, f32x4, 4); }
+        else if (cw == 2) { if (y_pool) W4OUT(true, f32x2, 2); else W4OUT(false, f32x2, 2); }
         else { if (y_pool) W4OUT(true, float, 1); else W4OUT(false, float, 1); }
 #undef W4OUT
     }

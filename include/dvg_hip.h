@@ -169,8 +169,9 @@ int dvg_winograd_weight(const float* w_oihw, float* u_k16, int cout, int cin, in
 /* upsample = 1 (ABI 6, m = 4): x is stored at (N, H/2, W/2, C) and read through nn.UpsamplingNearest2d(2) (vgg_64.py:93) -
  * the x half of a decoder block's first conv in Winograd form; the upsampled tensor never exists.                       */
 int dvg_winograd_input(const float* x, float* v, int N, int H, int W, int C, int m, int upsample, void* stream);
-int dvg_gemm_batched_k16(const float* x, const float* w_k16, float* y, int NB, int H, int W, int Cin, int Cout,
-                         void* stream);
+int dvg_gemm_batched_k16(const float* x, const float* w_k16, float* y, int NB, int H, int W, int Cin, int Cout, void* stream);
+int dvg_gemm_batched_plan(int NB, int H, int W, int Cin, int Cout, int* tile_w, int* nt, int* ni);  /* host only (within ABI 9): what that launch takes under the tile policy in force - *tile_w 8 (64-row tile) / 16 (128-row), *nt 64-wide Cout blocks per workgroup, *ni images per pipeline; -1: rejected shape */
+int dvg_winograd_transform_width(long tiles, int C);  /* host only (within ABI 9): channels per thread (4, 2, 1; 0: rejected shape) of the F(4x4) transform kernels */
 /* addend (ABI 6; optional, m = 4, no y_pool): raw partial sums (N,H,W,Cout) NHWC added before scale / shift / activation -
  * the hoisted skip half of a decoder block's first conv, as in dvg_conv3x3_bn_act_v2.                                  */
 int dvg_winograd_output(const float* mm, const float* scale, const float* shift, float* y, float* y_pool, int N, int H,
@@ -180,8 +181,7 @@ int dvg_winograd_output(const float* mm, const float* scale, const float* shift,
  * two consecutive eval-mode vgg_layers at one resolution whose intermediate activation has no other consumer (the inner
  * layers of a vgg block, vgg_64.py:24-43,70-87): mm (36, T, C) -> v_next (36, T, C); the activation is not written.     */
 int dvg_winograd_output_input(const float* mm, const float* scale, const float* shift, float* v_next, int N, int H, int W,
-                              int C, int act, float slope, const float* addend /* as dvg_winograd_output; may be NULL */,
-                              void* stream);
+                              int C, int act, float slope, const float* addend /* as dvg_winograd_output; may be NULL */, void* stream);
 /* Decoder stem -> first conv of the first decoder block (vgg_64.py:65-69 then :93,98-99): ConvTranspose2d(dim,C,4,1,0) on the
  * 1x1 latent + BN + LeakyReLU, `up`, and the Winograd input transform of the x half of upc2's concat conv in ONE launch - the
  * 4 x 4 x C map is never written.  vec (M, K), row stride ldv; w_kn as dvg_stem_gemm takes it ([KP][16 C], KP in {96, 128});
