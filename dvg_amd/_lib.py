@@ -1,168 +1,111 @@
-"""ctypes binding of libdvg_hip.so (the C ABI declared in include/dvg_hip.h).
+"""ctypes binding of libdvg_hip.so, derived at import from the one written form of its C ABI, include/dvg_hip.h.
 
-The product path has NO fallback: if the shared object is missing or a symbol is
-absent, `lib()` raises.  Nothing in here touches a GPU; loading works on a CPU-only
-box (the HIP runtime is only initialised by the first kernel launch).
+The compiler holds every `extern "C"` definition to its declaration in that header (each .hip file includes it); the strict
+parser below turns the same declarations into SIGNATURES and the header's `#define DVG_<NAME> <integer>` lines into CONSTANTS.
+An entry point is declared, defined and called: there is no table to keep (docs/DESIGN_NOTES_abi_binding.md).
+
+The product path has NO fallback: if the header or the shared object is missing, a declaration is not understood or a symbol
+is absent, this raises.  Nothing in here touches a GPU; loading works on a CPU-only box (the HIP runtime is only initialised
+by the first kernel launch).
 """
 from __future__ import annotations
 
 import ctypes as C
 import os
+import re
 import threading
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # DVG_HIP_LIB: an alternative BUILD of the same library (kernel A/B experiments, `make variant`); still no fallback
 LIB_PATH = os.environ.get("DVG_HIP_LIB") or os.path.join(_HERE, "csrc", "libdvg_hip.so")
-
-_p = C.c_void_p
-_i = C.c_int
-_f = C.c_float
-_d = C.c_double
-_l = C.c_long
-_ip = C.POINTER(C.c_int)
-
-# name -> (restype, argtypes); must list EVERY symbol of include/dvg_hip.h
-# (tests/test_abi.py parses the header and cross-checks this table).
-SIGNATURES = {
-    "dvg_abi_version": (_i, []),
-    "dvg_last_error": (C.c_char_p, []),
-    "dvg_stream_capture_id": (_l, [_p]),
-    "dvg_mfma_mode": (_i, []),
-    "dvg_build_info": (C.c_char_p, []),
-    "dvg_set_tile_policy": (None, [_i]),
-    "dvg_tile_policy": (_i, []),
-    "dvg_packed_row_floats": (_i, []),
-    "dvg_pack_conv_weight": (_i, [_p, _p, _i, _i, _i, _i, _p]),
-    "dvg_pack_convT_weight": (_i, [_p, _p, _i, _i, _i, _i, _p]),
-    "dvg_unpack_conv_weight": (_i, [_p, _p, _i, _i, _i, _i, _p]),
-    "dvg_unpack_convT_weight": (_i, [_p, _p, _i, _i, _i, _i, _p]),
-    "dvg_conv_first_stats_rows": (_i, [_i, _i, _i, _i]),
-    "dvg_pack_conv_weight_k16": (_i, [_p, _p, _i, _i, _i, _i, _i, _p]),
-    "dvg_conv_splitk_v2": (_i, [_i, _i, _i, _i, _i, _i]),
-    "dvg_conv_stats_rows_v2": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
-    "dvg_conv3x3_bn_act_v2": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _p, _l, _p, _p, _i, _p]),
-    "dvg_conv3x3_first_pair": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "dvg_conv4x4s2_bn_act_v2": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p, _l, _p]),
-    "dvg_convT4x4s2_bn_act_v2": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p, _l, _p, _p, _i, _p]),
-    "dvg_convT4x4s2_bn_act_proj": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p, _p, _i, _p]),
-    "dvg_winograd_weight": (_i, [_p, _p, _i, _i, _i, _p]),
-    "dvg_winograd_input": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "dvg_gemm_batched_k16": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p]),
-    "dvg_gemm_batched_plan": (_i, [_i, _i, _i, _i, _i, _ip, _ip, _ip]),
-    "dvg_winograd_transform_width": (_i, [_l, _i]),
-    "dvg_winograd_output": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p, _i, _p]),
-    "dvg_winograd_output_input": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p, _p]),
-    "dvg_stem_up_winograd_input": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _i, _i, _i, _f, _p]),
-    "dvg_winograd_output_up_input": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _p]),
-    "dvg_winograd_output_pool_input": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "dvg_conv3x3_first": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
-    "dvg_convT3x3_last": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "dvg_conv4x4s2_first": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
-    "dvg_convT4x4s2_last": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "dvg_moving_mnist_compose": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "dvg_clip_gather_u8": (_i, [_p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _p]),
-    "dvg_clip_gather_aug_u8": (_i, [_p, _p, _p, _p, _p, _l, _i, _i, _i, _i, _i, _i, _p]),
-    "dvg_mnist_scale_u8": (_i, [_p, _p, _i, _i, _i, _p, _p, _p]),
-    "dvg_moving_mnist_compose_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "dvg_resample_u8_band": (_i, [_p, _i, _i, _i, _i, _i, _i, _p]),
-    "dvg_resample_u8": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _p, _p, _i, _p, _p]),
-    "dvg_eval_frames": (_i, [_p, _p, _p, _p, _i, _i, _i, _p]),
-    "dvg_eval_frames_finn": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
-    "dvg_pairwise_frame_mse": (_i, [_p, _p, _i, _l, _i, _l, _i, _p]),
-    "dvg_frame_mosaic": (_i, [_p, _l, _p, _l, _p, _l, _i, _i, _i, _p] + [_i] * 9 + [_p, _i, _p, _i, _i, _p, _i, _i, _i, _i, _p, _p]),
-    "dvg_adam_step": (_i, [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p, _p]),
-    "dvg_pixel_proj": (_i, [_p, _p, _p, _l, _i, _i, _p]),
-    "dvg_convT_gather": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p]),
-    "dvg_channel_stats_rows": (_i, [_l]),
-    "dvg_channel_stats": (_i, [_p, _p, _l, _i, _i, _p]),
-    "dvg_bn_finalize": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _i, _d, _f, _f, _p, _i, _i, _p, _p]),
-    "dvg_channel_stats_pivot": (_i, [_p, _p, _p, _l, _i, _i, _p]),
-    "dvg_bn_finalize_pivot": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _d, _f, _f, _p, _i, _i, _p, _p]),
-    "dvg_bn_running_update": (_i, [_p, _p, _i, _i, _f, _f, _f, _p, _p, _p, _i, _p]),
-    "dvg_bn_act_apply": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "dvg_gemm_nt_bias_act": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "dvg_lstm_cell": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
-    "dvg_lstm_cell_pre": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
-    "dvg_lstm_cell_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
-    "dvg_lstm_cell_x": (_i, [_p, _i, _i, _p, _p, _p, _i, _p, _p, _p, _p, _i, _i, _p]),
-    "dvg_gru_cell": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
-    "dvg_gru_cell_pre": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _p]),
-    "dvg_rnn_cell": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
-    "dvg_gru_gates_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
-    "dvg_stem_gemm": (_i, [_p, _i, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _f, _p]),
-    "dvg_gp_precision": (_i, [_i, _i, _i]),
-    "dvg_gp_bwd_precision": (_i, [_i, _i]),
-    "dvg_gp_lds_bytes": (C.c_size_t, [_i, _i, _i]),
-    "dvg_gp_predict": (_i, [_p] * 14 + [_i, _i, _i, _i, _f, _i, _i, _p]),
-    "dvg_gp_step_group": (_i, [_i, _i, _i, _i]),
-    "dvg_gp_bwd_lds_bytes": (C.c_size_t, [_i, _i]),
-    "dvg_gp_bwd_chunk": (_i, [_i, _i]),
-    "dvg_gemm_tn": (_i, [_p] * 5 + [_i] * 8 + [_p]),
-    "dvg_gp_train_bwd": (_i, [_p] * 17 + [_i, _i, _i, _f, _i, _i, _p]),
-    "dvg_sum_steps_multi": (_i, [_p, _p, _p, _i, _i, _p]),
-    "dvg_gp_elbo": (_i, [_p, _p, _p, _p, _l, _l, _p, _p, _i, _i, _i, _i, _p]),
-    "dvg_gp_elbo_bwd": (_i, [_p, _p, _p, _p, _l, _l, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
-    "dvg_bn_act_bwd_rows": (_i, [_i, _i, _i, _i]),
-    "dvg_bn_act_bwd_reduce": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "dvg_bn_bwd_finalize": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _d, _i, _i, _i, _p]),
-    "dvg_bn_act_bwd_reduce_centered": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _i, _p]),
-    "dvg_bn_bwd_finalize_centered": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _d, _i, _i, _i, _p]),
-    "dvg_affine3_apply": (_i, [_p, _p, _p, _p, _p, _p, _l, _i, _p, _i, _i, _p]),
-    "dvg_act_bwd": (_i, [_p, _p, _p, _l, _i, _f, _p]),
-    "dvg_upsample2x_bwd": (_i, [_p, _p, _i, _i, _i, _i, _p]),
-    "dvg_group_sum": (_i, [_p, _p, _p, _i, _i, _l, _p]),
-    "dvg_colsum": (_i, [_p, _p, _i, _i, _i, _p]),
-    "dvg_wgrad_finish": (_i, [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i, _f, _p]),
-    "dvg_k4_to_w3": (_i, [_p, _p, _i, _i, _i, _i, _f, _p]),
-    "dvg_reduce_partials": (_i, [_p, _p, _i, _l, _p]),
-    "dvg_conv_wgrad_splits": (_i, [_i, _i, _i, _i, _i, _i]),
-    "dvg_conv_wgrad": (_i, [_i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "dvg_conv_wgrad_splits_multi": (_i, [_i, _i, _i, _i, _i, _i, _i]),
-    "dvg_conv_wgrad_multi": (_i, [_i, _i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p]),
-    "dvg_winograd_wgrad_operands": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _l, _l, _p]),
-    "dvg_winograd_wgrad_splits": (_i, [_l, _i, _i]),
-    "dvg_winograd_wgrad_gemm": (_i, [_p, _p, _p, _l, _i, _i, _p]),
-    "dvg_winograd_wgrad_gemm_items": (_i, [_p, _p, _i, _l, _p, _i, _i, _p]),
-    "dvg_winograd_wgrad_reduce": (_i, [_p, _i, _p, _i, _i, _p]),
-    "dvg_wgrad_thin_rows": (_i, [_i, _i, _i, _i]),
-    "dvg_wgrad_thin": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p]),
-    "dvg_lstm_gates_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _p]),
-    "dvg_nchw_to_nhwc": (_i, [_p, _p, _i, _i, _i, _i, _p]),
-    "dvg_nhwc_to_nchw": (_i, [_p, _p, _i, _i, _i, _i, _p]),
-    "dvg_zero_tick": (_i, [_p, _l, _p, _p, _p, _p, _p]),
-    "dvg_grad_sumsq_blocks": (_i, [_l]),
-    "dvg_grad_sumsq": (_i, [_p, _l, _p, _p]),
-    "dvg_grad_guard_finish": (_i, [_p, _i, _d, _i, _p, _p, _p]),
-    "dvg_adam_step_guarded": (_i, [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p, _p, _p, _p]),
-    "dvg_ema_update_blocks": (_i, [_l]),
-    "dvg_ema_update": (_i, [_p, _p, _l, _d, _p, _p, _p]),
-    "dvg_lr_schedule_tick": (_i, [_i, _i, _i, _i, _d, _d, _p, _p, _p]),
-    "dvg_adam_step_scheduled": (_i, [_p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p, _p, _p, _p, _p]),
-    "dvg_optim_step": (_i, [_i, _p, _p, _p, _p, _l, _f, _f, _f, _f, _f, _i, _p, _i, _p, _p, _p, _p, _p]),
-    "dvg_val_accumulate": (_i, [_p, _p, _p, _i, _i, _i, _p, _p, _p, _p]),
-    "dvg_frame_losses_blocks": (_i, [_l]),
-    "dvg_frame_losses": (_i, [_p, _p, _p, _p, _l, _i, _i, _p, _p, _p]),
-    "dvg_mse_sum_grad": (_i, [_p, _p, _p, _p, _l, _f, _p]),
-    "dvg_frame_losses_ext_blocks": (_i, [_i, _l, _i, _i]),
-    "dvg_frame_losses_ext": (_i, [_p, _p, _p, _p, _i, _i, _l, _i, _i, _i, _f, _p, _p, _p, _p]),
-    "dvg_frame_ssim_loss_blocks": (_i, [_i, _l, _i, _i]),
-    "dvg_frame_ssim_loss": (_i, [_p, _p, _p, _p, _i, _i, _l, _i, _i, _p, _i, _p, _p]),
-    "dvg_gp_var_norms": (_i, [_p, _p, _i, _i, _p]),
-    "dvg_gp_trigger_step": (_i, [_p, _i, _i, _i, _p, _i, _f, _p, _p, _p, _p, _i, _p]),
-    "dvg_gp_trigger_replay": (_i, [_p, _i, _p, _i, _f, _p, _p, _p]),
-    "dvg_gp_trigger_select": (_i, [_p, _p, _p, _p, _i, _i, _i, _l, _p, _p, _p, _p]),
-    # debug hooks (tools/diag_*.py)
-    "dvg_debug_set_clockbuf": (None, [_p, C.c_uint]),
-    "dvg_debug_set_gp_clockbuf": (None, [_p, C.c_uint]),
-    "dvg_debug_set_wgrad_clockbuf": (None, [_p, C.c_uint]),
-}
-
-_lock = threading.Lock()
-_lib = None
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "dvg_hip.h")
 
 
 class DvgLibraryError(RuntimeError):
     pass
+
+
+# the header's whole vocabulary; a pointer parameter, whatever it points to, binds as c_void_p
+_SCALAR = {"int": C.c_int, "long": C.c_long, "int64_t": C.c_int64, "float": C.c_float, "double": C.c_double,
+           "unsigned": C.c_uint, "unsigned int": C.c_uint}
+_RETURN = {"int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "const char*": C.c_char_p, "void": None}
+_TYPE_WORDS = frozenset("void char short int long float double signed unsigned const volatile struct union enum".split())
+_NAME = r"[A-Za-z_]\w*"
+_IDENTIFIER = re.compile(_NAME)
+_POINTER = re.compile(rf"{_NAME}(?: {_NAME})* ?(?:\* ?(?:const ?)?)+({_NAME})?")      # words, stars (each may be const), [name]
+_DECLARATION = re.compile(rf"(.+?[ *])({_NAME}) ?\(([^()]*)\)")                       # <ret> name(<params>): no nested parentheses
+_INTEGER = re.compile(r"[-+]?(?:0[xX][0-9a-fA-F]+|0|[1-9][0-9]*)")                    # no suffix, no octal
+_DIRECTIVE = re.compile(rf"# ?(include|ifdef|ifndef|endif|define)\b ?({_NAME})? ?(.*)")
+
+
+def _parameter(text: str):
+    """The ctypes class of one parameter (its name is optional); None when it is outside the grammar."""
+    if "*" in text:
+        m = _POINTER.fullmatch(text)
+        return C.c_void_p if m and m.group(1) not in _TYPE_WORDS else None
+    if text in _SCALAR:
+        return _SCALAR[text]
+    kind, _, name = text.rpartition(" ")
+    return _SCALAR.get(kind) if _IDENTIFIER.fullmatch(name) and name not in _TYPE_WORDS else None
+
+
+def parse_header(text: str, where: str = "include/dvg_hip.h"):
+    """(SIGNATURES, CONSTANTS) of a header made of comments, #include / #ifdef / #ifndef / #endif lines, an include guard,
+    `#define DVG_<NAME> <integer literal>` lines, at most one `extern "C" { }` block and statements `<ret> dvg_<name>(<params>);`
+    over the types above.  Anything else raises DvgLibraryError quoting the text: nothing is skipped."""
+    def refuse(why, quote):
+        raise DvgLibraryError(f"{where}: {why}: {quote}")
+    signatures, constants, code, guard = {}, {}, [], None
+    for line in re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S).splitlines():
+        line = " ".join(line.split())
+        if not line.startswith("#"):
+            code.append(line)
+            continue
+        m = _DIRECTIVE.fullmatch(line)
+        if not m:
+            refuse("preprocessor line not understood", line)
+        directive, name, value = m.groups()
+        if directive == "ifndef":
+            guard = name
+        if directive != "define" or (name == guard and not value):                   # `#ifndef G` + `#define G`: the include guard
+            continue
+        if not (name or "").startswith("DVG_") or not _INTEGER.fullmatch(value):
+            refuse("define is not `DVG_<NAME> <integer literal>`", line)
+        if constants.setdefault(name[4:], int(value, 0)) != int(value, 0):
+            refuse(f"define given twice with different values ({constants[name[4:]]} before)", line)
+    body = " ".join(" ".join(code).split())
+    m = re.fullmatch(r'extern "C" \{(.*)\}', body)
+    *statements, rest = (m.group(1) if m else body).split(";")
+    if rest.strip():
+        refuse("text after the last declaration", rest.strip())
+    for s in map(str.strip, statements):
+        m = _DECLARATION.fullmatch(s)
+        if m:
+            ret, name, params = re.sub(r" ?\* ?", "*", m.group(1)).strip(), m.group(2), m.group(3).strip()
+            args = [] if params == "void" else [_parameter(p.strip()) for p in params.split(",")]
+        if not m or ret not in _RETURN or not name.startswith("dvg_") or None in args:
+            refuse("not a declaration `<ret> dvg_<name>(<params>)` with int / long / int64_t / float / double / unsigned / pointer "
+                   "parameters, returning int / long / void / size_t / const char*", s)
+        if name in signatures:
+            refuse("entry point declared twice", s)
+        signatures[name] = (_RETURN[ret], args)
+    return signatures, constants
+
+
+def _read_header(path: str):
+    try:
+        with open(path) as f:
+            text = f.read()
+    except OSError as e:
+        raise DvgLibraryError(f"{path}: cannot read the C ABI header, and the binding exists nowhere else ({e})") from e
+    return parse_header(text, path)
+
+
+# name -> (restype, [argtypes]) of every entry point the header declares; NAME -> value of every `#define DVG_<NAME> <value>`
+SIGNATURES, CONSTANTS = _read_header(HEADER_PATH)
+
+_lock = threading.Lock()
+_lib = None
 
 
 def lib() -> C.CDLL:

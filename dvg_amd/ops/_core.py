@@ -4,13 +4,13 @@ from __future__ import annotations
 
 import torch
 
-from .._lib import check, lib
+from .._lib import CONSTANTS, check, lib
 
 
-ACT_NONE, ACT_LRELU, ACT_TANH, ACT_SIGMOID = 0, 1, 2, 3
+ACT_NONE, ACT_LRELU, ACT_TANH, ACT_SIGMOID = (CONSTANTS["ACT_" + k] for k in ("NONE", "LRELU", "TANH", "SIGMOID"))
 
 
-MODE_CONV3, MODE_CONV4S2, MODE_CONVT4S2 = 0, 1, 2
+MODE_CONV3, MODE_CONV4S2, MODE_CONVT4S2 = (CONSTANTS["MODE_" + k] for k in ("CONV3", "CONV4S2", "CONVT4S2"))
 
 
 def _stream() -> int:

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from .._derived import derived, register
-from .._lib import check, lib
+from .._lib import CONSTANTS, check, lib
 from ._core import ACT_LRELU, ACT_SIGMOID, ACT_TANH, _dev_f32, _p, _run, _stream, is_nhwc, nhwc_empty
 from .conv import SharedBlocks, _stats_buf, _wp_dims
 
@@ -262,10 +262,10 @@ def pairwise_frame_mse(samples, lo=None, hi=None):
     return out
 
 
-QUANT_TRUNC, QUANT_NEAREST = 0, 1                       # DVG_QUANT_*
-MOSAIC_BLACK, MOSAIC_RED, MOSAIC_GREEN = 0, 1, 2        # DVG_MOSAIC_* cell colours
-MOSAIC_SEL_NONE, MOSAIC_SEL_BEST, MOSAIC_SEL_PICK = 0, 1, 2
-MOSAIC_CELL_INTS = 8                                    # {src, base, stride, sel, b, k, colour, label}
+QUANT_TRUNC, QUANT_NEAREST = CONSTANTS["QUANT_TRUNC"], CONSTANTS["QUANT_NEAREST"]
+MOSAIC_BLACK, MOSAIC_RED, MOSAIC_GREEN = (CONSTANTS["MOSAIC_" + k] for k in ("BLACK", "RED", "GREEN"))       # cell colours
+MOSAIC_SEL_NONE, MOSAIC_SEL_BEST, MOSAIC_SEL_PICK = (CONSTANTS["MOSAIC_SEL_" + k] for k in ("NONE", "BEST", "PICK"))
+MOSAIC_CELL_INTS = CONSTANTS["MOSAIC_CELL_INTS"]        # {src, base, stride, sel, b, k, colour, label}
 
 
 def frame_mosaic(sources, cells, *, nc, H, W, F, R, Cc, cell_h, cell_w, pad_y=0, pad_x=0, oy=0, ox=0, best=None,

@@ -19,11 +19,13 @@ import zlib
 
 import numpy as np
 
-QUANT_TRUNC, QUANT_NEAREST = 0, 1
-BLACK, RED, GREEN = 0, 1, 2
-SEL_NONE, SEL_BEST, SEL_PICK = 0, 1, 2
-SRC_GT, SRC_POSTERIOR, SRC_SAMPLES = 0, 1, 2
-CELL_INTS = 8
+from ._lib import CONSTANTS
+
+QUANT_TRUNC, QUANT_NEAREST = CONSTANTS["QUANT_TRUNC"], CONSTANTS["QUANT_NEAREST"]
+BLACK, RED, GREEN = (CONSTANTS["MOSAIC_" + k] for k in ("BLACK", "RED", "GREEN"))
+SEL_NONE, SEL_BEST, SEL_PICK = (CONSTANTS["MOSAIC_SEL_" + k] for k in ("NONE", "BEST", "PICK"))
+SRC_GT, SRC_POSTERIOR, SRC_SAMPLES = 0, 1, 2            # the header numbers the sources in prose only
+CELL_INTS = CONSTANTS["MOSAIC_CELL_INTS"]
 _COLOURS = {None: BLACK, 'black': BLACK, 'red': RED, 'green': GREEN}
 # generate_frames.py:194-213, spelling included
 MAKE_GIFS_LABELS = ('Ground\ntsruth', 'Approx.\nposterior', 'Best SSIM', 'Random\nsample 1', 'Random\nsample 2',

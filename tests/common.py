@@ -1,5 +1,7 @@
 """Shared helpers for the parity tests (regenerate the seeded weights/inputs of make_golden.py)."""
 import importlib
+import os
+import re
 
 import torch
 
@@ -17,6 +19,28 @@ BACKBONE_CASES = {
     "vgg_128/eval": ("vgg", 128, 3, 1, False, 160),
     "dcgan_128/eval": ("dcgan", 128, 3, 2, False, 170),
 }
+
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def header_text():
+    """include/dvg_hip.h without its comments: what the host tests read the C ABI from (one place; shares no code with the
+    parser of dvg_amd/_lib.py, which tests/test_abi.py holds to it)."""
+    with open(os.path.join(ROOT, "include", "dvg_hip.h")) as f:
+        return re.sub(r"/\*.*?\*/|//[^\n]*", " ", f.read(), flags=re.S)
+
+
+def header_symbols():
+    return sorted(set(re.findall(r"\b(dvg_[a-zA-Z0-9_]+)\s*\(", header_text())))
+
+
+def header_declaration(name):
+    """(return type, [parameters]) of an entry point as the header spells them, whitespace collapsed; `(void)` gives []."""
+    m = re.search(rf"(?:^|[;{{\n])\s*([A-Za-z_][\w\s*]*?)\s*\b{name}\s*\(([^()]*)\)\s*;", header_text())
+    assert m, f"{name} is not declared in include/dvg_hip.h"
+    params = [" ".join(p.split()) for p in m.group(2).split(",")]
+    return " ".join(m.group(1).split()), [] if params == ["void"] else params
 
 
 def dev():

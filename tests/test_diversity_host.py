@@ -3,11 +3,11 @@ lines accept --diversity, and the fp64 reference the GPU tests compare against (
 numbers."""
 import ctypes
 import os
-import re
 
 import numpy as np
 
 from tests import diversity_ref as ref
+from tests.common import header_declaration
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -17,15 +17,8 @@ def test_library_exports_the_entry_point_and_the_header_agrees_with_the_binding(
     for name in ("libdvg_hip.so", "libdvg_hip_f32mfma.so"):
         h = ctypes.CDLL(os.path.join(os.path.dirname(_lib.LIB_PATH), name))
         assert hasattr(h, "dvg_pairwise_frame_mse"), name
-    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "dvg_hip.h")).read(), flags=re.S)
-    m = re.search(r"int\s+dvg_pairwise_frame_mse\s*\((.*?)\)\s*;", txt, flags=re.S)
-    assert m, "include/dvg_hip.h does not declare dvg_pairwise_frame_mse"
-    kinds = []
-    for arg in m.group(1).split(","):
-        arg = " ".join(arg.split())
-        kinds.append(ctypes.c_void_p if "*" in arg else {"int": ctypes.c_int, "long": ctypes.c_long}[arg.split()[0]])
-    restype, argtypes = _lib.SIGNATURES["dvg_pairwise_frame_mse"]
-    assert restype is ctypes.c_int and list(argtypes) == kinds
+    ret, params = header_declaration("dvg_pairwise_frame_mse")     # tests/test_abi.py holds every declaration's binding
+    assert ret == "int" and _lib.SIGNATURES["dvg_pairwise_frame_mse"][0] is ctypes.c_int and len(params) == 8
     assert _lib.lib().dvg_abi_version() == 9
 
 

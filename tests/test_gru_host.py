@@ -14,8 +14,7 @@ import torch
 
 from oracle import params
 from tests import gru_ref
-from tests.common import rel_err
-from tests.test_abi import header_symbols
+from tests.common import header_symbols, rel_err
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 FWD_BAR, GRAD_BAR = 1e-5, 2e-5         # the GPU tests' bars against fp64 (the project's own for the LSTM)

@@ -5,11 +5,11 @@ import argparse
 import ctypes
 import math
 import os
-import re
 
 import pytest
 
 from tests import lr_schedule_ref as ref
+from tests.common import header_declaration
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DECAYING = ("linear", "cosine")
@@ -160,22 +160,13 @@ def test_the_flags_are_not_part_of_the_resume_fingerprint():
 
 
 # ---- the entry points --------------------------------------------------------------------------------------------------------------
-def _header():
-    txt = open(os.path.join(ROOT, "include", "dvg_hip.h")).read()
-    return re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-
-
 @pytest.mark.parametrize("name", ["dvg_lr_schedule_tick", "dvg_adam_step_scheduled"])
 def test_header_binding_table_and_library_agree(name):
+    """Declared, returning int, exported by both builds, within ABI 9 (tests/test_abi.py holds the binding of every declaration
+    to the header, argument by argument)."""
     from dvg_amd import _lib
-    m = re.search(rf"\bint\s+{name}\s*\(([^)]*)\)\s*;", _header())
-    assert m, f"{name} is not declared in include/dvg_hip.h"
-    params = [a.strip() for a in m.group(1).split(",")]
-    restype, argtypes = _lib.SIGNATURES[name]
-    assert restype is ctypes.c_int and len(argtypes) == len(params), (name, len(argtypes), params)
-    for a, t in zip(params, argtypes):                                     # pointers bind as pointers, doubles as doubles
-        assert ("*" in a) == (t is ctypes.c_void_p), (name, a, t)
-        assert a.startswith("double ") == (t is ctypes.c_double), (name, a, t)
+    ret, params = header_declaration(name)
+    assert ret == "int" and _lib.SIGNATURES[name][0] is ctypes.c_int and len(_lib.SIGNATURES[name][1]) == len(params)
     assert hasattr(ctypes.CDLL(_lib.LIB_PATH), name), f"{name} is not exported by the built library"
     native = os.path.join(os.path.dirname(_lib.LIB_PATH), "libdvg_hip_f32mfma.so")
     assert hasattr(ctypes.CDLL(native), name)
