@@ -1100,6 +1100,22 @@ static int gemm_images_per_wg(int tw, int nt, int NB, int Hg, int Wg, int Cout) 
     return 1;
 }
 
+// Cout blocks per XCD group of the workgroup order: minimise (weight slabs of wb bytes + input tiles of ib bytes) one XCD's L2
+// fetches for its share of the launch; the result divides nblk_n, and a group holds at least one XCD's share of pixel tiles
+static int choose_nb_group(long tiles, int nblk_n, double wb, double ib) {
+    const double per_xcd = (double)tiles * nblk_n / 8.0;
+    int best = nblk_n;
+    double cost = 1e300;
+    for (int a = 1; a <= nblk_n; ++a) {
+        if (nblk_n % a) continue;
+        const double share_tiles = per_xcd / a;
+        if (share_tiles > (double)tiles) continue;   // more tiles than exist: the range would span several groups
+        const double c = a * wb + (share_tiles < 1.0 ? 1.0 : share_tiles) * ib;
+        if (c < cost) { cost = c; best = a; }
+    }
+    return best;
+}
+
 template <int MODE, int TI, int TH, int TW, int NT = 1, bool FIRST = false, bool PROJ = false>
 static int launch2(Igemm2Params p, int Hg, int Wg, float* ws, long ws_floats, hipStream_t stream) {
     using C = Cfg2<MODE, TI, TH, TW, NT, FIRST, PROJ>;
@@ -1121,23 +1137,8 @@ static int launch2(Igemm2Params p, int Hg, int Wg, float* ws, long ws_floats, hi
     p.clk = g_clk;
     p.clk_cap = g_clk_cap;
     const long wgs = (long)p.tiles_y * p.tiles_x * p.tiles_n * p.nblk_n * (MODE == M2_CONVT4S2 ? 4 : 1);
-    {
-        // Cout blocks per XCD group: minimise (weight slabs + input tiles) one XCD's L2 fetches for its share of the
-        // launch; a must divide nblk_n, and a group must hold at least one XCD's share of pixel tiles
-        const long tiles = (long)p.tiles_y * p.tiles_x * p.tiles_n;
-        const double per_xcd = (double)tiles * p.nblk_n / 8.0;
-        const double wb = (double)C::NTAPS * (p.C1 + p.C2) * C::BN * 4, ib = (double)C::BM * (p.C1 + p.C2) * 4;
-        int best = p.nblk_n;
-        double cost = 1e300;
-        for (int a = 1; a <= p.nblk_n; ++a) {
-            if (p.nblk_n % a) continue;
-            const double share_tiles = per_xcd / a;
-            if (share_tiles > (double)tiles) continue;   // more tiles than exist: the range would span several groups
-            const double c = a * wb + (share_tiles < 1.0 ? 1.0 : share_tiles) * ib;
-            if (c < cost) { cost = c; best = a; }
-        }
-        p.nb_group = best;
-    }
+    p.nb_group = choose_nb_group((long)p.tiles_y * p.tiles_x * p.tiles_n, p.nblk_n,
+                                 (double)C::NTAPS * (p.C1 + p.C2) * C::BN * 4, (double)C::BM * (p.C1 + p.C2) * 4);
     const int nchunks = (p.C1 + p.C2) / C::KC;
     int Ho, Wo;
     if (MODE == M2_CONV3 || MODE == M2_GEMM) { Ho = p.H; Wo = p.W; }
@@ -1217,6 +1218,385 @@ static int gemm_tile(int NB, int Hg, int Wg, int Cout, int* tw, int* nt) {
         *nt = 2;
     }
     return 0;
+}
+
+// ---- WX: the 3x3 conv with 1-D Winograd F(2,3) along x inside the kernel (bf16-triple build only) ---------------------------
+// GEMM rows are output pixel PAIRS (x = 2 j, 2 j + 1).  Per kernel row r the two outputs of a pair come from four products
+// instead of six: with d the input row and g the kernel row,
+//     v0 = d[2j] - d[2j+2]   v1 = d[2j+1] + d[2j+2]   v2 = d[2j+2] - d[2j+1]   v3 = d[2j+1] - d[2j+3]
+//     u0 = g0                u1 = (g0 + g1 + g2) / 2  u2 = (g0 - g1 + g2) / 2  u3 = g2
+//     m_f = sum over r, channels of v_f u_f           y[2j] = m0 + m1 + m2     y[2j+1] = m1 - m2 - m3
+// i.e. 12 "taps" (r, f) instead of 18 products per pair: 2/3 of the direct form's MFMAs.  Tile: 8 rows x 8 pairs (8 x 16
+// pixels), 2 x 2 waves, a wave holds 32 pairs x 32 channels x the four positions f in four accumulator tiles (64 registers, what
+// the 8 x 16 direct tile holds); the output transform is lane-local.  A stage = (16-channel chunk, kernel row r): its four taps'
+// weights (24.5 KB; dvg_pack_conv_weight_wx: tap = 4 r + f, so a stage's tile is one contiguous run) are staged per stage, the
+// four A planes v_f of all 10 halo rows (36 KB) once per chunk:
+//   stage r = 0   the next chunk's halo tile d is loaded (FIRST: the first layer's weights of its 16 channels)
+//   stage r = 1   d (FIRST: computed from the frame patch, as first_tile does in the direct kernel) goes to an fp32 staging
+//                 tile (12 KB) under the stage's MFMAs: every halo pixel is loaded / computed ONCE although the pairs' windows
+//                 overlap
+//   stage r = 2   v_f = d[a_f] +- d[b_f] in fp32 from the staging tile, split into bf16 triples (in registers while the taps
+//                 run), written over the A planes once every wave has read the chunk's last fragments
+// Thread slot (pair-row rp, f, channel quad q) of the transform: f and q are the thread's own in every pass, and the planes lie
+// 80 rows + 32 bytes apart, so that the 16 lanes of a ds_write_b64 group (4 f x 4 q of one pair) tile a 128-byte bank window.
+// The lane -> pair map of the fragments is the identity (a wave's 32 pairs are 32 consecutive 112-byte rows: the 16 rows of a
+// b128 read group are distinct mod 16), vertical 2 x 2 pool partners are register blocks (0, 1) and (2, 3), the partners in x are
+// the two outputs of one pair.  No split-K, no statistics.
+#if DVG_BF16X3
+struct CfgWX {
+    static constexpr int TH = 8, TP = 8, TW = 2 * TP, HH = TH + 2, HW = TW + 2, HP = HH * HW;
+    static constexpr int LD = 28, LDB = 24, WROW = DVG_WROW;
+    static constexpr int PLANE = HH * TP * LD + 8;                // floats between the planes of two positions
+    static constexpr int A_FLOATS = 4 * PLANE, B_FLOATS = 4 * 64 * LDB;
+    static constexpr int NLB = 4 * 64 * WROW / 4 / 256;           // float4s of a stage's weight tile per thread (6)
+    static constexpr int ND = (HP * 4 + 255) / 256;               // float4s of the halo tile per thread (3)
+    static constexpr int D_FLOATS = ND * 64 * 16;                 // staging tile, padded to whole store passes
+    static constexpr int NX = 4 * HH * TP * 4 / 256;              // transform passes (5, exactly)
+    static constexpr int FP_W = HW + 2, FP_FLOATS = (HH + 2) * FP_W;
+    static constexpr int lds_bytes(bool first) { return (A_FLOATS + B_FLOATS + D_FLOATS + (first ? FP_FLOATS : 0)) * 4; }
+    static_assert(4 * HH * TP * 4 % 256 == 0 && 4 * 64 * WROW / 4 % 256 == 0, "whole passes");
+};
+
+template <bool FIRST>
+__global__ __launch_bounds__(256, 2) void conv3_wx_kernel(const Igemm2Params p) {
+    using C = CfgWX;
+    constexpr int LD = C::LD, LDB = C::LDB, NLB = C::NLB, ND = C::ND, NX = C::NX;
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* const As = smem;
+    float* const Bs = As + C::A_FLOATS;
+    float* const Ds = Bs + C::B_FLOATS;
+    float* const Fp = Ds + C::D_FLOATS;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1, l31 = lane & 31, hh = lane >> 5;
+
+    // workgroup order as conv_igemm2_kernel: Cout block within its group fastest, then pixel tile, then group
+    const unsigned lid = xcd_remap(blockIdx.x, gridDim.x);
+    const int tiles_total = p.tiles_x * p.tiles_y * p.tiles_n;
+    const unsigned lr = lid / p.nb_group;
+    const int nb = (int)(lr / tiles_total) * p.nb_group + (int)(lid % p.nb_group);
+    unsigned t = lr % tiles_total;
+    const int tx_i = t % p.tiles_x; t /= p.tiles_x;
+    const int ty_i = t % p.tiles_y; t /= p.tiles_y;
+    const int n0 = (int)t, y0 = ty_i * C::TH, x0 = tx_i * C::TW, yin0 = y0 - 1, xin0 = x0 - 1, nb0 = nb * 64;
+
+    const int a_base = (wm * 32 + l31) * LD + hh * 4;
+    const int b_base = (wn * 32 + l31) * LDB + (hh ^ ((l31 >> 3) & 1)) * 4;
+
+    f32x16 acc[4];      // [position f]
+#pragma unroll
+    for (int f = 0; f < 4; ++f)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[f][i] = 0.f;
+
+    // halo slot i of this thread: pixel (tid + 256 i) >> 2 of the 10 x 18 tile, channel quad tid & 3
+    long offx[FIRST ? 1 : ND];
+    unsigned okmask = 0;
+#pragma unroll
+    for (int i = 0; i < ND; ++i) {
+        const int hp = (tid + i * 256) >> 2;
+        const int yy = yin0 + hp / C::HW, xx = xin0 + hp % C::HW;
+        const bool ok = hp < C::HP && (unsigned)yy < (unsigned)p.H && (unsigned)xx < (unsigned)p.W;
+        okmask |= ok ? (1u << i) : 0u;
+        if constexpr (!FIRST) offx[i] = ok ? (((long)n0 * p.H + yy) * p.W + xx) * p.C1 + (tid & 3) * 4 : 0;
+    }
+    // transform slot of this thread: position f, channel quad q, pair-row rp = (tid >> 4) + 16 pass.  v_f = d[a_f] + sg d[b_f]
+    const int xf = (tid >> 2) & 3, xq = tid & 3;
+    const int x_ia = xf == 0 ? 0 : (xf == 2 ? 2 : 1), x_ib = xf == 2 ? 1 : (xf == 3 ? 3 : 2);
+    const float x_sg = xf == 1 ? 1.f : -1.f;
+    const int x_pix = (tid >> 7) * C::HW + 2 * ((tid >> 4) & 7);       // halo pixel 2 j of pass 0's pair
+    const int x_da = (x_pix + x_ia) * 16 + xq * 4, x_db = (x_pix + x_ib) * 16 + xq * 4;
+    const int x_st = xf * C::PLANE + (tid >> 4) * LD + (xq >> 1) * 4 + (xq & 1) * 2;
+
+    f32x4 fw[FIRST ? 11 : 1];      // FIRST: [tap 0..8] weights of this thread's four channels, [9] scale, [10] shift
+    f32x4 ra[ND], rb[NLB];
+    auto gload_d = [&](int c0) {
+        if constexpr (FIRST) {
+            const float* w = p.first_w + c0 + (tid & 3) * 4;                      // [9 taps][64 channels]
+#pragma unroll
+            for (int tp = 0; tp < 9; ++tp) fw[tp] = *reinterpret_cast<const f32x4*>(w + tp * 64);
+            fw[9] = *reinterpret_cast<const f32x4*>(p.first_scale + c0 + (tid & 3) * 4);
+            fw[10] = *reinterpret_cast<const f32x4*>(p.first_shift + c0 + (tid & 3) * 4);
+        } else {
+            const float* src = p.x + c0;
+#pragma unroll
+            for (int i = 0; i < ND; ++i)      // the ADDRESS is selected, not the data (dvg_zero_slot)
+                ra[i] = *reinterpret_cast<const f32x4*>(((okmask >> i) & 1u) ? src + offx[i] : dvg_zero_slot);
+        }
+    };
+    auto store_d = [&]() {
+        if constexpr (FIRST) {
+            // the halo tile's channels of vgg_layer(1, 64) from the frame patch, as conv_igemm2_kernel's first_tile
+#pragma unroll
+            for (int i = 0; i < ND; ++i) {
+                const int hp = min((tid + i * 256) >> 2, C::HP - 1);
+                const float* f = Fp + (hp / C::HW) * C::FP_W + hp % C::HW;
+                f32x4 v = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int tp = 0; tp < 9; ++tp) {
+                    const float px = f[(tp / 3) * C::FP_W + tp % 3];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = fmaf(fw[tp][e], px, v[e]);
+                }
+                const float okf = (float)((okmask >> i) & 1u);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float a = v[e] * fw[9][e] + fw[10][e];
+                    v[e] = fmaxf(a, a * p.first_slope) * okf;
+                }
+                ra[i] = v;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < ND; ++i) reinterpret_cast<f32x4*>(Ds)[tid + i * 256] = ra[i];
+    };
+    auto gload_b = [&](int chunk, int r) {
+        const float* tile = p.w + (((size_t)chunk * (p.Cout >> 6) + nb) * 12 + r * 4) * (64 * C::WROW);
+#pragma unroll
+        for (int j = 0; j < NLB; ++j) rb[j] = reinterpret_cast<const f32x4*>(tile)[tid + j * 256];
+    };
+    auto store_b = [&]() {
+#pragma unroll
+        for (int j = 0; j < NLB; ++j) reinterpret_cast<f32x4*>(Bs)[tid + j * 256] = rb[j];      // the packed tile IS the LDS image
+    };
+    auto xform_read = [&](u32x2_t (&pa)[NX][3]) {
+#pragma unroll
+        for (int s = 0; s < NX; ++s) {
+            const f32x4 a = *reinterpret_cast<const f32x4*>(&Ds[x_da + s * 2 * C::HW * 16]);
+            const f32x4 b = *reinterpret_cast<const f32x4*>(&Ds[x_db + s * 2 * C::HW * 16]);
+            f32x4 v;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = fmaf(x_sg, b[e], a[e]);      // a +- b, one rounding
+            unsigned t0, t1, t2;
+            bf16x3_split_pair(v[0], v[1], t0, t1, t2);
+            pa[s][0][0] = t0; pa[s][1][0] = t1; pa[s][2][0] = t2;
+            bf16x3_split_pair(v[2], v[3], t0, t1, t2);
+            pa[s][0][1] = t0; pa[s][1][1] = t1; pa[s][2][1] = t2;
+        }
+    };
+    auto xform_store = [&](const u32x2_t (&pa)[NX][3]) {
+#pragma unroll
+        for (int s = 0; s < NX; ++s)
+#pragma unroll
+            for (int j = 0; j < 3; ++j) *reinterpret_cast<u32x2_t*>(&As[x_st + s * 16 * LD + j * 8]) = pa[s][j];
+    };
+
+    if constexpr (FIRST) {
+        const float* fr = p.first_frame + (size_t)n0 * p.H * p.W;
+        for (int i = tid; i < C::FP_FLOATS; i += 256) {
+            const int yy = yin0 - 1 + i / C::FP_W, xx = xin0 - 1 + i % C::FP_W;
+            Fp[i] = ((unsigned)yy < (unsigned)p.H && (unsigned)xx < (unsigned)p.W) ? fr[(size_t)yy * p.W + xx] : 0.f;   // layer 1's padding
+        }
+        __syncthreads();
+    }
+    gload_d(0);
+    gload_b(0, 0);
+    store_d();
+    store_b();
+    __syncthreads();
+    {
+        u32x2_t pa[NX][3];
+        xform_read(pa);
+        xform_store(pa);
+    }
+    __syncthreads();
+
+    // One stage = the four taps (r, f = 0..3) of a chunk.  R, what the stage prepares for its successors and whether it has one
+    // are compile-time: the loop below is peeled, the loads and stores inside it are unconditional (see conv_igemm2_kernel).
+    auto stage = [&](const int chunk, auto r_c, auto next_chunk_c, auto has_next_c) __attribute__((always_inline)) {
+        constexpr int R = decltype(r_c)::value;
+        constexpr bool NEXT_CHUNK = decltype(next_chunk_c)::value, HAS_NEXT = decltype(has_next_c)::value;
+        constexpr bool LOAD_D = NEXT_CHUNK && R == 0, STORE_D = NEXT_CHUNK && R == 1, XFORM = NEXT_CHUNK && R == 2;
+        if constexpr (LOAD_D) gload_d((chunk + 1) * 16);
+        if constexpr (HAS_NEXT) gload_b(R == 2 ? chunk + 1 : chunk, (R + 1) % 3);
+        // the staging tile has no reader between the transform of the previous chunk (stage 2) and the one of this chunk: d is
+        // written here, under the stage's MFMAs, not behind the barrier of its last tap
+        if constexpr (STORE_D) store_d();
+        u32x2_t pa[XFORM ? NX : 1][3];
+        if constexpr (XFORM) xform_read(pa);
+
+        f32x4 fa[2][3], fb[2][3];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            fa[0][j] = *reinterpret_cast<const f32x4*>(&As[a_base + R * C::TP * LD + j * 8]);
+            fb[0][j] = *reinterpret_cast<const f32x4*>(&Bs[b_base + j * 8]);
+        }
+#pragma unroll
+        for (int tt = 0; tt < 4; ++tt) {
+            const int cur = tt & 1, nxt = cur ^ 1;
+            if (tt + 1 < 4) {
+#pragma unroll
+                for (int j = 0; j < 3; ++j) {
+                    fa[nxt][j] = *reinterpret_cast<const f32x4*>(&As[a_base + (tt + 1) * C::PLANE + R * C::TP * LD + j * 8]);
+                    fb[nxt][j] = *reinterpret_cast<const f32x4*>(&Bs[b_base + (tt + 1) * 64 * LDB + j * 8]);
+                }
+            }
+            if (HAS_NEXT && tt == 3) {
+                // the last tap's fragments are in registers: after this barrier the next stage's tiles may be written
+                __syncthreads();
+                if constexpr (XFORM) xform_store(pa);
+                store_b();
+            }
+            // six bf16 MFMAs per K = 16 slab, small terms first: (l,h) (m,m) (h,l) (m,h) (h,m) (h,h)
+            auto mm = [&](int pa_, int pb_) {
+                acc[tt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8_t, fa[cur][pa_]),
+                                                                  __builtin_bit_cast(bf16x8_t, fb[cur][pb_]), acc[tt], 0, 0, 0);
+            };
+            mm(2, 0);
+            mm(1, 1);
+            mm(0, 2);
+            mm(1, 0);
+            mm(0, 1);
+            mm(0, 0);
+            // pin the software pipeline (see conv_igemm2_kernel): one ds_read_b128 per MFMA, a tap ahead of its consumer
+            constexpr int NREAD = 6, NMFMA = 6;
+            constexpr int NVMEM = (LOAD_D ? (FIRST ? 11 : ND) : 0) + (HAS_NEXT ? NLB : 0), VPT = (NVMEM + 2) / 3;
+            // tap 0's own fragments, behind the stage's other LDS reads (the transform's, FIRST: the frame patch's 9 per halo slot)
+            if (tt == 0) __builtin_amdgcn_sched_group_barrier(0x100, NREAD + (XFORM ? 2 * NX : 0) + (STORE_D && FIRST ? 9 * ND : 0), 0);
+            if (tt + 1 < 4) {
+#pragma unroll
+                for (int r = 0; r < NREAD; ++r) {
+                    __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                }
+                if (VPT > 0) __builtin_amdgcn_sched_group_barrier(0x020, VPT, 0);
+            } else if (HAS_NEXT) {      // the next stage's ds_writes between the last tap's MFMAs
+                constexpr int NW = NLB + (XFORM ? 3 * NX : 0);
+#pragma unroll
+                for (int r = 0; r < NW; ++r) {
+                    if (r < NMFMA) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x200, 1, 0);
+                }
+            } else if (!HAS_NEXT) {
+                __builtin_amdgcn_sched_group_barrier(0x008, NMFMA, 0);
+            }
+        }
+        if constexpr (HAS_NEXT) __syncthreads();
+    };
+    using std::integral_constant;
+    using T_ = integral_constant<bool, true>;
+    using F_ = integral_constant<bool, false>;
+    // progress-based wave priority, as conv_igemm2_kernel's 9-tap layers
+    int st = 0;
+    auto set_prio = [&]() {
+        switch (st++ & 3) {
+            case 0: __builtin_amdgcn_s_setprio(3); break;
+            case 1: __builtin_amdgcn_s_setprio(2); break;
+            case 2: __builtin_amdgcn_s_setprio(1); break;
+            default: __builtin_amdgcn_s_setprio(0); break;
+        }
+    };
+    const int nchunks = p.C1 / 16;
+    int chunk = 0;
+    for (; chunk + 1 < nchunks; ++chunk) {
+        set_prio();
+        stage(chunk, integral_constant<int, 0>{}, T_{}, T_{});
+        set_prio();
+        stage(chunk, integral_constant<int, 1>{}, T_{}, T_{});
+        set_prio();
+        stage(chunk, integral_constant<int, 2>{}, T_{}, T_{});
+    }
+    set_prio();
+    stage(chunk, integral_constant<int, 0>{}, F_{}, T_{});
+    set_prio();
+    stage(chunk, integral_constant<int, 1>{}, F_{}, T_{});
+    set_prio();
+    stage(chunk, integral_constant<int, 2>{}, F_{}, F_{});
+    __builtin_amdgcn_s_setprio(0);
+
+    // ---- epilogue: the lane-local output transform, then as conv_igemm2_kernel on the pair's two pixels --------------
+    const int c = nb0 + wn * 32 + l31;
+    const float sc = p.scale ? p.scale[c] : 1.f, sf = p.shift ? p.shift[c] : 0.f;
+    const bool want_y = !FIRST || n0 >= p.y_from;      // workgroup-uniform
+    float* const yb = p.y + (size_t)n0 * p.H * p.W * p.Cout + c;
+    float* const pb = p.y_pool ? p.y_pool + (size_t)n0 * (p.H >> 1) * (p.W >> 1) * p.Cout + c : nullptr;
+    const float* ab = nullptr;
+    if (p.addend) ab = p.addend + (size_t)(addend_image(p.add_map, p.add_B, n0)) * p.H * p.W * p.Cout + c;
+    auto epilogue = [&](auto act_c) {
+        constexpr int ACT = decltype(act_c)::value;  // -1: generic (runtime p.act)
+        float v[2][16];
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            v[0][reg] = (acc[0][reg] + acc[1][reg]) + acc[2][reg];
+            v[1][reg] = (acc[1][reg] - acc[2][reg]) - acc[3][reg];
+        }
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int m = wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * hh;      // pair m of the tile: row m >> 3, pair m & 7
+            const int off = ((y0 + (m >> 3)) * p.W + x0 + 2 * (m & 7)) * p.Cout;
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                float u = v[e][reg];
+                if (ab != nullptr) u += ab[off + e * p.Cout];
+                u = u * sc + sf;
+                if constexpr (ACT == DVG_ACT_LRELU) u = u > 0.f ? u : u * p.slope;
+                else if constexpr (ACT != DVG_ACT_NONE) u = apply_act(u, p.act, p.slope);
+                v[e][reg] = u;
+                if (want_y) yb[off + e * p.Cout] = u;
+            }
+        }
+        if (pb != nullptr) {
+            // a 2 x 2 window = the two outputs of one pair in two vertically adjacent rows: register blocks (0, 1) and (2, 3)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                if (((reg >> 2) & 1) == 0) {
+                    const int m = wm * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * hh;
+                    const float mx = fmaxf(fmaxf(v[0][reg], v[1][reg]), fmaxf(v[0][reg + 4], v[1][reg + 4]));
+                    pb[(((y0 + (m >> 3)) >> 1) * (p.W >> 1) + (x0 >> 1) + (m & 7)) * p.Cout] = mx;
+                }
+            }
+        }
+    };
+    if (p.act == DVG_ACT_LRELU) epilogue(std::integral_constant<int, DVG_ACT_LRELU>{});
+    else if (p.act == DVG_ACT_NONE) epilogue(std::integral_constant<int, DVG_ACT_NONE>{});
+    else epilogue(std::integral_constant<int, -1>{});
+}
+
+template <bool FIRST>
+static int launch_wx(Igemm2Params p, hipStream_t stream) {
+    using C = CfgWX;
+    p.tiles_y = p.H / C::TH;
+    p.tiles_x = p.W / C::TW;
+    p.tiles_n = p.N;
+    p.nblk_n = p.Cout / 64;
+    const long tiles = (long)p.tiles_y * p.tiles_x * p.tiles_n;
+    p.nb_group = choose_nb_group(tiles, p.nblk_n, 12.0 * p.C1 * 64 * 4, (double)C::TH * C::TW * p.C1 * 4);
+    static bool attr_set = false;
+    if (!attr_set) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3_wx_kernel<FIRST>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, C::lds_bytes(FIRST));
+        if (e != hipSuccess) return fail(DVG_ERR_HIP, "hipFuncSetAttribute: %s", hipGetErrorString(e));
+        attr_set = true;
+    }
+    hipLaunchKernelGGL((conv3_wx_kernel<FIRST>), dim3((unsigned)(tiles * p.nblk_n)), dim3(256), C::lds_bytes(FIRST), stream, p);
+    return check_launch("conv3_wx");
+}
+#endif  // DVG_BF16X3
+
+// dst[chunk][co / 64][tap = 4 r + f][co % 64][row of 16 k-values]  <-  u_f of kernel row r of w[co][ci][r][0..2] (see WX above).
+// The rows with a zero coefficient are written out by hand: no product with a literal zero.
+__global__ void pack_wx_kernel(const float* __restrict__ src, float* __restrict__ dst, int cout, int cin) {
+    const long total = (long)cout * cin * 12 / 2;
+    const int nblk = cout >> 6;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        const int k = (int)(i & 7) * 2;
+        long r = i >> 3;
+        const int co = r % cout; r /= cout;
+        const int tap = r % 12;
+        const int chunk = r / 12;
+        const int row = tap >> 2, f = tap & 3;
+        float u[2];
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+            const float* g = src + (((long)co * cin + chunk * 16 + k + e) * 3 + row) * 3;
+            if (f == 0) u[e] = g[0];
+            else if (f == 1) u[e] = ((g[0] + g[1]) + g[2]) * 0.5f;
+            else if (f == 2) u[e] = ((g[0] - g[1]) + g[2]) * 0.5f;
+            else u[e] = g[2];
+        }
+        wrow_store_pair(dst, (((size_t)chunk * nblk + (co >> 6)) * 12 + tap) * 64 + (co & 63), co & 63, k, u[0], u[1]);
+    }
+    wrow_drain();
 }
 
 __global__ void pack_k16_kernel(const float* __restrict__ src, float* __restrict__ dst, int cout, int cin, int kh,
@@ -1383,6 +1763,76 @@ extern "C" int dvg_conv3x3_first_pair(const float* frame, const float* w0, const
     DVG_REQUIRE(H % 8 == 0 && W % 16 == 0 && (long)N * (H / 8) * (W / 16) * (Cout / 64) >= 512, DVG_ERR_SHAPE,
                 "dvg_conv3x3_first_pair: H %% 8, W %% 16 and >= 512 workgroups needed (N=%d H=%d W=%d Cout=%d)", N, H, W, Cout);
     return launch2<M2_CONV3, 1, 8, 16, 1, true>(p, H, W, nullptr, 0, (hipStream_t)stream);
+}
+
+// ---- the WX form (1-D Winograd F(2,3) along x inside the kernel: conv3_wx_kernel) ----------------------------------------
+extern "C" int dvg_pack_conv_weight_wx(const float* w, float* w_packed, int cout, int cin, void* stream) {
+    DVG_REQUIRE(w && w_packed, DVG_ERR_NULL, "dvg_pack_conv_weight_wx: NULL pointer");
+    DVG_REQUIRE(cout > 0 && cout % 64 == 0 && cin > 0 && cin % 16 == 0, DVG_ERR_SHAPE,
+                "dvg_pack_conv_weight_wx: Cin must be a multiple of 16, Cout of 64");
+    DVG_REQUIRE(aligned16(w_packed), DVG_ERR_ALIGN, "dvg_pack_conv_weight_wx: w_packed must be 16-byte aligned");
+    const long total = (long)cout * cin * 12 / 2;      // threads: one per pair of k-values
+    hipLaunchKernelGGL(pack_wx_kernel, dim3(grid_for(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, w, w_packed, cout, cin);
+    return check_launch("dvg_pack_conv_weight_wx");
+}
+
+// preconditions the two WX entry points share: an error before the launch
+static int checks_wx(const Igemm2Params& p, const char* who) {
+    DVG_REQUIRE(p.N > 0 && p.H > 0 && p.W > 0, DVG_ERR_SHAPE, "%s: empty shape", who);
+    DVG_REQUIRE(p.C1 > 0 && p.C1 % 16 == 0 && p.C2 == 0 && p.skip == nullptr && !p.upsample, DVG_ERR_SHAPE,
+                "%s: Cin=%d must be a multiple of 16; no concat operand, no upsampling", who, p.C1 + p.C2);
+    DVG_REQUIRE(p.Cout > 0 && p.Cout % 64 == 0, DVG_ERR_SHAPE, "%s: Cout=%d must be a multiple of 64", who, p.Cout);
+    DVG_REQUIRE(p.H % 8 == 0 && p.W % 16 == 0, DVG_ERR_SHAPE, "%s: H=%d must be a multiple of 8, W=%d of 16", who, p.H, p.W);
+    DVG_REQUIRE((long)p.H * p.W * p.Cout < (1L << 31), DVG_ERR_SHAPE, "%s: image of %d x %d x %d floats too large", who, p.H, p.W, p.Cout);
+    DVG_REQUIRE(aligned16(p.x) && aligned16(p.w) && aligned16(p.y) && aligned16(p.y_pool) && aligned16(p.addend), DVG_ERR_ALIGN,
+                "%s: pointers must be 16-byte aligned", who);
+    DVG_REQUIRE(p.act >= DVG_ACT_NONE && p.act <= DVG_ACT_SIGMOID, DVG_ERR_SHAPE, "%s: bad act", who);
+    DVG_REQUIRE(DVG_BF16X3 != 0, DVG_ERR_SHAPE, "%s: the f32-MFMA build has no WX kernel", who);
+    return DVG_OK;
+}
+
+extern "C" int dvg_conv3x3_bn_act_wx(const float* x, const float* skip, const float* w_wx, const float* scale,
+                                     const float* shift, float* y, float* y_pool, int N, int H, int W, int C1, int C2,
+                                     int Cout, int upsample_x, int act, float slope, const float* addend,
+                                     const int* addend_map, int addend_block, void* stream) {
+    const char* who = "dvg_conv3x3_bn_act_wx";
+    DVG_REQUIRE(x && w_wx && y, DVG_ERR_NULL, "%s: x/w/y must not be NULL", who);
+    Igemm2Params p{x, skip, w_wx, scale, shift, y, y_pool, nullptr, N, H, W, C1, C2, Cout, upsample_x ? 1 : 0, act, slope,
+                   0, 0, 0, 0, 0, 1, 0, nullptr};
+    p.addend = addend;
+    p.add_map = addend ? addend_map : nullptr;
+    p.add_B = addend_block;
+    DVG_REQUIRE(p.add_map == nullptr || (addend_block > 0 && N % addend_block == 0), DVG_ERR_SHAPE, "%s: addend_block must divide N", who);
+    DVG_REQUIRE(addend == nullptr || y_pool == nullptr, DVG_ERR_SHAPE, "%s: addend excludes the pooled output", who);
+    if (int e = checks_wx(p, who)) return e;
+#if DVG_BF16X3
+    return launch_wx<false>(p, (hipStream_t)stream);
+#else
+    return DVG_ERR_SHAPE;
+#endif
+}
+
+extern "C" int dvg_conv3x3_first_pair_wx(const float* frame, const float* w0, const float* scale0, const float* shift0,
+                                         const float* w1_wx, const float* scale1, const float* shift1, float* y, float* y_pool,
+                                         int N, int H, int W, int Cout, int act, float slope, int y_from, void* stream) {
+    const char* who = "dvg_conv3x3_first_pair_wx";
+    DVG_REQUIRE(frame && w0 && scale0 && shift0 && w1_wx, DVG_ERR_NULL, "%s: NULL pointer", who);
+    DVG_REQUIRE(y_from >= 0 && y_from <= N && (y_from == 0 || y_pool != nullptr) && (y != nullptr || y_from == N), DVG_ERR_SHAPE,
+                "%s: y_from=%d needs 0 <= y_from <= N, a pooled output when > 0, y unless == N", who, y_from);
+    DVG_REQUIRE(aligned16(w0) && aligned16(scale0) && aligned16(shift0) && aligned16(y), DVG_ERR_ALIGN,
+                "%s: pointers must be 16-byte aligned", who);
+    // y holds the images [y_from, N): biased so that the kernel's image index applies (never dereferenced below y_from)
+    float* const y_biased = y ? y - (size_t)y_from * H * W * Cout : y_pool;
+    Igemm2Params p{frame /* never read as an activation */, nullptr, w1_wx, scale1, shift1, y_biased, y_pool, nullptr, N, H, W, 64, 0, Cout, 0,
+                   act, slope, 0, 0, 0, 0, 0, 1, 0, nullptr};
+    p.first_frame = frame; p.first_w = w0; p.first_scale = scale0; p.first_shift = shift0; p.first_slope = 0.2f;
+    p.y_from = y_from;
+    if (int e = checks_wx(p, who)) return e;
+#if DVG_BF16X3
+    return launch_wx<true>(p, (hipStream_t)stream);
+#else
+    return DVG_ERR_SHAPE;
+#endif
 }
 
 extern "C" int dvg_conv4x4s2_bn_act_v2(const float* x, const float* w_k16, const float* scale, const float* shift,

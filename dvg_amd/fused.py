@@ -164,6 +164,21 @@ def block_weight(kind, weight, lo=None, hi=None):
     return weight if blk.mode is None else weights.packed(weight, bool(blk.finish[0]), lo, hi, blk.cat)
 
 
+# The WX form of a direct 3x3 layer (ops.conv3x3_wx / ops.conv3x3_first_pair_wx: 1-D Winograd F(2,3) along x inside the kernel,
+# 2/3 of the MFMAs).  It is an ENERGY choice - fewer matrix-pipe issues, more VALU and LDS-store work per chunk - so it is taken
+# only where the launches are captured for several chains in flight (docs/DESIGN_NOTES_conv3_wx.md).  CONV3_WX = False: never.
+CONV3_WX = True
+CONV3_WX_MIN_WGS = 256      # one workgroup per CU, as the other energy tiles (DVG_TILE16_MIN_WGS)
+
+
+def conv3_wx_applies(n, cin, h, w, cout, *modules) -> bool:
+    """Eval mode, no grad, ENERGY tile policy, a 3x3 stride-1 conv with 64 input channels on a map at least 64 wide, at least
+    CONV3_WX_MIN_WGS workgroups."""
+    return (CONV3_WX and not torch.is_grad_enabled() and not any(m.training for m in modules)
+            and ops.lib().dvg_tile_policy() == 1 and cin == 64 and w >= 64 and ops.wx_ok(n, cin, h, w, cout)
+            and ops.wx_workgroups(n, h, w, cout) >= CONV3_WX_MIN_WGS)
+
+
 def _skip_half(kind, skip, ps, conv=None):
     """S = conv(skip, W_skip), raw accumulators; ps: the packed skip half of the weight.  conv (eval-mode rollouts): the
     Conv2d itself - a 3x3 skip half whose shape qualifies runs as F(4x4) (a quarter of the multiplies, the raw-accumulator form
@@ -173,6 +188,8 @@ def _skip_half(kind, skip, ps, conv=None):
         ctot = conv.weight.shape[1]
         if winograd_tile(n, c, h, w, conv.weight.shape[0]) == 4:
             return ops.conv3x3_winograd(skip, weights.winograd(conv.weight, 4, ctot - c, ctot), None, None, act=ACT_NONE)
+        if conv3_wx_applies(n, c, h, w, conv.weight.shape[0], conv):
+            return ops.conv3x3_wx(skip, weights.wx(conv.weight, ctot - c, ctot), None, None, act=ACT_NONE)
     return BLOCKS[kind].raw(skip, None, ps, None)
 
 
@@ -580,6 +597,8 @@ def conv3_bn_act(conv, bn, x, skip=None, *, upsample=False, pool=False, act=ACT_
                 to_v = m == 4 and not torch.is_grad_enabled() and _hand_over(next_conv, next_up, n, cout, h, w, pool)
                 return ops.conv3x3_winograd(x, weights.winograd(conv.weight, m), sc, sh, act=act, slope=slope, pool=pool,
                                             to_v=to_v, y_from=y_from)
+            if conv3_wx_applies(n, c, h, w, cout, conv, bn):
+                return _from(ops.conv3x3_wx(x, weights.wx(conv.weight), sc, sh, act=act, slope=slope, pool=pool), y_from)
         return _from(ops.conv3x3(x, skip, weights.packed(conv.weight), sc, sh, upsample=upsample, act=act, slope=slope,
                                  pool=pool), y_from)
     return _train_block("conv3", conv, bn, x, skip, up=upsample, act=act, slope=slope, pool=pool)
@@ -612,6 +631,10 @@ def conv3_first_pair(conv0, bn0, conv1, bn1, x_nchw, *, pool=False, slope=0.2, y
     y_from: as conv3_bn_act."""
     sc0, sh0 = folded_affine(conv0, bn0)
     sc1, sh1 = folded_affine(conv1, bn1)
+    n, _, h, w = x_nchw.shape
+    if conv3_wx_applies(n, 64, h, w, conv1.out_channels, conv0, bn0, conv1, bn1):
+        return ops.conv3x3_first_pair_wx(x_nchw, weights.first_pair_taps(conv0.weight), sc0, sh0, weights.wx(conv1.weight), sc1, sh1,
+                                         slope=slope, pool=pool, y_from=y_from)
     return ops.conv3x3_first_pair(x_nchw, weights.first_pair_taps(conv0.weight), sc0, sh0, weights.packed(conv1.weight), sc1, sh1,
                                   slope=slope, pool=pool, y_from=y_from)
 

@@ -13,6 +13,7 @@ from ._core import (  # noqa: F401
 )
 from .conv import (  # noqa: F401
     pack_conv_weight, pack_convT_weight, packed_row_floats, pack_igemm_weight, _wp_dims, unpack_conv_weight,
+    pack_wx_weight, wx_ok, wx_workgroups, conv3x3_wx,
     unpack_convT_weight, _splitk_ws, _SPLITK_WS, evict_captured_workspaces, _stats_buf, _tile_images, SharedBlocks,
     _MAP_CACHE, shared_map, group_sum, _check_addend, conv3x3, CONV4S2_MAX_FLOATS, conv4x4s2, convT4x4s2,
     PROJ_MAX_T, convT4x4s2_proj,
@@ -22,7 +23,7 @@ from .winograd import (  # noqa: F401
     conv3x3_winograd, stem_up_winograd_input,
 )
 from .edge import (  # noqa: F401
-    conv3x3_first, first_pair_ok, conv3x3_first_pair, convT3x3_last, conv4x4s2_first, convT4x4s2_last, pixel_proj,
+    conv3x3_first, first_pair_ok, conv3x3_first_pair, conv3x3_first_pair_wx, convT3x3_last, conv4x4s2_first, convT4x4s2_last, pixel_proj,
     _SKIP_PROJ_CACHE, clear_skip_proj_cache, _cached_skip_proj, _last_wmat, _last_wmat_cached,
     precompute_skip_proj, LastProj, convT_last_two_step, eval_frames, eval_frames_finn, pairwise_frame_mse, moving_mnist_compose, clip_gather, clip_gather_aug, CLIP_MAX_SHIFT,
     mnist_scale_u8, moving_mnist_compose_u8, frame_mosaic, QUANT_TRUNC, QUANT_NEAREST,

@@ -235,7 +235,49 @@ def conv3x3(x, skip, wp, scale, shift, *, upsample=False, act=ACT_LRELU, slope=0
     return (out, st) if stats else out
 
 
-CONV4S2_MAX_FLOATS = 1 << 31     # dvg_conv4x4s2_bn_act_v2: N * H * W * Cin must stay below (32-bit activation offsets)
+def pack_wx_weight(w: torch.Tensor) -> torch.Tensor:
+    """(Cout,Cin,3,3) weight in the layout `conv3x3_wx` / `conv3x3_first_pair_wx` read: per kernel row the four F(2,3) values
+    u0 = g0, u1 = (g0 + g1 + g2) / 2, u2 = (g0 - g1 + g2) / 2, u3 = g2; logical shape [Cin/16][12 taps = 4 r + f][Cout][row], in
+    memory [Cin/16][Cout/64][tap][64][row] (conv_igemm2.hip: pack_wx_kernel)."""
+    _dev_f32(w, "pack_wx_weight")
+    w = w.detach().contiguous()
+    co, ci, kh, kw = w.shape
+    if (kh, kw) != (3, 3):
+        raise RuntimeError(f"pack_wx_weight: a 3x3 kernel is needed, got {kh}x{kw}")
+    out = torch.empty((ci // 16, 12, co, packed_row_floats()), device=w.device, dtype=torch.float32)
+    check(lib().dvg_pack_conv_weight_wx(_p(w), _p(out), co, ci, _stream()), "pack_wx")
+    return out
+
+
+def wx_ok(n, cin, h, w, cout) -> bool:
+    """Shapes the WX kernels take (the host side of dvg_conv3x3_bn_act_wx checks the same)."""
+    return cin % 16 == 0 and cout % 64 == 0 and h % 8 == 0 and w % 16 == 0 and lib().dvg_mfma_mode() == 1
+
+
+def wx_workgroups(n, h, w, cout) -> int:
+    return n * (h // 8) * (w // 16) * (cout // 64)
+
+
+def conv3x3_wx(x, wp, scale, shift, *, act=ACT_LRELU, slope=0.2, pool=False, addend=None):
+    """conv3x3 without concat operand, upsampling, statistics or split-K, with 1-D Winograd F(2,3) along x inside the kernel
+    (dvg_conv3x3_bn_act_wx): 2/3 of the direct form's MFMAs.  wp: pack_wx_weight."""
+    _dev_f32(x, "conv3x3_wx.x")
+    assert is_nhwc(x), "conv3x3_wx: x must be NHWC in memory"
+    n, c1, h, w = x.shape
+    taps, cout, cin = _wp_dims(wp)
+    if taps != 12 or cin != c1:
+        raise RuntimeError(f"conv3x3_wx: packed weight {tuple(wp.shape)} does not match Cin={c1}")
+    y = nhwc_empty(n, cout, h, w, x.device)
+    yp = nhwc_empty(n, cout, h // 2, w // 2, x.device) if pool else None
+    addend, amap, ablk = _check_addend(addend, y, pool)
+    alg = 2.0 * n * h * w * cout * 9 * cin
+    by = 4.0 * (x.numel() + n * h * w * cout + wp.numel())
+    _run("conv3x3_igemm", alg * 12 / 18, by, lib().dvg_conv3x3_bn_act_wx, _p(x), None, _p(wp), _p(scale), _p(shift), _p(y),
+         _p(yp), n, h, w, c1, 0, cout, 0, act, slope, _p(addend), _p(amap), ablk, _stream(), alg_flops=alg)
+    return (y, yp) if pool else y
+
+
+CONV4S2_MAX_FLOATS = 1 << 31    # dvg_conv4x4s2_bn_act_v2: N * H * W * Cin must stay below (32-bit activation offsets)
 
 
 def conv4x4s2(x, wp, scale, shift, *, act=ACT_LRELU, slope=0.2, stats=False):

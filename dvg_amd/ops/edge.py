@@ -58,6 +58,28 @@ def conv3x3_first_pair(x_nchw, w0, scale0, shift0, wp1, scale1, shift1, *, act=A
     return (y, yp) if pool else y
 
 
+def conv3x3_first_pair_wx(x_nchw, w0, scale0, shift0, wx1, scale1, shift1, *, act=ACT_LRELU, slope=0.2, pool=False, y_from=0):
+    """conv3x3_first_pair with the 64 -> Cout layer in the WX form (dvg_conv3x3_first_pair_wx; wx1: pack_wx_weight): 12 instead
+    of 18 products per output pair.  `flops` is what the launch executes, `alg_flops` the direct form's count."""
+    _dev_f32(x_nchw, "conv3x3_first_pair_wx.x")
+    x = x_nchw if x_nchw.is_contiguous() else x_nchw.contiguous()
+    n, nc, h, wd = x.shape
+    taps, cout, cin = _wp_dims(wx1)
+    w0 = w0.detach()
+    if nc != 1 or tuple(w0.shape) != (9, 64) or not w0.is_contiguous() or (taps, cin) != (12, 64) or h % 8 or wd % 16:
+        raise RuntimeError(f"conv3x3_first_pair_wx: unsupported shapes x {tuple(x.shape)} w0 {tuple(w0.shape)} wx1 {tuple(wx1.shape)}")
+    if not 0 <= y_from <= n or (y_from and not pool):
+        raise RuntimeError("conv3x3_first_pair_wx: y_from needs the pooled output and 0 <= y_from <= N")
+    y = nhwc_empty(n - y_from, cout, h, wd, x.device) if y_from < n else None
+    yp = nhwc_empty(n, cout, h // 2, wd // 2, x.device) if pool else None
+    alg = 2.0 * n * h * wd * (64 * 9 + cout * 9 * 64)
+    flops = 2.0 * n * h * wd * (64 * 9 + cout * 6 * 64)
+    _run("conv3x3_igemm", flops, 4.0 * (x.numel() + (0 if y is None else y.numel()) + (0 if yp is None else yp.numel()) + wx1.numel()),
+         lib().dvg_conv3x3_first_pair_wx, _p(x), _p(w0), _p(scale0), _p(shift0), _p(wx1), _p(scale1), _p(shift1), _p(y), _p(yp),
+         n, h, wd, cout, act, slope, y_from, _stream(), alg_flops=alg)
+    return (y, yp) if pool else y
+
+
 def convT3x3_last(x, w, bias, nc, *, act=ACT_SIGMOID):
     _dev_f32(x, "convT3x3_last.x")
     assert is_nhwc(x)

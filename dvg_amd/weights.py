@@ -35,6 +35,13 @@ def packed(weight, transposed=False, lo=None, hi=None, dim=0):
                    lambda: ops.pack_igemm_weight(_sliced(weight, lo, hi, dim), transposed))
 
 
+def wx(weight, lo=None, hi=None):
+    """The F(2,3)-row repack (ops.pack_wx_weight) of a Conv2d 3x3 weight that the WX kernels read, optionally of the input
+    channels [lo, hi)."""
+    lo, hi, dim = _span(weight, lo, hi, 1)
+    return derived(weight, ("wx", lo, hi), (weight,), lambda: ops.pack_wx_weight(_sliced(weight, lo, hi, dim)))
+
+
 def split_packed(weight, c1: int, transposed=False):
     """The packed x half and skip half of a concat conv's weight: the channels [0, c1) and [c1, C) of dim 1 of a Conv2d
     weight, or - `transposed` - of dim 0 of a ConvTranspose2d weight."""

@@ -137,14 +137,14 @@ int dvg_conv3x3_bn_act_v2(const float* x, const float* skip, const float* w_k16,
  * transposed to [9 taps][64 channels]; scale0 / shift0 = the first layer's folded BatchNorm (64 each; LeakyReLU `slope`);
  * w1_k16 / scale1 / shift1 / y / y_pool / act as in dvg_conv3x3_bn_act_v2 with C1 = 64.  H % 8 == 0, W % 16 == 0,
  * N * H/8 * W/16 * Cout/64 >= 512.                                                                                        */
-int dvg_conv3x3_first_pair(const float* frame, const float* w0, const float* scale0, const float* shift0,
-                           const float* w1_k16, const float* scale1, const float* shift1, float* y, float* y_pool,
-                           int N, int H, int W, int Cout, int act, float slope,
-                           int y_from /* ABI 8: y holds the images [y_from, N) only - see dvg_winograd_output_pool_input */,
-                           void* stream);
+int dvg_conv3x3_first_pair(const float* frame, const float* w0, const float* scale0, const float* shift0, const float* w1_k16,
+                           const float* scale1, const float* shift1, float* y, float* y_pool, int N, int H, int W, int Cout, int act, float slope,
+                           int y_from /* ABI 8: y holds the images [y_from, N) only - see dvg_winograd_output_pool_input */, void* stream);
+int dvg_pack_conv_weight_wx(const float* w, float* w_packed, int cout, int cin, void* stream);  /* within ABI 9, bf16-triple build only (else DVG_ERR_SHAPE) - the WX form of the two entry points above: 1-D Winograd F(2,3) along x inside the kernel, GEMM rows are pixel pairs, 12 taps (kernel row r, position f) instead of 18 products per pair.  Packs a (Cout,Cin,3,3) weight as [Cin/16][Cout/64][tap = 4 r + f][64][row] with u0 = g0, u1 = (g0 + g1 + g2) / 2, u2 = (g0 - g1 + g2) / 2, u3 = g2 of kernel row g = w[co][ci][r][:], formed in fp32 */
+int dvg_conv3x3_bn_act_wx(const float* x, const float* skip, const float* w_wx, const float* scale, const float* shift, float* y, float* y_pool, int N, int H, int W, int C1, int C2, int Cout, int upsample_x, int act, float slope, const float* addend, const int* addend_map, int addend_block, void* stream);  /* as dvg_conv3x3_bn_act_v2 without workspace / statistics (no split-K).  Checked before the launch: Cin % 16 == 0, Cout % 64 == 0, H % 8 == 0, W % 16 == 0, 16-byte aligned pointers, C2 == 0 (skip NULL), upsample_x == 0.  Agrees with the direct form to fp32 rounding, not bit for bit */
+int dvg_conv3x3_first_pair_wx(const float* frame, const float* w0, const float* scale0, const float* shift0, const float* w1_wx, const float* scale1, const float* shift1, float* y, float* y_pool, int N, int H, int W, int Cout, int act, float slope, int y_from, void* stream);  /* as dvg_conv3x3_first_pair (no workgroup floor), w1_wx from dvg_pack_conv_weight_wx; the same checks */
 int dvg_conv4x4s2_bn_act_v2(const float* x, const float* w_k16, const float* scale, const float* shift, float* y, float* stats,
-                            int N, int H, int W, int Cin, int Cout, int act, float slope, float* workspace, long workspace_floats,
-                            void* stream);
+                            int N, int H, int W, int Cin, int Cout, int act, float slope, float* workspace, long workspace_floats, void* stream);
 /* dcgan_upconv = ConvTranspose2d(nin,nout,4,2,1)+BN+LReLU on cat([x, skip]) (dcgan_64.py:16-26,84-87) as four parity-class
  * implicit GEMMs (K = 4*Cin).  x NHWC (N,H,W,C1), skip NHWC (N,H,W,C2) or NULL; y NHWC (N,2H,2W,Cout).                 */
 int dvg_convT4x4s2_bn_act_v2(const float* x, const float* skip, const float* w_k16, const float* scale, const float* shift, float* y,
