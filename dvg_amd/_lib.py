@@ -36,6 +36,8 @@ _POINTER = re.compile(rf"{_NAME}(?: {_NAME})* ?(?:\* ?(?:const ?)?)+({_NAME})?")
 _DECLARATION = re.compile(rf"(.+?[ *])({_NAME}) ?\(([^()]*)\)")                       # <ret> name(<params>): no nested parentheses
 _INTEGER = re.compile(r"[-+]?(?:0[xX][0-9a-fA-F]+|0|[1-9][0-9]*)")                    # no suffix, no octal
 _DIRECTIVE = re.compile(rf"# ?(include|ifdef|ifndef|endif|define)\b ?({_NAME})? ?(.*)")
+_ENUM = re.compile(r"enum ?\{([^{}]*)\}")                                             # anonymous, no trailing comma
+_ENUMERATOR = re.compile(rf"(DVG_\w+) ?= ?({_INTEGER.pattern})")
 
 
 def _parameter(text: str):
@@ -52,10 +54,22 @@ def _parameter(text: str):
 def parse_header(text: str, where: str = "include/dvg_hip.h"):
     """(SIGNATURES, CONSTANTS) of a header made of comments, #include / #ifdef / #ifndef / #endif lines, an include guard,
     `#define DVG_<NAME> <integer literal>` lines, at most one `extern "C" { }` block and statements `<ret> dvg_<name>(<params>);`
-    over the types above.  Anything else raises DvgLibraryError quoting the text: nothing is skipped."""
+    over the types above or `enum { DVG_<NAME> = <integer literal>, ... };` (read by parse_header_enums).  Anything else raises
+    DvgLibraryError quoting the text: nothing is skipped."""
+    return _parse(text, where)[:2]
+
+
+def parse_header_enums(text: str, where: str = "include/dvg_hip.h"):
+    """ENUMS of the same header: NAME -> value over every enumerator of its anonymous `enum { DVG_<NAME> = <integer literal>, ... };`
+    statements - every enumerator with its value written out, the same literals as the defines.  Codes that entered the ABI as
+    a family of their own (DVG_GP_KERNEL_*) live here; CONSTANTS stays the set of the defines."""
+    return _parse(text, where)[2]
+
+
+def _parse(text: str, where: str):
     def refuse(why, quote):
         raise DvgLibraryError(f"{where}: {why}: {quote}")
-    signatures, constants, code, guard = {}, {}, [], None
+    signatures, constants, enums, code, guard = {}, {}, {}, [], None
     for line in re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S).splitlines():
         line = " ".join(line.split())
         if not line.startswith("#"):
@@ -79,6 +93,14 @@ def parse_header(text: str, where: str = "include/dvg_hip.h"):
     if rest.strip():
         refuse("text after the last declaration", rest.strip())
     for s in map(str.strip, statements):
+        m = _ENUM.fullmatch(s)
+        if m:
+            for item in map(str.strip, m.group(1).split(",")):
+                e = _ENUMERATOR.fullmatch(item)
+                if not e or e.group(1)[4:] in enums or e.group(1)[4:] in constants:
+                    refuse("enumerator is not a new `DVG_<NAME> = <integer literal>`", s)
+                enums[e.group(1)[4:]] = int(e.group(2), 0)
+            continue
         m = _DECLARATION.fullmatch(s)
         if m:
             ret, name, params = re.sub(r" ?\* ?", "*", m.group(1)).strip(), m.group(2), m.group(3).strip()
@@ -89,7 +111,7 @@ def parse_header(text: str, where: str = "include/dvg_hip.h"):
         if name in signatures:
             refuse("entry point declared twice", s)
         signatures[name] = (_RETURN[ret], args)
-    return signatures, constants
+    return signatures, constants, enums
 
 
 def _read_header(path: str):
@@ -98,11 +120,12 @@ def _read_header(path: str):
             text = f.read()
     except OSError as e:
         raise DvgLibraryError(f"{path}: cannot read the C ABI header, and the binding exists nowhere else ({e})") from e
-    return parse_header(text, path)
+    return _parse(text, path)
 
 
-# name -> (restype, [argtypes]) of every entry point the header declares; NAME -> value of every `#define DVG_<NAME> <value>`
-SIGNATURES, CONSTANTS = _read_header(HEADER_PATH)
+# name -> (restype, [argtypes]) of every entry point the header declares; NAME -> value of every `#define DVG_<NAME> <value>`;
+# NAME -> value of every enumerator `DVG_<NAME> = <value>`
+SIGNATURES, CONSTANTS, ENUMS = _read_header(HEADER_PATH)
 
 _lock = threading.Lock()
 _lib = None

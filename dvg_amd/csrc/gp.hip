@@ -45,6 +45,7 @@ struct GpParams {
                      // quarters of a small-batch call - once per SG steps instead of once per step.  Train-mode outputs only.
     unsigned long long* clk;  // debug only: 12 x u64 per workgroup (latent dim), for the first clk_cap workgroups
     unsigned clk_cap;
+    int kind;        // covariance family (DVG_GP_KERNEL_*), uniform per launch; read by the MATERN instantiations only
 };
 
 
@@ -91,6 +92,50 @@ __device__ __forceinline__ double rcp_t(double x) {
     return r;
 }
 
+// ---------------------------------------------------------------------------------------
+// Covariance family (DVG_GP_KERNEL_*; docs/DESIGN_NOTES_gp_kernels.md).  With d = z - x (signed), r = |d| / ell:
+//   rbf  s exp(-r^2 / 2)    matern12  s exp(-r)    matern32  s (1 + a) exp(-a), a = sqrt(3) r
+//   matern52  s (1 + a + a^2 / 3) exp(-a), a = sqrt(5) r
+// The kernels are templates on MATERN: false is the RBF, whose expression is the one these kernels always had (same
+// instructions, same bits); true switches on the launch-uniform `kind` between the three Matern members.  One exp per entry
+// either way.
+// ---------------------------------------------------------------------------------------
+template <typename T>
+struct GpCov {
+    T s, ninv, il;   // output scale, -1 / (2 ell^2) (rbf), 1 / ell (matern)
+    int kind;
+};
+template <bool MATERN, typename T>
+__device__ __forceinline__ GpCov<T> gp_cov_of(T s, T ell, int kind) {
+    return GpCov<T>{s, -T(0.5) / (ell * ell), MATERN ? T(1.) / ell : T(0.), kind};
+}
+template <bool MATERN, typename T>
+__device__ __forceinline__ T gp_cov(const GpCov<T>& c, T d) {
+    if (!MATERN) return c.s * exp_t(d * d * c.ninv);
+    const T r = abs_t(d) * c.il;
+    if (c.kind == DVG_GP_KERNEL_MATERN12) return c.s * exp_t(-r);
+    if (c.kind == DVG_GP_KERNEL_MATERN32) {
+        const T a = T(1.7320508075688772) * r;
+        return c.s * (T(1.) + a) * exp_t(-a);
+    }
+    const T a = T(2.23606797749979) * r;
+    return c.s * fma_t(a, fma_t(a, T(1. / 3.), T(1.)), T(1.)) * exp_t(-a);
+}
+// ell^2 rho(d), rho = (dk/dd) / k: the backward's chain rule is dk/dz = k rho, dk/dx = -k rho, dk/dell = -(d / ell) k rho and
+// the 1 / ell^2 (1 / ell^3) sits outside its loops.  rbf: -d (the factor those loops always had); matern12: -sign(d) ell
+// (0 at d = 0, the subgradient autograd takes); matern32: -3 d / (1 + a); matern52: -(5 d / 3) (1 + a) / (1 + a + a^2 / 3).
+template <bool MATERN, typename T>
+__device__ __forceinline__ T gp_rho_l2(const GpCov<T>& c, T ell, T d) {
+    if (!MATERN) return -d;
+    if (c.kind == DVG_GP_KERNEL_MATERN12) return d > T(0.) ? -ell : (d < T(0.) ? ell : T(0.));
+    if (c.kind == DVG_GP_KERNEL_MATERN32) {
+        const T a = T(1.7320508075688772) * (abs_t(d) * c.il);
+        return T(-3.) * d * rcp_t(T(1.) + a);
+    }
+    const T a = T(2.23606797749979) * (abs_t(d) * c.il);
+    return T(-5. / 3.) * d * (T(1.) + a) * rcp_t(fma_t(a, fma_t(a, T(1. / 3.), T(1.)), T(1.)));
+}
+
 // value of `v` in lane `src` (compile-time constant after unrolling): v_readlane_b32, not a ds_bpermute round trip
 __device__ __forceinline__ float read_lane(float v, int src) {
     return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), src));
@@ -116,7 +161,10 @@ extern __shared__ __attribute__((aligned(16))) unsigned char gp_lds_raw[];
 // PACKED: A holds only the lower triangle, row i at offset i (i + 1) / 2 (the 128 x 128 fp64 predictive covariance does not
 // fit beside the other operands as a full square).  Entries above the diagonal that the panel code touches inside a
 // diagonal block then alias in-bounds entries of the next row; they are read into registers the code never uses.
-template <int NT, typename T, bool PACKED = false>
+// COPY: a second instance of the same code for the caller that names it.  The compiler inlines an instance with ONE call site and
+// calls the others; the packed instance had one (the packed RBF kernel) before the Matern kernels existed and keeps it this way,
+// so that kernel's instruction stream stays what it was.
+template <int NT, typename T, bool PACKED = false, int COPY = 0>
 __device__ void block_cholesky(T* A, int n, int ld, int tid) {
     auto at = [ld](int i, int j) { return PACKED ? i * (i + 1) / 2 + j : i * ld + j; };
     constexpr int NB = 8;
@@ -265,7 +313,7 @@ __device__ void block_backward_subst(const T* L, int LM, T* X, int LB, int M, in
     }
 }
 
-template <int NT, typename T, bool PACKED = false>
+template <int NT, typename T, bool PACKED = false, bool MATERN = false>
 __global__ __launch_bounds__(NT) void gp_predict_kernel(const GpParams p) {
     T* sm = reinterpret_cast<T*>(gp_lds_raw);
     const int wg = blockIdx.x, tid = threadIdx.x;
@@ -299,7 +347,7 @@ __global__ __launch_bounds__(NT) void gp_predict_kernel(const GpParams p) {
     auto softplus = [](T x) { return x > T(20.) ? x : log1p_t(exp_t(x)); };
     const T s = p.raw_hypers ? softplus(p.outputscale[dq]) : p.outputscale[dq];
     const T ell = p.raw_hypers ? softplus(p.lengthscale[dq]) : p.lengthscale[dq];
-    const T ninv = -T(0.5) / (ell * ell);
+    const GpCov<T> kc = gp_cov_of<MATERN>(s, ell, p.kind);
     const T c0 = p.mean_const[dq];
     const T noise = p.noise ? (p.raw_hypers ? softplus(p.noise[dq]) + T(1e-4) : p.noise[dq]) : T(0.);
     const bool need_cov = (p.cov != nullptr) || (p.sample != nullptr);
@@ -311,7 +359,7 @@ __global__ __launch_bounds__(NT) void gp_predict_kernel(const GpParams p) {
     for (int i = tid; i < M * M; i += NT) {
         const int r = i / M, q = i % M;
         const T dz = zs[r] - zs[q];
-        L[r * LM + q] = s * exp_t(dz * dz * ninv) + (r == q ? p.jitter : T(0.));
+        L[r * LM + q] = gp_cov<MATERN>(kc, dz) + (r == q ? p.jitter : T(0.));
         Ls[r * LM + q] = (q <= r) ? p.chol_var[((size_t)dq * M + r) * M + q] : T(0.);
     }
     for (int i = tid; i < M * (B + 1); i += NT) {
@@ -319,7 +367,7 @@ __global__ __launch_bounds__(NT) void gp_predict_kernel(const GpParams p) {
         T v;
         if (b < B) {
             const T dx = zs[r] - xs[b];
-            v = s * exp_t(dx * dx * ninv);
+            v = gp_cov<MATERN>(kc, dx);
         } else {
             v = p.var_mean[(size_t)dq * M + r] - c0;
         }
@@ -424,7 +472,7 @@ __global__ __launch_bounds__(NT) void gp_predict_kernel(const GpParams p) {
                         const int r = tr * 4 + a, q = tq * 4 + b2;
                         if (r < B && q < B) {
                             const T dx = xs[r] - xs[q];
-                            T v = acc[a][b2] + s * exp_t(dx * dx * ninv);
+                            T v = acc[a][b2] + gp_cov<MATERN>(kc, dx);
                             if (r == q) v += noise;
                             if (PACKED) {
                                 Sg[sg(max(r, q), min(r, q))] = v;
@@ -443,7 +491,7 @@ __global__ __launch_bounds__(NT) void gp_predict_kernel(const GpParams p) {
         __syncthreads();
         if (p.clk && tid == 0 && (unsigned)wg < p.clk_cap) p.clk[(size_t)wg * 12 + 5] = clock64();
         if (p.sample != nullptr) {
-            block_cholesky<NT, T, PACKED>(Sg, B, LS, tid);   // ends with __syncthreads
+            block_cholesky<NT, T, PACKED, (PACKED && MATERN) ? 1 : 0>(Sg, B, LS, tid);   // ends with __syncthreads
         if (p.clk && tid == 0 && (unsigned)wg < p.clk_cap) p.clk[(size_t)wg * 12 + 6] = clock64();
             for (int b = tid; b < B; b += NT) {
                 T acc = mu[b];
@@ -467,7 +515,7 @@ __global__ __launch_bounds__(NT) void gp_predict_kernel(const GpParams p) {
 //   G2 = dL/dKzx = alpha gm^T + 2 P diag(gq) + L_S GW
 //   GK = dL/dK   = -tau alpha^T - P diag(gq) P^T + gk/2 (-K^-1 + L_S L_S^T - alpha alpha^T)
 //   dL_S = tril( Kzx GW^T + gk (K L_S - diag(1/L_S_ii)) ),  dm = tau + gk alpha,  dc = sum gm - sum dm
-// and the RBF chain rule maps (GK, G2) onto z, x, s, ell.  K^-1 is applied by blocked triangular solves with L; the
+// and the covariance's chain rule (dk/dd = k rho(d), gp_rho_l2) maps (GK, G2) onto z, x, s, ell.  K^-1 is applied by blocked triangular solves with L; the
 // explicit K^-1 of the KL trace term comes out of the same solves (identity columns appended to the right-hand sides).
 // ---------------------------------------------------------------------------------------
 struct GpBwdParams {
@@ -483,6 +531,7 @@ struct GpBwdParams {
     float jitter;
     unsigned long long* clk;  // debug only (dvg_debug_set_gp_clockbuf): 12 x u64 phase stamps per workgroup
     unsigned clk_cap;
+    int kind;                 // covariance family (see GpParams)
 };
 
 #define GP_STAMP(k) if (p.clk && tid == 0 && (unsigned)wg < p.clk_cap) p.clk[(size_t)wg * 12 + (k)] = clock64();
@@ -493,7 +542,7 @@ struct GpBwdParams {
 // is small and is kept whole: tt = Kzx gm (a first pass over the chunks), alpha, tau, K^-1 (solved once from the columns
 // [m - c | tt | I]), and the running sums GK (LDS), dL_S (accumulated in the output buffer by the thread that owns the entry),
 // dz / ds / dell (registers).  With one chunk (B <= 71 at M = 40) the arithmetic is the r03 kernel's.
-template <int NT, typename T>
+template <int NT, typename T, bool MATERN = false>
 __global__ __launch_bounds__(NT) void gp_train_bwd_kernel(const GpBwdParams p) {
     T* sm = reinterpret_cast<T*>(gp_lds_raw);
     const int wg = blockIdx.x, tid = threadIdx.x;
@@ -529,7 +578,8 @@ __global__ __launch_bounds__(NT) void gp_train_bwd_kernel(const GpBwdParams p) {
     T* red = gq + B;          // [16]
 
     const T s = p.outputscale[dq], ell = p.lengthscale[dq];
-    const T ninv = -T(0.5) / (ell * ell), c0 = p.mean_const[dq];
+    const T c0 = p.mean_const[dq];
+    const GpCov<T> kc = gp_cov_of<MATERN>(s, ell, p.kind);
     T gk = T(0.);               // the KL value is shared by the workgroup's steps: its upstream gradients add up
     if (p.gkl)
         for (int st = 0; st < ns; ++st) gk += (T)p.gkl[d + st * p.Dp];
@@ -551,7 +601,7 @@ __global__ __launch_bounds__(NT) void gp_train_bwd_kernel(const GpBwdParams p) {
     for (int i = tid; i < M * M; i += NT) {
         const int r = i / M, q = i % M;
         const T dz = zs[r] - zs[q];
-        const T v = s * exp_t(dz * dz * ninv) + (r == q ? p.jitter : T(0.));
+        const T v = gp_cov<MATERN>(kc, dz) + (r == q ? p.jitter : T(0.));
         Kj[r * LM + q] = v;
         L[r * LM + q] = v;
         Ls[r * LM + q] = (q <= r) ? p.chol_var[((size_t)dq * M + r) * M + q] : T(0.);
@@ -560,7 +610,7 @@ __global__ __launch_bounds__(NT) void gp_train_bwd_kernel(const GpBwdParams p) {
         for (int i = tid; i < M * bc; i += NT) {
             const int r = i / bc, b = i % bc;
             const T dx = zs[r] - xs[b0 + b];
-            Kzx[r * LB + b] = s * exp_t(dx * dx * ninv);
+            Kzx[r * LB + b] = gp_cov<MATERN>(kc, dx);
         }
     };
     const int c_fix = single ? B : 0;               // first of the M + 2 coupling columns of P
@@ -688,22 +738,24 @@ __global__ __launch_bounds__(NT) void gp_train_bwd_kernel(const GpBwdParams p) {
             }
         }
         __syncthreads();
-        // RBF chain rule, the terms over this chunk's points
+        // chain rule of the covariance, dk/dd = k rho(d) (gp_rho_l2 = ell^2 rho), the terms over this chunk's points
         for (int i = tid; i < M * bc; i += NT) {
             const int r = i / bc, b = i % bc;
             const T dx = zs[r] - xs[b0 + b];
             const T g = G2[r * LB + b] * Kzx[r * LB + b];
             ds_acc += g;
-            dl_acc = fma_t(g, dx * dx, dl_acc);
+            dl_acc = fma_t(g, -(dx * gp_rho_l2<MATERN>(kc, ell, dx)), dl_acc);
         }
         for (int i = tid; i < M; i += NT) {
             T acc = T(0.);
-            for (int b = 0; b < bc; ++b) acc = fma_t(G2[i * LB + b] * Kzx[i * LB + b], -(zs[i] - xs[b0 + b]), acc);
+            for (int b = 0; b < bc; ++b)
+                acc = fma_t(G2[i * LB + b] * Kzx[i * LB + b], gp_rho_l2<MATERN>(kc, ell, zs[i] - xs[b0 + b]), acc);
             dz_acc += acc;
         }
         for (int b = tid; b < bc; b += NT) {
             T acc = T(0.);
-            for (int i = 0; i < M; ++i) acc = fma_t(G2[i * LB + b] * Kzx[i * LB + b], zs[i] - xs[b0 + b], acc);
+            for (int i = 0; i < M; ++i)
+                acc = fma_t(G2[i * LB + b] * Kzx[i * LB + b], -gp_rho_l2<MATERN>(kc, ell, zs[i] - xs[b0 + b]), acc);
             p.dh[(size_t)((b0 + b) % Bs) * p.D + col_of(b0 + b)] = acc * il2;
         }
     }
@@ -721,20 +773,20 @@ __global__ __launch_bounds__(NT) void gp_train_bwd_kernel(const GpBwdParams p) {
     }
     for (int b = tid; b < B; b += NT) dc_part += gm[b];
     GP_STAMP(7)
-    // RBF chain rule, the terms over the inducing points (GK is complete)
+    // the same chain rule, the terms over the inducing points (GK is complete)
     for (int i = tid; i < M * M; i += NT) {
         const int r = i / M, q = i % M;
         const T kp = Kj[r * LM + q] - (r == q ? p.jitter : T(0.));
         const T dz = zs[r] - zs[q];
         const T g = GK[r * LM + q] * kp;
         ds_acc += g;
-        dl_acc = fma_t(g, dz * dz, dl_acc);
+        dl_acc = fma_t(g, -(dz * gp_rho_l2<MATERN>(kc, ell, dz)), dl_acc);
     }
     for (int i = tid; i < M; i += NT) {
         T acc = dz_acc;
         for (int j = 0; j < M; ++j) {
             const T kp = Kj[i * LM + j] - (i == j ? p.jitter : T(0.));
-            acc = fma_t((GK[i * LM + j] + GK[j * LM + i]) * kp, -(zs[i] - zs[j]), acc);
+            acc = fma_t((GK[i * LM + j] + GK[j * LM + i]) * kp, gp_rho_l2<MATERN>(kc, ell, zs[i] - zs[j]), acc);
         }
         p.dz[(size_t)wg * M + i] = acc * il2;
     }
@@ -909,11 +961,33 @@ extern "C" int dvg_gp_step_group(int B, int S, int P, int M) {
     return 1;
 }
 
-extern "C" int dvg_gp_predict(const float* h, const float* z, const float* var_mean, const float* chol_var,
-                              const float* mean_const, const float* outputscale, const float* lengthscale,
-                              const float* noise, const float* eps, float* mean, float* var, float* sample,
-                              float* cov, float* kl, int B, int D, int M, int train_mode, float jitter,
-                              int param_period, int step_group, void* stream) {
+static bool gp_kind_known(int kind) { return kind >= DVG_GP_KERNEL_RBF && kind <= DVG_GP_KERNEL_MATERN52; }
+
+// the kernel of one (arithmetic, layout, family) for the workgroup size `nt`
+template <typename T, bool PACKED, bool MATERN>
+static int gp_predict_launch(int nt, const GpParams& p, int grid, size_t lds, void* stream, const char* who) {
+    switch (nt) {
+        case 256: return gp_launch(gp_predict_kernel<256, T, PACKED, MATERN>, 256, p, grid, lds, stream, who);
+        case 512: return gp_launch(gp_predict_kernel<512, T, PACKED, MATERN>, 512, p, grid, lds, stream, who);
+        default: return gp_launch(gp_predict_kernel<1024, T, PACKED, MATERN>, 1024, p, grid, lds, stream, who);
+    }
+}
+template <typename T, bool MATERN>
+static int gp_bwd_launch(int nt, const GpBwdParams& p, int grid, size_t lds, void* stream, const char* who) {
+    switch (nt) {
+        case 256: return gp_launch(gp_train_bwd_kernel<256, T, MATERN>, 256, p, grid, lds, stream, who);
+        case 512: return gp_launch(gp_train_bwd_kernel<512, T, MATERN>, 512, p, grid, lds, stream, who);
+        default: return gp_launch(gp_train_bwd_kernel<1024, T, MATERN>, 1024, p, grid, lds, stream, who);
+    }
+}
+
+extern "C" int dvg_gp_predict_cov(const float* h, const float* z, const float* var_mean, const float* chol_var,
+                                  const float* mean_const, const float* outputscale, const float* lengthscale,
+                                  const float* noise, const float* eps, float* mean, float* var, float* sample,
+                                  float* cov, float* kl, int B, int D, int M, int train_mode, float jitter,
+                                  int param_period, int step_group, int cov_kind, void* stream) {
+    DVG_REQUIRE(gp_kind_known(cov_kind), DVG_ERR_SHAPE,
+                "dvg_gp_predict: unknown covariance kind %d (DVG_GP_KERNEL_*: 0 rbf, 1 matern12, 2 matern32, 3 matern52)", cov_kind);
     DVG_REQUIRE(h && z && var_mean && chol_var && mean_const && outputscale && lengthscale, DVG_ERR_NULL,
                 "dvg_gp_predict: NULL input");
     DVG_REQUIRE(B > 0 && D > 0 && M > 0 && M <= 64 && B <= 128, DVG_ERR_SHAPE,
@@ -931,39 +1005,40 @@ extern "C" int dvg_gp_predict(const float* h, const float* z, const float* var_m
     const size_t lds = dvg_gp_lds_bytes(Bw, M, need_cov);
     DVG_REQUIRE(lds <= GP_LDS_MAX, DVG_ERR_SHAPE, "dvg_gp_predict: %zu bytes of LDS needed (> 160 KiB)", lds);
     GpParams p{h, z, var_mean, chol_var, mean_const, outputscale, lengthscale, noise, eps, mean, var, sample, cov, kl,
-               B, D, M, train_mode & 1, jitter, (train_mode >> 1) & 1, Dp, SG, g_gp_clk, g_gp_clk_cap};
+               B, D, M, train_mode & 1, jitter, (train_mode >> 1) & 1, Dp, SG, g_gp_clk, g_gp_clk_cap, cov_kind};
     const int nt = gp_threads(GP_PREDICT_THREADS, nwg, Bw, false);
     const char* who = "dvg_gp_predict";
     const int variant = gp_predict_variant(Bw, M, need_cov);
     DVG_REQUIRE(SG == 1 || variant == 1, DVG_ERR_SHAPE,
                 "dvg_gp_predict: step_group=%d x B=%d points do not fit the LDS in fp64", SG, B);   // never trade precision for it
     D = nwg;        // the grid
-    if (variant == 2) {
-        switch (nt) {
-            case 256: return gp_launch(gp_predict_kernel<256, double, true>, 256, p, D, lds, stream, who);
-            case 512: return gp_launch(gp_predict_kernel<512, double, true>, 512, p, D, lds, stream, who);
-            default: return gp_launch(gp_predict_kernel<1024, double, true>, 1024, p, D, lds, stream, who);
-        }
-    }
-    if (variant == 1) {
-        switch (nt) {
-            case 256: return gp_launch(gp_predict_kernel<256, double>, 256, p, D, lds, stream, who);
-            case 512: return gp_launch(gp_predict_kernel<512, double>, 512, p, D, lds, stream, who);
-            default: return gp_launch(gp_predict_kernel<1024, double>, 1024, p, D, lds, stream, who);
-        }
-    }
-    switch (nt) {
-        case 256: return gp_launch(gp_predict_kernel<256, float>, 256, p, D, lds, stream, who);
-        case 512: return gp_launch(gp_predict_kernel<512, float>, 512, p, D, lds, stream, who);
-        default: return gp_launch(gp_predict_kernel<1024, float>, 1024, p, D, lds, stream, who);
-    }
+    const bool matern = cov_kind != DVG_GP_KERNEL_RBF;
+    if (variant == 2)
+        return matern ? gp_predict_launch<double, true, true>(nt, p, D, lds, stream, who)
+                      : gp_predict_launch<double, true, false>(nt, p, D, lds, stream, who);
+    if (variant == 1)
+        return matern ? gp_predict_launch<double, false, true>(nt, p, D, lds, stream, who)
+                      : gp_predict_launch<double, false, false>(nt, p, D, lds, stream, who);
+    return matern ? gp_predict_launch<float, false, true>(nt, p, D, lds, stream, who)
+                  : gp_predict_launch<float, false, false>(nt, p, D, lds, stream, who);
 }
 
-extern "C" int dvg_gp_train_bwd(const float* h, const float* z, const float* var_mean, const float* chol_var,
-                                const float* mean_const, const float* outputscale, const float* lengthscale,
-                                const float* gmean, const float* gvar, const float* gkl, float* dh, float* dz,
-                                float* dm, float* dls, float* dc, float* ds, float* dell, int B, int D, int M,
-                                float jitter, int param_period, int step_group, void* stream) {
+extern "C" int dvg_gp_predict(const float* h, const float* z, const float* var_mean, const float* chol_var,
+                              const float* mean_const, const float* outputscale, const float* lengthscale,
+                              const float* noise, const float* eps, float* mean, float* var, float* sample,
+                              float* cov, float* kl, int B, int D, int M, int train_mode, float jitter,
+                              int param_period, int step_group, void* stream) {
+    return dvg_gp_predict_cov(h, z, var_mean, chol_var, mean_const, outputscale, lengthscale, noise, eps, mean, var, sample, cov,
+                              kl, B, D, M, train_mode, jitter, param_period, step_group, DVG_GP_KERNEL_RBF, stream);
+}
+
+extern "C" int dvg_gp_train_bwd_cov(const float* h, const float* z, const float* var_mean, const float* chol_var,
+                                    const float* mean_const, const float* outputscale, const float* lengthscale,
+                                    const float* gmean, const float* gvar, const float* gkl, float* dh, float* dz,
+                                    float* dm, float* dls, float* dc, float* ds, float* dell, int B, int D, int M,
+                                    float jitter, int param_period, int step_group, int cov_kind, void* stream) {
+    DVG_REQUIRE(gp_kind_known(cov_kind), DVG_ERR_SHAPE,
+                "dvg_gp_train_bwd: unknown covariance kind %d (DVG_GP_KERNEL_*: 0 rbf, 1 matern12, 2 matern32, 3 matern52)", cov_kind);
     DVG_REQUIRE(h && z && var_mean && chol_var && mean_const && outputscale && lengthscale, DVG_ERR_NULL,
                 "dvg_gp_train_bwd: NULL input");
     DVG_REQUIRE(dh && dz && dm && dls && dc && ds && dell, DVG_ERR_NULL, "dvg_gp_train_bwd: NULL output");
@@ -979,24 +1054,25 @@ extern "C" int dvg_gp_train_bwd(const float* h, const float* z, const float* var
     DVG_REQUIRE(lds <= GP_LDS_MAX, DVG_ERR_SHAPE, "dvg_gp_train_bwd: %zu bytes of LDS needed (> 160 KiB)", lds);
     GpBwdParams p{h, z, var_mean, chol_var, mean_const, outputscale, lengthscale, gmean, gvar, gkl,
                   dh, dz, dm, dls, dc, ds, dell, B, D, M, dvg_gp_bwd_chunk(Bw, M), Dp, SG, jitter,
-                  g_gp_clk, g_gp_clk_cap};
+                  g_gp_clk, g_gp_clk_cap, cov_kind};
     const int nt = gp_threads(GP_BWD_THREADS, nwg, Bw, true);
     const char* who = "dvg_gp_train_bwd";
     D = nwg;        // the grid
     DVG_REQUIRE(SG == 1 || dvg_gp_bwd_precision(Bw, M) == 64, DVG_ERR_SHAPE,
                 "dvg_gp_train_bwd: step_group=%d x B=%d points do not fit the LDS in fp64", SG, B);
-    if (dvg_gp_bwd_precision(Bw, M) == 64) {
-        switch (nt) {
-            case 256: return gp_launch(gp_train_bwd_kernel<256, double>, 256, p, D, lds, stream, who);
-            case 512: return gp_launch(gp_train_bwd_kernel<512, double>, 512, p, D, lds, stream, who);
-            default: return gp_launch(gp_train_bwd_kernel<1024, double>, 1024, p, D, lds, stream, who);
-        }
-    }
-    switch (nt) {
-        case 256: return gp_launch(gp_train_bwd_kernel<256, float>, 256, p, D, lds, stream, who);
-        case 512: return gp_launch(gp_train_bwd_kernel<512, float>, 512, p, D, lds, stream, who);
-        default: return gp_launch(gp_train_bwd_kernel<1024, float>, 1024, p, D, lds, stream, who);
-    }
+    const bool matern = cov_kind != DVG_GP_KERNEL_RBF;
+    if (dvg_gp_bwd_precision(Bw, M) == 64)
+        return matern ? gp_bwd_launch<double, true>(nt, p, D, lds, stream, who) : gp_bwd_launch<double, false>(nt, p, D, lds, stream, who);
+    return matern ? gp_bwd_launch<float, true>(nt, p, D, lds, stream, who) : gp_bwd_launch<float, false>(nt, p, D, lds, stream, who);
+}
+
+extern "C" int dvg_gp_train_bwd(const float* h, const float* z, const float* var_mean, const float* chol_var,
+                                const float* mean_const, const float* outputscale, const float* lengthscale,
+                                const float* gmean, const float* gvar, const float* gkl, float* dh, float* dz,
+                                float* dm, float* dls, float* dc, float* ds, float* dell, int B, int D, int M,
+                                float jitter, int param_period, int step_group, void* stream) {
+    return dvg_gp_train_bwd_cov(h, z, var_mean, chol_var, mean_const, outputscale, lengthscale, gmean, gvar, gkl, dh, dz, dm, dls,
+                                dc, ds, dell, B, D, M, jitter, param_period, step_group, DVG_GP_KERNEL_RBF, stream);
 }
 
 static int gp_elbo_checks(const float* mean, const float* var, const float* kl, const float* target, const float* raw_noise,

@@ -15,18 +15,18 @@ from . import ops
 
 class _GPTrain(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, h, z, m, ls, c, s, ell, jitter):
-        r = ops.gp_predict(h, z, m, ls, c, s, ell, want_var=True, want_kl=True, train_mode=True, jitter=jitter)
+    def forward(ctx, h, z, m, ls, c, s, ell, jitter, kernel="rbf"):
+        r = ops.gp_predict(h, z, m, ls, c, s, ell, want_var=True, want_kl=True, train_mode=True, jitter=jitter, kernel=kernel)
         ctx.save_for_backward(h, z, m, ls, c, s, ell)
-        ctx.jitter = jitter
+        ctx.jitter, ctx.kernel = jitter, kernel
         return r["mean"], r["var"], r["kl"]
 
     @staticmethod
     def backward(ctx, dmean, dvar, dkl):
         h, z, m, ls, c, s, ell = ctx.saved_tensors
-        g = ops.gp_train_bwd(h, z, m, ls, c, s, ell, dmean, dvar, dkl, ctx.jitter)
+        g = ops.gp_train_bwd(h, z, m, ls, c, s, ell, dmean, dvar, dkl, ctx.jitter, kernel=ctx.kernel)
         return g["dh"], g["dz"].view_as(z), g["dm"], g["dls"], g["dc"].view_as(c), g["ds"].view_as(s), \
-            g["dell"].view_as(ell), None
+            g["dell"].view_as(ell), None, None
 
 
 STEP_GROUPS = True   # several time steps of a latent dim per workgroup where dvg_gp_step_group says so (tests switch it off to
@@ -39,22 +39,23 @@ class _GPTrainSteps(torch.autograd.Function):
     (ops.gp_step_group); backward sums the per-workgroup parameter gradients over the groups in one launch."""
 
     @staticmethod
-    def forward(ctx, h, z, m, ls, c, s, ell, jitter, S):
+    def forward(ctx, h, z, m, ls, c, s, ell, jitter, S, kernel="rbf"):
         D = z.shape[0]
         k = ops.gp_step_group(h.shape[0], S, D, z.shape[1]) if STEP_GROUPS else 1
         r = ops.gp_predict(h, z, m, ls, c, s, ell, want_var=True, want_kl=True, train_mode=True, jitter=jitter, param_period=D,
-                           step_group=k)
+                           step_group=k, kernel=kernel)
         ctx.save_for_backward(h, z, m, ls, c, s, ell)
-        ctx.jitter, ctx.S, ctx.k = jitter, S, k
+        ctx.jitter, ctx.S, ctx.k, ctx.kernel = jitter, S, k, kernel
         return r["mean"], r["var"], r["kl"]
 
     @staticmethod
     def backward(ctx, dmean, dvar, dkl):
         h, z, m, ls, c, s, ell = ctx.saved_tensors
-        g = ops.gp_train_bwd(h, z, m, ls, c, s, ell, dmean, dvar, dkl, ctx.jitter, param_period=z.shape[0], step_group=ctx.k)
+        g = ops.gp_train_bwd(h, z, m, ls, c, s, ell, dmean, dvar, dkl, ctx.jitter, param_period=z.shape[0], step_group=ctx.k,
+                             kernel=ctx.kernel)
         grads = [g["dz"], g["dm"], g["dls"], g["dc"], g["ds"], g["dell"]]
         dz, dm, dls, dc, ds, dell = ops.sum_steps(grads, g["groups"]) if g["groups"] > 1 else grads
-        return g["dh"], dz.view_as(z), dm.view_as(m), dls.view_as(ls), dc.view_as(c), ds.view_as(s), dell.view_as(ell), None, None
+        return g["dh"], dz.view_as(z), dm.view_as(m), dls.view_as(ls), dc.view_as(c), ds.view_as(s), dell.view_as(ell), None, None, None
 
 
 class _GPElboSteps(torch.autograd.Function):
@@ -81,7 +82,7 @@ def gp_train(layer, h, noise):
     s, ell, c = layer.hypers()
     mean, var, kl = _GPTrain.apply(h if h.is_contiguous() else h.contiguous(), vs.inducing_points,
                                    vs.variational_distribution.variational_mean,
-                                   vs.variational_distribution.chol_variational_covar, c, s, ell, JITTER)
+                                   vs.variational_distribution.chol_variational_covar, c, s, ell, JITTER, layer.kernel)
     if noise is not None:
         var = var + noise.view(-1, 1)
     return {"mean": mean, "var": var, "kl": kl, "sample": None, "cov": None}
@@ -105,7 +106,7 @@ def gp_elbo_steps(layer, mll, hin, htgt):
     s, ell, c = layer.hypers()
     hp = hin.permute(1, 0, 2).reshape(B, S * D)
     mean, var, kl = _GPTrainSteps.apply(hp, vs.inducing_points.squeeze(-1), vd.variational_mean, vd.chol_variational_covar,
-                                        c, s, ell, JITTER, S)
+                                        c, s, ell, JITTER, S, layer.kernel)
     tgt = htgt.permute(1, 0, 2).reshape(B, S * D).transpose(0, 1)          # (S * D, B), strided like h_target.transpose(0, 1)
     elbo = _GPElboSteps.apply(mean, var, kl, tgt, mll.likelihood.noise_covar.raw_noise.reshape(-1), mll.num_data, S)
     return elbo, mean.view(S, D, B).transpose(1, 2)

@@ -7,7 +7,7 @@ WhitenedVariationalStrategy / GaussianLikelihood / MultivariateNormal /
 VariationalELBO performed for the reference call sites (train.py:101-112,225-232,
 283-284; generate_frames.py:67-72,131,170,229,273,291) is stated in DESIGN.md
 ("GP: equations of record") and runs as ONE `dvg_gp_predict` launch per call:
-RBF assembly, both Cholesky factorisations, solves, predictive moments, KL and the
+covariance assembly (RBF or Matern), both Cholesky factorisations, solves, predictive moments, KL and the
 reparameterised sample, one workgroup per latent dimension.
 
 `GaussianLikelihood` and `VariationalELBO` are the minimal stand-ins for
@@ -87,6 +87,20 @@ def _announce(what: str, report: dict) -> None:
         print(f"{what}.load_state_dict: " + "; ".join(f"{k}: {', '.join(v)}" for k, v in report.items() if v), file=sys.stderr)
 
 
+def covariance(kernel: str, diff: torch.Tensor, s: torch.Tensor, ell: torch.Tensor) -> torch.Tensor:
+    """k(d) of ScaleKernel(RBFKernel) / ScaleKernel(MaternKernel(nu = 1/2, 3/2, 5/2)) on signed differences `diff` (D, ., .) with
+    output scale s and length scale ell (D,): what the kernels assemble (gp.hip: gp_cov), in torch, for the host-side
+    initialisation.  Equations: docs/DESIGN_NOTES_gp_kernels.md."""
+    ops.gp_kernel_code(kernel)      # an unknown name raises here
+    s, r = s.view(-1, 1, 1), diff.abs() / ell.view(-1, 1, 1)
+    if kernel == "rbf":
+        return s * torch.exp(-0.5 * diff * diff / ell.view(-1, 1, 1) ** 2)
+    if kernel == "matern12":
+        return s * torch.exp(-r)
+    a = math.sqrt(3.0 if kernel == "matern32" else 5.0) * r
+    return s * ((1.0 + a) if kernel == "matern32" else (1.0 + a + a * a / 3.0)) * torch.exp(-a)
+
+
 class _Holder(nn.Module):
     """Parameter container (never called)."""
 
@@ -115,7 +129,7 @@ class GPPrediction:
                                   vs.variational_distribution.chol_variational_covar, lay.mean_module.constant,
                                   lay.covar_module.raw_outputscale, lay.covar_module.base_kernel.raw_lengthscale,
                                   noise=self._raw_noise, eps=eps, want_cov=want_cov, want_kl=self._training,
-                                  train_mode=self._training, jitter=JITTER, raw_hypers=True)
+                                  train_mode=self._training, jitter=JITTER, raw_hypers=True, kernel=lay.kernel)
         s, ell, c = lay.hypers()
         noise = self._noise
         if noise is None and self._raw_noise is not None:
@@ -123,7 +137,7 @@ class GPPrediction:
         return ops.gp_predict(self._h, vs.inducing_points, vs.variational_distribution.variational_mean,
                               vs.variational_distribution.chol_variational_covar, c, s, ell,
                               noise=noise, eps=eps, want_cov=want_cov, want_kl=self._training,
-                              train_mode=self._training, jitter=JITTER)
+                              train_mode=self._training, jitter=JITTER, kernel=lay.kernel)
 
     def _moments(self):
         if self._res is None:
@@ -175,12 +189,17 @@ class GPPrediction:
 class GPRegressionLayer1(nn.Module):
     """D independent 1-D sparse variational GPs, M learnable inducing points each
     (gp_models.py:10-24): constant mean, ScaleKernel(RBFKernel), Cholesky variational
-    distribution, whitened variational strategy."""
+    distribution, whitened variational strategy.  kernel: "rbf" (the reference's) or "matern12" / "matern32" / "matern52" -
+    ScaleKernel(MaternKernel(nu)) with the same parameters and state_dict keys; a plain attribute, not part of the state."""
 
-    def __init__(self, num_dims=90, num_inducing_points=40):
+    kernel = "rbf"      # (a layer object pickled before the attribute existed is an RBF layer)
+
+    def __init__(self, num_dims=90, num_inducing_points=40, kernel="rbf"):
         super().__init__()
         D, M = num_dims, num_inducing_points
         self.num_dims, self.num_inducing_points = D, M
+        ops.gp_kernel_code(kernel)      # an unknown name raises here
+        self.kernel = kernel
         vs = _Holder()
         vs.inducing_points = nn.Parameter(torch.rand(D, M, 1))                    # gp_models.py:13
         vd = _Holder()
@@ -222,7 +241,7 @@ class GPRegressionLayer1(nn.Module):
         s, ell, c = [t.double() for t in self.hypers()]
         z = vs.inducing_points.squeeze(-1).double()
         diff = z.unsqueeze(-1) - z.unsqueeze(-2)
-        kzz = s.view(-1, 1, 1) * torch.exp(-0.5 * diff * diff / ell.view(-1, 1, 1) ** 2)
+        kzz = covariance(self.kernel, diff, s, ell)
         kzz = kzz + INIT_JITTER_TERMS * JITTER * torch.eye(z.shape[1], dtype=torch.float64, device=z.device)
         # one-off 40x40 fp64 inverse per latent dim at initialisation time (host of the path, not
         # on it): done on the CPU so that no BLAS/solver library is pulled onto the device

@@ -38,7 +38,7 @@ from .norm import (  # noqa: F401
 )
 from .gp import (  # noqa: F401
     gp_predict, gp_var_norms, gp_trigger_step, gp_trigger_replay, gp_trigger_select, gp_elbo, gp_elbo_bwd,
-    sum_steps, gp_step_group, gp_train_bwd,
+    sum_steps, gp_step_group, gp_train_bwd, GP_KERNELS, gp_kernel_code,
 )
 from .backward import (  # noqa: F401
     _LOSS_W, frame_losses, FRAME_LOSS_KINDS, frame_losses_ext, frame_ssim_loss, mse_sum_grad, conv_wgrad_partial, conv_wgrad_partial_multi, winograd_wgrad_ok,

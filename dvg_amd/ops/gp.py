@@ -4,8 +4,18 @@ from __future__ import annotations
 
 import torch
 
-from .._lib import check, lib
+from .._lib import ENUMS, check, lib
 from ._core import _dev_f32, _p, _run, _stream
+
+# the covariance families of the GP (--gp_kernel): name -> DVG_GP_KERNEL_<NAME> of include/dvg_hip.h
+GP_KERNELS = {name[len("GP_KERNEL_"):].lower(): code for name, code in ENUMS.items() if name.startswith("GP_KERNEL_")}
+
+
+def gp_kernel_code(kernel: str) -> int:
+    try:
+        return GP_KERNELS[kernel]
+    except KeyError:
+        raise RuntimeError(f"GP kernel {kernel!r} is not one of {', '.join(GP_KERNELS)}") from None
 
 
 # ----------------------------------------------------------------------------------
@@ -13,12 +23,13 @@ from ._core import _dev_f32, _p, _run, _stream
 # ----------------------------------------------------------------------------------
 def gp_predict(h, z, var_mean, chol_var, mean_const, outputscale, lengthscale, *, noise=None, eps=None,
                want_var=True, want_cov=False, want_kl=False, train_mode=False, jitter=1e-3, raw_hypers=False, param_period=0,
-               step_group=1):
+               step_group=1, kernel="rbf"):
     """h [B][D] (any strides); returns dict(mean [D][B], var, sample, cov, kl).  raw_hypers: outputscale / lengthscale /
     noise are the RAW parameters, soft-plus'ed (noise: + 1e-4 floor) inside the kernel.
     param_period = P > 0: h carries D = S x P columns - S time steps side by side - and column d uses the parameters of
     latent dim d % P (the parameter tensors have P rows).  step_group = k > 1: k consecutive steps of a latent dim are one
-    workgroup's problem (dvg_hip.h; train-mode outputs only) - same outputs."""
+    workgroup's problem (dvg_hip.h; train-mode outputs only) - same outputs.  kernel: the covariance family (GP_KERNELS)."""
+    kind = gp_kernel_code(kernel)
     _dev_f32(h, "gp_predict.h")
     h = h if h.is_contiguous() else h.contiguous()
     b, d = h.shape
@@ -38,9 +49,9 @@ def gp_predict(h, z, var_mean, chol_var, mean_const, outputscale, lengthscale, *
     if d % dp or args[0].numel() != dp * m or args[2].numel() != dp * m * m or args[3].numel() != dp:
         raise RuntimeError("gp_predict: parameter shapes do not match (D,M) / the parameter period")
     nz = None if noise is None else noise.detach().contiguous().view(-1)
-    _run("gp_predict", 0.0, 4.0 * (b * d + d * m * (m + 2) + 3 * d * b), lib().dvg_gp_predict, _p(h),
+    _run("gp_predict", 0.0, 4.0 * (b * d + d * m * (m + 2) + 3 * d * b), lib().dvg_gp_predict_cov, _p(h),
          *[_p(t) for t in args], _p(nz), _p(eps), _p(mean), _p(var), _p(sample), _p(cov), _p(kl), b, d, m,
-         int(train_mode) | (2 if raw_hypers else 0), jitter, int(param_period), int(step_group), _stream())
+         int(train_mode) | (2 if raw_hypers else 0), jitter, int(param_period), int(step_group), kind, _stream())
     return {"mean": mean, "var": var, "sample": sample, "cov": cov, "kl": kl}
 
 
@@ -159,10 +170,11 @@ def gp_step_group(b, steps, period, m):
     return lib().dvg_gp_step_group(int(b), int(steps), int(period), int(m))
 
 
-def gp_train_bwd(h, z, m, ls, c, s, ell, gmean, gvar, gkl, jitter=1e-3, param_period=0, step_group=1):
+def gp_train_bwd(h, z, m, ls, c, s, ell, gmean, gvar, gkl, jitter=1e-3, param_period=0, step_group=1, kernel="rbf"):
     """Gradients of the train-mode GP prediction (see dvg_gp_train_bwd); with param_period = P the parameter gradients come
     back per WORKGROUP: G x P rows, G = ceil(S / step_group) groups of the D = S x P columns of h (out["groups"] = G;
-    sum_steps adds the G copies up)."""
+    sum_steps adds the G copies up).  kernel: the covariance family of the forward call (GP_KERNELS)."""
+    kind = gp_kernel_code(kernel)
     h = h if h.is_contiguous() else h.contiguous()
     b, d = h.shape
     mm = z.shape[1]
@@ -176,7 +188,7 @@ def gp_train_bwd(h, z, m, ls, c, s, ell, gmean, gvar, gkl, jitter=1e-3, param_pe
            "groups": groups}
     args = [t.detach().contiguous().view(-1) for t in (z, m, ls, c, s, ell)]
     g = [None if t is None else t.contiguous() for t in (gmean, gvar, gkl)]
-    check(lib().dvg_gp_train_bwd(_p(h), *[_p(t) for t in args], *[_p(t) for t in g], _p(out["dh"]), _p(out["dz"]),
-                                 _p(out["dm"]), _p(out["dls"]), _p(out["dc"]), _p(out["ds"]), _p(out["dell"]), b, d,
-                                 mm, jitter, int(param_period), k, _stream()), "gp_train_bwd")
+    check(lib().dvg_gp_train_bwd_cov(_p(h), *[_p(t) for t in args], *[_p(t) for t in g], _p(out["dh"]), _p(out["dz"]),
+                                     _p(out["dm"]), _p(out["dls"]), _p(out["dc"]), _p(out["ds"]), _p(out["dell"]), b, d,
+                                     mm, jitter, int(param_period), k, kind, _stream()), "gp_train_bwd")
     return out

@@ -41,8 +41,8 @@ def rank_path(path: str, rank: int) -> str:
 
 # fields a fingerprint carries only when they differ from the value given here: a state without the field was written by a run
 # with that value (every state from before --predictor is an `lstm` state, every one from before --optimizer was honoured an
-# `adam` state), and such a run writes the fingerprint it always did
-ABSENT_MEANS = {"predictor": "lstm", "optimizer": "adam"}
+# `adam` state, every one from before --gp_kernel an `rbf` state), and such a run writes the fingerprint it always did
+ABSENT_MEANS = {"predictor": "lstm", "optimizer": "adam", "gp_kernel": "rbf"}
 
 
 def option_fingerprint(opt) -> dict:

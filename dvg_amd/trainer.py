@@ -16,6 +16,19 @@ from .rollout import frames_as_batch, gp_input
 from .utils import init_weights
 
 
+class GPKernelReport:
+    """train.py's epoch line of --gp_kernel (None without the flag or with rbf: no line, no read)."""
+
+    def __init__(self, gp_layer):
+        self.gp_layer = gp_layer
+
+    @torch.no_grad()
+    def epoch_line(self) -> str:
+        s, ell, _ = self.gp_layer.hypers()
+        ell_mean, s_mean = torch.stack([ell.mean(), s.mean()]).tolist()      # one read of the device, once per epoch
+        return '     gp kernel: %s  mean lengthscale %.4f  mean outputscale %.4f' % (self.gp_layer.kernel, ell_mean, s_mean)
+
+
 class Trainer:
     """The module-level state of the reference script, as an object (so tests can drive single steps)."""
 
@@ -31,7 +44,8 @@ class Trainer:
         predictor = lstm_models.PREDICTORS[getattr(opt, "predictor", "lstm")]
         self.frame_predictor = predictor(opt.g_dim, opt.g_dim, opt.rnn_size, opt.predictor_rnn_layers, opt.local_batch)
         self.frame_predictor.apply(init_weights)
-        self.gp_layer = GPRegressionLayer1(num_dims=opt.g_dim)
+        # --gp_kernel: the GP's covariance family, the reference's rbf (the default) or a Matern member
+        self.gp_layer = GPRegressionLayer1(num_dims=opt.g_dim, kernel=getattr(opt, "gp_kernel", "rbf"))
         self.likelihood = GaussianLikelihood(batch_size=opt.g_dim)
         self.modules = [self.encoder, self.decoder, self.frame_predictor, self.gp_layer, self.likelihood]
         for m in self.modules:
@@ -90,6 +104,7 @@ class Trainer:
         self.encoder_optimizer = make_optimizer(spec, "encoder", self.encoder.parameters(), lr, self.arena)
         # the epoch line of the new flags; None = nothing exists
         self.optim_report = spec and OptimizerReport(spec, self.optimizers(), self.arena.p.numel())
+        self.gp_report = GPKernelReport(self.gp_layer) if self.gp_layer.kernel != "rbf" else None
         self.scheduler = torch.optim.lr_scheduler.MultiStepLR(self.optimizer, milestones=[3, 5], gamma=0.1)
         # num_data = the GLOBAL batch (train.py:112 passes opt.batch_size): each rank's loss is ll_r/B_local - KL/num_data and
         # the ranks are averaged, which gives the reference's ll/B - KL/B at the same global batch for any number of ranks

@@ -36,6 +36,7 @@ from dvg_amd import datasets, mnist, ops, viz  # noqa: E402
 from dvg_amd.data import SyntheticMovingMNIST, make_batch_generator, synthetic_video  # noqa: E402
 from dvg_amd.rollout import (GraphedSampler, GraphedTrigger, condition, gp_input, posterior_from, sample_from, sample_rollout,  # noqa: E402
                              trigger_body, trigger_log, trigger_warmup)
+from dvg_amd.ops import GP_KERNELS  # noqa: E402
 from gp_models import GaussianLikelihood, GPRegressionLayer1  # noqa: E402
 
 
@@ -59,6 +60,8 @@ def build_parser():
     p.add_argument('--predictor', default='lstm', choices=('lstm', 'gru', 'rnn'),
                    help='--synthetic_ckpt: the frame predictor class to build (a loaded checkpoint runs the class it carries)')
     p.add_argument('--predictor_rnn_layers', type=int, default=2)
+    p.add_argument('--gp_kernel', default='rbf', choices=tuple(GP_KERNELS),
+                   help='--synthetic_ckpt: the covariance family of the GP layer to build (a loaded checkpoint runs the one its opt names: train.py --gp_kernel)')
     p.add_argument('--z_dim', type=int, default=10)
     p.add_argument('--g_dim', type=int, default=90)
     p.add_argument('--model', default='dcgan')
@@ -101,7 +104,8 @@ class Generator:
         self.encoder, self.decoder = ckpt['encoder'], ckpt['decoder']
         self.frame_predictor = ckpt['frame_predictor']
         self.likelihood = GaussianLikelihood(batch_size=opt.g_dim)
-        self.gp_layer = GPRegressionLayer1(opt.g_dim)
+        # the covariance family the checkpoint was trained with (train.py --gp_kernel, kept in its opt; absent: rbf)
+        self.gp_layer = GPRegressionLayer1(opt.g_dim, kernel=getattr(ckpt.get('opt') or opt, 'gp_kernel', 'rbf'))
         self.likelihood.load_state_dict(ckpt['likelihood'])
         self.gp_layer.load_state_dict(ckpt['gp_layer'])
         for m in (self.encoder, self.decoder, self.frame_predictor, self.gp_layer, self.likelihood):
@@ -356,7 +360,8 @@ def synthetic_checkpoint(opt):
     predictor = lstm_models.PREDICTORS[getattr(opt, 'predictor', 'lstm')]
     fp = predictor(opt.g_dim, opt.g_dim, opt.rnn_size, opt.predictor_rnn_layers, opt.batch_size)
     fp.apply(utils.init_weights)
-    gp, lik = GPRegressionLayer1(opt.g_dim), GaussianLikelihood(batch_size=opt.g_dim)
+    gp = GPRegressionLayer1(opt.g_dim, kernel=getattr(opt, 'gp_kernel', 'rbf'))
+    lik = GaussianLikelihood(batch_size=opt.g_dim)
     return {'encoder': enc, 'decoder': dec, 'frame_predictor': fp, 'likelihood': lik.state_dict(),
             'gp_layer': gp.state_dict(), 'opt': opt}
 

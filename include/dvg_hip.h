@@ -367,49 +367,49 @@ int dvg_stem_gemm(const float* vec, int ldv, const float* w_kn, int KP, const fl
 
 /* ------------------------------------------------------------------ *
  * Sparse variational GP trigger (gp_models.py:10-24 + gpytorch 0.3.x WhitenedVariationalStrategy / GaussianLikelihood /
- * MultivariateNormal; equations of record in DESIGN.md §GP).  One workgroup per latent dim. */
-
-/* Predictive distribution q(f(x)) for D independent 1-D GPs, M inducing points.
+ * MultivariateNormal; equations of record in DESIGN.md §GP).  One workgroup per latent dim.
+ * Predictive distribution q(f(x)) for D independent 1-D GPs, M inducing points.
  *   h            [B][D]   latent codes; GP d sees column d (the reference's h.transpose(0,1).view(D,B,1), train.py:225)
- *   z            [D][M]   inducing inputs
- *   var_mean     [D][M]   variational mean m
+ *   z            [D][M]   inducing inputs;  var_mean [D][M] variational mean m
  *   chol_var     [D][M][M] variational Cholesky factor (lower part is used)
  *   mean_const   [D], outputscale [D], lengthscale [D]  (already soft-plus'ed)
  *   noise        [D] or NULL: likelihood noise added to the variance/covariance (GaussianLikelihood.__call__, generate_frames.py:131,170)
- * Outputs (any may be NULL):
- *   mean [D][B]; var [D][B] (marginal variance; train-mode clamp at 0 when `train_mode` != 0); sample [D][B] = mean +
- *   chol(Sigma)*eps with eps [D][B] supplied by the caller (MultivariateNormal.rsample); cov [D][B][B] full predictive covariance
- *   (eval mode only).  kl [D] (train mode: KL(q(u)||p(u))).
+ * Outputs (any may be NULL): mean [D][B]; var [D][B] (marginal variance; train-mode clamp at 0 when `train_mode` != 0); sample
+ *   [D][B] = mean + chol(Sigma)*eps with eps [D][B] supplied by the caller (MultivariateNormal.rsample); cov [D][B][B] full
+ *   predictive covariance (eval mode only).  kl [D] (train mode: KL(q(u)||p(u))).
  * train_mode is a flag word: bit 0 = train-mode prediction (diagonal variance with the clamp, KL); bit 1 = outputscale /
  * lengthscale / noise point at the RAW parameters (covar_module.raw_outputscale, base_kernel.raw_lengthscale,
  * noise_covar.raw_noise) and the kernel applies soft-plus itself (noise: + the 1e-4 floor of GaussianLikelihood).
  * Arithmetic (ABI 6): inputs and outputs are fp32; INSIDE the kernel the covariance assembly, chol(K_ZZ), the triangular
  * solves, the k(x,x) - A^T A cancellation, the KL terms, chol(Sigma) and the sample are computed in fp64 whenever the fp64
- * working set fits the 160 KiB of LDS (M = 40: every B <= 128; above B = 95 the covariance is kept as a packed lower
- * triangle on top of the dead K_ZZ factors), otherwise in fp32.
- * dvg_gp_precision(B, M, cov||sample) returns 64 or 32 accordingly (DVG_GP_FP32=1 in the environment forces 32 for A/B
- * runs); dvg_gp_lds_bytes the LDS bytes of the variant that will run.
- * Limits: M <= 64, B <= 128 and dvg_gp_lds_bytes(B, M, cov||sample) <= 160 KiB. */
+ * working set fits the 160 KiB of LDS (M = 40: every B <= 128; above B = 95 the covariance is kept as a packed lower triangle on
+ * top of the dead K_ZZ factors), otherwise in fp32.  dvg_gp_precision(B, M, cov||sample) returns 64 or 32 accordingly;
+ * dvg_gp_lds_bytes the LDS bytes of the variant that will run.  Limits: M <= 64, B <= 128 and those bytes <= 160 KiB. */
 int dvg_gp_precision(int B, int M, int need_cov);
 size_t dvg_gp_lds_bytes(int B, int M, int need_cov);
+/* param_period (ABI 8; 0 = D): workgroup d reads the parameters (z, var_mean, chol_var, mean_const, outputscale, lengthscale, noise)
+ * of latent dim d % param_period - the S time steps of a training closure side by side as D = S * g_dim dims on ONE parameter set.
+ * step_group (ABI 8; <= 1: one workgroup per column of h): k > 1 (train-mode outputs only, k <= S): workgroup g * param_period + q
+ * takes the steps [g k, g k + k) of latent dim q as ONE problem of up to k * B points - K_ZZ, its factor and the KL term once per
+ * k steps.  Same outputs, same layout; mean / var bit-identical to k = 1. */
 int dvg_gp_predict(const float* h, const float* z, const float* var_mean, const float* chol_var, const float* mean_const,
                    const float* outputscale, const float* lengthscale, const float* noise, const float* eps, float* mean,
                    float* var, float* sample, float* cov, float* kl, int B, int D, int M, int train_mode, float jitter,
-                   int param_period /* ABI 8; 0 = D.  Workgroup d reads the parameters (z, var_mean, chol_var, mean_const,
-                                       outputscale, lengthscale, noise) of latent dim d % param_period: the S time steps of a
-                                       training closure side by side as D = S * g_dim dims on ONE parameter set */,
-                   int step_group /* ABI 8; <= 1: one workgroup per column of h.  k > 1 (train-mode outputs only, k <= S):
-                                     workgroup g * param_period + q takes the steps [g k, g k + k) of latent dim q as ONE
-                                     problem of up to k * B points - K_ZZ, its factor and the KL term once per k steps.
-                                     Same outputs, same layout; mean / var bit-identical to k = 1 */,
-                   void* stream);
+                   int param_period, int step_group, void* stream);
 /* the step_group the host side uses for a time-batched training call of S steps x P latent dims x B points (1 = no grouping) */
 int dvg_gp_step_group(int B, int S, int P, int M);
+/* Covariance family (same parameters; docs/DESIGN_NOTES_gp_kernels.md), r = |z - x| / l:  RBF s exp(-r^2 / 2);  MATERN12 s exp(-r);
+ * MATERN32 s (1 + a) exp(-a), a = sqrt(3) r;  MATERN52 s (1 + a + a^2 / 3) exp(-a), a = sqrt(5) r.  Bound as dvg_amd._lib.ENUMS.
+ * dvg_gp_predict_cov: dvg_gp_predict (= this call with DVG_GP_KERNEL_RBF) for the family cov_kind; any other code: DVG_ERR_SHAPE. */
+enum { DVG_GP_KERNEL_RBF = 0, DVG_GP_KERNEL_MATERN12 = 1, DVG_GP_KERNEL_MATERN32 = 2, DVG_GP_KERNEL_MATERN52 = 3 };
+int dvg_gp_predict_cov(const float* h, const float* z, const float* var_mean, const float* chol_var, const float* mean_const,
+                       const float* outputscale, const float* lengthscale, const float* noise, const float* eps, float* mean,
+                       float* var, float* sample, float* cov, float* kl, int B, int D, int M, int train_mode, float jitter,
+                       int param_period, int step_group, int cov_kind, void* stream);
 
 /* ------------------------------------------------------------------ *
- * Backward (training) entry points: what `loss.backward()` (train.py:170,194,240)
- * runs for the modules above.  Data gradients of the dense convs reuse the
- * forward implicit-GEMM kernels with re-packed weights:
+ * Backward (training) entry points: what `loss.backward()` (train.py:170,194,240) runs for the modules above.  Data gradients
+ * of the dense convs reuse the forward implicit-GEMM kernels with re-packed weights:
  *   dgrad(Conv2d 3x3)        = dvg_conv3x3_bn_act_v2    with the transposed/flipped k16 pack of W
  *   dgrad(Conv2d 4x4 s2)     = dvg_convT4x4s2_bn_act_v2 with the transposed k16 pack of W
  *   dgrad(ConvTranspose 4x4) = dvg_conv4x4s2_bn_act_v2  with the plain k16 pack of W */
@@ -417,9 +417,8 @@ int dvg_gp_step_group(int B, int S, int P, int M);
 /* BatchNorm + activation (+ 2x2 max-pool) backward, pass 1:
  *   dp = (dy + scatter_maxpool(dyp)) * act'(y)          (written to `dp`, NHWC)
  *   partial[r] = { sum dp, sum dp*u } per channel, r < dvg_bn_act_bwd_rows(...)
- * y = forward output (post activation), u = conv output before BN.  dy or dyp
- * may be NULL (not both); dyp != NULL selects the pooled variant.
- * groups: N must be a multiple; partial holds groups x dvg_bn_act_bwd_rows(N / groups, ...) rows, group-major.   */
+ * y = forward output (post activation), u = conv output before BN.  dy or dyp may be NULL (not both); dyp != NULL selects the
+ * pooled variant.  groups: N must be a multiple; partial holds groups x dvg_bn_act_bwd_rows(N / groups, ...) rows, group-major.   */
 int dvg_bn_act_bwd_rows(int N, int H, int W, int pool);
 int dvg_bn_act_bwd_reduce(const float* dy, const float* dyp, const float* y, const float* u,
                           float* dp, float* partial, int N, int H, int W, int C, int act,
@@ -654,27 +653,28 @@ int dvg_lstm_gates_bwd(const float* dh, const float* dc, const float* gates, con
 int dvg_gp_bwd_precision(int B, int M);
 size_t dvg_gp_bwd_lds_bytes(int B, int M);
 int dvg_gp_bwd_chunk(int B, int M);
+/* param_period, step_group (ABI 8): as dvg_gp_predict.  The PARAMETER gradients are written per workgroup: dz, dm [G * P][M], dls
+ * [G * P][M][M], dc, ds, dell [G * P] with P = param_period (or D) and G = ceil(S / max(step_group, 1)) - each row already summed
+ * over its workgroup's steps; dvg_sum_steps_multi adds the G rows per latent dim up (G = 1: nothing left).  dvg_gp_train_bwd_cov:
+ * the same for the covariance family cov_kind (DVG_GP_KERNEL_*, else DVG_ERR_SHAPE; dvg_gp_train_bwd = RBF), no second exp. */
 int dvg_gp_train_bwd(const float* h, const float* z, const float* var_mean, const float* chol_var, const float* mean_const,
                      const float* outputscale, const float* lengthscale, const float* gmean, const float* gvar, const float* gkl,
                      float* dh, float* dz, float* dm, float* dls, float* dc, float* ds, float* dell, int B, int D, int M,
-                     float jitter, int param_period /* ABI 8, as dvg_gp_predict */,
-                     int step_group /* ABI 8, as dvg_gp_predict.  The PARAMETER gradients are written per workgroup:
-                                       dz, dm [G * P][M], dls [G * P][M][M], dc, ds, dell [G * P] with P = param_period (or D)
-                                       and G = ceil(S / max(step_group, 1)) - each row already summed over its workgroup's
-                                       steps; dvg_sum_steps_multi adds the G rows per latent dim up (G = 1: nothing left) */,
-                     void* stream);
+                     float jitter, int param_period, int step_group, void* stream);
+int dvg_gp_train_bwd_cov(const float* h, const float* z, const float* var_mean, const float* chol_var, const float* mean_const,
+                         const float* outputscale, const float* lengthscale, const float* gmean, const float* gvar,
+                         const float* gkl, float* dh, float* dz, float* dm, float* dls, float* dc, float* ds, float* dell, int B,
+                         int D, int M, float jitter, int param_period, int step_group, int cov_kind, void* stream);
 /* dst_k[i] = sum over s < S of src_k[s * n_k + i] for count <= 8 tensors in one launch (host arrays of device pointers / sizes):
  * the per-(step, latent dim) parameter gradients of a closure's S side-by-side time steps -> one gradient per parameter.  ABI 8. */
 int dvg_sum_steps_multi(const float* const* src, float* const* dst, const long* n, int count, int S, void* stream);
 
-/* VariationalELBO(likelihood, gp_layer, num_data, combine_terms=True)(pred, target) with the GaussianLikelihood's
- * expected log-probability (train.py:102,112; called at train.py:164-169,225-226): per latent dim d
- *   elbo_d = (1/B) sum_b [ -((y_db - mean_db)^2 + var_db) / (2 sig2_d) - log(sig2_d)/2 - log(2 pi)/2 ] - kl_d / num_data,
- *   sig2_d = softplus(raw_noise_d) + 1e-4.
- * mean, var [D][B] and kl [D] are dvg_gp_predict's train-mode outputs; target is addressed as
- * target[d * t_stride_d + b * t_stride_b] (the reference passes h_target.transpose(0,1), a strided view).
- * dvg_gp_elbo_bwd: given gelbo [D] -> gmean, gvar [D][B], gkl [D], gtarget [D][B] (may be NULL), graw_noise [D]
- * (soft-plus chain included).  ABI 5. */
+/* VariationalELBO(likelihood, gp_layer, num_data, combine_terms=True)(pred, target) with the GaussianLikelihood's expected
+ * log-probability (train.py:102,112; called at train.py:164-169,225-226): per latent dim d, sig2_d = softplus(raw_noise_d) + 1e-4,
+ *   elbo_d = (1/B) sum_b [ -((y_db - mean_db)^2 + var_db) / (2 sig2_d) - log(sig2_d)/2 - log(2 pi)/2 ] - kl_d / num_data.
+ * mean, var [D][B] and kl [D] are dvg_gp_predict's train-mode outputs; target is addressed as target[d * t_stride_d + b *
+ * t_stride_b] (the reference passes h_target.transpose(0,1), a strided view).  dvg_gp_elbo_bwd: given gelbo [D] -> gmean, gvar
+ * [D][B], gkl [D], gtarget [D][B] (may be NULL), graw_noise [D] (soft-plus chain included).  ABI 5. */
 int dvg_gp_elbo(const float* mean, const float* var, const float* kl, const float* target, long t_stride_d,
                 long t_stride_b, const float* raw_noise, float* elbo, int B, int D, int num_data,
                 int noise_period /* ABI 8; 0 = D: workgroup d reads raw_noise[d % noise_period] */, void* stream);

@@ -63,6 +63,7 @@ from dvg_amd import datasets, ema as weight_ema, frame_loss, lr_schedule, optim,
 from dvg_amd.data import make_batch_generator  # noqa: E402
 # the Trainer (dvg_amd/trainer.py), the hipGraph replay of its iteration and the batch prefetcher (dvg_amd/train_graphs.py),
 # re-exported for `train.<name>`
+from dvg_amd.ops import GP_KERNELS  # noqa: E402
 from dvg_amd.optim import guard_options  # noqa: E402,F401
 from dvg_amd.train_graphs import BatchPrefetcher, GraphedIteration, SegmentedIteration  # noqa: E402,F401
 from dvg_amd.trainer import Trainer  # noqa: E402,F401
@@ -100,6 +101,11 @@ def build_parser():
                    help='the frame predictor\'s cell: the reference\'s models.lstm.lstm (default), .gru or .rnn; gru trains in the '
                         'sequence form like lstm, rnn step by step.  Part of the --resume fingerprint when it is not lstm')
     p.add_argument('--predictor_rnn_layers', type=int, default=2)
+    # (no attribute without the flag: the options of such a run - printed, pickled into its checkpoints - are what they always were)
+    p.add_argument('--gp_kernel', default=argparse.SUPPRESS, choices=tuple(GP_KERNELS),
+                   help='the covariance of the GP trigger: the reference\'s ScaleKernel(RBFKernel) (rbf, also what no flag means) or '
+                        'ScaleKernel(MaternKernel(nu)) with nu = 1/2, 3/2, 5/2 - same parameters, same checkpoint keys; stored in '
+                        'the checkpoint\'s opt, which generate_frames.py reads.  Part of the --resume fingerprint when it is not rbf')
     p.add_argument('--z_dim', type=int, default=10)
     p.add_argument('--g_dim', type=int, default=90)
     p.add_argument('--model', default='dcgan', help='dcgan | vgg')
@@ -190,7 +196,7 @@ def main(argv=None):
             print('[%02d] mse loss: %.5f (%d) %.5f' % (epoch, epoch_mse / opt.epoch_size,
                                                        epoch * opt.epoch_size * opt.batch_size, indices))
             print('     train frames/s: %.1f' % fps)
-        for part in (tr.guard, tr.ema, tr.lr_schedule, tr.frame_terms, tr.optim_report):   # one read of each one's device counters: per epoch, outside the iterations
+        for part in (tr.guard, tr.ema, tr.lr_schedule, tr.frame_terms, tr.optim_report, tr.gp_report):   # one read of each one's device counters: per epoch, outside the iterations
             line = part is not None and part.epoch_line()   # every rank reads its own (the same bits everywhere; frame loss: its shard's means), rank 0 prints
             line and rank == 0 and print(line)
         if epoch % opt.save_every == 0:
