@@ -129,6 +129,7 @@ __device__ __forceinline__ unsigned xcd_remap(unsigned bid, unsigned nwg) {
 //   SUM_WAVE_ORDER  ((0 + r0) + r1) + r2 ... left to right over the NT / 64 waves: gp.hip (gp_predict, gp_train_bwd, gp_elbo),
 //                   grad_guard.hip (grad_sumsq, grad_guard_finish), ema.hip (ema_update), ssim_loss.hip (16 waves).  The leading + 0 is gp.hip's loop; the
 //                   wave sums of grad_guard.hip and ema.hip are sums of squares from + 0, never - 0, so it changes none of their bits.
+//                   validate.hip (val_accumulate) and gp_score.hip (gp_score): fp64 sums and int64 counts, four waves.
 //   SUM_PAIRWISE    (r0 + r1) + (r2 + r3), four waves: finn_metrics.hip (eval_frames_finn) and eval_frames_kernel,
 //                   frame_losses_kernel in misc_kernels.hip.
 // One-wave kernels (gp_var_norms, gp_trigger_step, gp_trigger_replay) use wave_sum alone.

@@ -38,7 +38,7 @@ from .norm import (  # noqa: F401
 )
 from .gp import (  # noqa: F401
     gp_predict, gp_var_norms, gp_trigger_step, gp_trigger_replay, gp_trigger_select, gp_elbo, gp_elbo_bwd,
-    sum_steps, gp_step_group, gp_train_bwd, GP_KERNELS, gp_kernel_code,
+    sum_steps, gp_step_group, gp_train_bwd, GP_KERNELS, gp_kernel_code, gp_score, gp_score_slots, gp_score_accumulators,
 )
 from .backward import (  # noqa: F401
     _LOSS_W, frame_losses, FRAME_LOSS_KINDS, frame_losses_ext, frame_ssim_loss, mse_sum_grad, conv_wgrad_partial, conv_wgrad_partial_multi, winograd_wgrad_ok,
@@ -51,3 +51,10 @@ from .lr_schedule import LR_KINDS, lr_schedule_tick  # noqa: F401
 from .validate import val_accumulators, val_accumulate  # noqa: F401
 from .resample import resample_u8, resample_band  # noqa: F401
 from .._lib import check, lib  # noqa: F401
+
+
+def __getattr__(name):
+    if name == "GP_SCORE_SLOTS":      # (sums, counts) of dvg_gp_score, read from the library on first use (ops/gp.py)
+        from . import gp
+        return gp.__getattr__(name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

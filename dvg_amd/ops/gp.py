@@ -148,6 +148,57 @@ def gp_elbo_bwd(mean, var, kl, target, raw_noise, gelbo, num_data, need_gtarget=
     return gmean, gvar, gkl, gtarget, graw
 
 
+def gp_score_slots():
+    """(sums, counts) per row of dvg_gp_score's accumulators, asked of the library (dvg_gp_score_slots, host only): (14, 14)."""
+    import ctypes as C
+    a, c = C.c_int(0), C.c_int(0)
+    check(lib().dvg_gp_score_slots(C.addressof(a), C.addressof(c)), "gp_score_slots")
+    return a.value, c.value
+
+
+def __getattr__(name):
+    # GP_SCORE_SLOTS is read from the library the first time it is asked for, not while the package is imported: importing
+    # dvg_amd.ops loads no shared object, as before
+    if name == "GP_SCORE_SLOTS":
+        globals()[name] = gp_score_slots()
+        return globals()[name]
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
+def gp_score_accumulators(rows: int, device):
+    """(acc, cnt) for `rows` rows, zeroed: acc (rows, 14) fp64, cnt (rows, 14) int64 (dvg_hip.h names the slots)."""
+    na, nc = __getattr__("GP_SCORE_SLOTS")
+    return (torch.zeros((rows, na), dtype=torch.float64, device=device), torch.zeros((rows, nc), dtype=torch.int64, device=device))
+
+
+def gp_score(mean, var, target, acc, cnt, noise=None, noise_period=0) -> None:
+    """acc, cnt += the held-out scores of an eval-mode predictive (dvg_gp_score, csrc/gp_score.hip): mean, var (R, B) contiguous,
+    target (R, B) with any strides, noise None (the latent f is scored) or (P,) VARIANCES - row r uses noise[r % P], P =
+    noise_period or R - added to var inside the kernel; acc (R, 14) fp64, cnt (R, 14) int64 (gp_score_accumulators).  One launch
+    on the current stream, nothing read back."""
+    for t, n in ((mean, "mean"), (var, "var"), (target, "target")) + (() if noise is None else ((noise, "noise"),)):
+        _dev_f32(t, "gp_score." + n)
+        if t.device != mean.device:
+            raise RuntimeError(f"gp_score: {n} must be on mean's device")
+    if mean.dim() != 2 or mean.numel() == 0 or not mean.is_contiguous() or not var.is_contiguous() or \
+            tuple(var.shape) != tuple(mean.shape) or tuple(target.shape) != tuple(mean.shape):
+        raise RuntimeError(f"gp_score: mean {tuple(mean.shape)} and var {tuple(var.shape)} must be contiguous (R, B) tensors, "
+                           f"target {tuple(target.shape)} an (R, B) tensor with any strides")
+    r, b = mean.shape
+    period = int(noise_period)
+    if period < 0 or r % (period or r):
+        raise RuntimeError(f"gp_score: the noise period {period} must be >= 0 and divide R = {r}")
+    if noise is not None and (noise.numel() != (period or r) or not noise.is_contiguous()):
+        raise RuntimeError(f"gp_score: noise must be a contiguous tensor of {period or r} variances, got {tuple(noise.shape)}")
+    na, nc = __getattr__("GP_SCORE_SLOTS")
+    if (acc.dtype != torch.float64 or tuple(acc.shape) != (r, na) or not acc.is_contiguous() or acc.device != mean.device or
+            cnt.dtype != torch.int64 or tuple(cnt.shape) != (r, nc) or not cnt.is_contiguous() or cnt.device != mean.device):
+        raise RuntimeError(f"gp_score: acc must be a contiguous fp64 ({r}, {na}) and cnt a contiguous int64 ({r}, {nc}) tensor on "
+                           "mean's device (ops.gp_score_accumulators)")
+    _run("gp_score", 0.0, 12.0 * mean.numel(), lib().dvg_gp_score, _p(mean), _p(var), _p(noise), period, _p(target),
+         target.stride(0), target.stride(1), b, r, _p(acc), _p(cnt), _stream())
+
+
 def sum_steps(tensors, steps):
     """[t.view(steps, -1).sum(0) for t in tensors] as ONE launch (dvg_sum_steps_multi; up to 8 tensors): (steps * n_k,) -> (n_k,)."""
     import ctypes as C

@@ -10,6 +10,7 @@ mode, recurrent state and cache entry the pass touched is put back.  Without the
 no object, no launch, no file, no state key."""
 from __future__ import annotations
 
+import argparse
 import json
 import math
 import os
@@ -44,15 +45,23 @@ def add_arguments(parser) -> None:
                         help='--val_every: batches of the test split per validation')
     parser.add_argument('--val_nsample', default=4, type=_int_at_least(0, '--val_nsample'), metavar='S',
                         help='--val_every: sample rollouts per clip beside the posterior rollout (0 = the posterior rollout only)')
+    # (no attribute without the flag: the options of such a run - printed, pickled into its checkpoints - are what they always were)
+    parser.add_argument('--val_gp', action='store_true', default=argparse.SUPPRESS,      # docs/DESIGN_NOTES_gp_score.md
+                        help='--val_every: also score the GP trigger\'s predictive on the same clips - negative log predictive '
+                             'density, standardised residuals, 68 %% / 95 %% coverage, PIT histogram, variance ~ squared-error '
+                             'correlation of the one-step latent forecasts, on ground-truth frames and along the posterior rollout '
+                             '(dvg_gp_score); one more "val gp:" line and a "gp" entry per record')
 
 
 def options(opt):
-    """{"every", "batches", "nsample"} when the options ask for validation, else None (an options object from before the flags
-    has no such attribute).  Host only."""
+    """{"every", "batches", "nsample"} - and "gp": True with --val_gp - when the options ask for validation, else None (an options
+    object from before the flags has no such attribute).  Host only."""
     every = int(getattr(opt, "val_every", 0) or 0)
     if every < 0:
         raise SystemExit("train.py: --val_every must be >= 0")
     if every == 0:
+        if getattr(opt, "val_gp", False):
+            raise SystemExit("train.py: --val_gp scores the clips of a validation: it needs --val_every N")
         return None
     batches, nsample = int(getattr(opt, "val_batches", 8)), int(getattr(opt, "val_nsample", 4))
     if batches < 1 or nsample < 0:
@@ -60,7 +69,7 @@ def options(opt):
     if opt.n_eval <= opt.n_past:
         raise SystemExit(f"train.py: --val_every scores the predicted steps n_past ... n_eval - 1: --n_eval {opt.n_eval} leaves none "
                          f"after --n_past {opt.n_past}")
-    return {"every": every, "batches": batches, "nsample": nsample}
+    return dict({"every": every, "batches": batches, "nsample": nsample}, **({"gp": True} if getattr(opt, "val_gp", False) else {}))
 
 
 # ---- from the accumulators to numbers (Python fp64) --------------------------------------------------------------------------------------
@@ -174,6 +183,10 @@ class Validator:
         self.acc = torch.zeros((2, 2, 3, self.steps, 2), dtype=torch.float64, device=self.dev)
         self.cnt = torch.zeros((2, 2, 3, self.steps), dtype=torch.int64, device=self.dev)
         self.best = None        # (B,) int32: the best sample per row of the last batch scored
+        self.gp = None          # --val_gp: the GP scorer (dvg_amd/gp_score.py); without the flag no object, no launch, no key
+        if o.get("gp"):
+            from . import gp_score
+            self.gp = gp_score.GPScorer(opt.g_dim, gp_score.track_steps(opt.n_past, opt.n_eval), self.dev)
 
     def draws(self):
         """The K batches of a validation and their base samples, from the start of both streams: yields (x, eps) with x the
@@ -199,6 +212,7 @@ class Validator:
                 m.eval()
             self._score(*modules)
             flat = torch.cat([self.acc.flatten(), self.cnt.flatten().double()]).cpu()      # the one readback
+            gp = self.gp.read() if self.gp is not None else None                           # (--val_gp: and its own)
         finally:
             live.put_back()
         n = self.acc.numel()
@@ -206,14 +220,19 @@ class Validator:
         cnt = flat[n:].view(self.cnt.shape).long().tolist()
         tracks = {"posterior": summarise(acc[0][0], cnt[0][0]), "best": summarise(acc[1][0], cnt[1][0]),
                   "mean": summarise(acc[1][1], cnt[1][1])}
-        return {"clips": self.batches * int(self.opt.local_batch), "steps": self.steps, "nsample": self.nsample, "tracks": tracks,
-                "score": selection_score(tracks, self.nsample)}
+        res = {"clips": self.batches * int(self.opt.local_batch), "steps": self.steps, "nsample": self.nsample, "tracks": tracks,
+               "score": selection_score(tracks, self.nsample)}
+        if gp is not None:
+            res["gp"] = gp
+        return res
 
     def _score(self, enc, dec, fp, gp, lik):
         opt, T, S = self.opt, self.steps, self.nsample
         lo, hi, lfs = opt.n_past, opt.n_eval, bool(opt.last_frame_skip)
         self.acc.zero_()
         self.cnt.zero_()
+        if self.gp is not None:
+            self.gp.zero()
         for x, eps in self.draws():
             B = x[0].shape[0]
             fp.batch_size = B
@@ -222,6 +241,8 @@ class Validator:
             post = rollout.posterior_from(state, enc, dec, fp, gp, lik, lo, hi, lfs)
             m = ops.eval_frames_finn(gt, torch.stack(post[lo:hi]))                         # three (T, B)
             ops.val_accumulate(*(v.t().contiguous().view(B, 1, T) for v in m), self.acc[0], self.cnt[0])
+            if self.gp is not None:      # the one-step latent forecasts on the clips and along the posterior rollout just made
+                self.gp.score(enc, gp, lik, x, post, lo, hi)
             if S == 0:
                 continue
             ssim, psnr, mse = (torch.empty((B, S, T), device=self.dev) for _ in range(3))
@@ -292,6 +313,9 @@ class Validation:
                 os.makedirs(opt.output_path, exist_ok=True)
                 tr.save(os.path.join(opt.output_path, FILE_BEST))
         print(line("val", res, self.best_live["epoch"]), flush=True)
+        if "gp" in res:
+            from . import gp_score
+            print(gp_score.line("val gp", res["gp"]), flush=True)
         if tr.ema is not None:
             # the same clips and base samples on what model_ema.pth holds: every parameter from the average, every buffer live
             twins = [tr.ema.module_copy(m) for m in tr.modules]
@@ -304,6 +328,9 @@ class Validation:
                     os.makedirs(opt.output_path, exist_ok=True)
                     tr.ema.save(tr, os.path.join(opt.output_path, FILE_EMA_BEST))
             print(line("val(ema)", ema, self.best_ema["epoch"]), flush=True)
+            if "gp" in ema:
+                from . import gp_score
+                print(gp_score.line("val(ema) gp", ema["gp"]), flush=True)
         self.history.append(rec)
         if save:
             write_log(self.history, opt.output_path)

@@ -91,6 +91,11 @@ def build_parser():
                    help='make_gifs: also measure how different the samples are from EACH OTHER (utils.sample_diversity: mean '
                         'pairwise MSE / PSNR between samples and the number of distinct samples, per predicted step); printed per '
                         'batch and saved as `diversity`.  Ignored with --gp_trigger')
+    p.add_argument('--gp_report', action='store_true',
+                   help='make_gifs: also score the GP trigger\'s predictive on the --nbatches test batches (dvg_amd/gp_score.py: NLPD, '
+                        'standardised residuals, coverage, PIT, variance ~ error correlation of the one-step latent forecasts, on '
+                        'ground-truth frames and along the posterior rollout); printed at the end, written to <log_dir>/gen/gp_report.json '
+                        'and saved as `gp_report`.  Ignored with --gp_trigger')
     p.add_argument('--synthetic_data', action='store_true',
                    help='kth | bair | ucf: synthetic clips of that shape instead of the test split under --data_root; smmnist: '
                         'the in-repo sprites even where --data_root holds MNIST')
@@ -184,6 +189,16 @@ class Generator:
         best = ssim.mean(2).argsort(1)[:, -1]   # generate_frames.py:188-189,207: np.argsort(mean_ssim)[-1]
         return {'posterior': torch.stack(post), 'samples': torch.stack(all_gen), 'ssim': ssim, 'psnr': psnr,
                 'best': best, **extra}
+
+    def gp_scorer(self):
+        """--gp_report: a scorer for this checkpoint's latent size and step counts (dvg_amd/gp_score.py); feed it with
+        `score_gp(scorer, x, posterior)` per batch, read it once."""
+        from dvg_amd import gp_score
+        return gp_score.GPScorer(self.opt.g_dim, gp_score.track_steps(self.opt.n_past, self.opt.n_eval), self.dev)
+
+    def score_gp(self, scorer, x, posterior):
+        """One batch: x the ground-truth frames, posterior make_gifs' `posterior` (n_eval, B, C, H, W)."""
+        scorer.score(self.encoder, self.gp_layer, self.likelihood, x, posterior, self.opt.n_past, self.opt.n_eval)
 
     def write_gifs(self, x, res, idx, out_dir, name='lstm', rows=1):
         """generate_frames.py:185-217 on make_gifs' result: `<out_dir>/sample_<name>_<idx + i>.gif` for batch rows i < rows,
@@ -428,6 +443,10 @@ def main(argv=None):
         batches = (utils.normalize_data(opt, torch.cuda.FloatTensor, seq)[0] for seq in seqs)
     if args.diversity and args.gp_trigger:
         print("WARNING: --diversity scores make_gifs' samples; ignored with --gp_trigger", file=sys.stderr)
+    if args.gp_report and args.gp_trigger:
+        print("WARNING: --gp_report scores make_gifs' batches; ignored with --gp_trigger", file=sys.stderr)
+    scorer = gen.gp_scorer() if args.gp_report and not args.gp_trigger else None
+    written = []
     for i, test_x in enumerate(batches):
         if args.gp_trigger:
             res = gen.gp_trigger_gen(test_x, args.trigger_indices, total=opt.n_eval)
@@ -437,6 +456,8 @@ def main(argv=None):
                 gen.write_trigger_pngs(res, '%s/gen' % opt.log_dir)
         else:
             res = gen.make_gifs(test_x, args.nsample, diversity=args.diversity)
+            if scorer is not None:      # accumulated on the device over the batches; read once, after the last
+                gen.score_gp(scorer, test_x, res['posterior'])
             saved = {'posterior': res['posterior'][:, 0].cpu(), 'best': res['best'].cpu(), 'psnr': res['psnr'].cpu(),
                      'ssim': res['ssim'].cpu(),
                      'best_sample_0': res['samples'][int(res['best'][0]), :, 0].cpu()}
@@ -445,6 +466,7 @@ def main(argv=None):
             if 'diversity' in res:
                 saved['diversity'] = {k: v.cpu() for k, v in res['diversity'].items()}
             torch.save(saved, '%s/gen/sample_lstm_%d.pt' % (opt.log_dir, i))
+            scorer is None or written.append(('%s/gen/sample_lstm_%d.pt' % (opt.log_dir, i), saved))
             sel = res['best'].view(-1, 1, 1).expand(-1, 1, res['ssim'].shape[2])
             if 'mse' in res:
                 print('batch %d: best-of-%d by mean Finn SSIM (11x11 Gaussian window): SSIM %.4f, PSNR %.3f dB, MSE %.3e' % (
@@ -461,6 +483,19 @@ def main(argv=None):
                                                             float(dv['distinct'][:, -1].double().mean()), args.nsample))
             if not args.no_images:
                 gen.write_gifs(test_x, res, i, '%s/gen' % opt.log_dir, rows=args.gif_rows)
+    if scorer is not None and written:
+        from dvg_amd import gp_score
+        gen.gp_report = scorer.read()
+        for tag in gp_score.TRACKS:
+            pooled = gen.gp_report[tag]['pooled']
+            print('gp %s (%d entries, %d skipped): nlpd %.4f rmse %.5f mean var %.5f z mean %.3f z std %.3f cover 68/95 %.3f / %.3f '
+                  'pit err %.3f var~err corr %.3f smse %.4f' % (
+                      tag, pooled['taken'], pooled['skipped'], *(gp_score._num(pooled[k]) for k in (
+                          'nlpd', 'rmse', 'mean_var', 'z_mean', 'z_std', 'cover68', 'cover95', 'pit_err', 'var_err_corr', 'smse'))))
+            print(gp_score.curves(tag, gen.gp_report[tag]))
+        gp_score.write_report(gen.gp_report, '%s/gen' % opt.log_dir)
+        for path, saved in written:     # the saved tensors gain `gp_report`: the report of all the batches, known only now
+            torch.save(dict(saved, gp_report=gen.gp_report), path)
     return gen
 
 

@@ -30,32 +30,26 @@ extern "C" {
 #define DVG_ERR_NULL 2    /* required pointer is NULL                    */
 #define DVG_ERR_HIP 3     /* a HIP runtime call / kernel launch failed   */
 #define DVG_ERR_ALIGN 4   /* pointer not 16-byte aligned                 */
-
 /* activation codes for the fused epilogues */
 #define DVG_ACT_NONE 0
 #define DVG_ACT_LRELU 1   /* LeakyReLU(slope)   vgg_64.py:11, dcgan_64.py:10 */
 #define DVG_ACT_TANH 2    /* vgg_64.py:47, dcgan_64.py:45,78, lstm.py:55     */
 #define DVG_ACT_SIGMOID 3 /* vgg_64.py:91                                     */
-
 int dvg_abi_version(void);
 const char* dvg_last_error(void);
 /* 0 when `stream` is not being captured into a hipGraph, else a nonzero id unique to that capture (r04, additive).  For
  * callers that cache buffers whose INITIAL CONTENTS matter (the split-K counter tail below): a buffer first touched during a
  * capture is only initialised when that graph replays, so such a cache must be keyed by the capture.                     */
 long dvg_stream_capture_id(void* stream);
-
 /* ---- Weight re-layout (one launch per parameter, cached by the caller) ---- */
 /* Conv2d weight (Cout,Cin,KH,KW) [vgg_64.py:8, dcgan_64.py:8] -> packed [KH*KW][Cout][Cin] (Cin contiguous = implicit-GEMM K). */
 int dvg_pack_conv_weight(const float* w_oihw, float* w_packed, int cout, int cin, int kh, int kw, void* stream);
-
 /* ConvTranspose2d weight (Cin,Cout,KH,KW) [vgg_64.py:88, dcgan_64.py:20,76] -> packed [KH*KW][Cout][Cin] with the kernel
  * spatially FLIPPED, i.e. the weight of the equivalent direct correlation.                             */
 int dvg_pack_convT_weight(const float* w_iohw, float* w_packed, int cin, int cout, int kh, int kw, void* stream);
-
 /* Inverse of the two packs (used by the backward pass to scatter dW back). */
 int dvg_unpack_conv_weight(const float* w_packed, float* w_oihw, int cout, int cin, int kh, int kw, void* stream);
 int dvg_unpack_convT_weight(const float* w_packed, float* w_iohw, int cin, int cout, int kh, int kw, void* stream);
-
 /* ---- Encoder / decoder blocks ---- */
 /* vgg_layer = Conv2d(nin,nout,3,1,1)+BatchNorm2d+LeakyReLU(0.2)  (vgg_64.py:5-15) as ONE fp32-MFMA implicit GEMM
  * (M = N*H*W pixels, N = Cout, K = 9*Cin):
@@ -78,7 +72,6 @@ int dvg_unpack_convT_weight(const float* w_packed, float* w_iohw, int cin, int c
 /* rows of the `stats` partial buffer of the first-layer kernels (ks = 3 or 4); -1 if the shape is unsupported.  (The
  * implicit-GEMM convs: dvg_conv_stats_rows_v2 below.)                                                                     */
 int dvg_conv_first_stats_rows(int ks, int N, int H, int W);
-
 /* The three implicit-GEMM convs (conv_igemm2.hip; the "_v2" suffix is historical: the first schedule and its un-suffixed entry
  * points were retired in ABI 3).  Weights are packed by dvg_pack_conv_weight_k16 (transposed != 0: ConvTranspose2d weight
  * (Cin,Cout,KH,KW), flipped) into Cin/16 * KH*KW * Cout rows of dvg_packed_row_floats() floats,
@@ -153,7 +146,6 @@ int dvg_convT4x4s2_bn_act_v2(const float* x, const float* skip, const float* w_k
 /* ... on x alone with Cout = 64, then dvg_pixel_proj(y, proj_w [T][64]) -> proj_out (N*2H*2W, T), in ONE launch (within ABI 9): same bits, y (N,2H,2W,64) is never written; T <= 48, H, W % 8 == 0 */
 int dvg_convT4x4s2_bn_act_proj(const float* x, const float* w_k16, const float* scale, const float* shift, const float* proj_w, float* proj_out, int T,
                                int N, int H, int W, int C1, int Cout, int act, float slope, const float* addend, const int* addend_map, int addend_block, void* stream);
-
 /* Winograd F(m x m, 3x3), m = 2 or 4, form of vgg_layer for the deep eval-mode layers (vgg_64.py:5-15 at 16x16 / 8x8 maps
  * with 256-512 channels): fp32 data and transforms, 2.25x (m = 2) / 4x (m = 4) fewer multiply-adds, P = (m+2)^2 transform
  * positions.  y = act(scale * A^T[(G g G^T) .* (B^T d B)]A + shift):
@@ -793,6 +785,14 @@ int dvg_ema_update(float* ema, const float* param, long n, double decay, const i
  * does not depend on the launch.  B, S, T >= 1, B*S*T < 2^31; no allocation.  An addition within ABI 9. */
 int dvg_val_accumulate(const float* ssim, const float* psnr, const float* mse, int B, int S, int T, double* acc, long long* cnt,
                        int* best, void* stream);
+/* The held-out scores of the GP trigger's predictive (train.py --val_gp, generate_frames.py --gp_report here; docs/DESIGN_NOTES_gp_score.md).  It serves the places that read the predictive - generate_frames.py:131,170,229
+ * and train.py:283 - and has no reference counterpart: nothing there scores the variance.  mean, var (R, B) contiguous: an eval-mode predictive, R rows; noise NULL: the latent f is scored, else (P,) variances, P = noise_period
+ * (0 means P = R), row r uses noise[r % P]; target[r * t_stride_r + b * t_stride_b], as dvg_gp_elbo takes it.  Per entry in fp64: v = var + noise, y = target, e = y - mean; TAKEN if mean, var, y are finite and v > 0, else cnt[r][1] += 1
+ * and nothing else.  acc (double[R][14]) += 1/2 (ln 2 pi + ln v + e^2 / v), e, e^2, v, e / sqrt v, e^2 / v, y, y^2, v^2, e^4, v e^2, |e|, ln v, sqrt v;  cnt (long long[R][14]): [0] += 1, [2] += (e^2 <= v), [3] += (e^2 <=
+ * 3.8414588206941236 v), [4 + k] += 1 for the PIT decile k = #{ j : e |e| > c_j v }, c_j = the signed squares of the standard normal's quantiles at j / 10 (products and comparisons only: a host statement of the same
+ * multiplications gives the same integers).  Both are ADDED to, K batches = K launches; the caller zeroes them.  One workgroup per row, fixed order, no atomics: the same bits on every launch.  B, R >= 1, the period divides R.  dvg_gp_score_slots (host only): the two 14s.  Within ABI 9. */
+int dvg_gp_score_slots(int* acc_slots, int* cnt_slots);
+int dvg_gp_score(const float* mean, const float* var, const float* noise, int noise_period, const float* target, long t_stride_r, long t_stride_b, int B, int R, double* acc, long long* cnt, void* stream);
 
 #ifdef __cplusplus
 }

@@ -39,6 +39,8 @@ of any size; `--resize` scales every frame that is not image_width x image_width
 to Pillow's Image.resize (dvg_resample_u8; dvg_amd/resample.py, docs/DESIGN_NOTES_frames.md).  It applies to kth | bair | ucf trees too.
 `--val_every N` scores a fixed set of held-out clips every N epochs on rank 0 (eval-mode rollouts, Finn metrics, dvg_val_accumulate),
 logs them to `val_log.jsonl` and keeps `model_best.pth` (dvg_amd/validate.py, docs/DESIGN_NOTES_validation.md).
+`--val_gp` adds the held-out scores of the GP trigger's predictive to every validation: NLPD, standardised residuals, coverage, PIT,
+variance ~ error correlation of the one-step latent forecasts (dvg_gp_score; dvg_amd/gp_score.py, docs/DESIGN_NOTES_gp_score.md).
 `--lr_schedule KIND` makes `--lr` the base rate of all four optimisers and moves it every iteration by a device-side multiplier:
 warm-up, then constant | linear | cosine | step; one launch per iteration (dvg_amd/lr_schedule.py, docs/DESIGN_NOTES_lr_schedule.md).
 `--frame_loss l1|charbonnier`, `--gdl_weight G`, `--ssim_weight W`: another pixel penalty / the gradient-difference loss / 1 - SSIM in the frame terms
@@ -142,6 +144,7 @@ def options(argv=None, *, rank=0, world=1, local_batch=None):
     opt.rank, opt.world = rank, world
     opt.local_batch = parallel.shard_batch(opt.batch_size, world) if local_batch is None else local_batch
     optim.optimizer_options(opt)   # --optimizer and its companions: refused here, before anything is built
+    getattr(opt, "val_gp", False) and validate.options(opt)   # --val_gp without --val_every: likewise
     return opt
 
 
