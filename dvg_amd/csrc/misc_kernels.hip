@@ -449,6 +449,57 @@ __global__ __launch_bounds__(64) void gp_trigger_replay_kernel(const float* __re
     }
 }
 
+// The per-row form of the three kernels above for the sampler's variance rule (docs/DESIGN_NOTES_trigger_rows.md): EVERY batch
+// row owns a window win[b][0..W), a step `last[b]` of its latest draw and a column of the (n_eval, B) logs, and one launch does
+// a step's whole bookkeeping for all rows.  One wave per row: value = || var[:, b] ||_2 (gp_var_norms_kernel's arithmetic); the
+// window fills position `pos` (pos < W) or slides (pos == W; the row is read before anything is written); a deciding launch
+// takes trigger_window_decide's decision on the slid window, withholds it unless step - last[b] > min_gap, and writes
+// vec[b][:] = flag ? sample[:, b] : h_pred[b][:].  A launch that does not decide logs threshold +inf, flag 0 and touches
+// neither sample, h_pred nor vec.  pos / decide / step / slot are launch arguments: a replayed launch repeats itself.
+__global__ __launch_bounds__(64) void gp_trigger_rows_kernel(const float* __restrict__ var, const float* __restrict__ sample,
+                                                             const float* __restrict__ h_pred, float* __restrict__ vec, int D, int B,
+                                                             float* __restrict__ win, int W, int pos, int decide, float coef,
+                                                             int step, int min_gap, int* __restrict__ last,
+                                                             float* __restrict__ values, float* __restrict__ thresholds,
+                                                             int* __restrict__ flags, int slot) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    double s = 0.0;
+    for (int d = lane; d < D; d += 64) {
+        const double v = (double)var[(size_t)d * B + b];
+        s += v * v;
+    }
+    s = wave_sum(s);
+    const float value = (float)sqrt(s);
+    float* row = win + (size_t)b * W;
+    const bool slide = pos >= W;
+    // the slid window: lane i holds element i
+    float w = 0.f;
+    if (slide && lane < W) w = lane + 1 < W ? row[lane + 1] : value;
+    float thr = INFINITY;
+    int f = 0;
+    if (decide) {                                        // uniform over the launch: every lane takes part in the wave sums
+        const bool trig = trigger_window_decide(lane, w, W, coef, value, thr);
+        f = trig && (long)step - (long)last[b] > (long)min_gap ? 1 : 0;
+    }
+    __syncthreads();                                     // every lane has read its row[lane + 1] and last[b]
+    if (slide) {
+        if (lane < W) row[lane] = w;
+    } else if (lane == pos) {
+        row[pos] = value;
+    }
+    if (decide) {
+        const size_t o = (size_t)b * D;
+        for (int d = lane; d < D; d += 64) vec[o + d] = f ? sample[(size_t)d * B + b] : h_pred[o + d];
+    }
+    if (lane == 0) {
+        if (f) last[b] = step;
+        const size_t o = (size_t)slot * B + b;
+        values[o] = value;
+        thresholds[o] = thr;
+        flags[o] = f;
+    }
+}
+
 // What the step decodes and which recurrent state survives it (:289-296): a triggered step decodes the GP sample and does
 // NOT step the LSTM, otherwise `generation` steps it and decodes its output.  vec[b][d] = flag ? sample[d][b] : h_pred[b][d];
 // state_out[k] = flag ? state_old[k] : state_new[k] for the n_state tensors of `elems` floats each.
@@ -760,6 +811,24 @@ extern "C" int dvg_gp_trigger_select(const int* flag, const float* sample_db, co
     const long n = std::max((long)B * D, state_elems);
     hipLaunchKernelGGL(gp_trigger_select_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, p);
     return check_launch("dvg_gp_trigger_select");
+}
+
+// One step of the sampler's per-row variance rule: see gp_trigger_rows_kernel.  The caller sizes the logs: (slot + 1) * B entries.
+extern "C" int dvg_gp_trigger_rows(const float* var, const float* sample_db, const float* h_pred, float* vec, int D, int B,
+                                   float* win, int window, int pos, int decide, float coef, int step, int min_gap, int* last,
+                                   float* values, float* thresholds, int* flags, int slot, void* stream) {
+    DVG_REQUIRE(var && win && last && values && thresholds && flags, DVG_ERR_NULL, "dvg_gp_trigger_rows: NULL pointer");
+    DVG_REQUIRE(!decide || (sample_db && h_pred && vec), DVG_ERR_NULL,
+                "dvg_gp_trigger_rows: a deciding launch needs sample_db, h_pred and vec");
+    DVG_REQUIRE(D > 0 && B > 0, DVG_ERR_SHAPE, "dvg_gp_trigger_rows: D=%d and B=%d must be positive", D, B);
+    DVG_REQUIRE(window >= 1 && window <= 64, DVG_ERR_SHAPE, "dvg_gp_trigger_rows: window=%d must be in [1, 64]", window);
+    DVG_REQUIRE(pos >= 0 && pos <= window, DVG_ERR_SHAPE, "dvg_gp_trigger_rows: pos=%d must be in [0, window=%d]", pos, window);
+    DVG_REQUIRE(!decide || pos == window, DVG_ERR_SHAPE,
+                "dvg_gp_trigger_rows: a deciding launch slides a full window (pos=%d, window=%d)", pos, window);
+    DVG_REQUIRE(min_gap >= 0 && slot >= 0, DVG_ERR_SHAPE, "dvg_gp_trigger_rows: min_gap=%d and slot=%d must be >= 0", min_gap, slot);
+    hipLaunchKernelGGL(gp_trigger_rows_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, var, sample_db, h_pred, vec, D,
+                       B, win, window, pos, decide ? 1 : 0, coef, step, min_gap, last, values, thresholds, flags, slot);
+    return check_launch("dvg_gp_trigger_rows");
 }
 
 // The frame terms of train_model's loss and their gradient (train.py:227-239): see frame_losses_kernel.  pred [S][K][n], target

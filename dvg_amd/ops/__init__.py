@@ -37,7 +37,7 @@ from .norm import (  # noqa: F401
     channel_stats, set_sync_bn_state, sync_bn_state, sync_partial_rows, bn_finalize, bn_act_apply, bn_act_bwd,
 )
 from .gp import (  # noqa: F401
-    gp_predict, gp_var_norms, gp_trigger_step, gp_trigger_replay, gp_trigger_select, gp_elbo, gp_elbo_bwd,
+    gp_predict, gp_var_norms, gp_trigger_step, gp_trigger_replay, gp_trigger_select, gp_trigger_rows, TRIGGER_NEVER, gp_elbo, gp_elbo_bwd,
     sum_steps, gp_step_group, gp_train_bwd, GP_KERNELS, gp_kernel_code, gp_score, gp_score_slots, gp_score_accumulators,
 )
 from .backward import (  # noqa: F401

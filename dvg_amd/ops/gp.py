@@ -115,6 +115,47 @@ def gp_trigger_select(flag, sample_db, h_pred, states_old, states_new):
     return vec, outs
 
 
+TRIGGER_NEVER = -(1 << 30)     # last[b] of a row that has not drawn yet (include/dvg_hip.h, dvg_gp_trigger_rows)
+
+
+def gp_trigger_rows(var, win, last, values, thresholds, flags, *, pos, step, slot, decide=False, coef=0.0, min_gap=0,
+                    sample_db=None, h_pred=None):
+    """One step of the sampler's per-row variance rule (dvg_gp_trigger_rows): value[b] = || var[:, b] ||_2 of the predictive
+    variance (D,B); win (B,W) fills position `pos` < W or slides (pos == W) in place; the (n, B) logs values / thresholds / flags
+    get row `slot`.  decide: the row's flag = value > mean + coef * std of its slid window and step - last[b] > min_gap (last (B,)
+    int32, TRIGGER_NEVER before a first draw, updated in place); returns vec (B,D) = flag ? sample_db (D,B)^T : h_pred (B,D).
+    A launch that does not decide returns None, logs threshold +inf and flag 0."""
+    _dev_f32(var, "gp_trigger_rows.var")
+    if var.dim() != 2 or not var.is_contiguous():
+        raise RuntimeError("gp_trigger_rows: a contiguous (D,B) variance expected")
+    d, b = var.shape
+    dev = var.device
+    if win.dtype != torch.float32 or win.dim() != 2 or win.shape[0] != b or not win.is_contiguous() or win.device != dev:
+        raise RuntimeError(f"gp_trigger_rows: the window must be a contiguous float32 ({b}, W) tensor on var's device")
+    w = win.shape[1]
+    if last.dtype != torch.int32 or tuple(last.shape) != (b,) or not last.is_contiguous() or last.device != dev:
+        raise RuntimeError(f"gp_trigger_rows: last must be a contiguous int32 ({b},) tensor on var's device")
+    for t, n, dt in ((values, "values", torch.float32), (thresholds, "thresholds", torch.float32), (flags, "flags", torch.int32)):
+        if t.dtype != dt or t.dim() != 2 or t.shape[1] != b or not t.is_contiguous() or t.device != dev:
+            raise RuntimeError(f"gp_trigger_rows: {n} must be a contiguous {dt} (n, {b}) tensor on var's device")
+    if not 0 <= slot < min(values.shape[0], thresholds.shape[0], flags.shape[0]):
+        raise RuntimeError("gp_trigger_rows: log slot out of range")
+    vec = None
+    if decide:
+        if sample_db is None or h_pred is None:
+            raise RuntimeError("gp_trigger_rows: a deciding step needs the GP sample (D,B) and h_pred (B,D)")
+        _dev_f32(sample_db, "gp_trigger_rows.sample_db")
+        _dev_f32(h_pred, "gp_trigger_rows.h_pred")
+        if tuple(sample_db.shape) != (d, b) or tuple(h_pred.shape) != (b, d) or not sample_db.is_contiguous() or \
+                not h_pred.is_contiguous() or sample_db.device != dev or h_pred.device != dev:
+            raise RuntimeError(f"gp_trigger_rows: sample ({d},{b}) and h_pred ({b},{d}), both contiguous and on var's device, expected")
+        vec = torch.empty((b, d), device=dev, dtype=torch.float32)
+    check(lib().dvg_gp_trigger_rows(_p(var), _p(sample_db if decide else None), _p(h_pred if decide else None), _p(vec), d, b,
+                                    _p(win), w, int(pos), int(bool(decide)), float(coef), int(step), int(min_gap), _p(last),
+                                    _p(values), _p(thresholds), _p(flags), int(slot), _stream()), "gp_trigger_rows")
+    return vec
+
+
 def gp_elbo(mean, var, kl, target, raw_noise, num_data, noise_period=0):
     """VariationalELBO(combine_terms=True) with the Gaussian likelihood's expected log-probability -> (D,) (dvg_gp_elbo).
     mean, var (D,B) contiguous, kl (D,), target (D,B) with any strides, raw_noise (D,) or (D,1) - (P,) with noise_period = P:

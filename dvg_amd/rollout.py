@@ -18,6 +18,7 @@ from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
 
 from . import _derived, fused, graphs, ops
@@ -109,6 +110,7 @@ def condition(encoder, frame_predictor, x: Sequence[torch.Tensor], n_past: int, 
     batch) computes it once per batch and draws every sample with `sample_from`."""
     frame_predictor.hidden = _zero_hidden(frame_predictor)
     skip = None
+    hs = []
     if batch_conditioning and n_past >= 3 and not encoder.training:
         hs, skip = _encode_conditioning(encoder, x, n_past, last_frame_skip)
         side = None
@@ -130,8 +132,10 @@ def condition(encoder, frame_predictor, x: Sequence[torch.Tensor], n_past: int, 
     else:
         for i in range(1, n_past):
             h, skip = encoder(x[i - 1])
+            hs.append(h)
             _step_discard(frame_predictor, h)
-    return {"hidden": list(frame_predictor.hidden), "skip": skip, "frames": [x[i] for i in range(n_past)]}
+    # latents[i - 1] = enc(x[i - 1]), the latent fed at step i < n_past: what a VarianceTrigger records of the conditioning steps
+    return {"hidden": list(frame_predictor.hidden), "skip": skip, "frames": [x[i] for i in range(n_past)], "latents": list(hs)}
 
 
 def _predict_from(state: dict, encoder, decoder, frame_predictor, n_past: int, n_eval: int, last_frame_skip: bool,
@@ -154,11 +158,141 @@ def _predict_from(state: dict, encoder, decoder, frame_predictor, n_past: int, n
     return frames
 
 
+class VarianceTrigger:
+    """The sampler's second trigger rule (generate_frames.py --trigger variance; docs/DESIGN_NOTES_trigger_rows.md): a row of
+    the batch draws a GP sample at the prediction step where ITS OWN predictive-variance norm exceeds mean + coef * std of ITS
+    OWN window of the last `window` values (the reference's GPtrigger_gen rule, generate_frames.py:231,288-289, per sequence),
+    at most once every min_gap + 1 steps.  It changes WHEN a row draws, not what a draw does; the bookkeeping of a step is one
+    launch (ops.gp_trigger_rows).  The object holds the three numbers; the device state of one rollout comes from `new_state`."""
+
+    def __init__(self, window: int = 12, coef: float = 2.01, min_gap: int = 0):
+        if not 1 <= int(window) <= 64:
+            raise ValueError(f"VarianceTrigger: window must be in 1..64, not {window}")
+        if int(min_gap) < 0:
+            raise ValueError(f"VarianceTrigger: min_gap must be >= 0, not {min_gap}")
+        self.window, self.coef, self.min_gap = int(window), float(coef), int(min_gap)
+
+    def key(self):
+        return (self.window, self.coef, self.min_gap)
+
+    def can_draw(self) -> bool:
+        """False where the rule cannot draw whatever the values: the largest population z-score of one element among W is
+        sqrt(W - 1), so coef >= sqrt(W - 1) never draws (W = 1: never)."""
+        return self.window > 1 and self.coef < (self.window - 1) ** 0.5
+
+    def first_decision(self, n_past: int) -> int:
+        """The first step that decides: a prediction step whose value slid a full window."""
+        return max(n_past, self.window + 1)
+
+    def new_state(self, B: int, n_eval: int, device) -> dict:
+        """win (B,W) zeros, last (B,) int32 'never', values (n_eval,B) zeros, thresholds (n_eval,B) +inf, flags (n_eval,B) int32
+        zeros - views of ONE buffer (`blob`), so that a state is copied with one launch (`copy_state`)."""
+        W = self.window
+        sizes = (B * W, B, n_eval * B, n_eval * B, n_eval * B)
+        blob = torch.zeros(sum(sizes), dtype=torch.float32, device=device)
+        win, last, values, thr, flags = torch.split(blob, sizes)
+        st = {"blob": blob, "win": win.view(B, W), "last": last.view(torch.int32), "values": values.view(n_eval, B),
+              "thresholds": thr.view(n_eval, B), "flags": flags.view(torch.int32).view(n_eval, B)}
+        st["last"].fill_(ops.TRIGGER_NEVER)
+        st["thresholds"].fill_(float("inf"))
+        return st
+
+    @staticmethod
+    def copy_state(dst: dict, src: dict) -> None:
+        dst["blob"].copy_(src["blob"])
+
+    def _launch(self, st, i, var, decide, sample_db=None, h_pred=None):
+        return ops.gp_trigger_rows(var, st["win"], st["last"], st["values"], st["thresholds"], st["flags"],
+                                   pos=min(i - 1, self.window), step=i, slot=i, decide=decide, coef=self.coef,
+                                   min_gap=self.min_gap, sample_db=sample_db, h_pred=h_pred)
+
+    def record(self, st: dict, i: int, var: torch.Tensor) -> None:
+        """Step i >= 1 that does not decide: its value fills position i - 1 of every row's window or slides it."""
+        self._launch(st, i, var, False)
+
+    def decide(self, st: dict, i: int, var: torch.Tensor, sample_db: torch.Tensor, h_pred: torch.Tensor) -> torch.Tensor:
+        """Step i >= first_decision(n_past): the latent (B,D) the step decodes, row by row the GP sample or h_pred."""
+        return self._launch(st, i, var, True, sample_db, h_pred)
+
+    def record_conditioning(self, st: dict, latents, gp_layer, likelihood) -> None:
+        """The values of the conditioning steps 1 .. n_past - 1 from `condition()`'s latents: the variance only, no sample."""
+        for i, h in enumerate(latents, start=1):
+            self.record(st, i, likelihood(gp_layer(gp_input(gp_layer, h))).variance)
+
+
+def trigger_rows_host(values, n_past: int, window: int, coef: float, min_gap: int = 0, follow=None, guard: float = 0.0,
+                      followed=None):
+    """The variance rule on the host, in numpy float32 with the reference's own calls (generate_frames.py:231,288-289), row by
+    row: values (n_eval, B) float32 with row 0 unused -> (flags (n_eval, B) int32, thresholds (n_eval, B) float32, +inf where no
+    decision is taken).  The cross-check of ops.gp_trigger_rows and the decision of make_gifs(host_loop=True).
+    follow (n_eval, B) with guard > 0: a decision whose margin |value - threshold| / |threshold| is below `guard` takes
+    follow's flag instead of its own (parity runs against the device; `followed`, a list, gets its (step, row))."""
+    host = HostTriggerRows(values.shape[1], window, coef, min_gap)
+    flags = np.zeros(values.shape, dtype=np.int32)
+    thresholds = np.full(values.shape, np.inf, dtype=np.float32)
+    for i in range(1, values.shape[0]):
+        flags[i], thresholds[i] = host.step(i, values[i], i >= n_past, None if follow is None else follow[i], guard, followed)
+    return flags, thresholds
+
+
+class HostTriggerRows:
+    """`trigger_rows_host` one step at a time: every row's window and the step of its last draw, on the host."""
+
+    def __init__(self, B: int, window: int, coef: float, min_gap: int = 0):
+        self.window, self.coef, self.min_gap = window, coef, min_gap
+        self.ctx = [np.zeros(0, dtype=np.float32) for _ in range(B)]
+        self.last = [None] * B
+
+    def step(self, i: int, value_row, prediction_step: bool, follow=None, guard: float = 0.0, followed=None):
+        """(flags (B,) int32, thresholds (B,) float32) of step i; value_row (B,) float32."""
+        B = len(self.ctx)
+        flags, thresholds = np.zeros(B, dtype=np.int32), np.full(B, np.inf, dtype=np.float32)
+        for b in range(B):
+            value, context_array = value_row[b], self.ctx[b]
+            full = len(context_array) == self.window
+            context_array = np.concatenate([context_array[1:] if full else context_array, [value]])
+            self.ctx[b] = context_array
+            if not (full and prediction_step):
+                continue
+            threshold = np.mean(context_array) + self.coef * np.std(context_array)
+            draw = bool(value > threshold) and (self.last[b] is None or i - self.last[b] > self.min_gap)
+            if follow is not None and abs(float(value) - float(threshold)) < guard * abs(float(threshold)):
+                draw = bool(follow[b])
+                if followed is not None:
+                    followed.append((i, b))
+            if draw:
+                self.last[b] = i
+            flags[b], thresholds[b] = int(draw), threshold
+        return flags, thresholds
+
+
 @torch.no_grad()
 def sample_from(state: dict, encoder, decoder, frame_predictor, gp_layer, likelihood, n_past: int, n_eval: int,
                 last_frame_skip: bool = False, period: int = 15,
-                eps_by_step: Optional[Dict[int, torch.Tensor]] = None) -> List[torch.Tensor]:
-    """The prediction phase of one sample (generate_frames.py:163-176), starting from a `condition()` state."""
+                eps_by_step: Optional[Dict[int, torch.Tensor]] = None, trigger: Optional[VarianceTrigger] = None,
+                trigger_state: Optional[dict] = None) -> List[torch.Tensor]:
+    """The prediction phase of one sample (generate_frames.py:163-176), starting from a `condition()` state.
+    trigger: None = the period rule above; a VarianceTrigger = every row draws when its own variance says so (`period` is then
+    unused and eps_by_step[i], if given, is needed at every deciding step).  trigger_state: the rollout's device state
+    (VarianceTrigger.new_state; a fresh one if None), where the logs are left; the conditioning values are recorded into it
+    from state["latents"] - a state without that entry (GraphedSampler's prefix) says they, and every step before n_past,
+    already are."""
+    if trigger is not None:
+        ts = trigger_state
+        if ts is None:
+            ts = trigger.new_state(state["frames"][0].shape[0], n_eval, state["frames"][0].device)
+        if state.get("latents") is not None:
+            trigger.record_conditioning(ts, state["latents"], gp_layer, likelihood)
+
+        def rows(i, h, h_pred):
+            pred = likelihood(gp_layer(gp_input(gp_layer, h)))
+            if i <= trigger.window:                      # still filling: the variance only
+                trigger.record(ts, i, pred.variance)
+                return h_pred
+            z = pred.rsample(None if eps_by_step is None else eps_by_step[i])    # (D,B); the same launch leaves the variance
+            return trigger.decide(ts, i, pred.variance, z, h_pred)
+        return _predict_from(state, encoder, decoder, frame_predictor, n_past, n_eval, last_frame_skip, rows)
+
     def latent(i, h, h_pred):
         if not (period and i % period == 0):
             return h_pred
@@ -413,6 +547,9 @@ class ConcurrentRollouts:
         return [r.frames for r in self.rollouts[:nc]]
 
 
+_TRIGGER_LOGS = ("flags", "values", "thresholds")
+
+
 class GraphedSampler:
     """`make_gifs` for one batch (generate_frames.py:107-178) as hipGraphs.  Everything that does not depend on the sample is
     replayed once per batch (three graphs: the conditioning, then side by side the other two): the conditioning (`condition`: the past frames encoded as one batch, the LSTM warmed up,
@@ -435,10 +572,11 @@ class GraphedSampler:
     then fills its `mse` output as well.  The frames do not depend on it."""
 
     def __init__(self, encoder, decoder, frame_predictor, gp_layer, likelihood, x, n_past, n_eval,
-                 last_frame_skip=False, period=15, inflight=3, share_prefix=None, metrics="skimage"):
+                 last_frame_skip=False, period=15, inflight=3, share_prefix=None, metrics="skimage", trigger=None):
         if metrics not in ("skimage", "finn"):
             raise ValueError(f"GraphedSampler: metrics must be 'skimage' or 'finn', not {metrics!r}")
         self.metrics = metrics
+        self.trigger = trigger
         # several sample chains in flight keep the board at its power cap: their graphs are captured with the energy-lean tiles
         # (ops.tile_policy; same results to fp32 rounding); one chain at a time keeps the latency tiles
         with ops.tile_policy(max(1, inflight) >= 2):
@@ -455,6 +593,13 @@ class GraphedSampler:
         B, D = x[0].shape[0], gp_layer.num_dims
         self.x = torch.stack([t.contiguous() for t in x])            # conditioning frames + ground truth of the metrics
         self.steps = [i for i in range(n_past, n_eval) if period and i % period == 0]
+        trig = self.trigger
+        if trig is not None:
+            # every row decides for itself at every step from the first one whose value slid a full window: no row can draw
+            # before it, so the steps up to there are still the same for every sample
+            self.steps = list(range(trig.first_decision(n_past), n_eval))
+            self._trig_init = trig.new_state(B, n_eval, dev)      # never written after this line: what a rollout starts from
+            self._trig_pre = trig.new_state(B, n_eval, dev)       # the shared prefix's: conditioning values, then its steps'
         if share_prefix is None:
             share_prefix = SHARE_PREFIX
         self.t0 = min(self.steps) if self.steps else n_eval          # first step whose outcome depends on the sample
@@ -465,7 +610,8 @@ class GraphedSampler:
         self.chains = []
         for k in range(max(1, inflight)):
             self.chains.append({"eps": {i: torch.zeros(D, B, device=dev) for i in self.steps},
-                                "stream": graphs.pooled_stream("chain", k)})
+                                "stream": graphs.pooled_stream("chain", k),
+                                "trig": None if trig is None else trig.new_state(B, n_eval, dev)})
         self.post_stream = graphs.pooled_stream("post")
 
         def eager():
@@ -517,7 +663,12 @@ class GraphedSampler:
     def _prefix(self) -> dict:
         """The samples' steps n_past ... t0 - 1 from the conditioning state: frames, their metrics, the LSTM state after them."""
         st = self.b["state"]
-        frames = sample_from(st, *self._mods, n_past=self.n_past, n_eval=self.t0, **self._kw)
+        if self.trigger is not None:         # the conditioning steps' values and the prefix's own: every sample starts from them
+            self.trigger.copy_state(self._trig_pre, self._trig_init)
+            frames = sample_from(st, *self._mods, n_past=self.n_past, n_eval=self.t0, trigger=self.trigger,
+                                 trigger_state=self._trig_pre, **self._kw)
+        else:
+            frames = sample_from(st, *self._mods, n_past=self.n_past, n_eval=self.t0, **self._kw)
         ssim, psnr, mse = self._metrics(frames, self.n_past, self.t0)
         return {"hidden": list(self._mods[2].hidden), "skip": st["skip"], "frames": frames, "stack": torch.stack(frames),
                 "ssim": ssim, "psnr": psnr, "mse": mse}
@@ -528,7 +679,14 @@ class GraphedSampler:
         if self.t0 == self.n_eval:       # no trigger step inside the rollout: every sample IS the prefix
             return None, None, None, None
         state = self.b["pre"] if self.share else self.b["state"]
-        frames = sample_from(state, *self._mods, eps_by_step=ch["eps"], n_past=self.t0, n_eval=self.n_eval, **self._kw)
+        if self.trigger is not None:
+            # the chain's own window / last / logs, first set to what the rollout has recorded up to t0: the prefix's state (it
+            # carries no "latents": nothing is recorded twice) or, without a shared prefix, the initial one
+            self.trigger.copy_state(ch["trig"], self._trig_pre if self.share else self._trig_init)
+            frames = sample_from(state, *self._mods, eps_by_step=ch["eps"], n_past=self.t0, n_eval=self.n_eval,
+                                 trigger=self.trigger, trigger_state=ch["trig"], **self._kw)
+        else:
+            frames = sample_from(state, *self._mods, eps_by_step=ch["eps"], n_past=self.t0, n_eval=self.n_eval, **self._kw)
         ssim, psnr, mse = self._metrics(frames, self.t0, self.n_eval)
         return torch.stack(frames[self.t0 if self.share else 0:]), ssim, psnr, mse
 
@@ -539,11 +697,15 @@ class GraphedSampler:
 
     def run(self, nsample: int, samples: torch.Tensor, ssim: torch.Tensor, psnr: torch.Tensor,
             eps_by_sample: Optional[Sequence[Dict[int, torch.Tensor]]] = None,
-            mse: Optional[torch.Tensor] = None) -> torch.Tensor:
+            mse: Optional[torch.Tensor] = None, trigger_log: Optional[dict] = None) -> torch.Tensor:
         """Draws `nsample` samples: samples[s] <- the n_eval frames (n_eval,B,C,H,W), ssim[:, s] / psnr[:, s] <- (B,T); returns
         the posterior rollout's frames (n_eval,B,C,H,W) - a static buffer the next run() overwrites.
         eps_by_sample[s][i]: base sample of sample s at trigger step i (parity runs); None = torch's generator.
-        mse (metrics == "finn" only): mse[:, s] <- (B,T), the frames' mean squared error."""
+        mse (metrics == "finn" only): mse[:, s] <- (B,T), the frames' mean squared error.
+        trigger_log (a sampler with a VarianceTrigger only): its 'flags' (int32), 'values' and 'thresholds', each (nsample, n_eval, B),
+        get every sample's logs."""
+        if trigger_log is not None and self.trigger is None:
+            raise ValueError("GraphedSampler.run: a trigger log needs a sampler built with a VarianceTrigger")
         if (mse is not None) != (self.metrics == "finn"):
             raise ValueError("GraphedSampler.run: the mse output goes with metrics='finn', and only with it")
         cur = torch.cuda.current_stream()
@@ -561,6 +723,9 @@ class GraphedSampler:
             if mse is not None:
                 mse[:, :, :P].copy_(pre["mse"].unsqueeze(1).expand(-1, nsample, -1))
             if self.t0 == self.n_eval:
+                if trigger_log is not None:
+                    for k in _TRIGGER_LOGS:
+                        trigger_log[k].copy_(self._trig_pre[k].unsqueeze(0).expand(nsample, -1, -1))
                 cur.wait_stream(self.post_stream)
                 return self.b["post"]
         for ch in self.chains:
@@ -580,6 +745,9 @@ class GraphedSampler:
                 psnr[:, s, P:].copy_(ch["psnr"])
                 if mse is not None:
                     mse[:, s, P:].copy_(ch["mse"])
+                if trigger_log is not None:
+                    for k in _TRIGGER_LOGS:
+                        trigger_log[k][s].copy_(ch["trig"][k])
         for ch in self.chains:
             cur.wait_stream(ch["stream"])
         cur.wait_stream(self.post_stream)

@@ -34,8 +34,8 @@ sys.path.insert(0, ROOT)
 import utils  # noqa: E402
 from dvg_amd import datasets, mnist, ops, viz  # noqa: E402
 from dvg_amd.data import SyntheticMovingMNIST, make_batch_generator, synthetic_video  # noqa: E402
-from dvg_amd.rollout import (GraphedSampler, GraphedTrigger, condition, gp_input, posterior_from, sample_from, sample_rollout,  # noqa: E402
-                             trigger_body, trigger_log, trigger_warmup)
+from dvg_amd.rollout import (GraphedSampler, GraphedTrigger, HostTriggerRows, VarianceTrigger, condition, gp_input,  # noqa: E402
+                             posterior_from, sample_from, sample_rollout, trigger_body, trigger_log, trigger_warmup)
 from dvg_amd.ops import GP_KERNELS  # noqa: E402
 from gp_models import GaussianLikelihood, GPRegressionLayer1  # noqa: E402
 
@@ -99,8 +99,63 @@ def build_parser():
     p.add_argument('--synthetic_data', action='store_true',
                    help='kth | bair | ucf: synthetic clips of that shape instead of the test split under --data_root; smmnist: '
                         'the in-repo sprites even where --data_root holds MNIST')
+    p.add_argument('--trigger', default='period', choices=('period', 'variance'),
+                   help="make_gifs: WHEN a sample draws from the GP.  period = at the steps i % 15 == 0, every row of the batch at once "
+                        "(the reference's make_gifs); variance = every sequence by itself, at the prediction step where the norm of "
+                        "ITS predictive variance exceeds mean + --trigger_coef * std of ITS last --trigger_window values (the "
+                        "GPtrigger_gen rule, per row; docs/DESIGN_NOTES_trigger_rows.md).  Not with --gp_trigger")
+    p.add_argument('--trigger_window', type=_int_in(1, 64, '--trigger_window'), default=12,
+                   help='--trigger variance: values per window, 1..64 (the reference keeps 12)')
+    p.add_argument('--trigger_coef', type=float, default=2.01,
+                   help="--trigger variance: threshold = mean + coef * std; 2.01 is the reference's 2 + 0.01 * depth at depth 1")
+    p.add_argument('--trigger_min_gap', type=_int_in(0, None, '--trigger_min_gap'), default=0,
+                   help='--trigger variance: a row that drew at step j may draw again at step i only if i - j > this (0: no limit)')
     datasets.add_resize_arguments(p)      # --resize, --resize_fit: as train.py
     return p
+
+
+def _int_in(lo, hi, flag):
+    def convert(text):
+        v = int(text)
+        if v < lo or (hi is not None and v > hi):
+            raise argparse.ArgumentTypeError('%s must be %s, not %d' % (flag, '>= %d' % lo if hi is None else 'in %d..%d' % (lo, hi), v))
+        return v
+    return convert
+
+
+def parse_args(argv=None):
+    """build_parser().parse_args plus what argparse cannot say: --trigger variance goes with make_gifs only, and a coefficient
+    the window can never exceed gets one warning."""
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.trigger == 'variance':
+        if args.gp_trigger:
+            parser.error('--trigger variance is a rule of make_gifs; --gp_trigger runs GPtrigger_gen, which keeps its own')
+        if not VarianceTrigger(args.trigger_window, args.trigger_coef, args.trigger_min_gap).can_draw():
+            print('WARNING: no sequence will ever draw: ' + (
+                'a window of one value has no spread (--trigger_window 1)' if args.trigger_window == 1 else
+                '--trigger_coef %g >= sqrt(--trigger_window %d - 1) = %.3f, and no value of a window lies that many population '
+                'standard deviations above its mean' % (args.trigger_coef, args.trigger_window, (args.trigger_window - 1) ** 0.5)),
+                file=sys.stderr)
+    return args
+
+
+def variance_trigger(opt):
+    """The VarianceTrigger the options ask for, None for the period rule."""
+    if getattr(opt, 'trigger', 'period') != 'variance':
+        return None
+    return VarianceTrigger(getattr(opt, 'trigger_window', 12), getattr(opt, 'trigger_coef', 2.01), getattr(opt, 'trigger_min_gap', 0))
+
+
+def trigger_summary(flags, n_past):
+    """(mean, min, max draws per sequence, share of sequences that never drew, mean step of the first draw - nan if none drew)
+    over the rows and samples of `flags` (nsample, n_eval, B); torch ops on the device, read once."""
+    f = flags[:, n_past:].bool()
+    draws = f.sum(1).double()                                                  # (nsample, B)
+    drew = draws > 0
+    first = n_past + f.int().argmax(1).double()                                # first set step (0 where none: masked below)
+    mean_first = (first * drew).sum() / drew.sum() if bool(drew.any()) else torch.tensor(float('nan'))
+    return tuple(float(v) for v in (draws.mean(), draws.min(), draws.max(), 1.0 - drew.double().mean(), mean_first))
 
 
 class Generator:
@@ -117,6 +172,7 @@ class Generator:
             m.to(device).eval()
         self.frame_predictor.batch_size = opt.batch_size
         self._sampler, self._sampler_key = None, None
+        self.trigger = variance_trigger(opt)      # --trigger variance: rollout.VarianceTrigger; None = the period rule
         # the figures' random sample indices (generate_frames.py:190): a stream of their own, so that writing images draws
         # nothing from the global numpy / torch generators and every saved tensor is what it is without them
         self._viz_rng = np.random.RandomState(opt.seed)
@@ -126,11 +182,21 @@ class Generator:
         return self.likelihood(self.gp_layer(gp_input(self.gp_layer, h)))
 
     @torch.no_grad()
-    def make_gifs(self, x, nsample, eps_by_sample=None, diversity=False):
+    def make_gifs(self, x, nsample, eps_by_sample=None, diversity=False, host_loop=False, follow=None, guard=0.0):
         """`eps_by_sample[s][i]`: the N(0,1) base sample (D,B) of sample s at trigger step i (parity runs); None = torch RNG.
         diversity: also return utils.sample_diversity of the samples as `diversity` (computed after the sampler has run, from
-        the returned tensor; nothing about the rollouts or the other keys changes)."""
-        res = self._make_gifs(x, nsample, eps_by_sample)
+        the returned tensor; nothing about the rollouts or the other keys changes).
+        With --trigger variance the result gains `trigger`: flags (nsample, n_eval, B) int32, values, thresholds and the rule's
+        window / coef / min_gap.  host_loop=True (that rule only): the same kernels for everything else, but the variance is read
+        back at every step and the decision taken in numpy (rollout.HostTriggerRows) - the cross-check and the timing baseline of
+        the device rule; follow (a device run's flags) / guard: a host decision whose margin is inside `guard` takes the device's
+        flag and is listed in trigger['followed'] as (sample, step, row)."""
+        if host_loop:
+            if self.trigger is None:
+                raise ValueError("make_gifs: host_loop is the host side of --trigger variance")
+            res = self._make_gifs_host(x, nsample, eps_by_sample, follow, guard)
+        else:
+            res = self._make_gifs(x, nsample, eps_by_sample)
         if diversity:
             res['diversity'] = utils.sample_diversity(res['samples'], self.opt.n_past)
         return res
@@ -145,6 +211,13 @@ class Generator:
         extra = {'mse': mse, 'metrics': 'finn'} if finn else {}
         all_gen = []
         inflight = getattr(opt, 'inflight', 3)
+        trig = self.trigger
+        tlog, textra = None, {}
+        if trig is not None:
+            tlog = {'flags': torch.zeros(nsample, opt.n_eval, B, dtype=torch.int32, device=self.dev),
+                    'values': torch.zeros(nsample, opt.n_eval, B, device=self.dev),
+                    'thresholds': torch.full((nsample, opt.n_eval, B), float('inf'), device=self.dev)}
+            textra = {'trigger': dict(tlog, window=trig.window, coef=trig.coef, min_gap=trig.min_gap)}
         if inflight > 0:
             # One graph per batch for everything the samples share (conditioning, the posterior rollout's prediction steps, the
             # samples' steps before the first GP trigger step) and one per chain for the sample body: rollout.GraphedSampler.
@@ -155,30 +228,42 @@ class Generator:
             def key():
                 vers = tuple(t._version for m in (self.encoder, self.decoder, self.frame_predictor, self.gp_layer, self.likelihood)
                              for t in list(m.parameters()) + list(m.buffers()))
-                return (tuple(x[0].shape), len(x), opt.n_past, opt.n_eval, bool(opt.last_frame_skip), inflight, share, finn, vers)
+                return (tuple(x[0].shape), len(x), opt.n_past, opt.n_eval, bool(opt.last_frame_skip), inflight, share, finn, vers,
+                        ('period',) if trig is None else ('variance',) + trig.key())
             if self._sampler_key != key():
                 self._sampler = GraphedSampler(self.encoder, self.decoder, self.frame_predictor, self.gp_layer,
                                                self.likelihood, x, opt.n_past, opt.n_eval, opt.last_frame_skip,
                                                inflight=inflight, share_prefix=None if share else False,
-                                               metrics='finn' if finn else 'skimage')
+                                               metrics='finn' if finn else 'skimage', trigger=trig)
                 # the key AFTER the construction: the sampler's eager warm-up pass may be the GP layer's first call, which
                 # initialises its variational parameters in place (gp_models: variational_params_initialized); the graphs are
                 # captured after that pass, i.e. with the versions read here
                 self._sampler_key = key()
             self._sampler.set_batch(x)
             samples = torch.empty((nsample, opt.n_eval) + tuple(x[0].shape), device=self.dev)
-            post = self._sampler.run(nsample, samples, ssim, psnr, eps_by_sample, mse=mse).clone()
+            post = self._sampler.run(nsample, samples, ssim, psnr, eps_by_sample, mse=mse, trigger_log=tlog).clone()
             best = ssim.mean(2).argsort(1)[:, -1]
-            return {'posterior': post, 'samples': samples, 'ssim': ssim, 'psnr': psnr, 'best': best, **extra}
+            return {'posterior': post, 'samples': samples, 'ssim': ssim, 'psnr': psnr, 'best': best, **extra, **textra}
         # everything before the first predicted frame is the same for the posterior rollout and all nsample rollouts of this
         # batch (generate_frames.py:113-121 and :147-162 are the same computation): once per batch
         state = condition(self.encoder, self.frame_predictor, x, opt.n_past, opt.last_frame_skip, decoder=self.decoder)
         post = posterior_from(state, self.encoder, self.decoder, self.frame_predictor, self.gp_layer, self.likelihood,
                               opt.n_past, opt.n_eval, opt.last_frame_skip)
+        tkw = {}
+        if trig is not None:     # the conditioning steps' values once per batch; every sample starts from a copy of that state
+            base = trig.new_state(B, opt.n_eval, self.dev)
+            trig.record_conditioning(base, state['latents'], self.gp_layer, self.likelihood)
+            state = dict(state, latents=None)
+            tkw = {'trigger': trig, 'trigger_state': trig.new_state(B, opt.n_eval, self.dev)}
         for s in range(nsample):
+            if trig is not None:
+                trig.copy_state(tkw['trigger_state'], base)
             frames = sample_from(state, self.encoder, self.decoder, self.frame_predictor, self.gp_layer,
                                  self.likelihood, opt.n_past, opt.n_eval, opt.last_frame_skip,
-                                 eps_by_step=None if eps_by_sample is None else eps_by_sample[s])
+                                 eps_by_step=None if eps_by_sample is None else eps_by_sample[s], **tkw)
+            if trig is not None:
+                for k in ('flags', 'values', 'thresholds'):
+                    tlog[k][s].copy_(tkw['trigger_state'][k])
             if finn:             # utils.finn_eval_seq on device: dvg_eval_frames_finn, all steps in one launch
                 m = ops.eval_frames_finn(torch.stack(list(x[opt.n_past:opt.n_eval])), torch.stack(frames[opt.n_past:opt.n_eval]))
                 ssim[:, s], psnr[:, s], mse[:, s] = (v.t() for v in m)
@@ -188,7 +273,61 @@ class Generator:
             all_gen.append(torch.stack(frames))
         best = ssim.mean(2).argsort(1)[:, -1]   # generate_frames.py:188-189,207: np.argsort(mean_ssim)[-1]
         return {'posterior': torch.stack(post), 'samples': torch.stack(all_gen), 'ssim': ssim, 'psnr': psnr,
-                'best': best, **extra}
+                'best': best, **extra, **textra}
+
+    def _score(self, x, frames, s, ssim, psnr, mse):
+        """utils.eval_seq / utils.finn_eval_seq of sample s's predicted frames, on the device."""
+        opt = self.opt
+        if mse is not None:
+            m = ops.eval_frames_finn(torch.stack(list(x[opt.n_past:opt.n_eval])), torch.stack(frames[opt.n_past:opt.n_eval]))
+            ssim[:, s], psnr[:, s], mse[:, s] = (v.t() for v in m)
+        else:
+            for t in range(opt.n_eval - opt.n_past):
+                ssim[:, s, t], psnr[:, s, t] = ops.eval_frames(x[opt.n_past + t], frames[opt.n_past + t])
+
+    def _make_gifs_host(self, x, nsample, eps_by_sample, follow, guard):
+        """make_gifs with --trigger variance as the reference would run it (the pattern of _gp_trigger_gen_host): per step the
+        variance goes to the host (`np.linalg.norm(variance.cpu().numpy().transpose(), axis=1)`, generate_frames.py:230, every row),
+        numpy slides the windows and decides (:231,288-289), and the flags go back to pick every row's latent."""
+        from dvg_amd.rollout import _predict_from
+        opt, trig = self.opt, self.trigger
+        B, T = x[0].shape[0], opt.n_eval - opt.n_past
+        ssim, psnr = torch.zeros(B, nsample, T, device=self.dev), torch.zeros(B, nsample, T, device=self.dev)
+        finn = getattr(opt, 'metrics', 'skimage') == 'finn'
+        mse = torch.zeros(B, nsample, T, device=self.dev) if finn else None
+        state = condition(self.encoder, self.frame_predictor, x, opt.n_past, opt.last_frame_skip, decoder=self.decoder)
+        post = posterior_from(state, self.encoder, self.decoder, self.frame_predictor, self.gp_layer, self.likelihood,
+                              opt.n_past, opt.n_eval, opt.last_frame_skip)
+        cond_values = [self._variance_norms(self._gp(h)) for h in state['latents']]
+        logs = {'flags': np.zeros((nsample, opt.n_eval, B), dtype=np.int32), 'values': np.zeros((nsample, opt.n_eval, B), dtype=np.float32),
+                'thresholds': np.full((nsample, opt.n_eval, B), np.inf, dtype=np.float32)}
+        followed, all_gen = [], []
+        for s in range(nsample):
+            host = HostTriggerRows(B, trig.window, trig.coef, trig.min_gap)
+            for i, v in enumerate(cond_values, start=1):
+                host.step(i, v, False)
+                logs['values'][s, i] = v
+            near = []
+
+            def latent(i, h, h_pred):
+                pred = self._gp(h)
+                value = self._variance_norms(pred)
+                flags, thr = host.step(i, value, True, None if follow is None else follow[s][i], guard, near)
+                logs['values'][s, i], logs['flags'][s, i], logs['thresholds'][s, i] = value, flags, thr
+                if i <= trig.window:
+                    return h_pred
+                z = pred.rsample(None if eps_by_sample is None else eps_by_sample[s][i]).transpose(0, 1)
+                return torch.where(torch.from_numpy(flags).to(self.dev).bool().unsqueeze(1), z, h_pred).contiguous()
+            frames = _predict_from(state, self.encoder, self.decoder, self.frame_predictor, opt.n_past, opt.n_eval,
+                                   opt.last_frame_skip, latent)
+            followed += [(s, i, b) for i, b in near]
+            self._score(x, frames, s, ssim, psnr, mse)
+            all_gen.append(torch.stack(frames))
+        best = ssim.mean(2).argsort(1)[:, -1]
+        tr = {k: torch.from_numpy(v).to(self.dev) for k, v in logs.items()}
+        tr.update(window=trig.window, coef=trig.coef, min_gap=trig.min_gap, followed=followed)
+        return {'posterior': torch.stack(post), 'samples': torch.stack(all_gen), 'ssim': ssim, 'psnr': psnr, 'best': best,
+                'trigger': tr, **({'mse': mse, 'metrics': 'finn'} if finn else {})}
 
     def gp_scorer(self):
         """--gp_report: a scorer for this checkpoint's latent size and step counts (dvg_amd/gp_score.py); feed it with
@@ -387,7 +526,7 @@ def data_seed(seed):
 
 
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     if args.synthetic_ckpt:     # (a loaded checkpoint names its own dataset: checked below, once it is read)
         datasets.check_resize(args, 'generate_frames.py')
     assert torch.cuda.is_available(), "generate_frames.py needs a GPU: the DVG hot path has no CPU fallback"
@@ -411,6 +550,8 @@ def main(argv=None):
         opt.log_dir = args.log_dir
         opt.inflight = args.inflight
         opt.metrics = args.metrics
+        opt.trigger, opt.trigger_window = args.trigger, args.trigger_window
+        opt.trigger_coef, opt.trigger_min_gap = args.trigger_coef, args.trigger_min_gap
     os.makedirs('%s/gen/' % opt.log_dir, exist_ok=True)
     print("Random Seed: ", opt.seed)
     random.seed(opt.seed)
@@ -465,6 +606,8 @@ def main(argv=None):
                 saved.update(mse=res['mse'].cpu(), metrics=res['metrics'])
             if 'diversity' in res:
                 saved['diversity'] = {k: v.cpu() for k, v in res['diversity'].items()}
+            if 'trigger' in res:
+                saved['trigger'] = {k: v.cpu() if torch.is_tensor(v) else v for k, v in res['trigger'].items()}
             torch.save(saved, '%s/gen/sample_lstm_%d.pt' % (opt.log_dir, i))
             scorer is None or written.append(('%s/gen/sample_lstm_%d.pt' % (opt.log_dir, i), saved))
             sel = res['best'].view(-1, 1, 1).expand(-1, 1, res['ssim'].shape[2])
@@ -481,6 +624,12 @@ def main(argv=None):
                       'samples at the last step %.1f/%d' % (i, args.nsample, float(dv['pair_mse'].mean()),
                                                             float(10.0 * torch.log10(1.0 / dv['pair_mse'].mean())),
                                                             float(dv['distinct'][:, -1].double().mean()), args.nsample))
+            if 'trigger' in res:
+                tr = res['trigger']
+                mean, lo, hi, never, first = trigger_summary(tr['flags'], opt.n_past)
+                print('batch %d: variance trigger (window %d, coef %g, min gap %d): draws per sequence mean %.2f min %d max %d; %.1f %% '
+                      'of the sequences never drew; mean step of the first draw %.1f' % (
+                          i, tr['window'], tr['coef'], tr['min_gap'], mean, lo, hi, 100.0 * never, first))
             if not args.no_images:
                 gen.write_gifs(test_x, res, i, '%s/gen' % opt.log_dir, rows=args.gif_rows)
     if scorer is not None and written:

@@ -701,13 +701,13 @@ void dvg_debug_set_wgrad_clockbuf(void* buf, unsigned records);  /* wgrad_igemm_
  *                         triggered step decodes the GP sample and does NOT step the LSTM (:289-296); n_state <= 8 tensors of
  *                         state_elems floats (host arrays of device pointers)                                            */
 int dvg_gp_var_norms(const float* var, float* norms, int D, int B, void* stream);
-int dvg_gp_trigger_step(const float* var, int D, int B, int col, float* ctx, int window, float coef, int* flag, float* values,
-                        float* thresholds, int* flags, int slot, void* stream);
-int dvg_gp_trigger_replay(const float* values, int n, const float* ctx0, int window, float coef, int* flags, float* thresholds,
-                          void* stream);
-int dvg_gp_trigger_select(const int* flag, const float* sample_db, const float* h_pred, float* vec, int D, int B, int n_state,
-                          long state_elems, const float* const* state_old, const float* const* state_new,
-                          float* const* state_out, void* stream);
+int dvg_gp_trigger_step(const float* var, int D, int B, int col, float* ctx, int window, float coef, int* flag, float* values, float* thresholds, int* flags, int slot, void* stream);
+int dvg_gp_trigger_replay(const float* values, int n, const float* ctx0, int window, float coef, int* flags, float* thresholds, void* stream);
+int dvg_gp_trigger_select(const int* flag, const float* sample_db, const float* h_pred, float* vec, int D, int B, int n_state, long state_elems, const float* const* state_old, const float* const* state_new, float* const* state_out, void* stream);
+/* The same bookkeeping PER BATCH ROW, one launch per step: the sampler's variance rule (generate_frames.py --trigger variance; docs/DESIGN_NOTES_trigger_rows.md).  It stands for :230 (the norm - of every row, not of sample [3]), :231 (the slide), :288 (the threshold), :289-292 (which latent the step decodes).  One wave per row b: value = || var[:, b] ||_2, var (D,B), dvg_gp_var_norms' arithmetic; win (B, window), row b in place: pos < window fills win[b][pos] = value, pos == window slides win[b] <- [win[b][1:], value].
+ * decide != 0 (needs pos == window): threshold = mean(win[b]) + coef * std(win[b]) on the slid window with dvg_gp_trigger_step's rounding points; flag = value > threshold and step - last[b] > min_gap; a set flag stores last[b] = step (a row that never drew holds -2^30); vec (B,D)[b] = flag ? sample_db (D,B)[:, b] : h_pred (B,D)[b].  decide == 0 records only: threshold +inf, flag 0; sample_db, h_pred and vec may be NULL and are not touched.  values / thresholds / flags: entry [slot * B + b], the caller sizes them.
+ * pos, decide, step and slot are launch arguments, not device state: a captured launch replays as itself.  DVG_ERR_NULL for a missing pointer; DVG_ERR_SHAPE for D or B <= 0, window outside [1, 64], pos outside [0, window], decide with pos < window, min_gap < 0 or slot < 0 - all before any launch.  An addition within ABI 9. */
+int dvg_gp_trigger_rows(const float* var, const float* sample_db, const float* h_pred, float* vec, int D, int B, float* win, int window, int pos, int decide, float coef, int step, int min_gap, int* last, float* values, float* thresholds, int* flags, int slot, void* stream);
 /* ---- losses of the step closures and their gradients in one pass (train.py:188,223,227-239; ABI 8) ---------------------------
  * dvg_frame_losses: pred [S][K][n] - per time step the K decoder calls in the reference's call order (x_pred, x_target_pred,
  * x_pred_gp, :227-232) -, target [S][n] (the step's ground-truth frame): sums[k] = sum over steps and elements of
