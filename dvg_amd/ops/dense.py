@@ -54,14 +54,37 @@ def lstm_cell(x, h, c, w_ih, w_hh, b_ih, b_hh, want_gates=False):
 def lstm_cell_pre(pre, h, c, w_hh, h_out, c_out, gates_out):
     """One LSTMCell step whose input half `pre` = W_ih x + b_ih + b_hh (B,4H) is given (dvg_lstm_cell_pre); writes into the
     caller's h_out / c_out / gates_out (slices of the per-sequence buffers of autograd._LSTMSequence)."""
+    for t, nm in ((pre, "pre"), (h, "h"), (c, "c"), (h_out, "h_out"), (c_out, "c_out")):
+        _dev_f32(t, "lstm_cell_pre." + nm)
+    if h.dim() != 2:
+        raise RuntimeError("lstm_cell_pre: h must be (B, H)")
     b, hid = h.shape
+    _same("lstm_cell_pre", ((pre, (b, 4 * hid), "pre"), (h, (b, hid), "h"), (c, (b, hid), "c"), (w_hh, (4 * hid, hid), "w_hh"),
+                            (h_out, (b, hid), "h_out"), (c_out, (b, hid), "c_out"), (gates_out, (b, 4 * hid), "gates_out")))
     _run("lstm_cell", 2.0 * b * 4 * hid * hid, 4.0 * (4 * hid * hid + 9 * b * hid), lib().dvg_lstm_cell_pre, _p(pre), _p(h),
          _p(c), _p(w_hh), _p(h_out), _p(c_out), _p(gates_out), b, hid, _stream())
 
 
+def _same(name, buffers):
+    """Every (tensor or None, shape, label): a contiguous device tensor of exactly that shape (the kernels take bare pointers:
+    a wrong-shaped buffer is read or written out of bounds)."""
+    for t, shape, nm in buffers:
+        if t is not None and (tuple(t.shape) != shape or not t.is_contiguous() or not t.is_cuda):
+            raise RuntimeError(f"{name}: {nm} must be a contiguous device tensor of shape {shape}, got {tuple(t.shape)}")
+
+
 def lstm_cell_bwd(dh_a, dh_b, dc, gates, c_prev, c_new, w_hh_t, dG, dc_prev, dh_prev):
     """One BPTT step of an LSTMCell in one launch (dvg_lstm_cell_bwd): dG, dc_prev and dh_prev = dG W_hh."""
+    if dh_a is None and dh_b is None and dc is None:
+        raise RuntimeError("lstm_cell_bwd: no incoming gradient")
+    for t, nm in ((gates, "gates"), (c_new, "c_new"), (dG, "dG")):
+        _dev_f32(t, "lstm_cell_bwd." + nm)
+    if c_new.dim() != 2:
+        raise RuntimeError("lstm_cell_bwd: c_new must be (B, H)")
     b, hid = c_new.shape
+    _same("lstm_cell_bwd", ((dh_a, (b, hid), "dh_a"), (dh_b, (b, hid), "dh_b"), (dc, (b, hid), "dc"), (gates, (b, 4 * hid), "gates"),
+                            (c_prev, (b, hid), "c_prev"), (c_new, (b, hid), "c_new"), (w_hh_t, (hid, 4 * hid), "w_hh_t"),
+                            (dG, (b, 4 * hid), "dG"), (dc_prev, (b, hid), "dc_prev"), (dh_prev, (b, hid), "dh_prev")))
     _run("lstm_cell_bwd", 2.0 * b * 4 * hid * hid, 4.0 * (4 * hid * hid + 12 * b * hid), lib().dvg_lstm_cell_bwd, _p(dh_a),
          _p(dh_b), _p(dc), _p(gates), _p(c_prev), _p(c_new), _p(w_hh_t), _p(dG), _p(dc_prev), _p(dh_prev), b, hid, _stream())
 
