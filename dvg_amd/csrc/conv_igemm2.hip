@@ -1913,8 +1913,10 @@ extern "C" int dvg_convT4x4s2_bn_act_proj(const float* x, const float* w_k16, co
 // outermost, as dvg_winograd_weight writes them (gload_b); dvg_pack_conv_weight_k16's 1x1 layout [Cin/16][Cout/64][64][row]
 // is the same only at Cout == 64).  The 16 / 36 Winograd-domain products of dvg_winograd_*.
 // Cin % 64 == 0, Cout % 64 == 0, H % 8 == 0, W % 8 == 0.
-extern "C" int dvg_gemm_batched_k16(const float* x, const float* w_k16, float* y, int NB, int H, int W, int Cin, int Cout,
-                                    void* stream) {
+// nb_tile: the image count gemm_tile chooses (tile_w, nt) from - NB itself, or (dvg_gemm_batched_k16_as) the count of the launch
+// this one is a part of.
+static int gemm_batched(const float* x, const float* w_k16, float* y, int NB, int nb_tile, int H, int W, int Cin, int Cout,
+                        void* stream) {
     Igemm2Params p{x, nullptr, w_k16, nullptr, nullptr, y, nullptr, nullptr, NB, H, W, Cin, 0, Cout, 0, DVG_ACT_NONE, 0.f,
                    0, 0, 0, 0, 0, 1, 0, nullptr};
     if (int e = checks2(p, "dvg_gemm_batched_k16")) return e;
@@ -1926,7 +1928,7 @@ extern "C" int dvg_gemm_batched_k16(const float* x, const float* w_k16, float* y
     const long workspace_floats = 0;
     const int Hg = H, Wg = W, ti = 1, th = 8;
     int tw, nt;
-    DVG_REQUIRE(gemm_tile(NB, Hg, Wg, Cout, &tw, &nt) == 0, DVG_ERR_SHAPE, "dvg_gemm_batched_k16: no tile for %dx%d", H, W);
+    DVG_REQUIRE(gemm_tile(nb_tile, Hg, Wg, Cout, &tw, &nt) == 0, DVG_ERR_SHAPE, "dvg_gemm_batched_k16: no tile for %dx%d", H, W);
 #if DVG_BF16X3
     if (nt == 2) return launch2<M2_GEMM, 1, 8, 16, 2>(p, Hg, Wg, workspace, workspace_floats, (hipStream_t)stream);
 #endif
@@ -1935,13 +1937,37 @@ extern "C" int dvg_gemm_batched_k16(const float* x, const float* w_k16, float* y
     return fail(DVG_ERR_SHAPE, "dvg_gemm_batched_k16: no kernel");
 }
 
+extern "C" int dvg_gemm_batched_k16(const float* x, const float* w_k16, float* y, int NB, int H, int W, int Cin, int Cout,
+                                    void* stream) {
+    return gemm_batched(x, w_k16, y, NB, NB, H, W, Cin, Cout, stream);
+}
+
+// dvg_gemm_batched_k16 over NB images with the tile a launch of NB_as >= NB images of the same shape takes: the 25 live Winograd
+// positions of an upsampled input (winograd.hip: wino_pos) run on the tile of the 36-position launch they are a part of, so every
+// K sum is cut where that launch cuts it - the same bits - and the launch keeps the energy-lean tile its count alone would lose.
+// The images per pipeline (gemm_ni) follow NB: they change no sum.
+extern "C" int dvg_gemm_batched_k16_as(const float* x, const float* w_k16, float* y, int NB, int NB_as, int H, int W, int Cin,
+                                       int Cout, void* stream) {
+    DVG_REQUIRE(NB > 0 && NB_as >= NB, DVG_ERR_SHAPE, "dvg_gemm_batched_k16_as: NB=%d, NB_as=%d (NB_as >= NB > 0 needed)", NB, NB_as);
+    return gemm_batched(x, w_k16, y, NB, NB_as, H, W, Cin, Cout, stream);
+}
+
 // What dvg_gemm_batched_k16 launches for this shape under the tile policy in force, without launching (host only): *tile_w the
 // pixel tile's width (8: the 64-row tile, 16: the 128-row tile), *nt the 64-wide Cout blocks per workgroup (2: the 128 x 128
 // tile), *ni the images a workgroup runs back to back in one pipeline.  0, or -1 for a shape the launcher rejects.
-extern "C" int dvg_gemm_batched_plan(int NB, int H, int W, int Cin, int Cout, int* tile_w, int* nt, int* ni) {
-    if (!tile_w || !nt || !ni || NB <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return -1;
+static int gemm_plan(int NB, int nb_tile, int H, int W, int Cin, int Cout, int* tile_w, int* nt, int* ni) {
+    if (!tile_w || !nt || !ni || NB <= 0 || nb_tile < NB || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return -1;
     if (Cin % (16 * DVG_GEMM_GT) || Cout % 64 || H % 8 || W % 8) return -1;
-    if (gemm_tile(NB, H, W, Cout, tile_w, nt)) return -1;
+    if (gemm_tile(nb_tile, H, W, Cout, tile_w, nt)) return -1;
     *ni = gemm_images_per_wg(*tile_w, *nt, NB, H, W, Cout);
     return 0;
+}
+
+extern "C" int dvg_gemm_batched_plan(int NB, int H, int W, int Cin, int Cout, int* tile_w, int* nt, int* ni) {
+    return gemm_plan(NB, NB, H, W, Cin, Cout, tile_w, nt, ni);
+}
+
+// ... and what dvg_gemm_batched_k16_as launches
+extern "C" int dvg_gemm_batched_plan_as(int NB, int NB_as, int H, int W, int Cin, int Cout, int* tile_w, int* nt, int* ni) {
+    return gemm_plan(NB, NB_as, H, W, Cin, Cout, tile_w, nt, ni);
 }

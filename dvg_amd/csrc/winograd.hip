@@ -202,6 +202,16 @@ __device__ __forceinline__ void at4(const V (&q)[6], V (&o)[4]) {
     o[3] = b + 8.f * d + q[5];
 }
 
+// Live positions of an UPSAMPLED input (docs/DESIGN_NOTES_upconv_live.md): through nearest-x2 upsampling the six rows of an
+// F(4x4) input tile are the low-res rows [p, q, q, r, r, s], so row 2 of B^T, 4 (d1 - d2) - d3 + d4, is exactly +0 for every
+// finite input, and likewise along the columns: the 11 positions with a == 2 or b == 2 of V are zero, and so are those of
+// M = V U.  The LIVE forms below neither compute nor store them (producers) / read +0 in their place (consumers); the 25 others
+// are stored [25][T][C] at a' * 5 + b', a' = a - (a > 2).  Arithmetic of the live positions: bt4 / at4 as everywhere.
+__device__ __forceinline__ constexpr bool wino_dead(int a, int b) { return a == 2 || b == 2; }
+__device__ __forceinline__ constexpr int wino_pos(bool live, int a, int b) {
+    return live ? (a - (a > 2)) * 5 + (b - (b > 2)) : a * 6 + b;
+}
+
 __global__ void winograd4_weight_kernel(const float* __restrict__ w, float* __restrict__ u, int cout, int cin) {
     const float G[6][3] = {{0.25f, 0.f, 0.f}, {-1.f / 6, -1.f / 6, -1.f / 6}, {-1.f / 6, 1.f / 6, -1.f / 6},
                            {1.f / 24, 1.f / 12, 1.f / 6}, {1.f / 24, -1.f / 12, 1.f / 6}, {0.f, 0.f, 1.f}};
@@ -235,13 +245,13 @@ __global__ void winograd4_weight_kernel(const float* __restrict__ w, float* __re
 // V = f32x4 / f32x2 / float: channels per thread.  A thread owns a whole 6x6 patch (36 loads, 36 stores), so the grid is
 // tiles x C / width threads: at 8x8 maps and B = 64 that is 128 workgroups with float4 - the narrower forms fill the chip
 // (accesses stay coalesced: consecutive lanes take consecutive channels) and need a quarter of the registers.
-template <typename V>
+template <typename V, bool LIVE = false>
 __global__ __launch_bounds__(256) void winograd4_input_kernel(const float* __restrict__ x, float* __restrict__ v, int N,
                                                               int H, int W, int C4, long Tt, long t_off, int up) {
     // Tt / t_off: tiles per position of the destination and this call's first tile (the weight-gradient path concatenates
     // the tiles of several uses of a layer; Tt = N * tiles per image, t_off = 0 otherwise)
     // up = 1: x is stored at (N, H/2, W/2, C) and read through nearest-x2 upsampling (the x half of a decoder block's first
-    // conv, vgg_64.py:93,98-105: the upsampled tensor never exists)
+    // conv, vgg_64.py:93,98-105: the upsampled tensor never exists).  LIVE (up = 1 only): v is the compact [25][Tt][C]
     const int Ht = H >> 2, Wt = W >> 2, Hs = H >> up, Ws = W >> up;
     const long T = (long)N * Ht * Wt, total = T * C4;
     for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
@@ -268,10 +278,12 @@ __global__ __launch_bounds__(256) void winograd4_input_kernel(const float* __res
         }
 #pragma unroll
         for (int a = 0; a < 6; ++a) {
+            if (LIVE && a == 2) continue;
             V o[6];
             bt4(e[a], o);
 #pragma unroll
-            for (int b = 0; b < 6; ++b) reinterpret_cast<V*>(v)[((size_t)(a * 6 + b) * Tt + t_off + t) * C4 + c4] = o[b];
+            for (int b = 0; b < 6; ++b)
+                if (!(LIVE && b == 2)) reinterpret_cast<V*>(v)[((size_t)wino_pos(LIVE, a, b) * Tt + t_off + t) * C4 + c4] = o[b];
         }
     }
 }
@@ -323,8 +335,7 @@ __global__ __launch_bounds__(256) void winograd4_dy_kernel(const float* __restri
     }
 }
 
-template <bool POOL, typename V>
-
+template <bool POOL, typename V, bool MLIVE = false>
 __global__ __launch_bounds__(256) void winograd4_output_kernel(const float* __restrict__ m, const float* __restrict__ scale,
                                                                const float* __restrict__ shift, float* __restrict__ y,
                                                                float* __restrict__ y_pool, int N, int H, int W, int C4,
@@ -333,6 +344,7 @@ __global__ __launch_bounds__(256) void winograd4_output_kernel(const float* __re
     // y_from (POOL only, else 0): y holds the images [y_from, N); the images before store only their pooled output
     // addend (optional): raw partial sums in y's shape, y = act((A^T M A + addend) * scale + shift) - the hoisted skip half
     // of a decoder block's first conv (the same role as the igemm kernels' addend)
+    // MLIVE: m is the compact [25][T][C] of a layer that read its input through the upsampling; the dead positions enter as +0
     constexpr int VN = VecN<V>::N;
     const int Ht = H >> 2, Wt = W >> 2;
     const long T = (long)N * Ht * Wt, total = T * C4;
@@ -347,7 +359,9 @@ __global__ __launch_bounds__(256) void winograd4_output_kernel(const float* __re
         for (int b = 0; b < 6; ++b) {
             V q[6];
 #pragma unroll
-            for (int a = 0; a < 6; ++a) q[a] = reinterpret_cast<const V*>(m)[((size_t)(a * 6 + b) * T + t) * C4 + c4];
+            for (int a = 0; a < 6; ++a)
+                q[a] = (MLIVE && wino_dead(a, b)) ? vzero<V>()
+                                                  : reinterpret_cast<const V*>(m)[((size_t)wino_pos(MLIVE, a, b) * T + t) * C4 + c4];
             V col[4];
             at4(q, col);
 #pragma unroll
@@ -396,7 +410,7 @@ __global__ __launch_bounds__(256) void winograd4_output_kernel(const float* __re
 // 70-87): y = act(scale * A^T M A + shift) is staged in LDS (one image x CS channels per workgroup: 16 KB) and leaves as
 // V' = B^T y B - the activation never travels to HBM and back (M in, V' out: 4.5 units of traffic instead of 6.5) and one
 // launch of two disappears.  HW = 8 or 16 (map side); thread = one 4x4 tile x one channel.
-template <int HW>
+template <int HW, bool MLIVE = false>
 __global__ __launch_bounds__(256) void winograd4_out_in_kernel(const float* __restrict__ m, const float* __restrict__ scale,
                                                                const float* __restrict__ shift, float* __restrict__ v, int N,
                                                                int C, int act, float slope, const float* __restrict__ addend) {
@@ -412,7 +426,8 @@ __global__ __launch_bounds__(256) void winograd4_out_in_kernel(const float* __re
         for (int b = 0; b < 6; ++b) {
             float q[6];
 #pragma unroll
-            for (int a = 0; a < 6; ++a) q[a] = m[((size_t)(a * 6 + b) * T + t) * C + c];
+            for (int a = 0; a < 6; ++a)       // MLIVE: compact M, +0 for the dead positions (see wino_pos)
+                q[a] = (MLIVE && wino_dead(a, b)) ? 0.f : m[((size_t)wino_pos(MLIVE, a, b) * T + t) * C + c];
             float col[4];
             at4(q, col);
 #pragma unroll
@@ -469,7 +484,9 @@ __global__ __launch_bounds__(256) void winograd4_out_in_kernel(const float* __re
 //                 upsampling (vgg_64.py:93,98-105, the x half of the concat conv in Winograd form): y (HW x HW) is staged in
 //                 LDS and leaves as the input transform of up2(y) (2 HW x 2 HW, 4 x the tiles); neither y nor its upsampled
 //                 form is written.  Bit-identical to winograd4_output_kernel followed by winograd4_input_kernel<up = 1>.
-template <int HW, int CS, typename V, bool POOL, int NT, bool UP = false>
+//   MLIVE / VLIVE: m is read / v is written in the compact 25-position form (see wino_pos).  MLIVE: this layer read its input
+//                 through the upsampling (POOL = false, UP = false instantiations); VLIVE: the next one does (UP = true).
+template <int HW, int CS, typename V, bool POOL, int NT, bool UP = false, bool MLIVE = false, bool VLIVE = false>
 __global__ __launch_bounds__(NT) void winograd4_chain_kernel(const float* __restrict__ m, const float* __restrict__ scale,
                                                              const float* __restrict__ shift, float* __restrict__ y,
                                                              float* __restrict__ v, int N, int C, int act, float slope,
@@ -478,6 +495,7 @@ __global__ __launch_bounds__(NT) void winograd4_chain_kernel(const float* __rest
     constexpr int VN = VecN<V>::N;
     constexpr int WT = HW / 4, TI = WT * WT;         // tiles per image side / per image of layer L
     static_assert(!(POOL && UP), "pool and upsample exclude each other");
+    static_assert(!VLIVE || UP, "only the input transform of an upsampled map has dead positions");
     constexpr int SS = POOL ? HW / 2 : HW;           // side of the map staged in LDS
     constexpr int S2 = UP ? 2 * HW : SS;             // side of the map layer L + 1 reads (UP: through the upsampling)
     constexpr int WT2 = S2 / 4, TI2 = WT2 * WT2;
@@ -498,7 +516,9 @@ __global__ __launch_bounds__(NT) void winograd4_chain_kernel(const float* __rest
             V q[6];
             // read-once M: nontemporal, +0.9 % vgg_64 rollouts in flight (r05 same-box A/B, profiles/r05_ab_nontemporal.txt)
 #pragma unroll
-            for (int a = 0; a < 6; ++a) q[a] = __builtin_nontemporal_load(reinterpret_cast<const V*>(m) + ((size_t)(a * 6 + b) * T + t) * CVg + cg);
+            for (int a = 0; a < 6; ++a)
+                q[a] = (MLIVE && wino_dead(a, b)) ? vzero<V>()
+                                                  : __builtin_nontemporal_load(reinterpret_cast<const V*>(m) + ((size_t)wino_pos(MLIVE, a, b) * T + t) * CVg + cg);
             V col[4];
             at4(q, col);
 #pragma unroll
@@ -568,21 +588,23 @@ __global__ __launch_bounds__(NT) void winograd4_chain_kernel(const float* __rest
         }
 #pragma unroll
         for (int a = 0; a < 6; ++a) {
+            if (VLIVE && a == 2) continue;
             V o[6];
             bt4(e[a], o);
             // plain stores: a nontemporal V store measured noise (profiles/r05_ab_nontemporal.txt)
 #pragma unroll
-            for (int b = 0; b < 6; ++b) reinterpret_cast<V*>(v)[((size_t)(a * 6 + b) * T2 + t2) * CVg + cg] = o[b];
+            for (int b = 0; b < 6; ++b)
+                if (!(VLIVE && b == 2)) reinterpret_cast<V*>(v)[((size_t)wino_pos(VLIVE, a, b) * T2 + t2) * CVg + cg] = o[b];
         }
     }
 }
 
-template <int HW, int CS, typename V, bool POOL, int NT, bool UP = false>
+template <int HW, int CS, typename V, bool POOL, int NT, bool UP = false, bool MLIVE = false, bool VLIVE = false>
 static int launch_chain(const float* mm, const float* scale, const float* shift, float* y, float* v, int N, int C, int act,
                         float slope, hipStream_t st, const float* addend = nullptr, int y_from = 0) {
     constexpr int S2 = POOL ? HW / 2 : HW;
     constexpr size_t lds = (size_t)S2 * S2 * CS * 4;
-    auto kern = winograd4_chain_kernel<HW, CS, V, POOL, NT, UP>;
+    auto kern = winograd4_chain_kernel<HW, CS, V, POOL, NT, UP, MLIVE, VLIVE>;
     static bool attr = false;
     if (!attr && lds > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -600,7 +622,8 @@ static int launch_chain(const float* mm, const float* scale, const float* shift,
 // channels into LDS (thread = one output column (pixel, channel), its K weights in registers, the latent vectors broadcast from
 // LDS - the arithmetic of stem_kernel, bit for bit) and writes the input transform of the UPSAMPLED 8 x 8 map (the arithmetic
 // of winograd4_input_kernel<up = 1>): the 4 x 4 map never travels.  wt: the weight transposed to [KP][16 C], rows K..KP-1 zero.
-template <int KP>
+// LIVE: v is the compact [25][4 M][C] (see wino_pos).
+template <int KP, bool LIVE = false>
 __global__ __launch_bounds__(256) void stem_up_input_kernel(const float* __restrict__ vec, int ldv, const float* __restrict__ wt,
                                                             const float* __restrict__ scale, const float* __restrict__ shift,
                                                             float* __restrict__ v, int M, int C, int K, int act, float slope) {
@@ -660,10 +683,12 @@ __global__ __launch_bounds__(256) void stem_up_input_kernel(const float* __restr
         float* dst = v + t * C + blockIdx.x * 16 + ucl;
 #pragma unroll
         for (int a = 0; a < 6; ++a) {
+            if (LIVE && a == 2) continue;
             float o[6];
             bt4(e[a], o);
 #pragma unroll
-            for (int b = 0; b < 6; ++b) dst[(size_t)(a * 6 + b) * T * C] = o[b];
+            for (int b = 0; b < 6; ++b)
+                if (!(LIVE && b == 2)) dst[(size_t)wino_pos(LIVE, a, b) * T * C] = o[b];
         }
     }
 }
@@ -722,6 +747,25 @@ extern "C" int dvg_winograd_input(const float* x, float* v, int N, int H, int W,
             hipLaunchKernelGGL(winograd4_input_kernel<float>, dim3(wgrid(tiles * C)), dim3(256), 0, st, x, v, N, H, W, C, tiles, 0L, up);
     }
     return check_launch("dvg_winograd_input");
+}
+
+// dvg_winograd_input(m = 4, upsample = 1) without the 11 positions that are zero for every upsampled input: v (25, T, C), the
+// live positions in the compact order a' * 5 + b' (wino_pos).  Equal to the matching slices of the dense form, bit for bit.
+extern "C" int dvg_winograd_input_up_live(const float* x, float* v, int N, int H, int W, int C, void* stream) {
+    DVG_REQUIRE(x && v, DVG_ERR_NULL, "dvg_winograd_input_up_live: NULL pointer");
+    DVG_REQUIRE(N > 0 && H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0 && C > 0 && C % 4 == 0, DVG_ERR_SHAPE,
+                "dvg_winograd_input_up_live: H and W multiples of 4, C %% 4 == 0 needed");
+    DVG_REQUIRE(aligned16(x) && aligned16(v), DVG_ERR_ALIGN, "dvg_winograd_input_up_live: alignment");
+    const long tiles = (long)N * (H / 4) * (W / 4);
+    const hipStream_t st = (hipStream_t)stream;
+    const int cw = wino4_width(tiles, C);
+    if (cw == 4)
+        hipLaunchKernelGGL((winograd4_input_kernel<f32x4, true>), dim3(wgrid(tiles * (C / 4))), dim3(256), 0, st, x, v, N, H, W, C / 4, tiles, 0L, 1);
+    else if (cw == 2)
+        hipLaunchKernelGGL((winograd4_input_kernel<f32x2, true>), dim3(wgrid(tiles * (C / 2))), dim3(256), 0, st, x, v, N, H, W, C / 2, tiles, 0L, 1);
+    else
+        hipLaunchKernelGGL((winograd4_input_kernel<float, true>), dim3(wgrid(tiles * C)), dim3(256), 0, st, x, v, N, H, W, C, tiles, 0L, 1);
+    return check_launch("dvg_winograd_input_up_live");
 }
 
 // Channels per thread (4, 2 or 1) of the F(4x4) transform kernels dvg_winograd_input, dvg_winograd_output and
@@ -803,12 +847,36 @@ extern "C" int dvg_winograd_output_input(const float* mm, const float* scale, co
     return check_launch("dvg_winograd_output_input");
 }
 
+// dvg_winograd_output_input for a layer that read its input through the upsampling: mm is the compact M (25, T, C) (wino_pos),
+// the dead positions enter the output transform as +0; v_next stays the dense (36, T, C).  H == W in {8, 16, 32}, the kernels and
+// the choice between them as in dvg_winograd_output_input: the same bits as that call on the zero-filled dense M.
+extern "C" int dvg_winograd_output_input_live(const float* mm, const float* scale, const float* shift, float* v_next, int N,
+                                              int H, int W, int C, int act, float slope, const float* addend, void* stream) {
+    DVG_REQUIRE(mm && v_next, DVG_ERR_NULL, "dvg_winograd_output_input_live: NULL pointer");
+    DVG_REQUIRE(aligned16(addend), DVG_ERR_ALIGN, "dvg_winograd_output_input_live: addend alignment");
+    DVG_REQUIRE(N > 0 && H == W && (H == 8 || H == 16 || H == 32) && C > 0 && C % 64 == 0, DVG_ERR_SHAPE,
+                "dvg_winograd_output_input_live: 8x8, 16x16 or 32x32 maps, C %% 64 == 0 needed (got %dx%d, C=%d)", H, W, C);
+    DVG_REQUIRE(act >= 0 && act <= 3, DVG_ERR_SHAPE, "dvg_winograd_output_input_live: bad act");
+    DVG_REQUIRE(aligned16(mm) && aligned16(v_next), DVG_ERR_ALIGN, "dvg_winograd_output_input_live: alignment");
+    const hipStream_t st = (hipStream_t)stream;
+    if (H == 8) {
+        hipLaunchKernelGGL((winograd4_out_in_kernel<8, true>), dim3((unsigned)((long)N * (C / 64))), dim3(256), 0, st, mm, scale,
+                           shift, v_next, N, C, act, slope, addend);
+        return check_launch("dvg_winograd_output_input_live");
+    }
+    if (H == 32)
+        return launch_chain<32, 32, f32x4, false, 512, false, true>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st, addend);
+    if ((long)N * (C / 64) < 1024)
+        return launch_chain<16, 32, float, false, 512, false, true>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st, addend);
+    return launch_chain<16, 64, f32x2, false, 512, false, true>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st, addend);
+}
+
 // stem_up_input_kernel: vec (M, K) row stride ldv; w_kn the stem weight as [KP][16 C] (dvg_stem_gemm's operand: column
 // (h * 4 + w) * C + c, rows K..KP-1 zero); v_next (36, 4 M, C) = the F(4x4,3x3) input transform of
 // UpsamplingNearest2d(2)(act(scale * convT(vec) + shift)).  C % 16 == 0, KP in {96, 128}.
-extern "C" int dvg_stem_up_winograd_input(const float* vec, int ldv, const float* w_kn, int KP, const float* scale,
-                                          const float* shift, float* v_next, int M, int C, int K, int act, float slope,
-                                          void* stream) {
+template <bool LIVE>
+static int stem_up_input(const float* vec, int ldv, const float* w_kn, int KP, const float* scale, const float* shift,
+                         float* v_next, int M, int C, int K, int act, float slope, void* stream) {
     DVG_REQUIRE(vec && w_kn && v_next, DVG_ERR_NULL, "dvg_stem_up_winograd_input: NULL pointer");
     DVG_REQUIRE(M > 0 && C > 0 && C % 16 == 0 && K > 0 && K <= KP && (KP == 96 || KP == 128) && ldv >= K, DVG_ERR_SHAPE,
                 "dvg_stem_up_winograd_input: bad shape M=%d C=%d K=%d KP=%d (C %% 16 == 0, KP 96 or 128)", M, C, K, KP);
@@ -816,26 +884,54 @@ extern "C" int dvg_stem_up_winograd_input(const float* vec, int ldv, const float
     DVG_REQUIRE(aligned16(v_next), DVG_ERR_ALIGN, "dvg_stem_up_winograd_input: alignment");
     const dim3 grid(C / 16, (M + 7) / 8);
     if (KP == 96)
-        hipLaunchKernelGGL(stem_up_input_kernel<96>, grid, dim3(256), 0, (hipStream_t)stream, vec, ldv, w_kn, scale, shift, v_next,
-                           M, C, K, act, slope);
+        hipLaunchKernelGGL((stem_up_input_kernel<96, LIVE>), grid, dim3(256), 0, (hipStream_t)stream, vec, ldv, w_kn, scale, shift,
+                           v_next, M, C, K, act, slope);
     else
-        hipLaunchKernelGGL(stem_up_input_kernel<128>, grid, dim3(256), 0, (hipStream_t)stream, vec, ldv, w_kn, scale, shift, v_next,
-                           M, C, K, act, slope);
+        hipLaunchKernelGGL((stem_up_input_kernel<128, LIVE>), grid, dim3(256), 0, (hipStream_t)stream, vec, ldv, w_kn, scale, shift,
+                           v_next, M, C, K, act, slope);
     return check_launch("dvg_stem_up_winograd_input");
+}
+
+extern "C" int dvg_stem_up_winograd_input(const float* vec, int ldv, const float* w_kn, int KP, const float* scale,
+                                          const float* shift, float* v_next, int M, int C, int K, int act, float slope,
+                                          void* stream) {
+    return stem_up_input<false>(vec, ldv, w_kn, KP, scale, shift, v_next, M, C, K, act, slope, stream);
+}
+
+// ... with v_next the compact (25, 4 M, C): the live positions of dvg_stem_up_winograd_input's result (wino_pos), same bits.
+extern "C" int dvg_stem_up_winograd_input_live(const float* vec, int ldv, const float* w_kn, int KP, const float* scale,
+                                               const float* shift, float* v_next, int M, int C, int K, int act, float slope,
+                                               void* stream) {
+    return stem_up_input<true>(vec, ldv, w_kn, KP, scale, shift, v_next, M, C, K, act, slope, stream);
 }
 
 // Last layer of a decoder block -> first conv of the next block (vgg_64.py:98-105): M (36, T, C) of an H x H layer ->
 // V' (36, 4 T, C), the F(4x4,3x3) input transform of UpsamplingNearest2d(2)(act(scale * A^T M A + shift)) (winograd4_chain_kernel
-// <UP>); neither the activation nor its upsampled form is written.  H == W == 8 (the next block works at 16 x 16).
+// <UP>); neither the activation nor its upsampled form is written.  H == W in {8, 16} (the next block works at twice that).
 extern "C" int dvg_winograd_output_up_input(const float* mm, const float* scale, const float* shift, float* v_next, int N, int H,
                                             int W, int C, int act, float slope, void* stream) {
     DVG_REQUIRE(mm && v_next, DVG_ERR_NULL, "dvg_winograd_output_up_input: NULL pointer");
-    DVG_REQUIRE(N > 0 && H == W && H == 8 && C > 0 && C % 64 == 0, DVG_ERR_SHAPE,
-                "dvg_winograd_output_up_input: 8x8 maps, C %% 64 == 0 needed (got %dx%d, C=%d)", H, W, C);
+    DVG_REQUIRE(N > 0 && H == W && (H == 8 || H == 16) && C > 0 && C % 64 == 0, DVG_ERR_SHAPE,
+                "dvg_winograd_output_up_input: 8x8 or 16x16 maps, C %% 64 == 0 needed (got %dx%d, C=%d)", H, W, C);
     DVG_REQUIRE(act >= 0 && act <= 3, DVG_ERR_SHAPE, "dvg_winograd_output_up_input: bad act");
     DVG_REQUIRE(aligned16(mm) && aligned16(v_next), DVG_ERR_ALIGN, "dvg_winograd_output_up_input: alignment");
     const hipStream_t st = (hipStream_t)stream;
+    if (H == 16) return launch_chain<16, 32, float, false, 512, true>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st);
     return launch_chain<8, 32, float, false, 512, true>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st);
+}
+
+// ... with v_next the compact (25, 4 T, C): the live positions of dvg_winograd_output_up_input's result (wino_pos), same bits.
+extern "C" int dvg_winograd_output_up_input_live(const float* mm, const float* scale, const float* shift, float* v_next, int N,
+                                                 int H, int W, int C, int act, float slope, void* stream) {
+    DVG_REQUIRE(mm && v_next, DVG_ERR_NULL, "dvg_winograd_output_up_input_live: NULL pointer");
+    DVG_REQUIRE(N > 0 && H == W && (H == 8 || H == 16) && C > 0 && C % 64 == 0, DVG_ERR_SHAPE,
+                "dvg_winograd_output_up_input_live: 8x8 or 16x16 maps, C %% 64 == 0 needed (got %dx%d, C=%d)", H, W, C);
+    DVG_REQUIRE(act >= 0 && act <= 3, DVG_ERR_SHAPE, "dvg_winograd_output_up_input_live: bad act");
+    DVG_REQUIRE(aligned16(mm) && aligned16(v_next), DVG_ERR_ALIGN, "dvg_winograd_output_up_input_live: alignment");
+    const hipStream_t st = (hipStream_t)stream;
+    if (H == 16)
+        return launch_chain<16, 32, float, false, 512, true, false, true>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st);
+    return launch_chain<8, 32, float, false, 512, true, false, true>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st);
 }
 
 // Last layer of an encoder stage (vgg_64.py:51-56): M (36, T, C) -> y = act(scale * A^T M A + shift) (N,H,W,C) NHWC, the
@@ -893,4 +989,28 @@ extern "C" int dvg_winograd_output(const float* m, const float* scale, const flo
 #undef W4OUT
     }
     return check_launch("dvg_winograd_output");
+}
+
+// dvg_winograd_output(m = 4, no pooled output) for a layer that read its input through the upsampling: m is the compact
+// M (25, T, C) (wino_pos), the dead positions enter the output transform as +0: the same bits as dvg_winograd_output on the
+// zero-filled dense M.  addend as there.
+extern "C" int dvg_winograd_output_live(const float* m, const float* scale, const float* shift, float* y, int N, int H, int W,
+                                        int C, int act, float slope, const float* addend, void* stream) {
+    DVG_REQUIRE(m && y, DVG_ERR_NULL, "dvg_winograd_output_live: NULL pointer");
+    DVG_REQUIRE(N > 0 && H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0 && C > 0 && C % 4 == 0, DVG_ERR_SHAPE,
+                "dvg_winograd_output_live: H and W multiples of 4, C %% 4 == 0 needed");
+    DVG_REQUIRE(act >= 0 && act <= 3, DVG_ERR_SHAPE, "dvg_winograd_output_live: bad act");
+    DVG_REQUIRE(aligned16(m) && aligned16(y) && aligned16(scale) && aligned16(shift) && aligned16(addend), DVG_ERR_ALIGN,
+                "dvg_winograd_output_live: alignment");
+    const hipStream_t st = (hipStream_t)stream;
+    const long tiles = (long)N * (H / 4) * (W / 4);
+#define W4OUT(V_, CW_)                                                                                                         \
+    hipLaunchKernelGGL((winograd4_output_kernel<false, V_, true>), dim3(wgrid(tiles * (C / CW_))), dim3(256), 0, st, m, scale, \
+                       shift, y, (float*)nullptr, N, H, W, C / CW_, act, slope, addend, 0)
+    const int cw = wino4_width(tiles, C);
+    if (cw == 4) W4OUT(f32x4, 4);
+    else if (cw == 2) W4OUT(f32x2, 2);
+    else W4OUT(float, 1);
+#undef W4OUT
+    return check_launch("dvg_winograd_output_live");
 }

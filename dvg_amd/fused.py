@@ -70,7 +70,13 @@ def winograd_tile(n, c, h, w, cout) -> int:
 # x half of a decoder block's upsample + concat conv in Winograd F(4x4) form when the skip half is hoisted (eval-mode
 # rollouts); UPCONV_WINOGRAD = False: the transposed-conv (K4) form (module attribute; an environment switch until r06)
 UPCONV_WINOGRAD = True
-_UPCONV_WINO_MAX = 16     # largest output map side that takes this form (32 x 32 measured slower than the K4 transposed form)
+_UPCONV_WINO_MAX = 16     # largest output map side that takes this form (32 x 32 measured slower than the K4 transposed form;
+#                           with the live positions below +118.8 frames/s in flight, inside the noise band of the gain rule:
+#                           docs/DESIGN_NOTES_upconv_live.md section 6)
+# ... on the 25 transform positions that are not identically zero for an upsampled input (ops.LIVE_POSITIONS: row 2 of B^T
+# cancels on a repeated row), on the eval-mode no-grad paths: 25/36 of the GEMM and of the V / M traffic of these layers, the
+# same bits (docs/DESIGN_NOTES_upconv_live.md).  UPCONV_WINO_LIVE = False: all 36 positions.
+UPCONV_WINO_LIVE = True
 
 
 def folded_affine(conv: nn.Module, bn: nn.BatchNorm2d):
@@ -545,8 +551,9 @@ def conv3_bn_act(conv, bn, x, skip=None, *, upsample=False, pool=False, act=ACT_
         sc, sh = folded_affine(conv, bn)
         n, c1, h, w = x.shape
         cout = conv.weight.shape[0]
-        return ops.conv3x3_winograd(x, weights.winograd(conv.weight, 4, 0, c1), sc, sh, act=act, slope=slope, upsample=True,
-                                    addend=hs[1], to_v=_hand_over(next_conv, None, n, cout, h, w))
+        u = weights.winograd_live(conv.weight, 0, c1) if x.live else weights.winograd(conv.weight, 4, 0, c1)
+        return ops.conv3x3_winograd(x, u, sc, sh, act=act, slope=slope, upsample=True, addend=hs[1],
+                                    to_v=_hand_over(next_conv, None, n, cout, h, w), live=x.live)
     if isinstance(x, ops.WinoV):
         if bn.training or skip is not None or upsample:
             raise RuntimeError("conv3_bn_act: a WinoV input needs an eval-mode plain 3x3 layer")
@@ -555,8 +562,9 @@ def conv3_bn_act(conv, bn, x, skip=None, *, upsample=False, pool=False, act=ACT_
         cout = conv.weight.shape[0]
         if winograd_tile(n, c, h, w, cout) != 4:
             raise RuntimeError("conv3_bn_act: WinoV handed to a layer that is not F(4x4,3x3)")
-        return ops.conv3x3_winograd(x, weights.winograd(conv.weight, 4), sc, sh, act=act, slope=slope, pool=pool,
-                                    to_v=_hand_over(next_conv, next_up, n, cout, h, w, pool), y_from=y_from)
+        to_v = _hand_over(next_conv, next_up, n, cout, h, w, pool)
+        return ops.conv3x3_winograd(x, weights.winograd(conv.weight, 4), sc, sh, act=act, slope=slope, pool=pool, to_v=to_v,
+                                    y_from=y_from, up_live=UPCONV_WINO_LIVE and to_v == "up")
     if _needs_grad(x, skip, conv.weight, bn.weight):
         from .autograd import conv_block_autograd
         return conv_block_autograd("conv3", conv, bn, x, skip, upsample=upsample, pool=pool, act=act, slope=slope)
@@ -577,8 +585,10 @@ def conv3_bn_act(conv, bn, x, skip=None, *, upsample=False, pool=False, act=ACT_
                     # 8x8 139.8 -> 125.8 us, 16x16 145.2 -> 134.4 us, 32x32 (K = 128: bandwidth-bound GEMM) 174.7 -> 189.5 us
                     if 2 * hx_ <= _UPCONV_WINO_MAX and winograd_tile(n_, c1_, 2 * hx_, 2 * wx_, cout_) == 4:
                         to_v = not torch.is_grad_enabled() and _hand_over(next_conv, None, n_, cout_, 2 * hx_, 2 * wx_)
-                        return ops.conv3x3_winograd(x, weights.winograd(conv.weight, 4, 0, c1_), sc, sh, act=act, slope=slope,
-                                                    upsample=True, addend=hs[1], to_v=to_v)
+                        live = UPCONV_WINO_LIVE and not torch.is_grad_enabled()
+                        u = weights.winograd_live(conv.weight, 0, c1_) if live else weights.winograd(conv.weight, 4, 0, c1_)
+                        return ops.conv3x3_winograd(x, u, sc, sh, act=act, slope=slope, upsample=True, addend=hs[1], to_v=to_v,
+                                                    live=live)
                 if upsample and UPCONV_AS_CONVT:
                     if _last_proj_applies(next_last, conv, x):
                         w_last = next_last.weight
@@ -596,7 +606,7 @@ def conv3_bn_act(conv, bn, x, skip=None, *, upsample=False, pool=False, act=ACT_
             if m:
                 to_v = m == 4 and not torch.is_grad_enabled() and _hand_over(next_conv, next_up, n, cout, h, w, pool)
                 return ops.conv3x3_winograd(x, weights.winograd(conv.weight, m), sc, sh, act=act, slope=slope, pool=pool,
-                                            to_v=to_v, y_from=y_from)
+                                            to_v=to_v, y_from=y_from, up_live=UPCONV_WINO_LIVE and to_v == "up")
             if conv3_wx_applies(n, c, h, w, cout, conv, bn):
                 return _from(ops.conv3x3_wx(x, weights.wx(conv.weight), sc, sh, act=act, slope=slope, pool=pool), y_from)
         return _from(ops.conv3x3(x, skip, weights.packed(conv.weight), sc, sh, upsample=upsample, act=act, slope=slope,
@@ -711,7 +721,7 @@ def stem_bn_act(conv, bn, vec, *, act=ACT_LRELU, slope=0.2, next_up=None):
         sc, sh = folded_affine(conv, bn)
         wt = weights.gemm_operand(conv.weight, "stem_t")
         if wt is not None and (kh, kw) == (4, 4) and cout % 16 == 0 and _chain_up_to(next_up, n, cout, 4, 4, stem=True):
-            return ops.stem_up_winograd_input(vec, wt, dim, sc, sh, cout, act=act, slope=slope)
+            return ops.stem_up_winograd_input(vec, wt, dim, sc, sh, cout, act=act, slope=slope, live=UPCONV_WINO_LIVE)
     out = ops.nhwc_empty(n, cout, kh, kw, vec.device)
     out2d = out.permute(0, 2, 3, 1).reshape(n, kh * kw * cout)
     if not bn.training:

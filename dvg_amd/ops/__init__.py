@@ -19,7 +19,7 @@ from .conv import (  # noqa: F401
     PROJ_MAX_T, convT4x4s2_proj,
 )
 from .winograd import (  # noqa: F401
-    winograd_weight, winograd_ok, WinoV, winograd_chain_ok, winograd_up_chain_ok, winograd_pool_chain_ok,
+    winograd_weight, winograd_ok, WinoV, LIVE_POSITIONS, winograd_chain_ok, winograd_up_chain_ok, winograd_pool_chain_ok,
     conv3x3_winograd, stem_up_winograd_input,
 )
 from .edge import (  # noqa: F401

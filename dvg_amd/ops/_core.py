@@ -2,6 +2,8 @@
 raw pointers, the NHWC-in-memory tensor helpers and the activation / mode codes of include/dvg_hip.h."""
 from __future__ import annotations
 
+import collections
+
 import torch
 
 from .._lib import CONSTANTS, check, lib
@@ -22,14 +24,14 @@ class KernelTimer:
     stream the kernels are launched on (torch's current stream)."""
 
     def __init__(self):
-        self.records = []  # (name, flops, bytes, ev0, ev1)
+        self.records = []  # (name, flops, bytes, ev0, ev1, alg_flops, entry point)
 
     def summary(self):
         """Per kernel name: launches, ms, EXECUTED flops, algorithmic bytes, and `alg_flops` = the direct-form FLOPs of the
         layer a launch belongs to (differs from `flops` only for the Winograd GEMMs, which execute 1/2.25 or 1/4 of them)."""
         torch.cuda.synchronize()
         agg = {}
-        for name, fl, by, e0, e1, alg in self.records:
+        for name, fl, by, e0, e1, alg, _ in self.records:
             a = agg.setdefault(name, {"launches": 0, "ms": 0.0, "flops": 0.0, "bytes": 0.0, "alg_flops": 0.0})
             a["launches"] += 1
             a["ms"] += e0.elapsed_time(e1)
@@ -37,6 +39,11 @@ class KernelTimer:
             a["bytes"] += by
             a["alg_flops"] += fl if alg is None else alg
         return agg
+
+    def entry_points(self):
+        """Launches per C entry point (dvg_*): `name` says what a launch is for, this says which kernel family ran - the
+        live-only Winograd forms keep the names of the dense ones."""
+        return collections.Counter(r[6] for r in self.records)
 
 
 _timer = None
@@ -56,7 +63,7 @@ def _run(name, flops, nbytes, fn, *args, alg_flops=None):
     e0.record()
     check(fn(*args), name)
     e1.record()
-    _timer.records.append((name, flops, nbytes, e0, e1, alg_flops))
+    _timer.records.append((name, flops, nbytes, e0, e1, alg_flops, getattr(fn, "__name__", "")))
 
 
 def _p(t):

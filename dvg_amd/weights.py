@@ -66,6 +66,19 @@ def winograd(weight, m, lo=None, hi=None, dgrad=False):
     return derived(weight, ("wino", m, lo, hi, dgrad), (weight,), build)
 
 
+def winograd_live(weight, lo=None, hi=None):
+    """The 25 slabs of winograd(weight, 4, lo, hi) at ops.LIVE_POSITIONS: the U of an F(4x4) layer that reads its input through
+    nearest-x2 upsampling and runs on the live positions alone (ops.conv3x3_winograd(live=True)).  A gather of the packed 36-slab
+    tensor - the position is its outermost axis - once per weight version."""
+    lo, hi, _ = _span(weight, lo, hi, 1)
+
+    def build():
+        u = winograd(weight, 4, lo, hi)
+        return u.index_select(0, torch.tensor(ops.LIVE_POSITIONS, device=u.device))
+
+    return derived(weight, ("wino_live", lo, hi), (weight,), build)
+
+
 def k4_weight(weight, c1: int) -> torch.Tensor:
     """nearest-x2 upsampling followed by a 3x3 conv (pad 1) IS a stride-2 transposed conv with the 4x4 kernel
     K4 = W (*) ones(2x2): of the 9 taps of an output pixel only 4 distinct low-resolution inputs contribute.  Returns K4

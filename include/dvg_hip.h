@@ -158,34 +158,27 @@ int dvg_convT4x4s2_bn_act_proj(const float* x, const float* w_k16, const float* 
  * r06: dvg_winograd_weight / dvg_pack_conv_weight_k16 were rewritten (same layout, same values) after the m = 4 transform wrote
  * zero rows into U whenever ANOTHER PROCESS was busy on the device ("Sharing a device").                */
 int dvg_winograd_weight(const float* w_oihw, float* u_k16, int cout, int cin, int m, void* stream);
-/* upsample = 1 (ABI 6, m = 4): x is stored at (N, H/2, W/2, C) and read through nn.UpsamplingNearest2d(2) (vgg_64.py:93) -
- * the x half of a decoder block's first conv in Winograd form; the upsampled tensor never exists.                       */
+/* upsample = 1 (ABI 6, m = 4): x is stored at (N, H/2, W/2, C) and read through nn.UpsamplingNearest2d(2) (vgg_64.py:93) - the x half of a decoder block's first conv in Winograd form; the upsampled tensor never exists. */
 int dvg_winograd_input(const float* x, float* v, int N, int H, int W, int C, int m, int upsample, void* stream);
 int dvg_gemm_batched_k16(const float* x, const float* w_k16, float* y, int NB, int H, int W, int Cin, int Cout, void* stream);
 int dvg_gemm_batched_plan(int NB, int H, int W, int Cin, int Cout, int* tile_w, int* nt, int* ni);  /* host only (within ABI 9): what that launch takes under the tile policy in force - *tile_w 8 (64-row tile) / 16 (128-row), *nt 64-wide Cout blocks per workgroup, *ni images per pipeline; -1: rejected shape */
 int dvg_winograd_transform_width(long tiles, int C);  /* host only (within ABI 9): channels per thread (4, 2, 1; 0: rejected shape) of the F(4x4) transform kernels */
-/* addend (ABI 6; optional, m = 4, no y_pool): raw partial sums (N,H,W,Cout) NHWC added before scale / shift / activation -
- * the hoisted skip half of a decoder block's first conv, as in dvg_conv3x3_bn_act_v2.                                  */
-int dvg_winograd_output(const float* mm, const float* scale, const float* shift, float* y, float* y_pool, int N, int H,
-                        int W, int C, int act, float slope, int m, const float* addend,
-                        int y_from /* ABI 8; 0 unless y_pool is given: as dvg_winograd_output_pool_input */, void* stream);
+/* addend (ABI 6; optional, m = 4, no y_pool): raw partial sums (N,H,W,Cout) NHWC added before scale / shift / activation - the hoisted skip half of a decoder block's first conv, as in dvg_conv3x3_bn_act_v2. */
+int dvg_winograd_output(const float* mm, const float* scale, const float* shift, float* y, float* y_pool, int N, int H, int W, int C, int act, float slope, int m, const float* addend, int y_from /* ABI 8; 0 unless y_pool is given: as dvg_winograd_output_pool_input */, void* stream);
 /* dvg_winograd_output of layer L and dvg_winograd_input of layer L+1 in one pass (m = 4, H == W in {8, 16, 32}, C % 64 == 0) for
  * two consecutive eval-mode vgg_layers at one resolution whose intermediate activation has no other consumer (the inner
  * layers of a vgg block, vgg_64.py:24-43,70-87): mm (36, T, C) -> v_next (36, T, C); the activation is not written.     */
-int dvg_winograd_output_input(const float* mm, const float* scale, const float* shift, float* v_next, int N, int H, int W,
-                              int C, int act, float slope, const float* addend /* as dvg_winograd_output; may be NULL */, void* stream);
+int dvg_winograd_output_input(const float* mm, const float* scale, const float* shift, float* v_next, int N, int H, int W, int C, int act, float slope, const float* addend /* as dvg_winograd_output; may be NULL */, void* stream);
 /* Decoder stem -> first conv of the first decoder block (vgg_64.py:65-69 then :93,98-99): ConvTranspose2d(dim,C,4,1,0) on the
  * 1x1 latent + BN + LeakyReLU, `up`, and the Winograd input transform of the x half of upc2's concat conv in ONE launch - the
  * 4 x 4 x C map is never written.  vec (M, K), row stride ldv; w_kn as dvg_stem_gemm takes it ([KP][16 C], KP in {96, 128});
  * v_next (36, 4 M, C).  Bit-identical to dvg_stem_gemm followed by dvg_winograd_input(upsample = 1).  C % 16 == 0.  ABI 8.  */
-int dvg_stem_up_winograd_input(const float* vec, int ldv, const float* w_kn, int KP, const float* scale, const float* shift,
-                               float* v_next, int M, int C, int K, int act, float slope, void* stream);
+int dvg_stem_up_winograd_input(const float* vec, int ldv, const float* w_kn, int KP, const float* scale, const float* shift, float* v_next, int M, int C, int K, int act, float slope, void* stream);
 /* Last layer of a decoder block -> first conv of the next block (vgg_64.py:93,98-105: `up` + the x half of the concat conv in
- * Winograd form): mm (36, T, C) of an 8 x 8 layer -> v_next (36, 4 T, C), the input transform of
+ * Winograd form): mm (36, T, C) of an 8 x 8 (or 16 x 16) layer -> v_next (36, 4 T, C), the input transform of
  * UpsamplingNearest2d(2)(act(scale * A^T M A + shift)); neither the activation nor its upsampled form is written.  Bit-identical
- * to dvg_winograd_output followed by dvg_winograd_input(upsample = 1).  H == W == 8, C % 64 == 0.  ABI 8.               */
-int dvg_winograd_output_up_input(const float* mm, const float* scale, const float* shift, float* v_next, int N, int H, int W,
-                                 int C, int act, float slope, void* stream);
+ * to dvg_winograd_output followed by dvg_winograd_input(upsample = 1).  H == W in {8, 16}, C % 64 == 0.  ABI 8.         */
+int dvg_winograd_output_up_input(const float* mm, const float* scale, const float* shift, float* v_next, int N, int H, int W, int C, int act, float slope, void* stream);
 /* Last layer of an encoder stage (vgg_64.py:51-56, `mp` :49): M (36, T, C) -> the stage's skip tensor y = act(scale * A^T M A
  * + shift) (N,H,W,C) NHWC AND V' (36, T / 4, C), the F(4x4,3x3) input transform of maxpool2x2(y) for the first layer of the
  * next stage.  The pooled tensor itself is never written.  H == W in {16, 32}, C % 64 == 0.  Bit-identical to
@@ -193,8 +186,15 @@ int dvg_winograd_output_up_input(const float* mm, const float* scale, const floa
  * y_from (ABI 8): y holds the images [y_from, N) only; the skip tensor of the images before is not stored (y may be NULL when
  * y_from == N).  A rollout keeps the skip tensors of the last conditioning frame alone and discards those of every predicted
  * frame (generate_frames.py:154-157: `h, skip = h` only while i < n_past); v_next always covers all N images.            */
-int dvg_winograd_output_pool_input(const float* m, const float* scale, const float* shift, float* y, float* v_next, int N,
-                                   int H, int W, int C, int act, float slope, int y_from, void* stream);
+int dvg_winograd_output_pool_input(const float* m, const float* scale, const float* shift, float* y, float* v_next, int N, int H, int W, int C, int act, float slope, int y_from, void* stream);
+/* LIVE positions (within ABI 9; docs/DESIGN_NOTES_upconv_live.md): an input read through nearest-x2 upsampling has rows [p q q r r s] per F(4x4) tile, on which row 2 of B^T is exactly 0, likewise along columns: the 11 positions a == 2 or b == 2 of V and M are zero.  The calls below leave them out - V, M (25, T, C) at a' * 5 + b', a' = a - (a > 2); U the 25 matching slabs - and equal their dense forms (the name without _live / _as) bit for bit: producers write the live slices, consumers read +0 for the dead positions. */
+int dvg_winograd_input_up_live(const float* x, float* v, int N, int H, int W, int C, void* stream);  /* dvg_winograd_input(m = 4, upsample = 1) */
+int dvg_stem_up_winograd_input_live(const float* vec, int ldv, const float* w_kn, int KP, const float* scale, const float* shift, float* v_next, int M, int C, int K, int act, float slope, void* stream);
+int dvg_winograd_output_up_input_live(const float* mm, const float* scale, const float* shift, float* v_next, int N, int H, int W, int C, int act, float slope, void* stream);  /* v_next compact */
+int dvg_gemm_batched_k16_as(const float* x, const float* w_k16, float* y, int NB, int NB_as, int H, int W, int Cin, int Cout, void* stream);  /* NB images on the tile (tile_w, nt) a launch of NB_as >= NB images takes (25 as 36: every K sum cut as the dense launch cuts it) */
+int dvg_gemm_batched_plan_as(int NB, int NB_as, int H, int W, int Cin, int Cout, int* tile_w, int* nt, int* ni);  /* host only: its plan; *ni from NB */
+int dvg_winograd_output_input_live(const float* mm, const float* scale, const float* shift, float* v_next, int N, int H, int W, int C, int act, float slope, const float* addend, void* stream);  /* mm compact */
+int dvg_winograd_output_live(const float* mm, const float* scale, const float* shift, float* y, int N, int H, int W, int C, int act, float slope, const float* addend, void* stream);  /* dvg_winograd_output(m = 4, no y_pool), mm compact */
 
 /* First encoder layer: Conv2d(nc,Cout,3,1,1)+BN+LReLU with nc in {1..4} (vgg_64.py:23 `vgg_layer(nc, 64)`).  HBM-bound direct
  * convolution.  x is NCHW (N,nc,H,W) exactly as the caller's frame tensor (utils.py:90-91); w is the ORIGINAL (Cout,nc,3,3) weight;
