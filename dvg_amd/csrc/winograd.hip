@@ -409,7 +409,8 @@ __global__ __launch_bounds__(256) void winograd4_output_kernel(const float* __re
 // same resolution whose intermediate activation has no other consumer (the inner layers of a vgg block, vgg_64.py:24-43,
 // 70-87): y = act(scale * A^T M A + shift) is staged in LDS (one image x CS channels per workgroup: 16 KB) and leaves as
 // V' = B^T y B - the activation never travels to HBM and back (M in, V' out: 4.5 units of traffic instead of 6.5) and one
-// launch of two disappears.  HW = 8 or 16 (map side); thread = one 4x4 tile x one channel.
+// launch of two disappears.  HW = 8 (map side; the only one instantiated, dense and MLIVE: 16 and 32 take winograd4_chain_kernel);
+// thread = one 4x4 tile x one channel.
 template <int HW, bool MLIVE = false>
 __global__ __launch_bounds__(256) void winograd4_out_in_kernel(const float* __restrict__ m, const float* __restrict__ scale,
                                                                const float* __restrict__ shift, float* __restrict__ v, int N,
@@ -474,7 +475,7 @@ __global__ __launch_bounds__(256) void winograd4_out_in_kernel(const float* __re
 // layer that consumes the result, in ONE pass per (image, CS-channel block):
 //   POOL = false: two consecutive layers of a vgg block at the same resolution HW (8, 16 or 32) - as winograd4_out_in_kernel,
 //                 but V channels per thread and CS channels per workgroup, so that a workgroup's global accesses are runs of
-//                 CS * 4 bytes (the <16> instantiation above moves 64-byte runs: 3.2-3.7 TB/s; 256-byte runs: > 5);
+//                 CS * 4 bytes (the kernel above at HW = 16 moved 64-byte runs: 3.2-3.7 TB/s; 256-byte runs: > 5);
 //   POOL = true : the LAST layer of an encoder stage (vgg_64.py:51-56): the full-resolution activation is the skip tensor and
 //                 goes to HBM (y), its 2x2 max-pool is staged in LDS and leaves as the next stage's input transform - the
 //                 pooled tensor is never written or re-read and one launch disappears.
@@ -701,7 +702,15 @@ static int wino4_width(long tiles, int C) {
     return 1;
 }
 
-static int chain_variant() { return 0; }      // (the variants below were A/B'd per shape: numbers in the comments)
+// f(V{}, cw): V the vector type of wino4_width's cw channels per thread - every F(4x4) transform launch picks its instantiation here
+template <typename F>
+static void with_width(long tiles, int C, F f) {
+    switch (wino4_width(tiles, C)) {
+        case 4: f(f32x4{}, 4); break;
+        case 2: f(f32x2{}, 2); break;
+        default: f(float{}, 1);
+    }
+}
 
 static inline unsigned wgrid(long n) {
     long g = (n + 255) / 256;
@@ -725,47 +734,36 @@ extern "C" int dvg_winograd_weight(const float* w_oihw, float* u_k16, int cout, 
     return check_launch("dvg_winograd_weight");
 }
 
-extern "C" int dvg_winograd_input(const float* x, float* v, int N, int H, int W, int C, int m, int upsample, void* stream) {
-    DVG_REQUIRE(x && v, DVG_ERR_NULL, "dvg_winograd_input: NULL pointer");
+// Body of dvg_winograd_input and of its live-only form (`who`: the entry point called, for dvg_last_error()).  LIVE: m = 4 and
+// upsample = 1, v compact.
+template <bool LIVE>
+static int winograd_input(const char* who, const float* x, float* v, int N, int H, int W, int C, int m, int up, void* stream) {
+    DVG_REQUIRE(x && v, DVG_ERR_NULL, "%s: NULL pointer", who);
     DVG_REQUIRE((m == 2 || m == 4) && N > 0 && H > 0 && W > 0 && H % m == 0 && W % m == 0 && C > 0 && C % 4 == 0,
-                DVG_ERR_SHAPE, "dvg_winograd_input: m 2 or 4, H and W multiples of m, C %% 4 == 0 needed");
-    DVG_REQUIRE(upsample == 0 || (upsample == 1 && m == 4 && H % 2 == 0 && W % 2 == 0), DVG_ERR_SHAPE,
-                "dvg_winograd_input: upsample needs m = 4 and even H, W");
-    const int up = upsample;
-    DVG_REQUIRE(aligned16(x) && aligned16(v), DVG_ERR_ALIGN, "dvg_winograd_input: alignment");
+                DVG_ERR_SHAPE, "%s: m 2 or 4, H and W multiples of m, C %% 4 == 0 needed", who);
+    DVG_REQUIRE(up == 0 || (up == 1 && m == 4 && H % 2 == 0 && W % 2 == 0), DVG_ERR_SHAPE,
+                "%s: upsample needs m = 4 and even H, W", who);
+    DVG_REQUIRE(aligned16(x) && aligned16(v), DVG_ERR_ALIGN, "%s: alignment", who);
     const long tiles = (long)N * (H / m) * (W / m);
     const hipStream_t st = (hipStream_t)stream;
-    if (m == 2) {
+    if (m == 2)
         hipLaunchKernelGGL(winograd_input_kernel, dim3(wgrid(tiles * (C / 4))), dim3(256), 0, st, x, v, N, H, W, C / 4);
-    } else {
-        const int cw = wino4_width(tiles, C);
-        if (cw == 4)
-            hipLaunchKernelGGL(winograd4_input_kernel<f32x4>, dim3(wgrid(tiles * (C / 4))), dim3(256), 0, st, x, v, N, H, W, C / 4, tiles, 0L, up);
-        else if (cw == 2)
-            hipLaunchKernelGGL(winograd4_input_kernel<f32x2>, dim3(wgrid(tiles * (C / 2))), dim3(256), 0, st, x, v, N, H, W, C / 2, tiles, 0L, up);
-        else
-            hipLaunchKernelGGL(winograd4_input_kernel<float>, dim3(wgrid(tiles * C)), dim3(256), 0, st, x, v, N, H, W, C, tiles, 0L, up);
-    }
-    return check_launch("dvg_winograd_input");
+    else
+        with_width(tiles, C, [&](auto tag, int cw) {
+            hipLaunchKernelGGL((winograd4_input_kernel<decltype(tag), LIVE>), dim3(wgrid(tiles * (C / cw))), dim3(256), 0, st, x, v,
+                               N, H, W, C / cw, tiles, 0L, up);
+        });
+    return check_launch(who);
+}
+
+extern "C" int dvg_winograd_input(const float* x, float* v, int N, int H, int W, int C, int m, int upsample, void* stream) {
+    return winograd_input<false>("dvg_winograd_input", x, v, N, H, W, C, m, upsample, stream);
 }
 
 // dvg_winograd_input(m = 4, upsample = 1) without the 11 positions that are zero for every upsampled input: v (25, T, C), the
 // live positions in the compact order a' * 5 + b' (wino_pos).  Equal to the matching slices of the dense form, bit for bit.
 extern "C" int dvg_winograd_input_up_live(const float* x, float* v, int N, int H, int W, int C, void* stream) {
-    DVG_REQUIRE(x && v, DVG_ERR_NULL, "dvg_winograd_input_up_live: NULL pointer");
-    DVG_REQUIRE(N > 0 && H > 0 && W > 0 && H % 4 == 0 && W % 4 == 0 && C > 0 && C % 4 == 0, DVG_ERR_SHAPE,
-                "dvg_winograd_input_up_live: H and W multiples of 4, C %% 4 == 0 needed");
-    DVG_REQUIRE(aligned16(x) && aligned16(v), DVG_ERR_ALIGN, "dvg_winograd_input_up_live: alignment");
-    const long tiles = (long)N * (H / 4) * (W / 4);
-    const hipStream_t st = (hipStream_t)stream;
-    const int cw = wino4_width(tiles, C);
-    if (cw == 4)
-        hipLaunchKernelGGL((winograd4_input_kernel<f32x4, true>), dim3(wgrid(tiles * (C / 4))), dim3(256), 0, st, x, v, N, H, W, C / 4, tiles, 0L, 1);
-    else if (cw == 2)
-        hipLaunchKernelGGL((winograd4_input_kernel<f32x2, true>), dim3(wgrid(tiles * (C / 2))), dim3(256), 0, st, x, v, N, H, W, C / 2, tiles, 0L, 1);
-    else
-        hipLaunchKernelGGL((winograd4_input_kernel<float, true>), dim3(wgrid(tiles * C)), dim3(256), 0, st, x, v, N, H, W, C, tiles, 0L, 1);
-    return check_launch("dvg_winograd_input_up_live");
+    return winograd_input<true>("dvg_winograd_input_up_live", x, v, N, H, W, C, 4, 1, stream);
 }
 
 // Channels per thread (4, 2 or 1) of the F(4x4) transform kernels dvg_winograd_input, dvg_winograd_output and
@@ -790,61 +788,58 @@ extern "C" int dvg_winograd_wgrad_operands(const float* x, const float* dy, floa
     DVG_REQUIRE(aligned16(x) && aligned16(dy) && aligned16(v) && aligned16(dm), DVG_ERR_ALIGN,
                 "dvg_winograd_wgrad_operands: alignment");
     const hipStream_t st = (hipStream_t)stream;
-#define WOPS(KERNEL_, SRC_, DST_, C_, ...)                                                                                        \
-    do {                                                                                                                       \
-        const int cw_ = wino4_width(tiles, (C_));                                                                              \
-        if (cw_ == 4)                                                                                                          \
-            hipLaunchKernelGGL(KERNEL_<f32x4>, dim3(wgrid(tiles * ((C_) / 4))), dim3(256), 0, st, SRC_, DST_, N, H, W, (C_) / 4, t_total, t_off __VA_ARGS__); \
-        else if (cw_ == 2)                                                                                                     \
-            hipLaunchKernelGGL(KERNEL_<f32x2>, dim3(wgrid(tiles * ((C_) / 2))), dim3(256), 0, st, SRC_, DST_, N, H, W, (C_) / 2, t_total, t_off __VA_ARGS__); \
-        else                                                                                                                   \
-            hipLaunchKernelGGL(KERNEL_<float>, dim3(wgrid(tiles * (C_))), dim3(256), 0, st, SRC_, DST_, N, H, W, (C_), t_total, t_off __VA_ARGS__);           \
-    } while (0)
     if (x && v) {
-        WOPS(winograd4_input_kernel, x, v, Cin, , 0);
+        with_width(tiles, Cin, [&](auto tag, int cw) {
+            hipLaunchKernelGGL(winograd4_input_kernel<decltype(tag)>, dim3(wgrid(tiles * (Cin / cw))), dim3(256), 0, st, x, v, N, H,
+                               W, Cin / cw, t_total, t_off, 0);
+        });
         if (int e = check_launch("dvg_winograd_wgrad_operands (input)")) return e;
     }
     if (dy && dm) {
-        WOPS(winograd4_dy_kernel, dy, dm, Cout, );
+        with_width(tiles, Cout, [&](auto tag, int cw) {
+            hipLaunchKernelGGL(winograd4_dy_kernel<decltype(tag)>, dim3(wgrid(tiles * (Cout / cw))), dim3(256), 0, st, dy, dm, N, H,
+                               W, Cout / cw, t_total, t_off);
+        });
         if (int e = check_launch("dvg_winograd_wgrad_operands (dy)")) return e;
     }
-#undef WOPS
     return DVG_OK;
 }
 
 // M (36, T, C) of layer L -> V (36, T, C) of layer L + 1 (winograd4_out_in_kernel / winograd4_chain_kernel): H == W in
 // {8, 16, 32}, F(4x4,3x3), C % 64 == 0.  The activation y = act(scale * A^T M A + shift) itself is not written.
+// MLIVE: mm is the compact M (25, T, C).  `who`: the entry point called.
+template <bool MLIVE>
+static int output_input(const char* who, const float* mm, const float* scale, const float* shift, float* v_next, int N, int H,
+                        int W, int C, int act, float slope, const float* addend, void* stream) {
+    DVG_REQUIRE(mm && v_next, DVG_ERR_NULL, "%s: NULL pointer", who);
+    DVG_REQUIRE(aligned16(addend), DVG_ERR_ALIGN, "%s: addend alignment", who);
+    DVG_REQUIRE(N > 0 && H == W && (H == 8 || H == 16 || H == 32) && C > 0 && C % 64 == 0, DVG_ERR_SHAPE,
+                "%s: 8x8, 16x16 or 32x32 maps, C %% 64 == 0 needed (got %dx%d, C=%d)", who, H, W, C);
+    DVG_REQUIRE(act >= 0 && act <= 3, DVG_ERR_SHAPE, "%s: bad act", who);
+    DVG_REQUIRE(aligned16(mm) && aligned16(v_next), DVG_ERR_ALIGN, "%s: alignment", who);
+    const hipStream_t st = (hipStream_t)stream;
+    // The kernel per map side, chosen by measurement in r03 (tools/bench_wino_parts.py, us at B = 64 / B = 576) against the
+    // forms that are gone since:
+    //    8x8  512ch: winograd4_out_in_kernel<8> 7.6 / 73 = chain<8,64,float>: the older kernel stays
+    //   16x16 256ch: chain<16,32,float> 13.8 / 160, chain<16,64,f32x2> 15.1 / 140 - the first below 1024 workgroups of the
+    //                second, the second from there on (winograd4_out_in_kernel<16>, 64-byte runs: 20.3 / 212)
+    //   32x32 128ch: chain<32,32,f32x4> (128 KB of LDS) 27.3 / 284 (chain<32,16,f32x2> 36.5 / 388; separate output and
+    //                input passes 42.2 / 389)
+    if (H == 8) {
+        hipLaunchKernelGGL((winograd4_out_in_kernel<8, MLIVE>), dim3((unsigned)((long)N * (C / 64))), dim3(256), 0, st, mm, scale,
+                           shift, v_next, N, C, act, slope, addend);
+        return check_launch(who);
+    }
+    if (H == 32)
+        return launch_chain<32, 32, f32x4, false, 512, false, MLIVE>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st, addend);
+    if ((long)N * (C / 64) < 1024)
+        return launch_chain<16, 32, float, false, 512, false, MLIVE>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st, addend);
+    return launch_chain<16, 64, f32x2, false, 512, false, MLIVE>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st, addend);
+}
+
 extern "C" int dvg_winograd_output_input(const float* mm, const float* scale, const float* shift, float* v_next, int N, int H,
                                          int W, int C, int act, float slope, const float* addend, void* stream) {
-    DVG_REQUIRE(mm && v_next, DVG_ERR_NULL, "dvg_winograd_output_input: NULL pointer");
-    DVG_REQUIRE(aligned16(addend), DVG_ERR_ALIGN, "dvg_winograd_output_input: addend alignment");
-    DVG_REQUIRE(N > 0 && H == W && (H == 8 || H == 16 || H == 32) && C > 0 && C % 64 == 0, DVG_ERR_SHAPE,
-                "dvg_winograd_output_input: 8x8, 16x16 or 32x32 maps, C %% 64 == 0 needed (got %dx%d, C=%d)", H, W, C);
-    DVG_REQUIRE(act >= 0 && act <= 3, DVG_ERR_SHAPE, "dvg_winograd_output_input: bad act");
-    DVG_REQUIRE(aligned16(mm) && aligned16(v_next), DVG_ERR_ALIGN, "dvg_winograd_output_input: alignment");
-    const hipStream_t st = (hipStream_t)stream;
-    const int var = chain_variant();
-    // Measured per shape (tools/bench_wino_parts.py, us at B = 64 / B = 576; the variants were A/B'd per shape in r03):
-    //   16x16 256ch: r02 kernel (64-byte runs) 20.3 / 212; <16,64,f32x2> 15.1 / 140; <16,32,float> 13.8 / 160
-    //   32x32 128ch: separate output + input passes 42.2 / 389; <32,16,f32x2> 36.5 / 388; <32,32,f32x4> (128 KB of LDS) 27.3 / 284
-    //    8x8  512ch: r02 kernel 7.6 / 73 = <8,64,float> - kept
-    if (H == 8) {
-        hipLaunchKernelGGL(winograd4_out_in_kernel<8>, dim3((unsigned)((long)N * (C / 64))), dim3(256), 0, st, mm, scale, shift,
-                           v_next, N, C, act, slope, addend);
-    } else if (H == 16) {
-        if (var == 9) {
-            hipLaunchKernelGGL(winograd4_out_in_kernel<16>, dim3((unsigned)((long)N * (C / 16))), dim3(256), 0, st, mm, scale,
-                               shift, v_next, N, C, act, slope, addend);
-        } else if (var == 2 || (var == 0 && (long)N * (C / 64) < 1024)) {
-            return launch_chain<16, 32, float, false, 512>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st, addend);
-        } else {
-            return launch_chain<16, 64, f32x2, false, 512>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st, addend);
-        }
-    } else {
-        if (var == 1) return launch_chain<32, 16, f32x2, false, 512>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st, addend);
-        return launch_chain<32, 32, f32x4, false, 512>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st, addend);
-    }
-    return check_launch("dvg_winograd_output_input");
+    return output_input<false>("dvg_winograd_output_input", mm, scale, shift, v_next, N, H, W, C, act, slope, addend, stream);
 }
 
 // dvg_winograd_output_input for a layer that read its input through the upsampling: mm is the compact M (25, T, C) (wino_pos),
@@ -852,23 +847,7 @@ extern "C" int dvg_winograd_output_input(const float* mm, const float* scale, co
 // the choice between them as in dvg_winograd_output_input: the same bits as that call on the zero-filled dense M.
 extern "C" int dvg_winograd_output_input_live(const float* mm, const float* scale, const float* shift, float* v_next, int N,
                                               int H, int W, int C, int act, float slope, const float* addend, void* stream) {
-    DVG_REQUIRE(mm && v_next, DVG_ERR_NULL, "dvg_winograd_output_input_live: NULL pointer");
-    DVG_REQUIRE(aligned16(addend), DVG_ERR_ALIGN, "dvg_winograd_output_input_live: addend alignment");
-    DVG_REQUIRE(N > 0 && H == W && (H == 8 || H == 16 || H == 32) && C > 0 && C % 64 == 0, DVG_ERR_SHAPE,
-                "dvg_winograd_output_input_live: 8x8, 16x16 or 32x32 maps, C %% 64 == 0 needed (got %dx%d, C=%d)", H, W, C);
-    DVG_REQUIRE(act >= 0 && act <= 3, DVG_ERR_SHAPE, "dvg_winograd_output_input_live: bad act");
-    DVG_REQUIRE(aligned16(mm) && aligned16(v_next), DVG_ERR_ALIGN, "dvg_winograd_output_input_live: alignment");
-    const hipStream_t st = (hipStream_t)stream;
-    if (H == 8) {
-        hipLaunchKernelGGL((winograd4_out_in_kernel<8, true>), dim3((unsigned)((long)N * (C / 64))), dim3(256), 0, st, mm, scale,
-                           shift, v_next, N, C, act, slope, addend);
-        return check_launch("dvg_winograd_output_input_live");
-    }
-    if (H == 32)
-        return launch_chain<32, 32, f32x4, false, 512, false, true>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st, addend);
-    if ((long)N * (C / 64) < 1024)
-        return launch_chain<16, 32, float, false, 512, false, true>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st, addend);
-    return launch_chain<16, 64, f32x2, false, 512, false, true>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st, addend);
+    return output_input<true>("dvg_winograd_output_input_live", mm, scale, shift, v_next, N, H, W, C, act, slope, addend, stream);
 }
 
 // stem_up_input_kernel: vec (M, K) row stride ldv; w_kn the stem weight as [KP][16 C] (dvg_stem_gemm's operand: column
@@ -908,30 +887,30 @@ extern "C" int dvg_stem_up_winograd_input_live(const float* vec, int ldv, const 
 // Last layer of a decoder block -> first conv of the next block (vgg_64.py:98-105): M (36, T, C) of an H x H layer ->
 // V' (36, 4 T, C), the F(4x4,3x3) input transform of UpsamplingNearest2d(2)(act(scale * A^T M A + shift)) (winograd4_chain_kernel
 // <UP>); neither the activation nor its upsampled form is written.  H == W in {8, 16} (the next block works at twice that).
+// VLIVE: v_next is the compact (25, 4 T, C).  `who`: the entry point called.
+template <bool VLIVE>
+static int output_up_input(const char* who, const float* mm, const float* scale, const float* shift, float* v_next, int N, int H,
+                           int W, int C, int act, float slope, void* stream) {
+    DVG_REQUIRE(mm && v_next, DVG_ERR_NULL, "%s: NULL pointer", who);
+    DVG_REQUIRE(N > 0 && H == W && (H == 8 || H == 16) && C > 0 && C % 64 == 0, DVG_ERR_SHAPE,
+                "%s: 8x8 or 16x16 maps, C %% 64 == 0 needed (got %dx%d, C=%d)", who, H, W, C);
+    DVG_REQUIRE(act >= 0 && act <= 3, DVG_ERR_SHAPE, "%s: bad act", who);
+    DVG_REQUIRE(aligned16(mm) && aligned16(v_next), DVG_ERR_ALIGN, "%s: alignment", who);
+    const hipStream_t st = (hipStream_t)stream;
+    if (H == 16)
+        return launch_chain<16, 32, float, false, 512, true, false, VLIVE>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st);
+    return launch_chain<8, 32, float, false, 512, true, false, VLIVE>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st);
+}
+
 extern "C" int dvg_winograd_output_up_input(const float* mm, const float* scale, const float* shift, float* v_next, int N, int H,
                                             int W, int C, int act, float slope, void* stream) {
-    DVG_REQUIRE(mm && v_next, DVG_ERR_NULL, "dvg_winograd_output_up_input: NULL pointer");
-    DVG_REQUIRE(N > 0 && H == W && (H == 8 || H == 16) && C > 0 && C % 64 == 0, DVG_ERR_SHAPE,
-                "dvg_winograd_output_up_input: 8x8 or 16x16 maps, C %% 64 == 0 needed (got %dx%d, C=%d)", H, W, C);
-    DVG_REQUIRE(act >= 0 && act <= 3, DVG_ERR_SHAPE, "dvg_winograd_output_up_input: bad act");
-    DVG_REQUIRE(aligned16(mm) && aligned16(v_next), DVG_ERR_ALIGN, "dvg_winograd_output_up_input: alignment");
-    const hipStream_t st = (hipStream_t)stream;
-    if (H == 16) return launch_chain<16, 32, float, false, 512, true>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st);
-    return launch_chain<8, 32, float, false, 512, true>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st);
+    return output_up_input<false>("dvg_winograd_output_up_input", mm, scale, shift, v_next, N, H, W, C, act, slope, stream);
 }
 
 // ... with v_next the compact (25, 4 T, C): the live positions of dvg_winograd_output_up_input's result (wino_pos), same bits.
 extern "C" int dvg_winograd_output_up_input_live(const float* mm, const float* scale, const float* shift, float* v_next, int N,
                                                  int H, int W, int C, int act, float slope, void* stream) {
-    DVG_REQUIRE(mm && v_next, DVG_ERR_NULL, "dvg_winograd_output_up_input_live: NULL pointer");
-    DVG_REQUIRE(N > 0 && H == W && (H == 8 || H == 16) && C > 0 && C % 64 == 0, DVG_ERR_SHAPE,
-                "dvg_winograd_output_up_input_live: 8x8 or 16x16 maps, C %% 64 == 0 needed (got %dx%d, C=%d)", H, W, C);
-    DVG_REQUIRE(act >= 0 && act <= 3, DVG_ERR_SHAPE, "dvg_winograd_output_up_input_live: bad act");
-    DVG_REQUIRE(aligned16(mm) && aligned16(v_next), DVG_ERR_ALIGN, "dvg_winograd_output_up_input_live: alignment");
-    const hipStream_t st = (hipStream_t)stream;
-    if (H == 16)
-        return launch_chain<16, 32, float, false, 512, true, false, true>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st);
-    return launch_chain<8, 32, float, false, 512, true, false, true>(mm, scale, shift, nullptr, v_next, N, C, act, slope, st);
+    return output_up_input<true>("dvg_winograd_output_up_input_live", mm, scale, shift, v_next, N, H, W, C, act, slope, stream);
 }
 
 // Last layer of an encoder stage (vgg_64.py:51-56): M (36, T, C) -> y = act(scale * A^T M A + shift) (N,H,W,C) NHWC, the
@@ -948,12 +927,28 @@ extern "C" int dvg_winograd_output_pool_input(const float* mm, const float* scal
     DVG_REQUIRE(act >= 0 && act <= 3, DVG_ERR_SHAPE, "dvg_winograd_output_pool_input: bad act");
     DVG_REQUIRE(aligned16(mm) && aligned16(y) && aligned16(v_next), DVG_ERR_ALIGN, "dvg_winograd_output_pool_input: alignment");
     const hipStream_t st = (hipStream_t)stream;
-    const int var = chain_variant();
     // us at B = 64 / 576 against output(+pool) followed by input: 16 -> 8 (256 ch) 12.2 / 120 vs 18.3 / 124; 32 -> 16 (128 ch)
-    // 21.7 / 244 vs 30.0 / 247 (the 16-channel variant: 33.5 / 324)
-    (void)var;
+    // 21.7 / 244 vs 30.0 / 247 (a 16-channel form, gone since: 33.5 / 324)
     if (H == 16) return launch_chain<16, 64, f32x2, true, 512>(mm, scale, shift, y, v_next, N, C, act, slope, st, nullptr, y_from);
     return launch_chain<32, 32, f32x2, true, 1024>(mm, scale, shift, y, v_next, N, C, act, slope, st, nullptr, y_from);
+}
+
+// The F(4x4) launch of dvg_winograd_output and of its live-only form (MLIVE: m compact, no pooled output), checks done
+template <bool MLIVE>
+static void winograd4_output(const float* m, const float* scale, const float* shift, float* y, float* y_pool, int N, int H, int W,
+                             int C, int act, float slope, const float* addend, int y_from, hipStream_t st) {
+    const long tiles = (long)N * (H / 4) * (W / 4);
+    with_width(tiles, C, [&](auto tag, int cw) {
+        using V = decltype(tag);
+        auto launch = [&](auto kern) {
+            hipLaunchKernelGGL(kern, dim3(wgrid(tiles * (C / cw))), dim3(256), 0, st, m, scale, shift, y, y_pool, N, H, W, C / cw,
+                               act, slope, addend, y_from);
+        };
+        if constexpr (!MLIVE) {
+            if (y_pool) return launch(winograd4_output_kernel<true, V>);
+        }
+        launch(winograd4_output_kernel<false, V, MLIVE>);
+    });
 }
 
 // y_from (ABI 8; 0 unless y_pool is given): y holds the images [y_from, N) only, the images before store only y_pool
@@ -977,17 +972,8 @@ extern "C" int dvg_winograd_output(const float* m, const float* scale, const flo
         hipLaunchKernelGGL(winograd_output_kernel<true>, dim3(g), dim3(256), 0, st, m, scale, shift, y, y_pool, N, H, W, C / 4, act, slope, y_from);
     else if (mt == 2)
         hipLaunchKernelGGL(winograd_output_kernel<false>, dim3(g), dim3(256), 0, st, m, scale, shift, y, y_pool, N, H, W, C / 4, act, slope, 0);
-    else {
-        const long tiles = (long)N * (H / 4) * (W / 4);
-#define W4OUT(POOL_, V_, CW_)                                                                                             \
-    hipLaunchKernelGGL((winograd4_output_kernel<POOL_, V_>), dim3(wgrid(tiles * (C / CW_))), dim3(256), 0, st, m, scale, shift, \
-                       y, y_pool, N, H, W, C / CW_, act, slope, addend, y_from)
-        const int cw = wino4_width(tiles, C);
-        if (cw == 4) { if (y_pool) W4OUT(true, f32x4, 4); else W4OUT(false, f32x4, 4); }
-        else if (cw == 2) { if (y_pool) W4OUT(true, f32x2, 2); else W4OUT(false, f32x2, 2); }
-        else { if (y_pool) W4OUT(true, float, 1); else W4OUT(false, float, 1); }
-#undef W4OUT
-    }
+    else
+        winograd4_output<false>(m, scale, shift, y, y_pool, N, H, W, C, act, slope, addend, y_from, st);
     return check_launch("dvg_winograd_output");
 }
 
@@ -1002,15 +988,6 @@ extern "C" int dvg_winograd_output_live(const float* m, const float* scale, cons
     DVG_REQUIRE(act >= 0 && act <= 3, DVG_ERR_SHAPE, "dvg_winograd_output_live: bad act");
     DVG_REQUIRE(aligned16(m) && aligned16(y) && aligned16(scale) && aligned16(shift) && aligned16(addend), DVG_ERR_ALIGN,
                 "dvg_winograd_output_live: alignment");
-    const hipStream_t st = (hipStream_t)stream;
-    const long tiles = (long)N * (H / 4) * (W / 4);
-#define W4OUT(V_, CW_)                                                                                                         \
-    hipLaunchKernelGGL((winograd4_output_kernel<false, V_, true>), dim3(wgrid(tiles * (C / CW_))), dim3(256), 0, st, m, scale, \
-                       shift, y, (float*)nullptr, N, H, W, C / CW_, act, slope, addend, 0)
-    const int cw = wino4_width(tiles, C);
-    if (cw == 4) W4OUT(f32x4, 4);
-    else if (cw == 2) W4OUT(f32x2, 2);
-    else W4OUT(float, 1);
-#undef W4OUT
+    winograd4_output<true>(m, scale, shift, y, nullptr, N, H, W, C, act, slope, addend, 0, (hipStream_t)stream);
     return check_launch("dvg_winograd_output_live");
 }

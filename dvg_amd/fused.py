@@ -493,10 +493,13 @@ def _chain_up_to(next_up, n, c, h, w, stem=False) -> bool:
             and ((h, w) == (4, 4) if stem else ops.winograd_up_chain_ok(n, c, h, w)) and _hoist_ready(conv_n, skip_n))
 
 
-def _hand_over(next_conv, next_up, n, c, h, w, pool=False):
+def _hand_over(x, next_conv, next_up, n, c, h, w, pool=False):
     """What an F(4x4) layer with an (n,c,h,w) output hands to its only consumer instead of the activation: True - the input
     transform of next_conv (through this layer's 2x2 max-pool with `pool`), "up" - that of next_up's conv through the
-    upsampling, False - nothing, it writes the activation."""
+    upsampling, False - nothing, it writes the activation.  x, the layer's input: a tensor hands over under no_grad only; an
+    ops.WinoV is not asked again (it exists only where its producer found grad mode off)."""
+    if not isinstance(x, ops.WinoV) and torch.is_grad_enabled():
+        return False
     if _chain_to(next_conv, n, c, h, w, pool):
         return True
     return "up" if not pool and _chain_up_to(next_up, n, c, h, w) else False
@@ -528,6 +531,24 @@ def _last_proj_applies(next_last, conv, x) -> bool:
             and x.shape[3] % 8 == 0)
 
 
+def _upconv_x_winograd(conv, affine, x, s, live, act, slope, next_conv):
+    """x half of an eval-mode upsample + concat conv in Winograd F(4x4) form (`live`: on the ops.LIVE_POSITIONS alone): x is read
+    through the nearest-x2 upsampling, or is that input transform already (an upsampled ops.WinoV); the hoisted skip half s enters
+    the output transform as `addend`.  A quarter of the direct form's multiplies (the K4 transposed-conv form: 4/9)."""
+    n, c1, h, w = x.shape if isinstance(x, ops.WinoV) else (x.shape[0], x.shape[1], 2 * x.shape[2], 2 * x.shape[3])
+    u = weights.winograd_live(conv.weight, 0, c1) if live else weights.winograd(conv.weight, 4, 0, c1)
+    to_v = _hand_over(x, next_conv, None, n, conv.weight.shape[0], h, w)
+    return ops.conv3x3_winograd(x, u, *affine, act=act, slope=slope, upsample=True, addend=s, to_v=to_v, live=live)
+
+
+def _winograd_layer(conv, affine, x, m, act, slope, pool, y_from, next_conv, next_up):
+    """A plain eval-mode 3x3 layer in Winograd F(m x m) form; x a tensor or a same-resolution ops.WinoV (m = 4)."""
+    n, _, h, w = x.shape
+    to_v = m == 4 and _hand_over(x, next_conv, next_up, n, conv.weight.shape[0], h, w, pool)
+    return ops.conv3x3_winograd(x, weights.winograd(conv.weight, m), *affine, act=act, slope=slope, pool=pool, to_v=to_v,
+                                y_from=y_from, up_live=UPCONV_WINO_LIVE and to_v == "up")
+
+
 def conv3_bn_act(conv, bn, x, skip=None, *, upsample=False, pool=False, act=ACT_LRELU, slope=0.2, next_conv=None, y_from=0,
                  next_up=None, next_last=None):
     """vgg_layer (vgg_64.py:5-15) with optional fused cat/upsample on the input and
@@ -548,23 +569,13 @@ def conv3_bn_act(conv, bn, x, skip=None, *, upsample=False, pool=False, act=ACT_
             _hoisted_skip(conv, x, skip, functools.partial(_skip_half, "conv3", skip, conv=conv), force=True)
         if hs is None:
             raise RuntimeError("conv3_bn_act: an upsampled WinoV needs the eval-mode concat conv with its skip half hoisted")
-        sc, sh = folded_affine(conv, bn)
-        n, c1, h, w = x.shape
-        cout = conv.weight.shape[0]
-        u = weights.winograd_live(conv.weight, 0, c1) if x.live else weights.winograd(conv.weight, 4, 0, c1)
-        return ops.conv3x3_winograd(x, u, sc, sh, act=act, slope=slope, upsample=True, addend=hs[1],
-                                    to_v=_hand_over(next_conv, None, n, cout, h, w), live=x.live)
+        return _upconv_x_winograd(conv, folded_affine(conv, bn), x, hs[1], x.live, act, slope, next_conv)
     if isinstance(x, ops.WinoV):
         if bn.training or skip is not None or upsample:
             raise RuntimeError("conv3_bn_act: a WinoV input needs an eval-mode plain 3x3 layer")
-        sc, sh = folded_affine(conv, bn)
-        n, c, h, w = x.shape
-        cout = conv.weight.shape[0]
-        if winograd_tile(n, c, h, w, cout) != 4:
+        if winograd_tile(*x.shape, conv.weight.shape[0]) != 4:
             raise RuntimeError("conv3_bn_act: WinoV handed to a layer that is not F(4x4,3x3)")
-        to_v = _hand_over(next_conv, next_up, n, cout, h, w, pool)
-        return ops.conv3x3_winograd(x, weights.winograd(conv.weight, 4), sc, sh, act=act, slope=slope, pool=pool, to_v=to_v,
-                                    y_from=y_from, up_live=UPCONV_WINO_LIVE and to_v == "up")
+        return _winograd_layer(conv, folded_affine(conv, bn), x, 4, act, slope, pool, y_from, next_conv, next_up)
     if _needs_grad(x, skip, conv.weight, bn.weight):
         from .autograd import conv_block_autograd
         return conv_block_autograd("conv3", conv, bn, x, skip, upsample=upsample, pool=pool, act=act, slope=slope)
@@ -575,39 +586,26 @@ def conv3_bn_act(conv, bn, x, skip=None, *, upsample=False, pool=False, act=ACT_
             hs = _hoisted_skip(conv, x, skip, functools.partial(_skip_half, "conv3", skip, conv=conv))
             if hs is not None:
                 if upsample and UPCONV_WINOGRAD:
-                    # x half of upsample + concat conv in Winograd form: the input transform reads x through the nearest-x2
-                    # upsampling, the hoisted skip half enters the output transform as `addend` - a quarter of the direct
-                    # form's multiplies (the K4 transposed-conv form below: 4/9), and the next layer of the block can take
-                    # its input transform straight from this layer's output transform
-                    n_, c1_, hx_, wx_ = x.shape
-                    cout_ = conv.weight.shape[0]
-                    # measured per layer pair at B = 64 (tools/_exp_up.py; this layer + the next one, K4 form -> Winograd form):
-                    # 8x8 139.8 -> 125.8 us, 16x16 145.2 -> 134.4 us, 32x32 (K = 128: bandwidth-bound GEMM) 174.7 -> 189.5 us
-                    if 2 * hx_ <= _UPCONV_WINO_MAX and winograd_tile(n_, c1_, 2 * hx_, 2 * wx_, cout_) == 4:
-                        to_v = not torch.is_grad_enabled() and _hand_over(next_conv, None, n_, cout_, 2 * hx_, 2 * wx_)
+                    # this layer + the next one at B = 64, K4 form -> Winograd form (tools/bench_upconv_form.py): 8x8 139.8 -> 125.8 us,
+                    # 16x16 145.2 -> 134.4 us, 32x32 (K = 128: bandwidth-bound GEMM) 174.7 -> 189.5 us
+                    n, c1, hx, wx = x.shape
+                    if 2 * hx <= _UPCONV_WINO_MAX and winograd_tile(n, c1, 2 * hx, 2 * wx, conv.weight.shape[0]) == 4:
                         live = UPCONV_WINO_LIVE and not torch.is_grad_enabled()
-                        u = weights.winograd_live(conv.weight, 0, c1_) if live else weights.winograd(conv.weight, 4, 0, c1_)
-                        return ops.conv3x3_winograd(x, u, sc, sh, act=act, slope=slope, upsample=True, addend=hs[1], to_v=to_v,
-                                                    live=live)
+                        return _upconv_x_winograd(conv, (sc, sh), x, hs[1], live, act, slope, next_conv)
                 if upsample and UPCONV_AS_CONVT:
+                    k4 = weights.k4_packed(conv.weight, x.shape[1])
                     if _last_proj_applies(next_last, conv, x):
                         w_last = next_last.weight
-                        d = ops.convT4x4s2_proj(x, weights.k4_packed(conv.weight, x.shape[1]), sc, sh,
-                                                ops._last_wmat_cached(w_last, 0, 64, 9 * w_last.shape[1]), act=act, slope=slope,
-                                                addend=hs[1])
+                        d = ops.convT4x4s2_proj(x, k4, sc, sh, ops._last_wmat_cached(w_last, 0, 64, 9 * w_last.shape[1]), act=act,
+                                                slope=slope, addend=hs[1])
                         return ops.LastProj(d, (x.shape[0], 64, 2 * x.shape[2], 2 * x.shape[3]), w_last)
-                    return ops.convT4x4s2(x, None, weights.k4_packed(conv.weight, x.shape[1]), sc, sh, act=act, slope=slope,
-                                          addend=hs[1])
+                    return ops.convT4x4s2(x, None, k4, sc, sh, act=act, slope=slope, addend=hs[1])
                 return ops.conv3x3(x, None, hs[0], sc, sh, upsample=upsample, act=act, slope=slope, addend=hs[1])
         if skip is None and not upsample:
-            n, c, h, w = x.shape
-            cout = conv.weight.shape[0]
-            m = winograd_tile(n, c, h, w, cout)
+            m = winograd_tile(*x.shape, conv.weight.shape[0])
             if m:
-                to_v = m == 4 and not torch.is_grad_enabled() and _hand_over(next_conv, next_up, n, cout, h, w, pool)
-                return ops.conv3x3_winograd(x, weights.winograd(conv.weight, m), sc, sh, act=act, slope=slope, pool=pool,
-                                            to_v=to_v, y_from=y_from, up_live=UPCONV_WINO_LIVE and to_v == "up")
-            if conv3_wx_applies(n, c, h, w, cout, conv, bn):
+                return _winograd_layer(conv, (sc, sh), x, m, act, slope, pool, y_from, next_conv, next_up)
+            if conv3_wx_applies(*x.shape, conv.weight.shape[0], conv, bn):
                 return _from(ops.conv3x3_wx(x, weights.wx(conv.weight), sc, sh, act=act, slope=slope, pool=pool), y_from)
         return _from(ops.conv3x3(x, skip, weights.packed(conv.weight), sc, sh, upsample=upsample, act=act, slope=slope,
                                  pool=pool), y_from)
