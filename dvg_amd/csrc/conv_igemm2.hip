@@ -34,7 +34,7 @@ constexpr int DVG_GEMM128_GT = DVG_BF16X3 ? 2 : 4;
 //  16-channel slabs per stage of the 64-row GEMM tile: 4 (K = 64, 60 KB of LDS with the 128-row tile); 8 was measured 10-25 %
 //  slower on every Winograd shape (80 KB per workgroup: the second workgroup no longer fits the CU)
 constexpr int DVG_GEMM_GT = 4;
-//  the batched GEMM takes the 128-row tile from this many (128-row) workgroups on - four residency rounds (tile2 below; r06 A/B
+//  the batched GEMM takes the 128-row tile from this many (128-row) workgroups on - four residency rounds (plan2 below; r06 A/B
 //  under the steady-state power cap: profiles/r06_ab_gemm128_threshold.txt)
 constexpr int DVG_GEMM128_MIN_WGS = 4 * 768;
 //  under the ENERGY tile policy (dvg_set_tile_policy) the batched GEMM takes the 128 x 128 tile (64 x 64 per wave, NT = 2, two
@@ -56,49 +56,49 @@ constexpr int DVG_TILE16_MIN_WGS = 256;
 enum { M2_CONV3 = 0, M2_CONV4S2 = 1, M2_CONVT4S2 = 2, M2_GEMM = 3 };
 
 struct Igemm2Params {
-    const float* x;
-    const float* skip;
-    const float* w;      // packed [Cin/16][Cout/64][taps][64][DVG_WROW] (dvg_pack_conv_weight_k16); GEMM: [image][Cout/64][Cin/16][64][DVG_WROW]
-    const float* scale;
-    const float* shift;
-    float* y;
-    float* y_pool;
-    float* stats;
-    int N, H, W, C1, C2, Cout, upsample, act;
-    float slope;
-    int tiles_y, tiles_x, tiles_n, nblk_n;
-    int splitk;  // K split across workgroups (v2 only): raw partial tiles go to `ws`, dvg finishes with splitk_finish
-    int cps;     // K chunks (of 16 channels) per split
-    float* ws;   // [splitk][N*Ho*Wo][Cout]
-    const float* addend;  // optional raw (pre-scale) partial sums, NHWC like y: y = act((acc + addend) * scale + shift)
-    unsigned long long* clk;  // debug only (dvg_debug_set_clockbuf): per-workgroup {clock64, wall_clock64} at entry/exit
-    unsigned clk_cap;         // records the buffer holds (workgroups beyond it do not stamp)
-    int nb_group;  // Cout blocks per XCD-contiguous group of the workgroup order (launch2 picks it; v2 only)
-    int stage_prio;  // progress-based s_setprio in the stage loop (launch2 decides; see the stage loop)
-    long w_image_stride;  // M2_GEMM: floats between the packed weights of consecutive images n
-    int gemm_ni;          // M2_GEMM: consecutive images one workgroup runs back to back (one pipeline, one epilogue per image)
+    const float* x = nullptr;
+    const float* skip = nullptr;
+    const float* w = nullptr;      // packed [Cin/16][Cout/64][taps][64][DVG_WROW] (dvg_pack_conv_weight_k16); GEMM: [image][Cout/64][Cin/16][64][DVG_WROW]
+    const float* scale = nullptr;
+    const float* shift = nullptr;
+    float* y = nullptr;
+    float* y_pool = nullptr;
+    float* stats = nullptr;
+    int N = 0, H = 0, W = 0, C1 = 0, C2 = 0, Cout = 0, upsample = 0, act = 0;
+    float slope = 0.f;
+    int tiles_y = 0, tiles_x = 0, tiles_n = 0, nblk_n = 0;
+    int splitk = 1;  // K split across workgroups (v2 only): raw partial tiles go to `ws`, dvg finishes with splitk_finish
+    int cps = 0;     // K chunks (of 16 channels) per split
+    float* ws = nullptr;   // [splitk][N*Ho*Wo][Cout]
+    const float* addend = nullptr;  // optional raw (pre-scale) partial sums, NHWC like y: y = act((acc + addend) * scale + shift)
+    unsigned long long* clk = nullptr;  // debug only (dvg_debug_set_clockbuf): per-workgroup {clock64, wall_clock64} at entry/exit
+    unsigned clk_cap = 0;         // records the buffer holds (workgroups beyond it do not stamp)
+    int nb_group = 0;  // Cout blocks per XCD-contiguous group of the workgroup order (launch2 picks it; v2 only)
+    int stage_prio = 0;  // progress-based s_setprio in the stage loop (launch2 decides; see the stage loop)
+    long w_image_stride = 0;  // M2_GEMM: floats between the packed weights of consecutive images n
+    int gemm_ni = 0;          // M2_GEMM: consecutive images one workgroup runs back to back (one pipeline, one epilogue per image)
     // Time-batched decoder calls (ABI 6): the images form groups of add_B; group g = n / add_B reads its addend from block
     // add_map[g] of `addend` (an addend of add_B-image blocks) - the skip half of a concat conv is shared by the three
     // decoder calls of a time step and, once the skip is frozen, by all later steps (train.py:217-231).  NULL: image n.
-    const int* add_map;
-    int add_B;
+    const int* add_map = nullptr;
+    int add_B = 0;
     // FIRST (dvg_conv3x3_first_pair): the input of this 64-channel 3x3 layer is itself the first layer of the encoder,
     // vgg_layer(1, 64) on the raw frame (vgg_64.py:23-24): the workgroup computes the halo tile of that layer from the frame
     // patch under it instead of loading it, so the 64-channel activation between the two layers is never written or read
-    const float* first_frame;   // (N, 1, H, W)
-    const float* first_w;       // the first layer's weights transposed to [9 taps][64 channels]
-    const float* first_scale;   // folded BatchNorm of the first layer, 64 each
-    const float* first_shift;
-    float first_slope;
+    const float* first_frame = nullptr;   // (N, 1, H, W)
+    const float* first_w = nullptr;       // the first layer's weights transposed to [9 taps][64 channels]
+    const float* first_scale = nullptr;   // folded BatchNorm of the first layer, 64 each
+    const float* first_shift = nullptr;
+    float first_slope = 0.f;
     // FIRST: images n < y_from do not store the full-resolution output (only y_pool): a rollout discards the encoder's skip
     // tensors once the skip is frozen (generate_frames.py:154-157), and of the conditioning batch only the last frame's are
     // kept.  y is biased by -y_from images on the host, so image y_from lands at the start of the caller's buffer.
-    int y_from;
+    int y_from = 0;
     // PROJ (dvg_convT4x4s2_bn_act_proj): the 64-channel activation of the decoder's last block is not stored; the workgroup
     // projects its pixels onto the last ConvTranspose2d's T = ks * ks * nc tap outputs (what dvg_pixel_proj would make of y)
-    const float* proj_w;   // [T][64], as dvg_pixel_proj takes it
-    float* proj_out;       // [N * Ho * Wo][T]: the d1 of dvg_convT_gather
-    int proj_T;
+    const float* proj_w = nullptr;   // [T][64], as dvg_pixel_proj takes it
+    float* proj_out = nullptr;       // [N * Ho * Wo][T]: the d1 of dvg_convT_gather
+    int proj_T = 0;
 };
 
 // image of `addend` that output image n adds (see Igemm2Params::add_map)
@@ -1074,7 +1074,7 @@ static int g_tile_policy = 0;
 extern "C" void dvg_set_tile_policy(int energy) { g_tile_policy = energy ? 1 : 0; }
 extern "C" int dvg_tile_policy(void) { return g_tile_policy; }
 
-// number of K splits for a v2 launch: only when the grid would leave CUs idle and K is deep enough
+// number of K splits a v2 launch runs: only when the grid would leave CUs idle and K is deep enough
 // (r05, stride-2 conv after the parity split: splitting further - 768 / 1 024 workgroup slots - or not at all measured -0.5 ... -3 % on
 // the dcgan_64 rollout, in flight and on one chain: profiles/r05_ab_conv4s2.txt)
 static int choose_splitk(long wgs, int nchunks) {
@@ -1082,7 +1082,9 @@ static int choose_splitk(long wgs, int nchunks) {
     long s = 512 / wgs;
     if (s > 8) s = 8;
     if (s > nchunks / 4) s = nchunks / 4;   // at least 4 chunks (= 4 stages of 72-144 MFMAs) per split
-    return s < 2 ? 1 : (int)s;
+    if (s < 2) return 1;
+    const int cps = (int)((nchunks + s - 1) / s);
+    return (nchunks + cps - 1) / cps;  // no empty split: the kernel's peeled stage loop needs >= 1 chunk per workgroup
 }
 
 // GEMM mode: consecutive images one workgroup runs back to back in one software pipeline (launch2, dvg_gemm_batched_plan).
@@ -1116,45 +1118,92 @@ static int choose_nb_group(long tiles, int nblk_n, double wb, double ib) {
     return best;
 }
 
-template <int MODE, int TI, int TH, int TW, int NT = 1, bool FIRST = false, bool PROJ = false>
-static int launch2(Igemm2Params p, int Hg, int Wg, float* ws, long ws_floats, hipStream_t stream) {
-    using C = Cfg2<MODE, TI, TH, TW, NT, FIRST, PROJ>;
-    if (Hg % TH || Wg % TW || p.Cout % C::BN) return fail(DVG_ERR_SHAPE, "conv_igemm2: tile does not divide shape");
-    p.tiles_y = Hg / TH;
-    p.tiles_x = Wg / TW;
-    p.tiles_n = (p.N + TI - 1) / TI;
-    if (MODE == M2_GEMM) {
-        // images per workgroup: ONE.  The kernel can run gemm_ni images back to back in one software pipeline (one prologue
-        // per workgroup instead of one per image) and with 3 workgroups per CU (138 VGPRs) 2-4 images per workgroup measured
-        // a few % faster on the K <= 256 shapes; at 4 per CU (127 VGPRs, __launch_bounds__ above) the extra wave hides the
-        // prologues and the finer-grained workgroups balance the CUs better: 1 image is fastest or tied on every vgg_64
-        // shape (tools/ab_gemm_ni.sh: e.g. 16x16 256->256 48.4 us vs 52.0 (2) / 59.0 (4); 8x8 512->256 31.7 vs 41.7 / 57.6).
-        const int ni = gemm_images_per_wg(TW, NT, p.N, Hg, Wg, p.Cout);
-        p.gemm_ni = ni;
-        p.tiles_n = p.N / ni;
+// Which launches may split K - the host's one statement of Cfg2::CAN_SPLIT (launch2 ties the two with a static_assert): not the
+// 16-wide tiles, not the batched GEMM, not the fused forms (FIRST, PROJ).  Until r05 the 16-wide case was implied by the tiles'
+// threshold (512 workgroups > choose_splitk's 384); with DVG_TILE16_MIN_WGS = 256 it has to be said: a host side that expected a
+// split where the kernel made none read per-tile statistics rows as finish-block rows (train-mode BatchNorm statistics off by
+// 16 % at B = 16: caught by tests/test_gpu_backward.py).
+constexpr bool can_split2(int mode, int tw, bool fused) { return mode != M2_GEMM && tw != 16 && !fused; }
+
+// What the host decides about one launch, all of it: plan2 is the only place that computes any of these.
+struct Plan2 {
+    int ti, th, tw, nt, ni;  // tile: images x rows x columns, 64-wide Cout blocks (2: GEMM only); GEMM: images per pipeline, else 1
+    int Hg, Wg, Ho, Wo;      // the grid the tiles cover (the output's; the transposed conv's input: a tile per parity), the output
+    int ty, tx, tn;          // tiles along y, x and the images
+    long tiles, wgs;         // ty * tx * tn (x 4 parities) = statistics rows of an unsplit launch; workgroups per K split
+    bool can_split, pool;
+    int splitk, cps;         // K splits the launch runs (none is empty), 16-channel chunks per split
+    long units;              // finish kernel (splitk > 1): pixels (pooled: 2 x 2 quads), ...
+    int upb, fgrid;          // ... per block, blocks
+    int stats_rows;
+};
+
+// The plan of a launch under the tile policy in force; -1: no tile for this map.  fused: FIRST / PROJ.  n_tile (GEMM): the image
+// count the tile is chosen from - N itself (0), or the count of the launch this one is a part of (dvg_gemm_batched_k16_as).
+// Tile: 4 images x 4 x 4 on 4 x 4 maps, else 8 x 16 unless the map is 8 wide / that leaves too few workgroups.
+static int plan2(Plan2* pl, int mode, int N, int H, int W, int Cin, int Cout, bool with_ws, bool pool, bool fused = false,
+                 int n_tile = 0) {
+    Plan2 q{};
+    const int par = mode == M2_CONVT4S2 ? 4 : 1, sh = mode == M2_CONV4S2 ? 2 : 1;
+    q.Hg = H / sh; q.Wg = W / sh;
+    q.Ho = mode == M2_CONVT4S2 ? 2 * H : q.Hg; q.Wo = mode == M2_CONVT4S2 ? 2 * W : q.Wg;
+    q.ti = 1; q.th = 8; q.tw = 8; q.nt = 1; q.ni = 1;
+    if (q.Hg == 4 && q.Wg == 4) {
+        q.ti = q.th = q.tw = 4;
+    } else if (q.Hg % 8 || q.Wg % 8) {
+        return -1;
+    } else if (q.Wg % 16 == 0) {
+        const long w16 = (long)(n_tile ? n_tile : N) * (q.Hg / 8) * (q.Wg / 16) * par;      // 8 x 16 pixel tiles
+        if (w16 * (Cout / 64) >= (g_tile_policy ? DVG_TILE16_MIN_WGS : 512)) q.tw = 16;
+        // batched GEMM.  The 64-row tile (K = 64 per stage, 3 workgroups per CU) is faster on every launch of a B = 64 step
+        // (r04 same-box: 365 us per pass against 381), the 128-row tile (K = 32, LEAN, 3 per CU: twice the weight-fragment
+        // reuse) from about four residency rounds on (the conditioning batch: 2077 us per pass against 2267)
+        // (f32 MFMA build: the 64-row tile at 4 per CU throughout, as measured in r03)
+        if (mode == M2_GEMM && q.tw == 16 && (!DVG_BF16X3 || w16 * (Cout / 64) < DVG_GEMM128_MIN_WGS)) q.tw = 8;
+        // ... and nt = 2, the 128 x 128 workgroup tile (64 x 64 per wave: half the fragment reads and half the L2 -> LDS bytes per
+        // MFMA of the 128 x 64 tile) from DVG_GEMM_NT2 workgroups on: the energy-lean tile (see the constant; bf16 triples only)
+        if (mode == M2_GEMM && DVG_BF16X3 && g_tile_policy && Cout % 128 == 0 && w16 * (Cout / 128) >= DVG_GEMM_NT2) { q.tw = 16; q.nt = 2; }
     }
+    if (mode == M2_GEMM && q.ti != 1) return -1;
+    if (mode == M2_GEMM) q.ni = gemm_images_per_wg(q.tw, q.nt, N, q.Hg, q.Wg, Cout);
+    q.ty = q.Hg / q.th; q.tx = q.Wg / q.tw; q.tn = mode == M2_GEMM ? N / q.ni : (N + q.ti - 1) / q.ti;
+    q.tiles = (long)q.ty * q.tx * q.tn * par;
+    q.wgs = q.tiles * (Cout / (64 * q.nt));
+    q.can_split = can_split2(mode, q.tw, fused); q.pool = pool;
+    q.splitk = (with_ws && q.can_split) ? choose_splitk(q.wgs, Cin / 16) : 1;
+    q.cps = (Cin / 16 + q.splitk - 1) / q.splitk;
+    q.units = pool ? (long)N * (q.Ho / 2) * (q.Wo / 2) : (long)N * q.Ho * q.Wo;
+    q.upb = finish_units_per_block(q.units);
+    q.fgrid = (int)((q.units + q.upb - 1) / q.upb);
+    q.stats_rows = q.splitk > 1 ? q.fgrid : (int)q.tiles;
+    *pl = q;
+    return 0;
+}
+
+template <int TI_, int TH_, int TW_, int NT_ = 1>
+struct Tile2 { static constexpr int TI = TI_, TH = TH_, TW = TW_, NT = NT_; };
+
+template <int MODE, class T, bool FIRST = false, bool PROJ = false>
+static int launch2(Igemm2Params p, const Plan2& pl, float* ws, long ws_floats, hipStream_t stream) {
+    constexpr int TI = T::TI, TH = T::TH, TW = T::TW, NT = T::NT;
+    using C = Cfg2<MODE, TI, TH, TW, NT, FIRST, PROJ>;
+    static_assert(C::CAN_SPLIT == can_split2(MODE, TW, FIRST || PROJ), "the host's split rule is the kernels'");
+    if (pl.ti != TI || pl.th != TH || pl.tw != TW || pl.nt != NT || pl.can_split != C::CAN_SPLIT || pl.pool != (p.y_pool != nullptr))
+        return fail(DVG_ERR_SHAPE, "conv_igemm2: the plan is not this launch's");
+    if (pl.Hg % TH || pl.Wg % TW || p.Cout % C::BN || pl.cps % C::CHUNKS_PER_STAGE)      // (whole stages per split)
+        return fail(DVG_ERR_SHAPE, "conv_igemm2: tile does not divide shape");
+    p.tiles_y = pl.ty; p.tiles_x = pl.tx; p.tiles_n = pl.tn;
+    // GEMM: the kernel runs gemm_ni images back to back in one software pipeline (one prologue per workgroup instead of one per
+    // image) - as many as gemm_images_per_wg says: up to 6 where that makes the launch one residency round, else one
+    if (MODE == M2_GEMM) p.gemm_ni = pl.ni;
     p.nblk_n = p.Cout / C::BN;
-    p.clk = g_clk;
-    p.clk_cap = g_clk_cap;
-    const long wgs = (long)p.tiles_y * p.tiles_x * p.tiles_n * p.nblk_n * (MODE == M2_CONVT4S2 ? 4 : 1);
+    p.clk = g_clk; p.clk_cap = g_clk_cap;
     p.nb_group = choose_nb_group((long)p.tiles_y * p.tiles_x * p.tiles_n, p.nblk_n,
                                  (double)C::NTAPS * (p.C1 + p.C2) * C::BN * 4, (double)C::BM * (p.C1 + p.C2) * 4);
-    const int nchunks = (p.C1 + p.C2) / C::KC;
-    int Ho, Wo;
-    if (MODE == M2_CONV3 || MODE == M2_GEMM) { Ho = p.H; Wo = p.W; }
-    else if (MODE == M2_CONV4S2) { Ho = p.H >> 1; Wo = p.W >> 1; }
-    else { Ho = p.H * 2; Wo = p.W * 2; }
-    const long out_floats = (long)p.N * Ho * Wo * p.Cout;
-    int S = (ws != nullptr && C::CAN_SPLIT) ? choose_splitk(wgs, nchunks) : 1;
-    if (S > 1 && (long)S * out_floats > ws_floats) return fail(DVG_ERR_SHAPE, "conv_igemm2: split-K workspace too small");
-    p.cps = (nchunks + S - 1) / S;
-    p.cps = (p.cps + C::CHUNKS_PER_STAGE - 1) / C::CHUNKS_PER_STAGE * C::CHUNKS_PER_STAGE;   // whole stages per split
-    S = (nchunks + p.cps - 1) / p.cps;  // no empty split: the kernel's peeled stage loop needs >= 1 chunk per workgroup
-    p.splitk = S;
-    p.ws = ws;
-    float* y_pool = p.y_pool;
-    float* stats = p.stats;
-    const unsigned grid = (unsigned)(wgs * S);
+    const int S = pl.splitk;
+    if (S > 1 && (long)S * p.N * pl.Ho * pl.Wo * p.Cout > ws_floats) return fail(DVG_ERR_SHAPE, "conv_igemm2: split-K workspace too small");
+    p.cps = pl.cps; p.splitk = S; p.ws = ws;
+    const unsigned grid = (unsigned)(pl.wgs * S);
     // Stage priority (see the stage loop): measured +2..5 % wherever co-resident workgroups run in lockstep (single-round
     // launches of every mode) and on all 9-tap layers (144 MFMAs per stage); on multi-round launches of the short-stage
     // modes (4 / 8 taps, 64 MFMAs per stage) a starved workgroup's next-stage loads issue late: -3..-18 % -> off there.
@@ -1168,57 +1217,29 @@ static int launch2(Igemm2Params p, int Hg, int Wg, float* ws, long ws_floats, hi
     }
     hipLaunchKernelGGL((conv_igemm2_kernel<MODE, TI, TH, TW, NT, FIRST, PROJ>), dim3(grid), dim3(256), C::LDS_BYTES, stream, p);
     if (int e = check_launch("conv_igemm2")) return e;
-    if (S > 1) {
-        const bool pool = y_pool != nullptr;
-        const long units = pool ? (long)p.N * (Ho / 2) * (Wo / 2) : (long)p.N * Ho * Wo;
-        const int upb = finish_units_per_block(units);
-        const unsigned fgrid = (unsigned)((units + upb - 1) / upb);
-        if (pool)
-            hipLaunchKernelGGL((splitk_finish_kernel<true>), dim3(fgrid), dim3(256), 0, stream, ws, S, p.scale, p.shift, p.y,
-                               y_pool, stats, p.N, Ho, Wo, p.Cout, p.act, p.slope, upb, p.addend, p.add_map, p.add_B);
-        else
-            hipLaunchKernelGGL((splitk_finish_kernel<false>), dim3(fgrid), dim3(256), 0, stream, ws, S, p.scale, p.shift, p.y,
-                               y_pool, stats, p.N, Ho, Wo, p.Cout, p.act, p.slope, upb, p.addend, p.add_map, p.add_B);
-        return check_launch("splitk_finish");
-    }
-    return DVG_OK;
+    if (S == 1) return DVG_OK;
+    auto finish = pl.pool ? splitk_finish_kernel<true> : splitk_finish_kernel<false>;
+    hipLaunchKernelGGL(finish, dim3(pl.fgrid), dim3(256), 0, stream, ws, S, p.scale, p.shift, p.y, p.y_pool, p.stats, p.N, pl.Ho,
+                       pl.Wo, p.Cout, p.act, p.slope, pl.upb, p.addend, p.add_map, p.add_B);
+    return check_launch("splitk_finish");
 }
 
-
-// spatial tile on the grid the tiles cover; 8x16 unless the map is 8 wide / that leaves < 2 workgroups per CU
-static int tile2(int mode, int N, int Hg, int Wg, int Cout, int* ti, int* th, int* tw) {
-    const int par = mode == M2_CONVT4S2 ? 4 : 1;
-    if (Hg == 4 && Wg == 4) { *ti = 4; *th = 4; *tw = 4; return 0; }
-    if (Hg % 8 || Wg % 8) return -1;
-    *ti = 1; *th = 8; *tw = 8;
-    if (Wg % 16 == 0) {
-        const long wgs = (long)N * (Hg / 8) * (Wg / 16) * (Cout / 64) * par;
-        if (wgs >= (g_tile_policy ? DVG_TILE16_MIN_WGS : 512)) *tw = 16;
-        if (mode == M2_GEMM && *tw == 16) {
-            // batched GEMM.  The 64-row tile (K = 64 per stage, 3 workgroups per CU) is faster on every launch of a B = 64 step
-            // (r04 same-box: 365 us per pass against 381), the 128-row tile (K = 32, LEAN, 3 per CU: twice the weight-fragment
-            // reuse) from about four residency rounds on (the conditioning batch: 2077 us per pass against 2267)
-            // (f32 MFMA build: the 64-row tile at 4 per CU throughout, as measured in r03)
-            if (!DVG_BF16X3 || wgs < DVG_GEMM128_MIN_WGS) *tw = 8;
-        }
-    }
-    return 0;
+// The tile -> instantiation choice of every entry point but the FIRST form: launch2 at the plan's tile.  1 x 8 x 16 and 1 x 8 x 8
+// exist in every mode; EXTRA names what a mode has besides (the 3 x 3 conv, the PROJ form and the GEMM have no 4 x 4 x 4 tile;
+// NT = 2 is the GEMM's, in the bf16-triple build).
+enum { T2_444 = 1, T2_NT2 = 2 };
+template <int MODE, int EXTRA = 0, bool PROJ = false>
+static int launch_tile(const Igemm2Params& p, const Plan2& pl, const char* who, float* ws, long ws_floats, void* stream) {
+    auto go = [&](auto t) { return launch2<MODE, decltype(t), false, PROJ>(p, pl, ws, ws_floats, (hipStream_t)stream); };
+    if constexpr ((EXTRA & T2_NT2) != 0 && DVG_BF16X3 != 0)
+        if (pl.ti == 1 && pl.tw == 16 && pl.nt == 2) return go(Tile2<1, 8, 16, 2>{});
+    if constexpr ((EXTRA & T2_444) != 0)
+        if (pl.ti == 4 && pl.nt == 1) return go(Tile2<4, 4, 4>{});
+    if (pl.ti == 1 && pl.tw == 16 && pl.nt == 1) return go(Tile2<1, 8, 16>{});
+    if (pl.ti == 1 && pl.tw == 8 && pl.nt == 1) return go(Tile2<1, 8, 8>{});
+    return fail(DVG_ERR_SHAPE, "%s: no kernel", who);
 }
 
-// The batched GEMM's tile (dvg_gemm_batched_k16, dvg_gemm_batched_plan): *tw = 8 the 64-row tile, 16 the 128-row tile; *nt = 2
-// the 128 x 128 workgroup tile (64 x 64 per wave: half the fragment reads and half the L2 -> LDS bytes per MFMA of the 128 x 64
-// tile) from DVG_GEMM_NT2 workgroups on: the energy-lean tile (see the constant above; bf16-triple build only).
-static int gemm_tile(int NB, int Hg, int Wg, int Cout, int* tw, int* nt) {
-    int ti, th;
-    if (tile2(M2_GEMM, NB, Hg, Wg, Cout, &ti, &th, tw) != 0 || ti != 1) return -1;
-    *nt = 1;
-    if (DVG_BF16X3 && g_tile_policy && Cout % 128 == 0 && Wg % 16 == 0 &&
-        (long)NB * (Hg / 8) * (Wg / 16) * (Cout / 128) >= DVG_GEMM_NT2) {
-        *tw = 16;
-        *nt = 2;
-    }
-    return 0;
-}
 
 // ---- WX: the 3x3 conv with 1-D Winograd F(2,3) along x inside the kernel (bf16-triple build only) ---------------------------
 // GEMM rows are output pixel PAIRS (x = 2 j, 2 j + 1).  Per kernel row r the two outputs of a pair come from four products
@@ -1659,42 +1680,38 @@ extern "C" int dvg_pack_conv_weight_k16(const float* w, float* w_packed, int cou
     return check_launch("dvg_pack_conv_weight_k16");
 }
 
-static long v2_wgs(int mode, int N, int Hg, int Wg, int Cout, int ti, int th, int tw) {
-    return (long)((N + ti - 1) / ti) * (Hg / th) * (Wg / tw) * (Cout / 64) * (mode == M2_CONVT4S2 ? 4 : 1);
-}
-
-// K splits of a launch with this tile: the 16-wide tiles never split (Cfg2::CAN_SPLIT: their kernels do not carry the split-K
-// epilogue).  Until r05 that was implied by their threshold (512 workgroups > choose_splitk's 384); with DVG_TILE16_MIN_WGS = 256
-// it has to be said: a host side that expected a split where the kernel made none read per-tile statistics rows as finish-block
-// rows (train-mode BatchNorm statistics off by 16 % at B = 16: caught by tests/test_gpu_backward.py).
-static int v2_splits(int mode, int N, int Hg, int Wg, int Cout, int Cin, int ti, int th, int tw) {
-    if (tw == 16) return 1;
-    return choose_splitk(v2_wgs(mode, N, Hg, Wg, Cout, ti, th, tw), Cin / 16);
-}
-
-// K splits the v2 launch of this shape will use when a workspace is supplied (1 = no split)
+// K splits the v2 launch of this shape runs when a workspace is supplied (1 = no split)
 extern "C" int dvg_conv_splitk_v2(int mode, int N, int H, int W, int Cin, int Cout) {
-    int Hg = H, Wg = W;
-    if (mode == M2_CONV4S2) { Hg = H / 2; Wg = W / 2; }
-    int ti, th, tw;
-    if (Cin % 16 || Cout % 64 || tile2(mode, N, Hg, Wg, Cout, &ti, &th, &tw)) return -1;
-    return v2_splits(mode, N, Hg, Wg, Cout, Cin, ti, th, tw);
+    Plan2 pl;
+    if (Cin % 16 || Cout % 64 || plan2(&pl, mode, N, H, W, Cin, Cout, true, false)) return -1;
+    return pl.splitk;
 }
 
 extern "C" int dvg_conv_stats_rows_v2(int mode, int N, int H, int W, int Cin, int Cout, int pool, int with_workspace) {
-    int Hg = H, Wg = W;
-    if (mode == M2_CONV4S2) { Hg = H / 2; Wg = W / 2; }
-    int ti, th, tw;
-    if (tile2(mode, N, Hg, Wg, Cout, &ti, &th, &tw)) return -1;
-    if (with_workspace && v2_splits(mode, N, Hg, Wg, Cout, Cin, ti, th, tw) > 1) {
-        int Ho = H, Wo = W;
-        if (mode == M2_CONV4S2) { Ho = H / 2; Wo = W / 2; }
-        if (mode == M2_CONVT4S2) { Ho = 2 * H; Wo = 2 * W; }
-        const long units = pool ? (long)N * (Ho / 2) * (Wo / 2) : (long)N * Ho * Wo;
-        const int upb = finish_units_per_block(units);
-        return (int)((units + upb - 1) / upb);
-    }
-    return ((N + ti - 1) / ti) * (Hg / th) * (Wg / tw) * (mode == M2_CONVT4S2 ? 4 : 1);
+    Plan2 pl;
+    if (plan2(&pl, mode, N, H, W, Cin, Cout, with_workspace != 0, pool != 0)) return -1;
+    return pl.stats_rows;
+}
+
+// The head every entry point fills: operands, folded BatchNorm, output, shape and activation.  Everything else keeps its default
+// until it is assigned by name.
+static Igemm2Params params2(const float* x, const float* skip, const float* w, const float* scale, const float* shift, float* y,
+                            int N, int H, int W, int C1, int C2, int Cout, int act, float slope) {
+    Igemm2Params p{};
+    p.x = x; p.skip = skip; p.w = w; p.scale = scale; p.shift = shift; p.y = y;
+    p.N = N; p.H = H; p.W = W; p.C1 = C1; p.C2 = C2; p.Cout = Cout;
+    p.act = act; p.slope = slope;
+    return p;
+}
+
+// the addend triple (Igemm2Params::add_map) of entry point `who`
+static int set_addend(Igemm2Params& p, const char* who, const float* addend, const int* addend_map, int addend_block) {
+    p.addend = addend;
+    p.add_map = addend ? addend_map : nullptr;
+    p.add_B = addend_block;
+    DVG_REQUIRE(p.add_map == nullptr || (addend_block > 0 && p.N % addend_block == 0), DVG_ERR_SHAPE,
+                "%s: addend_block must divide N", who);
+    return DVG_OK;
 }
 
 static int checks2(const Igemm2Params& p, const char* who) {
@@ -1710,34 +1727,42 @@ static int checks2(const Igemm2Params& p, const char* who) {
     return DVG_OK;
 }
 
-#define D2(MODE, TI_, TH_, TW_) \
-    if (ti == TI_ && th == TH_ && tw == TW_)                                             \
-        return launch2<MODE, TI_, TH_, TW_>(p, Hg, Wg, workspace, workspace_floats, (hipStream_t)stream);
-
-
-
 extern "C" int dvg_conv3x3_bn_act_v2(const float* x, const float* skip, const float* w_k16, const float* scale,
                                      const float* shift, float* y, float* y_pool, float* stats, int N, int H, int W,
                                      int C1, int C2, int Cout, int upsample_x, int act, float slope,
                                      float* workspace, long workspace_floats, const float* addend,
                                      const int* addend_map, int addend_block, void* stream) {
-    Igemm2Params p{x, skip, w_k16, scale, shift, y, y_pool, stats, N, H, W, C1, C2, Cout, upsample_x ? 1 : 0, act, slope,
-                   0, 0, 0, 0, 0, 1, 0, nullptr};
-    p.addend = addend;
-    p.add_map = addend ? addend_map : nullptr;
-    p.add_B = addend_block;
-    DVG_REQUIRE(p.add_map == nullptr || (addend_block > 0 && N % addend_block == 0), DVG_ERR_SHAPE,
-                "dvg_conv3x3_bn_act_v2: addend_block must divide N");
-    if (int e = checks2(p, "dvg_conv3x3_bn_act_v2")) return e;
+    const char* who = "dvg_conv3x3_bn_act_v2";
+    Igemm2Params p = params2(x, skip, w_k16, scale, shift, y, N, H, W, C1, C2, Cout, act, slope);
+    p.y_pool = y_pool;
+    p.stats = stats;
+    p.upsample = upsample_x ? 1 : 0;
+    if (int e = set_addend(p, who, addend, addend_map, addend_block)) return e;
+    if (int e = checks2(p, who)) return e;
     DVG_REQUIRE(aligned16(addend) && (addend == nullptr || y_pool == nullptr), DVG_ERR_SHAPE,
-                "dvg_conv3x3_bn_act_v2: addend must be 16-byte aligned and excludes the pooled output");
-    DVG_REQUIRE(H % 8 == 0 && W % 8 == 0, DVG_ERR_SHAPE, "dvg_conv3x3_bn_act_v2: H=%d W=%d must be multiples of 8", H, W);
-    int Hg = H, Wg = W, ti, th, tw;
-    DVG_REQUIRE(tile2(M2_CONV3, N, Hg, Wg, Cout, &ti, &th, &tw) == 0 && ti == 1, DVG_ERR_SHAPE,
-                "dvg_conv3x3_bn_act_v2: no tile for %dx%d", H, W);
-    D2(M2_CONV3, 1, 8, 16)
-    D2(M2_CONV3, 1, 8, 8)
-    return fail(DVG_ERR_SHAPE, "dvg_conv3x3_bn_act_v2: no kernel");
+                "%s: addend must be 16-byte aligned and excludes the pooled output", who);
+    DVG_REQUIRE(H % 8 == 0 && W % 8 == 0, DVG_ERR_SHAPE, "%s: H=%d W=%d must be multiples of 8", who, H, W);
+    Plan2 pl;
+    DVG_REQUIRE(plan2(&pl, M2_CONV3, N, H, W, C1 + C2, Cout, workspace != nullptr, y_pool != nullptr) == 0 && pl.ti == 1,
+                DVG_ERR_SHAPE, "%s: no tile for %dx%d", who, H, W);
+    return launch_tile<M2_CONV3>(p, pl, who, workspace, workspace_floats, stream);
+}
+
+// What the two first-pair entry points share: the y_from rule, the biased y and the first layer's fields (Igemm2Params::first_*).
+static int first_pair_params(Igemm2Params* out, const char* who, const float* frame, const float* w0, const float* scale0,
+                             const float* shift0, const float* w1, const float* scale1, const float* shift1, float* y,
+                             float* y_pool, int N, int H, int W, int Cout, int act, float slope, int y_from) {
+    DVG_REQUIRE(y_from >= 0 && y_from <= N && (y_from == 0 || y_pool != nullptr) && (y != nullptr || y_from == N), DVG_ERR_SHAPE,
+                "%s: y_from=%d needs 0 <= y_from <= N, a pooled output when > 0, y unless == N", who, y_from);
+    // y holds the images [y_from, N): biased so that the kernel's image index applies (never dereferenced below y_from)
+    float* const y_biased = y ? y - (size_t)y_from * H * W * Cout : y_pool;
+    Igemm2Params p = params2(frame /* never read as an activation */, nullptr, w1, scale1, shift1, y_biased, N, H, W, 64, 0, Cout,
+                             act, slope);
+    p.y_pool = y_pool;
+    p.first_frame = frame; p.first_w = w0; p.first_scale = scale0; p.first_shift = shift0; p.first_slope = 0.2f;
+    p.y_from = y_from;
+    *out = p;
+    return DVG_OK;
 }
 
 // vgg_64's first stage c1 = vgg_layer(1, 64) -> vgg_layer(64, Cout) (vgg_64.py:23-26) in eval mode as ONE launch: the second
@@ -1750,19 +1775,18 @@ extern "C" int dvg_conv3x3_bn_act_v2(const float* x, const float* skip, const fl
 extern "C" int dvg_conv3x3_first_pair(const float* frame, const float* w0, const float* scale0, const float* shift0,
                                       const float* w1_k16, const float* scale1, const float* shift1, float* y, float* y_pool,
                                       int N, int H, int W, int Cout, int act, float slope, int y_from, void* stream) {
-    DVG_REQUIRE(frame && w0 && scale0 && shift0, DVG_ERR_NULL, "dvg_conv3x3_first_pair: NULL pointer");
-    DVG_REQUIRE(y_from >= 0 && y_from <= N && (y_from == 0 || y_pool != nullptr) && (y != nullptr || y_from == N), DVG_ERR_SHAPE,
-                "dvg_conv3x3_first_pair: y_from=%d needs 0 <= y_from <= N, a pooled output when > 0, y unless == N", y_from);
-    // y holds the images [y_from, N): biased so that the kernel's image index applies (never dereferenced below y_from)
-    float* const y_biased = y ? y - (size_t)y_from * H * W * Cout : y_pool;
-    Igemm2Params p{frame /* never read as an activation */, nullptr, w1_k16, scale1, shift1, y_biased, y_pool, nullptr, N, H, W, 64, 0, Cout, 0,
-                   act, slope, 0, 0, 0, 0, 0, 1, 0, nullptr};
-    p.first_frame = frame; p.first_w = w0; p.first_scale = scale0; p.first_shift = shift0; p.first_slope = 0.2f;
-    p.y_from = y_from;
-    if (int e = checks2(p, "dvg_conv3x3_first_pair")) return e;
+    const char* who = "dvg_conv3x3_first_pair";
+    DVG_REQUIRE(frame && w0 && scale0 && shift0, DVG_ERR_NULL, "%s: NULL pointer", who);
+    Igemm2Params p;
+    if (int e = first_pair_params(&p, who, frame, w0, scale0, shift0, w1_k16, scale1, shift1, y, y_pool, N, H, W, Cout, act, slope,
+                                  y_from))
+        return e;
+    if (int e = checks2(p, who)) return e;
     DVG_REQUIRE(H % 8 == 0 && W % 16 == 0 && (long)N * (H / 8) * (W / 16) * (Cout / 64) >= 512, DVG_ERR_SHAPE,
-                "dvg_conv3x3_first_pair: H %% 8, W %% 16 and >= 512 workgroups needed (N=%d H=%d W=%d Cout=%d)", N, H, W, Cout);
-    return launch2<M2_CONV3, 1, 8, 16, 1, true>(p, H, W, nullptr, 0, (hipStream_t)stream);
+                "%s: H %% 8, W %% 16 and >= 512 workgroups needed (N=%d H=%d W=%d Cout=%d)", who, N, H, W, Cout);
+    Plan2 pl;
+    if (plan2(&pl, M2_CONV3, N, H, W, 64, Cout, false, y_pool != nullptr, true)) return fail(DVG_ERR_SHAPE, "%s: no tile", who);
+    return launch2<M2_CONV3, Tile2<1, 8, 16>, true>(p, pl, nullptr, 0, (hipStream_t)stream);
 }
 
 // ---- the WX form (1-D Winograd F(2,3) along x inside the kernel: conv3_wx_kernel) ----------------------------------------
@@ -1797,12 +1821,10 @@ extern "C" int dvg_conv3x3_bn_act_wx(const float* x, const float* skip, const fl
                                      const int* addend_map, int addend_block, void* stream) {
     const char* who = "dvg_conv3x3_bn_act_wx";
     DVG_REQUIRE(x && w_wx && y, DVG_ERR_NULL, "%s: x/w/y must not be NULL", who);
-    Igemm2Params p{x, skip, w_wx, scale, shift, y, y_pool, nullptr, N, H, W, C1, C2, Cout, upsample_x ? 1 : 0, act, slope,
-                   0, 0, 0, 0, 0, 1, 0, nullptr};
-    p.addend = addend;
-    p.add_map = addend ? addend_map : nullptr;
-    p.add_B = addend_block;
-    DVG_REQUIRE(p.add_map == nullptr || (addend_block > 0 && N % addend_block == 0), DVG_ERR_SHAPE, "%s: addend_block must divide N", who);
+    Igemm2Params p = params2(x, skip, w_wx, scale, shift, y, N, H, W, C1, C2, Cout, act, slope);
+    p.y_pool = y_pool;
+    p.upsample = upsample_x ? 1 : 0;
+    if (int e = set_addend(p, who, addend, addend_map, addend_block)) return e;
     DVG_REQUIRE(addend == nullptr || y_pool == nullptr, DVG_ERR_SHAPE, "%s: addend excludes the pooled output", who);
     if (int e = checks_wx(p, who)) return e;
 #if DVG_BF16X3
@@ -1817,16 +1839,12 @@ extern "C" int dvg_conv3x3_first_pair_wx(const float* frame, const float* w0, co
                                          int N, int H, int W, int Cout, int act, float slope, int y_from, void* stream) {
     const char* who = "dvg_conv3x3_first_pair_wx";
     DVG_REQUIRE(frame && w0 && scale0 && shift0 && w1_wx, DVG_ERR_NULL, "%s: NULL pointer", who);
-    DVG_REQUIRE(y_from >= 0 && y_from <= N && (y_from == 0 || y_pool != nullptr) && (y != nullptr || y_from == N), DVG_ERR_SHAPE,
-                "%s: y_from=%d needs 0 <= y_from <= N, a pooled output when > 0, y unless == N", who, y_from);
+    Igemm2Params p;
+    if (int e = first_pair_params(&p, who, frame, w0, scale0, shift0, w1_wx, scale1, shift1, y, y_pool, N, H, W, Cout, act, slope,
+                                  y_from))
+        return e;
     DVG_REQUIRE(aligned16(w0) && aligned16(scale0) && aligned16(shift0) && aligned16(y), DVG_ERR_ALIGN,
                 "%s: pointers must be 16-byte aligned", who);
-    // y holds the images [y_from, N): biased so that the kernel's image index applies (never dereferenced below y_from)
-    float* const y_biased = y ? y - (size_t)y_from * H * W * Cout : y_pool;
-    Igemm2Params p{frame /* never read as an activation */, nullptr, w1_wx, scale1, shift1, y_biased, y_pool, nullptr, N, H, W, 64, 0, Cout, 0,
-                   act, slope, 0, 0, 0, 0, 0, 1, 0, nullptr};
-    p.first_frame = frame; p.first_w = w0; p.first_scale = scale0; p.first_shift = shift0; p.first_slope = 0.2f;
-    p.y_from = y_from;
     if (int e = checks_wx(p, who)) return e;
 #if DVG_BF16X3
     return launch_wx<true>(p, (hipStream_t)stream);
@@ -1838,46 +1856,38 @@ extern "C" int dvg_conv3x3_first_pair_wx(const float* frame, const float* w0, co
 extern "C" int dvg_conv4x4s2_bn_act_v2(const float* x, const float* w_k16, const float* scale, const float* shift,
                                        float* y, float* stats, int N, int H, int W, int Cin, int Cout, int act,
                                        float slope, float* workspace, long workspace_floats, void* stream) {
-    Igemm2Params p{x, nullptr, w_k16, scale, shift, y, nullptr, stats, N, H, W, Cin, 0, Cout, 0, act, slope, 0, 0, 0, 0, 0,
-                   1, 0, nullptr};
-    if (int e = checks2(p, "dvg_conv4x4s2_bn_act_v2")) return e;
-    DVG_REQUIRE(H % 2 == 0 && W % 2 == 0, DVG_ERR_SHAPE, "dvg_conv4x4s2_bn_act_v2: odd input");
+    const char* who = "dvg_conv4x4s2_bn_act_v2";
+    Igemm2Params p = params2(x, nullptr, w_k16, scale, shift, y, N, H, W, Cin, 0, Cout, act, slope);
+    p.stats = stats;
+    if (int e = checks2(p, who)) return e;
+    DVG_REQUIRE(H % 2 == 0 && W % 2 == 0, DVG_ERR_SHAPE, "%s: odd input", who);
     DVG_REQUIRE((long)N * H * W * Cin < (1L << 31), DVG_ERR_SHAPE,
-                "dvg_conv4x4s2_bn_act_v2: input of %d x %d x %d x %d floats too large (32-bit offsets)", N, H, W, Cin);
-    int Hg = H / 2, Wg = W / 2, ti, th, tw;
-    DVG_REQUIRE(tile2(M2_CONV4S2, N, Hg, Wg, Cout, &ti, &th, &tw) == 0, DVG_ERR_SHAPE,
-                "dvg_conv4x4s2_bn_act_v2: unsupported map %dx%d", H, W);
-    D2(M2_CONV4S2, 1, 8, 16)
-    D2(M2_CONV4S2, 1, 8, 8)
-    D2(M2_CONV4S2, 4, 4, 4)
-    return fail(DVG_ERR_SHAPE, "dvg_conv4x4s2_bn_act_v2: no kernel");
+                "%s: input of %d x %d x %d x %d floats too large (32-bit offsets)", who, N, H, W, Cin);
+    Plan2 pl;
+    DVG_REQUIRE(plan2(&pl, M2_CONV4S2, N, H, W, Cin, Cout, workspace != nullptr, false) == 0, DVG_ERR_SHAPE,
+                "%s: unsupported map %dx%d", who, H, W);
+    return launch_tile<M2_CONV4S2, T2_444>(p, pl, who, workspace, workspace_floats, stream);
 }
 
 extern "C" int dvg_convT4x4s2_bn_act_v2(const float* x, const float* skip, const float* w_k16, const float* scale,
                                         const float* shift, float* y, float* stats, int N, int H, int W, int C1,
                                         int C2, int Cout, int act, float slope, float* workspace, long workspace_floats,
                                         const float* addend, const int* addend_map, int addend_block, void* stream) {
-    Igemm2Params p{x, skip, w_k16, scale, shift, y, nullptr, stats, N, H, W, C1, C2, Cout, 0, act, slope, 0, 0, 0, 0, 0,
-                   1, 0, nullptr};
-    p.addend = addend;
-    p.add_map = addend ? addend_map : nullptr;
-    p.add_B = addend_block;
-    DVG_REQUIRE(p.add_map == nullptr || (addend_block > 0 && N % addend_block == 0), DVG_ERR_SHAPE,
-                "dvg_convT4x4s2_bn_act_v2: addend_block must divide N");
-    if (int e = checks2(p, "dvg_convT4x4s2_bn_act_v2")) return e;
-    DVG_REQUIRE(aligned16(addend), DVG_ERR_ALIGN, "dvg_convT4x4s2_bn_act_v2: addend must be 16-byte aligned");
-    int Hg = H, Wg = W, ti, th, tw;
-    DVG_REQUIRE(tile2(M2_CONVT4S2, N, Hg, Wg, Cout, &ti, &th, &tw) == 0, DVG_ERR_SHAPE,
-                "dvg_convT4x4s2_bn_act_v2: unsupported map %dx%d", H, W);
-    D2(M2_CONVT4S2, 1, 8, 16)
-    D2(M2_CONVT4S2, 1, 8, 8)
-    D2(M2_CONVT4S2, 4, 4, 4)
-    return fail(DVG_ERR_SHAPE, "dvg_convT4x4s2_bn_act_v2: no kernel");
+    const char* who = "dvg_convT4x4s2_bn_act_v2";
+    Igemm2Params p = params2(x, skip, w_k16, scale, shift, y, N, H, W, C1, C2, Cout, act, slope);
+    p.stats = stats;
+    if (int e = set_addend(p, who, addend, addend_map, addend_block)) return e;
+    if (int e = checks2(p, who)) return e;
+    DVG_REQUIRE(aligned16(addend), DVG_ERR_ALIGN, "%s: addend must be 16-byte aligned", who);
+    Plan2 pl;
+    DVG_REQUIRE(plan2(&pl, M2_CONVT4S2, N, H, W, C1 + C2, Cout, workspace != nullptr, false) == 0, DVG_ERR_SHAPE,
+                "%s: unsupported map %dx%d", who, H, W);
+    return launch_tile<M2_CONVT4S2, T2_444>(p, pl, who, workspace, workspace_floats, stream);
 }
 
 // dvg_convT4x4s2_bn_act_v2 on x alone (C2 = 0) with Cout = 64, followed by dvg_pixel_proj(y, proj_w) - in one launch: the
 // activation y is never written; proj_out (N * 2H * 2W, T) holds what the projection of y would (same bits: see the kernel's
-// PROJ epilogue).  No statistics, no split-K; maps that tile2 gives the 8 x 16 or the 8 x 8 tile.  Any failed precondition is
+// PROJ epilogue).  No statistics, no split-K; maps that plan2 gives the 8 x 16 or the 8 x 8 tile.  Any failed precondition is
 // an error before the launch.
 extern "C" int dvg_convT4x4s2_bn_act_proj(const float* x, const float* w_k16, const float* scale, const float* shift,
                                           const float* proj_w, float* proj_out, int T, int N, int H, int W, int C1, int Cout,
@@ -1892,20 +1902,24 @@ extern "C" int dvg_convT4x4s2_bn_act_proj(const float* x, const float* w_k16, co
     DVG_REQUIRE(aligned16(x) && aligned16(w_k16) && aligned16(proj_w) && aligned16(addend), DVG_ERR_ALIGN,
                 "%s: pointers must be 16-byte aligned", who);
     DVG_REQUIRE(act >= DVG_ACT_NONE && act <= DVG_ACT_SIGMOID, DVG_ERR_SHAPE, "%s: bad act", who);
-    Igemm2Params p{x, nullptr, w_k16, scale, shift, nullptr, nullptr, nullptr, N, H, W, C1, 0, Cout, 0, act, slope, 0, 0, 0, 0, 0,
-                   1, 0, nullptr};
-    p.addend = addend;
-    p.add_map = addend ? addend_map : nullptr;
-    p.add_B = addend_block;
-    DVG_REQUIRE(p.add_map == nullptr || (addend_block > 0 && N % addend_block == 0), DVG_ERR_SHAPE, "%s: addend_block must divide N", who);
+    Igemm2Params p = params2(x, nullptr, w_k16, scale, shift, nullptr, N, H, W, C1, 0, Cout, act, slope);
+    if (int e = set_addend(p, who, addend, addend_map, addend_block)) return e;
     p.proj_w = proj_w;
     p.proj_out = proj_out;
     p.proj_T = T;
-    int ti, th, tw;
-    DVG_REQUIRE(tile2(M2_CONVT4S2, N, H, W, Cout, &ti, &th, &tw) == 0 && ti == 1, DVG_ERR_SHAPE,
+    Plan2 pl;
+    DVG_REQUIRE(plan2(&pl, M2_CONVT4S2, N, H, W, C1, Cout, false, false, true) == 0 && pl.ti == 1, DVG_ERR_SHAPE,
                 "%s: unsupported map %dx%d (multiples of 8 needed)", who, H, W);
-    if (tw == 16) return launch2<M2_CONVT4S2, 1, 8, 16, 1, false, true>(p, H, W, nullptr, 0, (hipStream_t)stream);
-    return launch2<M2_CONVT4S2, 1, 8, 8, 1, false, true>(p, H, W, nullptr, 0, (hipStream_t)stream);
+    return launch_tile<M2_CONVT4S2, 0, true>(p, pl, who, nullptr, 0, stream);
+}
+
+// What dvg_gemm_batched_k16 launches for NB images with the tile of an nb_tile-image launch, under the tile policy in force: the
+// batched GEMM's shape rules and its plan (tw = 8 the 64-row tile, 16 the 128-row tile; nt = 2 the 128 x 128 workgroup tile; ni the
+// images a workgroup runs back to back in one pipeline).  0, or -1 for a shape the launcher rejects.
+static int gemm_plan(Plan2* pl, int NB, int nb_tile, int H, int W, int Cin, int Cout) {
+    if (NB <= 0 || nb_tile < NB || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return -1;
+    if (Cin % (16 * DVG_GEMM_GT) || Cout % 64 || H % 8 || W % 8) return -1;
+    return plan2(pl, M2_GEMM, NB, H, W, Cin, Cout, false, false, false, nb_tile);
 }
 
 // Batched GEMM on the igemm machinery: y[b][px][co] = sum_ci x[b][px][ci] * w[b][ci][co] for b < NB "images" of H x W
@@ -1913,28 +1927,19 @@ extern "C" int dvg_convT4x4s2_bn_act_proj(const float* x, const float* w_k16, co
 // outermost, as dvg_winograd_weight writes them (gload_b); dvg_pack_conv_weight_k16's 1x1 layout [Cin/16][Cout/64][64][row]
 // is the same only at Cout == 64).  The 16 / 36 Winograd-domain products of dvg_winograd_*.
 // Cin % 64 == 0, Cout % 64 == 0, H % 8 == 0, W % 8 == 0.
-// nb_tile: the image count gemm_tile chooses (tile_w, nt) from - NB itself, or (dvg_gemm_batched_k16_as) the count of the launch
+// nb_tile: the image count the tile (tile_w, nt) is chosen from - NB itself, or (dvg_gemm_batched_k16_as) the count of the launch
 // this one is a part of.
 static int gemm_batched(const float* x, const float* w_k16, float* y, int NB, int nb_tile, int H, int W, int Cin, int Cout,
                         void* stream) {
-    Igemm2Params p{x, nullptr, w_k16, nullptr, nullptr, y, nullptr, nullptr, NB, H, W, Cin, 0, Cout, 0, DVG_ACT_NONE, 0.f,
-                   0, 0, 0, 0, 0, 1, 0, nullptr};
-    if (int e = checks2(p, "dvg_gemm_batched_k16")) return e;
-    DVG_REQUIRE(Cin % (16 * DVG_GEMM_GT) == 0 && H % 8 == 0 && W % 8 == 0, DVG_ERR_SHAPE,
-                "dvg_gemm_batched_k16: Cin=%d must be a multiple of %d, H=%d W=%d multiples of 8", Cin, 16 * DVG_GEMM_GT, H, W);
-    DVG_REQUIRE((long)H * W * Cin < (1L << 31), DVG_ERR_SHAPE, "dvg_gemm_batched_k16: image of %d x %d x %d floats too large", H, W, Cin);
+    const char* who = "dvg_gemm_batched_k16";
+    Igemm2Params p = params2(x, nullptr, w_k16, nullptr, nullptr, y, NB, H, W, Cin, 0, Cout, DVG_ACT_NONE, 0.f);
+    if (int e = checks2(p, who)) return e;
+    Plan2 pl;
+    DVG_REQUIRE(gemm_plan(&pl, NB, nb_tile, H, W, Cin, Cout) == 0, DVG_ERR_SHAPE,
+                "%s: Cin=%d must be a multiple of %d, H=%d W=%d multiples of 8 with a tile", who, Cin, 16 * DVG_GEMM_GT, H, W);
+    DVG_REQUIRE((long)H * W * Cin < (1L << 31), DVG_ERR_SHAPE, "%s: image of %d x %d x %d floats too large", who, H, W, Cin);
     p.w_image_stride = (long)Cin / 16 * Cout * DVG_WROW;
-    float* workspace = nullptr;
-    const long workspace_floats = 0;
-    const int Hg = H, Wg = W, ti = 1, th = 8;
-    int tw, nt;
-    DVG_REQUIRE(gemm_tile(nb_tile, Hg, Wg, Cout, &tw, &nt) == 0, DVG_ERR_SHAPE, "dvg_gemm_batched_k16: no tile for %dx%d", H, W);
-#if DVG_BF16X3
-    if (nt == 2) return launch2<M2_GEMM, 1, 8, 16, 2>(p, Hg, Wg, workspace, workspace_floats, (hipStream_t)stream);
-#endif
-    D2(M2_GEMM, 1, 8, 16)
-    D2(M2_GEMM, 1, 8, 8)
-    return fail(DVG_ERR_SHAPE, "dvg_gemm_batched_k16: no kernel");
+    return launch_tile<M2_GEMM, T2_NT2>(p, pl, who, nullptr, 0, stream);
 }
 
 extern "C" int dvg_gemm_batched_k16(const float* x, const float* w_k16, float* y, int NB, int H, int W, int Cin, int Cout,
@@ -1952,22 +1957,16 @@ extern "C" int dvg_gemm_batched_k16_as(const float* x, const float* w_k16, float
     return gemm_batched(x, w_k16, y, NB, NB_as, H, W, Cin, Cout, stream);
 }
 
-// What dvg_gemm_batched_k16 launches for this shape under the tile policy in force, without launching (host only): *tile_w the
-// pixel tile's width (8: the 64-row tile, 16: the 128-row tile), *nt the 64-wide Cout blocks per workgroup (2: the 128 x 128
-// tile), *ni the images a workgroup runs back to back in one pipeline.  0, or -1 for a shape the launcher rejects.
-static int gemm_plan(int NB, int nb_tile, int H, int W, int Cin, int Cout, int* tile_w, int* nt, int* ni) {
-    if (!tile_w || !nt || !ni || NB <= 0 || nb_tile < NB || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0) return -1;
-    if (Cin % (16 * DVG_GEMM_GT) || Cout % 64 || H % 8 || W % 8) return -1;
-    if (gemm_tile(nb_tile, H, W, Cout, tile_w, nt)) return -1;
-    *ni = gemm_images_per_wg(*tile_w, *nt, NB, H, W, Cout);
+// gemm_plan of what dvg_gemm_batched_k16_as launches, for a caller (host only): *tile_w the pixel tile's width, *nt the 64-wide
+// Cout blocks per workgroup, *ni the images per pipeline
+extern "C" int dvg_gemm_batched_plan_as(int NB, int NB_as, int H, int W, int Cin, int Cout, int* tile_w, int* nt, int* ni) {
+    Plan2 pl;
+    if (!tile_w || !nt || !ni || gemm_plan(&pl, NB, NB_as, H, W, Cin, Cout)) return -1;
+    *tile_w = pl.tw; *nt = pl.nt; *ni = pl.ni;
     return 0;
 }
 
+// ... and of what dvg_gemm_batched_k16 launches
 extern "C" int dvg_gemm_batched_plan(int NB, int H, int W, int Cin, int Cout, int* tile_w, int* nt, int* ni) {
-    return gemm_plan(NB, NB, H, W, Cin, Cout, tile_w, nt, ni);
-}
-
-// ... and what dvg_gemm_batched_k16_as launches
-extern "C" int dvg_gemm_batched_plan_as(int NB, int NB_as, int H, int W, int Cin, int Cout, int* tile_w, int* nt, int* ni) {
-    return gemm_plan(NB, NB_as, H, W, Cin, Cout, tile_w, nt, ni);
+    return dvg_gemm_batched_plan_as(NB, NB, H, W, Cin, Cout, tile_w, nt, ni);
 }

@@ -76,9 +76,11 @@ def unpack_convT_weight(wp: torch.Tensor, kh: int, kw: int) -> torch.Tensor:
 # conv blocks.  All take / return NHWC-in-memory (N,C,H,W) tensors.
 # `stats=True` returns (y, stats_partial) with stats_partial [rows][2][Cout].
 # ----------------------------------------------------------------------------------
-def _splitk_ws(mode, n, h, w, cin, cout, out_numel, device):
-    """Workspace for the split-K path of the implicit GEMM (None when the launch fills the chip on its own)."""
-    s = lib().dvg_conv_splitk_v2(mode, n, h, w, cin, cout)
+def _splitk_ws(mode, n, h, w, cin, cout, out_numel, device, s=None):
+    """Workspace for the split-K path of the implicit GEMM (None when the launch fills the chip on its own).  s: what
+    dvg_conv_splitk_v2 answers for this shape, when the caller has asked already."""
+    if s is None:
+        s = lib().dvg_conv_splitk_v2(mode, n, h, w, cin, cout)
     if s <= 1:
         return None
     # One buffer per (stream, size), reused by every launch of that size on that stream (launches on a stream are ordered).
@@ -119,12 +121,20 @@ def _stats_buf(rows: int, cout: int, device, tile_images: int = 0):
     return st
 
 
-def _tile_images(mode, n, h, w, cin, cout, gh, gw, ws):
-    """Images per statistics row of an igemm launch (see _stats_buf): 4 on 4x4 tile grids, else 1; 0 when the launch
-    splits K (its finish kernel writes the statistics)."""
-    if ws is not None and lib().dvg_conv_splitk_v2(mode, n, h, w, cin, cout) != 1:
-        return 0
-    return 4 if (gh, gw) == (4, 4) else 1
+def _tile_images(mode, h, w, s):
+    """Images per statistics row of an igemm launch that runs s K splits (see _stats_buf): 4 on 4x4 tile grids, else 1; 0 when
+    the launch splits K (its finish kernel writes the statistics)."""
+    return 0 if s > 1 else 4 if ((h // 2, w // 2) if mode == MODE_CONV4S2 else (h, w)) == (4, 4) else 1
+
+
+def _igemm_buffers(mode, n, h, w, cin, cout, y, pool, stats):
+    """(split-K workspace or None, statistics buffer or None) of the igemm launch that writes y: each query asked once."""
+    s = lib().dvg_conv_splitk_v2(mode, n, h, w, cin, cout)
+    ws = _splitk_ws(mode, n, h, w, cin, cout, y.numel(), y.device, s)
+    if not stats:
+        return ws, None
+    rows = lib().dvg_conv_stats_rows_v2(mode, n, h, w, cin, cout, int(pool), int(ws is not None))
+    return ws, _stats_buf(rows, cout, y.device, _tile_images(mode, h, w, s))
 
 
 class SharedBlocks:
@@ -222,10 +232,7 @@ def conv3x3(x, skip, wp, scale, shift, *, upsample=False, act=ACT_LRELU, slope=0
     y = nhwc_empty(n, cout, h, w, x.device)
     yp = nhwc_empty(n, cout, h // 2, w // 2, x.device) if pool else None
     addend, amap, ablk = _check_addend(addend, y, pool)
-    ws = _splitk_ws(MODE_CONV3, n, h, w, cin, cout, y.numel(), x.device)
-    if stats:
-        rows = lib().dvg_conv_stats_rows_v2(MODE_CONV3, n, h, w, cin, cout, int(pool), int(ws is not None))
-    st = _stats_buf(rows, cout, x.device, _tile_images(MODE_CONV3, n, h, w, cin, cout, h, w, ws)) if stats else None
+    ws, st = _igemm_buffers(MODE_CONV3, n, h, w, cin, cout, y, pool, stats)
     fl, by = 2.0 * n * h * w * cout * 9 * cin, 4.0 * (x.numel() + (skip.numel() if c2 else 0) + n * h * w * cout +
                                                       wp.numel())
     _run("conv3x3_igemm", fl, by, lib().dvg_conv3x3_bn_act_v2, _p(x), _p(skip), _p(wp), _p(scale), _p(shift), _p(y),
@@ -313,10 +320,7 @@ def conv4x4s2(x, wp, scale, shift, *, act=ACT_LRELU, slope=0.2, stats=False):
         ti = {t.tile_images for t in sts}
         st.tile_images = ti.pop() if len(ti) == 1 else 0
         return y, st
-    ws = _splitk_ws(MODE_CONV4S2, n, h, w, cin, cout, y.numel(), x.device)
-    if stats:
-        rows = lib().dvg_conv_stats_rows_v2(MODE_CONV4S2, n, h, w, cin, cout, 0, int(ws is not None))
-    st = _stats_buf(rows, cout, x.device, _tile_images(MODE_CONV4S2, n, h, w, cin, cout, h // 2, w // 2, ws)) if stats else None
+    ws, st = _igemm_buffers(MODE_CONV4S2, n, h, w, cin, cout, y, False, stats)
     fl, by = 2.0 * n * (h // 2) * (w // 2) * cout * 16 * cin, 4.0 * (x.numel() + y.numel() + wp.numel())
     _run("conv4x4s2_igemm", fl, by, lib().dvg_conv4x4s2_bn_act_v2, _p(x), _p(wp), _p(scale), _p(shift), _p(y), _p(st),
          n, h, w, cin, cout, act, slope, _p(ws), 0 if ws is None else ws.numel(), _stream())
@@ -338,10 +342,7 @@ def convT4x4s2(x, skip, wp, scale, shift, *, act=ACT_LRELU, slope=0.2, stats=Fal
         raise RuntimeError(f"convT4x4s2: packed weight {tuple(wp.shape)} does not match Cin={c1 + c2}")
     y = nhwc_empty(n, cout, 2 * h, 2 * w, x.device)
     addend, amap, ablk = _check_addend(addend, y, False)
-    ws = _splitk_ws(MODE_CONVT4S2, n, h, w, cin, cout, y.numel(), x.device)
-    if stats:
-        rows = lib().dvg_conv_stats_rows_v2(MODE_CONVT4S2, n, h, w, cin, cout, 0, int(ws is not None))
-    st = _stats_buf(rows, cout, x.device, _tile_images(MODE_CONVT4S2, n, h, w, cin, cout, h, w, ws)) if stats else None
+    ws, st = _igemm_buffers(MODE_CONVT4S2, n, h, w, cin, cout, y, False, stats)
     fl = 2.0 * n * h * w * cout * 16 * cin
     by = 4.0 * (x.numel() + (skip.numel() if c2 else 0) + y.numel() + wp.numel())
     _run("convT4x4s2_igemm", fl, by, lib().dvg_convT4x4s2_bn_act_v2, _p(x), _p(skip), _p(wp), _p(scale), _p(shift),

@@ -33,51 +33,44 @@ def first_pair_ok(n, nc, h, w, cout) -> bool:
     return nc == 1 and h % 8 == 0 and w % 16 == 0 and cout % 64 == 0 and n * (h // 8) * (w // 16) * (cout // 64) >= 512
 
 
+def _first_pair(wx, x_nchw, w0, scale0, shift0, w1, scale1, shift1, act, slope, pool, y_from):
+    """The body of conv3x3_first_pair (wx False) and conv3x3_first_pair_wx (True).  They differ in the taps of the packed 64 ->
+    Cout weight (9 / 12), the workgroup floor (the direct form's alone), the products executed per output (9 / 6 x 64; `alg` is
+    the direct form's count) and the entry point."""
+    name, wname = ("conv3x3_first_pair_wx", "wx1") if wx else ("conv3x3_first_pair", "wp1")
+    _dev_f32(x_nchw, name + ".x")
+    x = x_nchw if x_nchw.is_contiguous() else x_nchw.contiguous()
+    n, nc, h, wd = x.shape
+    taps, cout, cin = _wp_dims(w1)
+    w0 = w0.detach()
+    ok = h % 8 == 0 and wd % 16 == 0 if wx else first_pair_ok(n, nc, h, wd, cout)
+    if nc != 1 or tuple(w0.shape) != (9, 64) or not w0.is_contiguous() or (taps, cin) != (12 if wx else 9, 64) or not ok:
+        raise RuntimeError(f"{name}: unsupported shapes x {tuple(x.shape)} w0 {tuple(w0.shape)} {wname} {tuple(w1.shape)}")
+    if not 0 <= y_from <= n or (y_from and not pool):
+        raise RuntimeError(f"{name}: y_from needs the pooled output and 0 <= y_from <= N")
+    y = nhwc_empty(n - y_from, cout, h, wd, x.device) if y_from < n else None
+    yp = nhwc_empty(n, cout, h // 2, wd // 2, x.device) if pool else None
+    alg = 2.0 * n * h * wd * (64 * 9 + cout * 9 * 64)
+    flops = 2.0 * n * h * wd * (64 * 9 + cout * 6 * 64) if wx else alg
+    _run("conv3x3_igemm", flops, 4.0 * (x.numel() + (0 if y is None else y.numel()) + (0 if yp is None else yp.numel()) + w1.numel()),
+         lib().dvg_conv3x3_first_pair_wx if wx else lib().dvg_conv3x3_first_pair, _p(x), _p(w0), _p(scale0), _p(shift0), _p(w1),
+         _p(scale1), _p(shift1), _p(y), _p(yp), n, h, wd, cout, act, slope, y_from, _stream(), alg_flops=alg)
+    return (y, yp) if pool else y
+
+
 def conv3x3_first_pair(x_nchw, w0, scale0, shift0, wp1, scale1, shift1, *, act=ACT_LRELU, slope=0.2, pool=False, y_from=0):
     """vgg_layer(1, 64) -> vgg_layer(64, Cout) (+ 2x2 max-pool) of the encoder's first stage in eval mode as ONE launch
     (dvg_conv3x3_first_pair): the 64-channel activation between the two layers is never materialised.
     w0: the first layer's (64,1,3,3) weight as a contiguous (9, 64) tensor [tap][channel].
     y_from (pool only): the full-resolution output is stored for the images [y_from, N) only - y has N - y_from images, None
     when y_from == N (a rollout discards the skip tensors of every frame but the last conditioning one)."""
-    _dev_f32(x_nchw, "conv3x3_first_pair.x")
-    x = x_nchw if x_nchw.is_contiguous() else x_nchw.contiguous()
-    n, nc, h, wd = x.shape
-    taps, cout, cin = _wp_dims(wp1)
-    w0 = w0.detach()
-    if nc != 1 or tuple(w0.shape) != (9, 64) or not w0.is_contiguous() or (taps, cin) != (9, 64) or \
-            not first_pair_ok(n, nc, h, wd, cout):
-        raise RuntimeError(f"conv3x3_first_pair: unsupported shapes x {tuple(x.shape)} w0 {tuple(w0.shape)} wp1 {tuple(wp1.shape)}")
-    if not 0 <= y_from <= n or (y_from and not pool):
-        raise RuntimeError("conv3x3_first_pair: y_from needs the pooled output and 0 <= y_from <= N")
-    y = nhwc_empty(n - y_from, cout, h, wd, x.device) if y_from < n else None
-    yp = nhwc_empty(n, cout, h // 2, wd // 2, x.device) if pool else None
-    flops = 2.0 * n * h * wd * (64 * 9 + cout * 9 * 64)
-    _run("conv3x3_igemm", flops, 4.0 * (x.numel() + (0 if y is None else y.numel()) + (0 if yp is None else yp.numel()) + wp1.numel()),
-         lib().dvg_conv3x3_first_pair, _p(x), _p(w0), _p(scale0), _p(shift0), _p(wp1), _p(scale1), _p(shift1), _p(y), _p(yp),
-         n, h, wd, cout, act, slope, y_from, _stream(), alg_flops=flops)
-    return (y, yp) if pool else y
+    return _first_pair(False, x_nchw, w0, scale0, shift0, wp1, scale1, shift1, act, slope, pool, y_from)
 
 
 def conv3x3_first_pair_wx(x_nchw, w0, scale0, shift0, wx1, scale1, shift1, *, act=ACT_LRELU, slope=0.2, pool=False, y_from=0):
     """conv3x3_first_pair with the 64 -> Cout layer in the WX form (dvg_conv3x3_first_pair_wx; wx1: pack_wx_weight): 12 instead
     of 18 products per output pair.  `flops` is what the launch executes, `alg_flops` the direct form's count."""
-    _dev_f32(x_nchw, "conv3x3_first_pair_wx.x")
-    x = x_nchw if x_nchw.is_contiguous() else x_nchw.contiguous()
-    n, nc, h, wd = x.shape
-    taps, cout, cin = _wp_dims(wx1)
-    w0 = w0.detach()
-    if nc != 1 or tuple(w0.shape) != (9, 64) or not w0.is_contiguous() or (taps, cin) != (12, 64) or h % 8 or wd % 16:
-        raise RuntimeError(f"conv3x3_first_pair_wx: unsupported shapes x {tuple(x.shape)} w0 {tuple(w0.shape)} wx1 {tuple(wx1.shape)}")
-    if not 0 <= y_from <= n or (y_from and not pool):
-        raise RuntimeError("conv3x3_first_pair_wx: y_from needs the pooled output and 0 <= y_from <= N")
-    y = nhwc_empty(n - y_from, cout, h, wd, x.device) if y_from < n else None
-    yp = nhwc_empty(n, cout, h // 2, wd // 2, x.device) if pool else None
-    alg = 2.0 * n * h * wd * (64 * 9 + cout * 9 * 64)
-    flops = 2.0 * n * h * wd * (64 * 9 + cout * 6 * 64)
-    _run("conv3x3_igemm", flops, 4.0 * (x.numel() + (0 if y is None else y.numel()) + (0 if yp is None else yp.numel()) + wx1.numel()),
-         lib().dvg_conv3x3_first_pair_wx, _p(x), _p(w0), _p(scale0), _p(shift0), _p(wx1), _p(scale1), _p(shift1), _p(y), _p(yp),
-         n, h, wd, cout, act, slope, y_from, _stream(), alg_flops=alg)
-    return (y, yp) if pool else y
+    return _first_pair(True, x_nchw, w0, scale0, shift0, wx1, scale1, shift1, act, slope, pool, y_from)
 
 
 def convT3x3_last(x, w, bias, nc, *, act=ACT_SIGMOID):

@@ -15,7 +15,7 @@ from tests.backward_ref import (MODE_CONV3, MODE_CONV4S2, MODE_CONVT4S2, MODE_NA
                                 conv_forward, conv_input, round16, sum_bound, weight_shape)
 
 LATENCY, ENERGY = 0, 1          # dvg_set_tile_policy
-TILE16_MIN_WGS = {LATENCY: 512, ENERGY: 256}      # tile2: the 8 x 16 tile from this many workgroups of it on
+TILE16_MIN_WGS = {LATENCY: 512, ENERGY: 256}      # plan2: the 8 x 16 tile from this many workgroups of it on
 
 
 # ---- the reference -----------------------------------------------------------------------------------------------------------
@@ -158,6 +158,45 @@ def split_chunks(nchunks, splits):
     return [(k * cps, min(nchunks, (k + 1) * cps)) for k in range(s)]
 
 
+# ---- the launch plan, restated (conv_igemm2.hip: plan2) ---------------------------------------------------------------------
+def plan_tile(mode, n, hg, wg, cout, policy):
+    """The tile rule on the grid the tiles cover (the output grid of conv3 / conv4s2, the input grid of convT4s2), or None."""
+    if (hg, wg) == (4, 4):
+        return (4, 4, 4)
+    if hg % 8 or wg % 8:
+        return None
+    par = 4 if mode == MODE_CONVT4S2 else 1
+    if wg % 16 == 0 and n * (hg // 8) * (wg // 16) * (cout // 64) * par >= TILE16_MIN_WGS[policy]:
+        return (1, 8, 16)
+    return (1, 8, 8)
+
+
+def plan_splitk(wgs, nchunks):
+    """choose_splitk: the first pick, then as many splits as are not empty at ceil(nchunks / pick) chunks each."""
+    if wgs >= 384 or nchunks < 8:
+        return 1
+    s = min(512 // wgs, 8, nchunks // 4)
+    return 1 if s < 2 else len(split_chunks(nchunks, s))
+
+
+def plan(mode, n, h, w, cin, cout, policy, pool=False, with_ws=True):
+    """dict(tile, wgs per split, tiles, splits, cps, rows) of a launch, or None where there is no tile: splits / cps as the launch
+    runs them, rows = the statistics rows (the finish kernel's blocks of max(8, ceil(units / 1024)) pixels - pooled: 2 x 2 quads -
+    when K is split, else one per tile)."""
+    hg, wg = (h // 2, w // 2) if mode == MODE_CONV4S2 else (h, w)
+    tile = plan_tile(mode, n, hg, wg, cout, policy)
+    if tile is None:
+        return None
+    ti, th, tw = tile
+    tiles = -(-n // ti) * (hg // th) * (wg // tw) * (4 if mode == MODE_CONVT4S2 else 1)
+    wgs, nchunks = tiles * (cout // 64), cin // 16
+    s = plan_splitk(wgs, nchunks) if with_ws and tw != 16 else 1      # the 16-wide kernels carry no split-K epilogue
+    ho, wo = {MODE_CONV3: (h, w), MODE_CONV4S2: (h // 2, w // 2), MODE_CONVT4S2: (2 * h, 2 * w)}[mode]
+    units = n * (ho // 2) * (wo // 2) if pool else n * ho * wo
+    upb = max(8, -(-units // 1024))
+    return dict(tile=tile, wgs=wgs, tiles=tiles, splits=s, cps=-(-nchunks // s), rows=-(-units // upb) if s > 1 else tiles)
+
+
 def bf16_planes(t):
     """The exact bf16 triple (h, m, l) of fp32 values, each plane as fp64 (dvg_common.h: bf16x3_split_pair - h = t rounded to
     nearest bf16, m = the remainder rounded to nearest bf16, l the rest)."""
@@ -221,8 +260,8 @@ def ordered_fp32_ref(mode, x, skip, w, upsample, addend=None, splits=1, per_mfma
 
 # ---- the cases (docs/DESIGN_NOTES_forward_tests.md has the table) -----------------------------------------------------------
 # shape: conv3 (N, H, W, C1, C2, Cout) on the conv's own grid (x enters at half of it when `up`); conv4s2 (N, H, W, Cin, Cout) on
-# the input grid; convT4s2 (N, H, W, C1, C2, Cout) on the input grid.  tile / splits: what tile2, choose_splitk and launch2's
-# rounding of the chunks per split give the case under the LATENCY policy, tile_e / splits_e under the ENERGY policy
+# the input grid; convT4s2 (N, H, W, C1, C2, Cout) on the input grid.  tile / splits: what plan2 (the tile rule, choose_splitk with its
+# rounding of the chunks per split) gives the case under the LATENCY policy, tile_e / splits_e under the ENERGY policy
 # (tests/test_forward_ref_host.py asserts both against the library).  addend: (block, map) of a shared addend.
 def _case(mode, n, h, w, c1, c2, cout, tile, splits, *, up=False, pool=False, addend=None, tile_e=None, why=""):
     name = f"{MODE_NAME[mode]}-n{n}-{h}x{w}-c{c1}+{c2}-o{cout}" + ("-up" if up else "") + ("-pool" if pool else "") + \
@@ -260,6 +299,11 @@ FWD_CASES = [
     _case(MODE_CONVT4S2, 6, 4, 4, 32, 0, 64, (4, 4, 4), 1, addend=_ADD, why="a 4-image tile spans two groups; tail of 2"),
     _case(MODE_CONVT4S2, 2, 8, 8, 256, 0, 64, (1, 8, 8), 4, why="K = 1024 per parity, for the comparison with conv4s2"),
     _case(MODE_CONVT4S2, 16, 16, 16, 16, 0, 128, (1, 8, 8), 1, tile_e=(1, 8, 16), why="8 x 16 tile under the energy policy"),
+    # ragged splits: choose_splitk's first pick (6, 8, 6, 6) would leave a split empty, the launch runs one or two fewer
+    _case(MODE_CONV3, 1, 8, 8, 400, 0, 64, (1, 8, 8), 5, why="25 chunks, 5 splits of 5 / 5 / 5 / 5 / 5; not 6"),
+    _case(MODE_CONV3, 1, 8, 8, 528, 0, 64, (1, 8, 8), 7, why="33 chunks, 7 splits of 5 / 5 / 5 / 5 / 5 / 5 / 3; not 8"),
+    _case(MODE_CONV4S2, 1, 16, 16, 400, 0, 64, (1, 8, 8), 5, why="25 chunks, 5 splits of 5 / 5 / 5 / 5 / 5; not 6"),
+    _case(MODE_CONVT4S2, 1, 4, 4, 400, 0, 64, (4, 4, 4), 5, why="25 chunks, 5 splits of 5 / 5 / 5 / 5 / 5; not 6; four workgroups"),
 ]
 CASE_BY_NAME = {c["name"]: c for c in FWD_CASES}
 CASE_NAMES = [c["name"] for c in FWD_CASES]

@@ -18,37 +18,10 @@ def _lib():
 
 
 # ---- the dispatch of every case ---------------------------------------------------------------------------------------------
-def _tile2(mode, n, hg, wg, cout, policy):
-    """tile2's rule on the grid the tiles cover (the output grid of conv3 / conv4s2, the input grid of convT4s2)."""
-    if (hg, wg) == (4, 4):
-        return (4, 4, 4)
-    if hg % 8 or wg % 8:
-        return None
-    par = 4 if mode == MODE_CONVT4S2 else 1
-    if wg % 16 == 0 and n * (hg // 8) * (wg // 16) * (cout // 64) * par >= fr.TILE16_MIN_WGS[policy]:
-        return (1, 8, 16)
-    return (1, 8, 8)
-
-
-def _choose_splitk(wgs, nchunks):
-    if wgs >= 384 or nchunks < 8:
-        return 1
-    s = min(512 // wgs, 8, nchunks // 4)
-    return 1 if s < 2 else s
-
-
 def _geometry(case, policy):
-    """(tile, workgroups per split, tiles, splits after launch2's rounding, chunks per split) recomputed from the three rules."""
-    mode, n = case["mode"], case["n"]
-    hg, wg = (case["h"] // 2, case["w"] // 2) if mode == MODE_CONV4S2 else (case["h"], case["w"])
-    tile = _tile2(mode, n, hg, wg, case["cout"], policy)
-    ti, th, tw = tile
-    tiles = -(-n // ti) * (hg // th) * (wg // tw) * (4 if mode == MODE_CONVT4S2 else 1)
-    wgs = tiles * (case["cout"] // 64)
-    nchunks = (case["c1"] + case["c2"]) // 16
-    s = 1 if tw == 16 else _choose_splitk(wgs, nchunks)          # the 16-wide kernels carry no split-K epilogue
-    cps = -(-nchunks // s)
-    return tile, wgs, tiles, -(-nchunks // cps), cps
+    """(tile, workgroups per split, tiles, splits the launch runs, chunks per split) from the rules restated in forward_ref.plan."""
+    g = fr.plan(case["mode"], case["n"], case["h"], case["w"], case["c1"] + case["c2"], case["cout"], policy)
+    return g["tile"], g["wgs"], g["tiles"], g["splits"], g["cps"]
 
 
 @pytest.mark.parametrize("name", fr.CASE_NAMES)
@@ -64,7 +37,7 @@ def test_case_still_has_the_tile_and_the_split_it_was_chosen_for(name):
             rows = lib.dvg_conv_stats_rows_v2(mode, n, h, w, cin, cout, int(case["pool"]), 0)
         print(f"{name} policy {policy}: tile {tile} workgroups {wgs} tiles {tiles} splits {s_lib} x {cps} chunks")
         assert tile == case["tile"][policy]
-        assert s_lib == s == case["splits"][policy]          # (launch2's rounding leaves these counts as they are)
+        assert s_lib == s == case["splits"][policy]          # the count the launch runs: no empty split
         assert len(fr.split_chunks(cin // 16, s_lib)) == s_lib
         assert rows == tiles
     assert lib.dvg_tile_policy() == before
@@ -106,7 +79,9 @@ def test_the_case_list_is_the_issue_s():
         (1, 3, 16, 16, 64, 0, 64, False, False, None), (1, 32, 32, 32, 16, 0, 256, False, False, None),
         (2, 1, 8, 8, 16, 0, 64, False, False, None), (2, 5, 4, 4, 16, 16, 64, False, False, None),
         (2, 3, 4, 4, 48, 96, 64, False, False, None), (2, 6, 4, 4, 32, 0, 64, False, False, add),
-        (2, 2, 8, 8, 256, 0, 64, False, False, None), (2, 16, 16, 16, 16, 0, 128, False, False, None)]
+        (2, 2, 8, 8, 256, 0, 64, False, False, None), (2, 16, 16, 16, 16, 0, 128, False, False, None),
+        (0, 1, 8, 8, 400, 0, 64, False, False, None), (0, 1, 8, 8, 528, 0, 64, False, False, None),
+        (1, 1, 16, 16, 400, 0, 64, False, False, None), (2, 1, 4, 4, 400, 0, 64, False, False, None)]
     assert [n for n, p in fr.VARIANTS if p == ENERGY] == [
         "conv3-n16-32x32-c32+0-o128-pool", "conv4s2-n32-32x32-c16+0-o256", "convT4s2-n16-16x16-c16+0-o128"]
     assert all(fr.CASE_BY_NAME[n]["tile"][ENERGY] == (1, 8, 16) for n, p in fr.VARIANTS if p == ENERGY)
