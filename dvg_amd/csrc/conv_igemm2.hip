@@ -174,7 +174,8 @@ struct Cfg2 {
     static constexpr int row_c(int reg) { return 4 * (int)((P0PACK >> (4 * (reg >> 2))) & 15u) + (reg & 3); }
     static constexpr int BM = TI * TH * TW, MT = BM / 64, BN = 64 * NT;
     static constexpr int NTAPS = GEMM ? 1 : ((MODE == M2_CONV3) ? 9 : 16);
-    // (NT = 2: two slabs, K = 32, so that two 48 KB workgroups share a CU)
+    // (NT = 2: two slabs, K = 32 - 24 KB of A per workgroup, the weights are not staged: WREG below.  A K = 64 stage was no faster,
+    // three workgroups per CU spill: docs/DESIGN_NOTES_gemm_wreg.md §3)
     static constexpr int GT = (MODE == M2_CONV3) ? 9 : (MODE == M2_CONV4S2 ? 4 : (GEMM ? (NT == 2 ? 2 : (BM == 128 ? DVG_GEMM128_GT : DVG_GEMM_GT)) : 4));  // taps (GEMM: 16-channel slabs) per stage
     static constexpr int NG = (MODE == M2_CONV4S2) ? 16 / GT : 1;                     // stages per K chunk
     static constexpr int CHUNKS_PER_STAGE = GEMM ? GT : 1;                            // 16-channel chunks one stage consumes
@@ -193,7 +194,15 @@ struct Cfg2 {
     static constexpr int NLA = NLA1 * (GEMM ? GT : 1);
     static constexpr int SLAB = NLA1 * 64 * LD;                                       // floats of one A slab (GEMM mode)
     // the A region is padded to whole 256-thread store passes (NLA * 64 rows): the halo store is branch-free
-    static constexpr int A_FLOATS = NLA * 64 * LD, B_FLOATS = GT * BN * LDB;
+    // WREG (the NT = 2 tile): the weight tile is not staged in LDS.  A B fragment is one 16-byte piece per lane and plane of a
+    // packed row, the LDS image of the tile is its memory image, and a wave's 64 columns are ONE 64-column block of the packed
+    // tensor that only its partner wave (same wn) shares: each wave loads its own B fragments from global memory into the
+    // registers the MFMAs read (`global_load_dwordx4`, one K = 16 slab ahead of its MFMAs; the partner's loads of the same
+    // lines hit the CU's vector L1).  Per MFMA that halves the LDS bytes again (fragment reads 0.5 -> 0.25 KB, tile stores 0.25
+    // -> 0.125 KB) and the tile holds its A stage alone (24 KB instead of 48 KB).  Same MFMAs, same operands, same order: the
+    // same bits (docs/DESIGN_NOTES_gemm_wreg.md).
+    static constexpr bool WREG = X3 && GEMM && NT == 2;
+    static constexpr int A_FLOATS = NLA * 64 * LD, B_FLOATS = WREG ? 0 : GT * BN * LDB;
     // FIRST: the frame patch under the halo tile, (HH + 2) x (HW + 2) floats, in LDS (the first layer's weights, scale and
     // shift of a stage's 16 channels travel in registers): 77.8 KB, two workgroups per CU.  (r03 dropped the A tile's 12 padding
     // rows here on the reading that "two 80.6 KB allocations are both admitted and then corrupt each other's last
@@ -407,6 +416,23 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
             rb[j] = reinterpret_cast<const f32x4*>(tile)[i + blk];
         }
     };
+    // WREG: the wave's B fragments of ONE 16-channel slab straight from the packed tensor - its 64 columns are the 64-column
+    // block nb * NT + wn, whose slabs of an image are consecutive runs of 64 rows; the lane's piece of 32-column tile nt and
+    // plane j lies where b_base puts it in the LDS image (row nt * 32 + l31, the swapped 16-byte half hh, planes 32 bytes
+    // apart): one lane pointer, immediates for (nt, j).  bq[slab & 1] holds a slab.  bq_ptr: the lane's piece of the slab the
+    // NEXT load fetches - it walks the slabs of the workgroup's one image.
+    [[maybe_unused]] f32x4 bq[C::WREG ? 2 : 1][NT][NP];
+    constexpr int BQ_SLAB = 64 * C::WROW * (int)sizeof(float);       // bytes of one slab of a 64-column block
+    [[maybe_unused]] const char* bq_ptr = reinterpret_cast<const char*>(wbase)
+        + (((size_t)nb * NT + wn) * (Cin / C::KC) + split * p.cps) * BQ_SLAB + (l31 * LDB + (hh ^ ((l31 >> 3) & 1)) * 4) * (int)sizeof(float);
+    [[maybe_unused]] auto gload_bq = [&](const int buf) __attribute__((always_inline)) {
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int j = 0; j < NP; ++j)
+                bq[buf][nt][j] = *reinterpret_cast<const f32x4*>(bq_ptr + (nt * 32 * LDB + j * PSTEP) * (int)sizeof(float));
+        bq_ptr += BQ_SLAB;
+    };
     auto lds_store_a = [&](f32x4 (&ra)[NLA], const int par_ = 0) {
         if constexpr (FIRST) first_tile(ra);
 #pragma unroll
@@ -468,9 +494,10 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
         __syncthreads();
     }
     gload_a(chunk_begin * C::KC, ra);
-    gload_b(chunk_begin, 0, rb);
+    if constexpr (C::WREG) gload_bq(0);
+    else gload_b(chunk_begin, 0, rb);
     lds_store_a(ra);
-    lds_store_b(rb);
+    if constexpr (!C::WREG) lds_store_b(rb);
     __syncthreads();
     unsigned long long clk1 = 0;
     if (p.clk) clk1 = clock64();
@@ -486,8 +513,8 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
         constexpr int ngrp = (grp + 1) % NG;
         constexpr bool next_a = has_next && (ngrp == 0 || C::PAR4);        // PAR4: every stage has its own A tile
         const int nchunk = nchunk_override >= 0 ? nchunk_override : chunk + (ngrp == 0 ? CPS : 0);
-        if constexpr (next_a) gload_a(nchunk * C::KC, ra, C::PAR4 ? ngrp : 0);
-        if constexpr (has_next) gload_b(nchunk, ngrp, rb);
+        if constexpr (next_a && !C::WREG) gload_a(nchunk * C::KC, ra, C::PAR4 ? ngrp : 0);
+        if constexpr (has_next && !C::WREG) gload_b(nchunk, ngrp, rb);
 
         // ---- all taps of this stage from LDS; fragments double-buffered across taps ----
         // a lane's fragment of a tap: NP 16-byte pieces per 32-row tile - f32: its k-values 0..3 and 4..7 of the lane's
@@ -500,6 +527,7 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt)
                     fa[0][mt][j] = *reinterpret_cast<const f32x4*>(&As[a_base[mt] + ao + j * PSTEP]);
+                if constexpr (!C::WREG)
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt)
                     fb[0][nt][j] = *reinterpret_cast<const f32x4*>(&Bs[b_base[nt] + j * PSTEP]);
@@ -508,6 +536,14 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
 #pragma unroll
         for (int tt = 0; tt < GT; ++tt) {
             const int cur = tt & 1, nxt = cur ^ 1;
+            // WREG: slab tt's B fragments are in bq[cur] (loaded one slab ago); the NEXT slab's - the next stage's first one after
+            // this stage's last - go to bq[nxt], which slab tt - 1 has released.  Unconditional inside the peeled loop.
+            static_assert(!C::WREG || GT % 2 == 0, "WREG: slab parity = buffer parity across stages");
+            if constexpr (C::WREG) {
+                if (tt + 1 < GT || has_next) gload_bq(nxt);
+                // (the next stage's A loads behind the slab's B loads: the VMEM groups below take them in this order)
+                if constexpr (next_a) if (tt == 0) gload_a(nchunk * C::KC, ra, 0);
+            }
             // LEAN (the 64 x 64 wave tile): the next tap's planes are read when the current tap no longer needs the plane -
             // h up front into a second buffer, l after the two groups that use l, m after the three that use m - so that 16
             // instead of 48 VGPRs double-buffer the fragments (the whole set twice does not fit 256 registers)
@@ -517,6 +553,7 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
 #pragma unroll
                 for (int mt = 0; mt < MT; ++mt)
                     fa[nxt][mt][j] = *reinterpret_cast<const f32x4*>(&As[a_base[mt] + ao + j * PSTEP]);
+                if constexpr (!C::WREG)
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt)
                     fb[nxt][nt][j] = *reinterpret_cast<const f32x4*>(&Bs[b_base[nt] + (tt + 1) * 64 * LDB + j * PSTEP]);
@@ -540,17 +577,22 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
                 // forming an MFMA-less pass between two barriers (84.7 % vs 80.8 % of peak: docs/DESIGN_NOTES_r01-r03.md §3.1).
                 __syncthreads();
                 if constexpr (next_a) lds_store_a(ra, C::PAR4 ? ngrp : 0);
-                lds_store_b(rb);
+                if constexpr (!C::WREG) lds_store_b(rb);
             }
             if constexpr (X3) {
                 // six bf16 MFMAs per 32 x 32 tile and K = 16 slab, small terms first: (l,h) (m,m) (h,l) (m,h) (h,m) (h,h)
+                // the B fragment of 32-column tile nt, plane pb: WREG from the slab's registers, else from the LDS double buffer
+                auto bfrag = [&](int nt, int pb) -> f32x4 {
+                    if constexpr (C::WREG) return bq[cur][nt][pb];
+                    else return fb[cur][nt][pb];
+                };
                 auto mm = [&](int pa, int pb) {
 #pragma unroll
                     for (int mt = 0; mt < MT; ++mt)
 #pragma unroll
                         for (int nt = 0; nt < NT; ++nt)
                             acc[mt * NT + nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
-                                __builtin_bit_cast(bf16x8_t, fa[cur][mt][pa]), __builtin_bit_cast(bf16x8_t, fb[cur][nt][pb]),
+                                __builtin_bit_cast(bf16x8_t, fa[cur][mt][pa]), __builtin_bit_cast(bf16x8_t, bfrag(nt, pb)),
                                 acc[mt * NT + nt], 0, 0, 0);
                 };
                 if constexpr (LEAN) {
@@ -582,20 +624,22 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
             // Pin the software pipeline: hipcc otherwise sinks the next tap's ds_reads down to their first use
             // (ds_read x3 -> s_waitcnt -> mfma x8), exposing the LDS latency every 8 MFMAs.  One ds_read_b128 per two
             // MFMAs, issued a full tap (16 / 8 MFMAs) ahead of its consumer.
-            constexpr int NREAD = NP * (MT + NT), NMFMA = (X3 ? 6 : 8) * MT * NT, MPR = NMFMA >= 2 * NREAD ? 2 : 1;
+            constexpr int NREAD = NP * (MT + (C::WREG ? 0 : NT)), NMFMA = (X3 ? 6 : 8) * MT * NT, MPR = NMFMA >= 2 * NREAD ? 2 : 1;
             // next stage's global loads: left free, hipcc sinks them to the end of the stage (latency exposed at their
             // ds_write); all at the top they delay the first MFMAs.  Spread over the taps that are followed by another tap,
             // starting at tap 2 in the 9-tap mode and at tap 0 in the 4- / 8-tap modes, at least two and as many per tap as it
             // takes to place ALL of them (84.7 % of peak; two or three per tap from tap 0: 84.4, 84.3 - the same notes)
-            constexpr int NVMEM = (next_a ? (FIRST ? 11 : NLA) : 0) + (has_next ? NLB : 0);
+            constexpr int NVMEM = (next_a ? (FIRST ? 11 : NLA) : 0) + (has_next && !C::WREG ? NLB : 0);
             constexpr int VT0 = GT >= 9 ? 2 : 0;
             constexpr int SLOTS = (GT - 1 - VT0) > 0 ? (GT - 1 - VT0) : 1;
             constexpr int VNEED = (NVMEM + SLOTS - 1) / SLOTS;
             constexpr int VPT = VNEED > 2 ? VNEED : 2;
             constexpr int VTAPS = (NVMEM + VPT - 1) / VPT;
             if (tt == 0) __builtin_amdgcn_sched_group_barrier(0x100, NREAD, 0);  // tap 0's own fragments
+            // WREG: the next slab's B loads lead the slab, a full slab of MFMAs ahead of their consumers
+            if (C::WREG && (tt + 1 < GT || has_next)) __builtin_amdgcn_sched_group_barrier(0x020, NT * NP, 0);
             if (LEAN && tt + 1 < GT) {
-                constexpr int G = MT * NT, R = MT + NT;
+                constexpr int G = MT * NT, R = MT + (C::WREG ? 0 : NT);
 #pragma unroll
                 for (int r = 0; r < R; ++r) {      // next h planes behind the first MFMAs
                     __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
@@ -613,6 +657,7 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
                     __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
                 }
+                if (G > R) __builtin_amdgcn_sched_group_barrier(0x008, G - R, 0);      // (WREG: no B reads - the slab's last MFMAs)
             } else if (tt + 1 < GT) {
 #pragma unroll
                 for (int r = 0; r < NREAD; ++r) {
@@ -621,7 +666,7 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
                 }
                 if (NMFMA > MPR * NREAD) __builtin_amdgcn_sched_group_barrier(0x008, NMFMA - MPR * NREAD, 0);
             } else if (has_next) {     // the next stage's ds_writes between the last tap's MFMAs
-                constexpr int NW = (next_a ? NLA * (X3 ? 3 : 1) : 0) + NLB;
+                constexpr int NW = (next_a ? NLA * (X3 ? 3 : 1) : 0) + (C::WREG ? 0 : NLB);
 #pragma unroll
                 for (int r = 0; r < NW; ++r) {
                     if (r < NMFMA) __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
@@ -668,15 +713,30 @@ __global__ __launch_bounds__(256, (MODE == M2_GEMM && TW == 8) ? DVG_GEMM_WGS_PE
         const unsigned lane_off = (unsigned)(4 * hh * p.Cout + l31);
         float* const ybase = p.y + (size_t)n0 * p.H * p.W * p.Cout + nb0 + __builtin_amdgcn_readfirstlane(wn) * 32 * NT;
         const int wm_u = __builtin_amdgcn_readfirstlane(wm);
-        for (int img = 0; img < p.gemm_ni; ++img) {
-            for (int sg = 0; sg < spi; ++sg) {
-                const bool wrap = sg == spi - 1, last = wrap && img == p.gemm_ni - 1;
-                ld_a_off = (long)(n0 + img + (wrap ? 1 : 0)) * a_img;
-                ld_w = wbase + (size_t)(img + (wrap ? 1 : 0)) * p.w_image_stride;
-                const int nchunk = wrap ? chunk_begin : chunk_begin + (sg + 1) * CPS;
+        const int ni = C::WREG ? 1 : p.gemm_ni;
+        for (int img = 0; img < ni; ++img) {
+            if constexpr (C::WREG) {
+                // The image's last stage stands outside the loop over its stages.  With `last ? stage<false> : stage<true>` inside
+                // that loop hipcc kept the 64 accumulators twice (the looping stage wrote a second set and copied it back: 64
+                // v_mov per stage and 128 of the 240 VGPRs), which leaves no room for the B slabs in flight.
+                // One image per workgroup (ni == 1: launch2 checks it - only the 64-row tile chains images), so that stage is
+                // the one without a successor.
+                for (int sg = 0; sg + 1 < spi; ++sg) {
+                    set_prio(st++);
+                    stage(chunk_begin + sg * CPS, integral_constant<int, 0>{}, integral_constant<bool, true>{}, chunk_begin + (sg + 1) * CPS);
+                }
                 set_prio(st++);
-                if (last) stage(chunk_begin + sg * CPS, integral_constant<int, 0>{}, integral_constant<bool, false>{});
-                else stage(chunk_begin + sg * CPS, integral_constant<int, 0>{}, integral_constant<bool, true>{}, nchunk);
+                stage(chunk_begin + (spi - 1) * CPS, integral_constant<int, 0>{}, integral_constant<bool, false>{});
+            } else {
+                for (int sg = 0; sg < spi; ++sg) {
+                    const bool wrap = sg == spi - 1, last = wrap && img == p.gemm_ni - 1;
+                    ld_a_off = (long)(n0 + img + (wrap ? 1 : 0)) * a_img;
+                    ld_w = wbase + (size_t)(img + (wrap ? 1 : 0)) * p.w_image_stride;
+                    const int nchunk = wrap ? chunk_begin : chunk_begin + (sg + 1) * CPS;
+                    set_prio(st++);
+                    if (last) stage(chunk_begin + sg * CPS, integral_constant<int, 0>{}, integral_constant<bool, false>{});
+                    else stage(chunk_begin + sg * CPS, integral_constant<int, 0>{}, integral_constant<bool, true>{}, nchunk);
+                }
             }
             float* const yb = ybase + (size_t)img * p.H * p.W * p.Cout;      // raw products: M[n0 + img][pixel][co]
 #pragma unroll
@@ -1190,6 +1250,7 @@ static int launch2(Igemm2Params p, const Plan2& pl, float* ws, long ws_floats, h
     static_assert(C::CAN_SPLIT == can_split2(MODE, TW, FIRST || PROJ), "the host's split rule is the kernels'");
     if (pl.ti != TI || pl.th != TH || pl.tw != TW || pl.nt != NT || pl.can_split != C::CAN_SPLIT || pl.pool != (p.y_pool != nullptr))
         return fail(DVG_ERR_SHAPE, "conv_igemm2: the plan is not this launch's");
+    if (C::WREG && pl.ni != 1) return fail(DVG_ERR_SHAPE, "conv_igemm2: the 128 x 128 tile runs one image per workgroup");
     if (pl.Hg % TH || pl.Wg % TW || p.Cout % C::BN || pl.cps % C::CHUNKS_PER_STAGE)      // (whole stages per split)
         return fail(DVG_ERR_SHAPE, "conv_igemm2: tile does not divide shape");
     p.tiles_y = pl.ty; p.tiles_x = pl.tx; p.tiles_n = pl.tn;
